@@ -463,8 +463,8 @@ def cpu_baseline(cfg, seconds_budget=28.0):
     return out
 
 
-def _time_steps(trainer, batch, steps, warmup, world):
-    """Times `steps` steps.  The native step owns static input buffers (HIP-graph replay): the batch is written into them ONCE,
+def _time_steps(trainer, batch, steps, warmup, world, last=None):
+    """Times `steps` steps (the last one's (loss, reconstruction) go into the dict `last` when one is given).  The native step owns static input buffers (HIP-graph replay): the batch is written into them ONCE,
     before the timed region ("inputs already resident in HBM"), and every step runs on those buffers -- a training loop would
     let its data loader fill `trainer.p4 / trainer.mask` the same way.  The module-API harness takes the batch per step, as
     the reference's loop does."""
@@ -486,14 +486,45 @@ def _time_steps(trainer, batch, steps, warmup, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _ = step()
+        loss, recon = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     assert torch.isfinite(loss).item(), "non-finite loss"
+    if last is not None:
+        last.update(loss=loss, recon=recon)
     return elapsed
+
+
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, trainer, last):
+    """--dump-outputs: what the timed path handed its caller after the last timed step, as float64 .npy files -- loss (1,),
+    recon (2, B, N, 4) (get_real's two parts), and the encoder + decoder parameters after that step's Adam update and their
+    gradients, flattened in parameters() order.  If recon would take the total past DUMP_BYTES, a fixed seeded sample of
+    its jets (sorted) is written instead and recon_jets.npy names them."""
+    import numpy as np
+    params = [p for m in (trainer.encoder, trainer.decoder) for p in m.parameters()]
+    with torch.no_grad():
+        out = {"loss": last["loss"].detach().reshape(1),
+               "params": torch.cat([p.detach().reshape(-1) for p in params]),
+               "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])}
+        recon = last["recon"].detach()
+        room = DUMP_BYTES - sum(8 * t.numel() for t in out.values())
+        per_jet = 8 * recon[:, 0].numel()
+        if 8 * recon.numel() > room:
+            keep = max(1, (room - 8 * recon.shape[1]) // (per_jet + 8))
+            jets = torch.randperm(recon.shape[1], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            out["recon_jets"] = jets
+            recon = recon[:, jets.to(recon.device)]
+        out["recon"] = recon
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.to("cpu", torch.float64).numpy())
+    print(f"bench.py: wrote {', '.join(sorted(out))} to {path}", file=sys.stderr)
 
 
 def small_batch_legs(dev, cfg, G, NativeTrainStep):
@@ -641,7 +672,12 @@ def main():
     ap.add_argument("--harness", choices=["native", "native-nograph", "module", "modular", "captured"], default=None,
                     help="native: one C call per step replayed from a HIP graph (default); module: the reference's loop on the "
                          "nn.Module API")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, reconstruction, updated parameters, "
+                         "gradients) as DIR/<name>.npy, float64, <= 64 MB in all (rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -689,8 +725,8 @@ def main():
             return enc, CapturedModuleStep(enc, dec, batch_size=jets or per_gpu, lr=5e-4, l1_lambda=1e-8)
         return enc, NativeTrainStep(enc, dec, batch_size=jets or per_gpu, lr=5e-4, l1_lambda=1e-8, use_graph=which == "native")
 
-    def timed(tr, b):
-        e = _time_steps(tr, b, args.steps, args.warmup, world)
+    def timed(tr, b, last=None):
+        e = _time_steps(tr, b, args.steps, args.warmup, world, last)
         if world > 1:                                      # MAX over ranks
             t = torch.tensor([e], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -700,7 +736,10 @@ def main():
     enc, trainer = build(harness)
     p4, labels = synthetic_jets(per_gpu, N, seed=rank)     # per-rank shard, resident in HBM
     batch = {"p4": p4.to(dev), "labels": labels.to(dev)}
-    elapsed = timed(trainer, batch)
+    last = {}
+    elapsed = timed(trainer, batch, last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last)
     other = None
     if world > 1 and harness != "module" and args.batch is None and args.global_batch is None and cfg["B"] % world == 0:
         # the OTHER scaling figure next to the primary one, timed in the same run (all ranks take part): strong = the config's batch

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """
 Generate the golden vectors under tests/golden/ by importing the *reference*
-implementation (zichunhao/lgn-autoencoder, mounted read-only at /root/reference).
+implementation (zichunhao/lgn-autoencoder, a read-only checkout of it; the tests never read it, only these fixtures).
 
-Run in the build container only (the reference never travels to the GPU box):
+Run from outside this repository, with the reference checkout first on the path:
 
-    cd /tmp && PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=/root/reference \
-        python3 /root/repo/tests/golden/gen_golden.py
+    cd "$(mktemp -d)" && PYTHONDONTWRITEBYTECODE=1 PYTHONPATH=<reference checkout> \
+        python3 <this repo>/tests/golden/gen_golden.py
 
 The outputs are plain data (inputs, parameters, expected outputs, expected gradients, key
 orders); no reference source text is stored.  Everything is float64.
@@ -35,6 +35,9 @@ Fixtures
   g8_harness.npz      the reference's own equivariance harness (lgn/models/autotest/lgn_tests.py:292-423) run on the g1 weights
                       (maxdim 2) and the g2 weights (maxdim 3): gamma / theta grids, output and internal-feature deviation
                       tables, permutation results, on fixed zero-padded jets (SURVEY 8c "G6 harness")
+  g16_dropin.json     the drop-in boundary: every `lgn` import of the reference's callers of the hot path (main.py, test.py,
+                      covariance_test.py, anomaly_detection.py, utils/**), and the keyword arguments utils.initialize.
+                      initialize_autoencoder passes to LGNEncoder / LGNDecoder for one fixed argument set (names and values only)
 
 `python gen_golden.py g6 g7` regenerates only the named fixtures.
 """
@@ -326,6 +329,58 @@ def harness():
     print("g8_harness.npz", len(store))
 
 
+def dropin():
+    """g16_dropin.json: what tests/test_dropin_imports.py checks this repo's package against, recorded from the reference."""
+    import argparse
+    import ast
+    import glob
+    ref = os.path.dirname(os.path.abspath(list(sys.modules["lgn"].__path__)[0]))
+    files = [os.path.join(ref, f) for f in ("main.py", "test.py", "covariance_test.py", "anomaly_detection.py")]
+    files += glob.glob(os.path.join(ref, "utils", "**", "*.py"), recursive=True)
+    found = set()
+    for path in (f for f in files if os.path.isfile(f)):
+        with open(path) as fh:
+            tree = ast.parse(fh.read(), filename=path)
+        where = os.path.relpath(path, ref)
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.module and node.level == 0 and node.module.split(".")[0] == "lgn":
+                found.update((node.module, a.name, where) for a in node.names)
+            elif isinstance(node, ast.Import):
+                found.update((a.name, None, where) for a in node.names if a.name.split(".")[0] == "lgn")
+    import utils.initialize as init
+    calls = {}
+
+    class Recorder:
+        def __init__(self, cls):
+            self.cls = cls
+
+        def __call__(self, **kw):
+            net = self.cls(**kw)
+            calls[self.cls.__name__] = {"kwargs": {k: (str(v) if isinstance(v, (torch.device, torch.dtype)) else
+                                                       "<encoder.cg_dict>" if k == "cg_dict" else v) for k, v in kw.items()},
+                                        "num_learnable_parameters": net.num_learnable_parameters}
+            return net
+
+    args = dict(num_jet_particles=30, tau_jet_scalars=1, tau_jet_vectors=1, map_to_latent="min&max", tau_latent_scalars=1,
+                tau_latent_vectors=8, maxdim=[2], encoder_num_channels=[3, 3, 4, 4], decoder_num_channels=[4, 4, 3, 3],
+                weight_init="randn", level_gain=[1.0], num_basis_fn=10, activation="leakyrelu", scale=1.0, jet_features=False,
+                mlp=True, mlp_depth=6, mlp_width=6, device=CPU, dtype=F64, optimizer="adam", lr=5e-4)
+    saved = init.LGNEncoder, init.LGNDecoder
+    init.LGNEncoder, init.LGNDecoder = Recorder(LGNEncoder), Recorder(LGNDecoder)
+    try:
+        enc, dec = init.initialize_autoencoder(argparse.Namespace(**args), print_models=False)
+    finally:
+        init.LGNEncoder, init.LGNDecoder = saved
+    assert enc.cg_dict is dec.cg_dict
+    out = {"imports": sorted(([m, n, w] for m, n, w in found), key=str),
+           "initialize_autoencoder": {"args": {k: (str(v) if isinstance(v, (torch.device, torch.dtype)) else v) for k, v in args.items()},
+                                      "calls": calls, "shared_cg_dict": True}}
+    with open(os.path.join(OUT, "g16_dropin.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("g16_dropin.json", len(out["imports"]), "imports")
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     only = set(sys.argv[1:])
@@ -369,5 +424,7 @@ if __name__ == "__main__":
         e2e("g14_e2e_mlpwidth5_maxdim3.npz", 2, 10, 3, (2, 4, 6), (6, 4, 2), seed=15, pad_rows=((1, 6),), mlp_width=5)
     if want("g12"):       # 150 particles at maxdim 3 (the product of two BASELINE axes; the jet's packed features exceed a CU's LDS)
         e2e("g12_e2e_n150_maxdim3.npz", 1, 150, 3, (4, 4, 6, 6), (6, 6, 4, 4), seed=9, pad_rows=((0, 137),))
+    if want("g16"):
+        dropin()
     if want("g10"):
         e2e("g10_e2e_jetfeat.npz", 3, 12, 2, (2, 2, 3, 3), (3, 3, 2, 2), seed=6, pad_rows=((2, 9),), jet_features=True, extra_scalars=1)
