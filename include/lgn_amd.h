@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define LGN_AMD_ABI_VERSION 17   /* bump on ANY struct or signature change (lgn/_native.py: ABI_VERSION) */
+#define LGN_AMD_ABI_VERSION 18   /* bump on ANY struct or signature change (lgn/_native.py: ABI_VERSION) */
 
 int lgn_abi_version(void);
 const char* lgn_last_error(void);
@@ -197,7 +197,8 @@ int lgn_local_fwd_static_f64(int kind, int nodes, int C, int CO, const double* X
                              const int* w0, double* wpacked, double* outT, double* s_copy, int q_s, void* stream);
 
 /* ---- whole training step (utils/train.py:283-343 inner loop); fused maxdim = 2 or table-driven networks -------
- * One call enqueues encoder -> decoder -> get_real('sum') -> Chamfer -> full backward (~80 launches, no host
+ * One call enqueues encoder -> decoder -> get_real(., d->get_real) -> Chamfer [+ jet-feature MSE, d->jet_loss_scale]
+ * -> full backward (~80 launches, no host
  * sync, all buffers caller-owned and static => capturable in a HIP graph).  Parameters of both networks
  * live in ONE flat buffer `params`; gradients are written into `grads` at the same offsets (the call zero-
  * fills `grads` first; parameters that cannot receive gradient keep an exact 0).
@@ -242,8 +243,18 @@ typedef struct lgn_net_desc {
   int dec_N;               /* whole-step call only: particles the decoder reconstructs when that differs from the encoder's node count N
                               (jet_features: the encoder works on N = particles + 1 nodes, lgn_encoder.py:372-411); 0 = N.  With
                               dec_N != N or n_in_scalars > 1 the step runs its four end stages as launches of their own (maxdim = 2
-                              networks; table-driven networks refuse) */
+                              networks; table-driven networks refuse).  Checked at plan time: >= 0, and the decoder's end stages
+                              at dec_N particles fit LGN_LDS_LIMIT */
+  /* Loss options of the whole-step call (ABI 18; a zero-initialised descriptor is the 'sum' / no-jet-term step of ABI 17): */
+  int get_real;            /* LGN_REAL_*: how the real reconstruction x is taken from the two planes (utils/utils.py:194-207) */
+  double jet_loss_scale;   /* >= 0; adds jet_loss_scale * sum_mu (sum_i x_i - sum_j t_j)_mu^2 per jet, sums over all N rows, padding
+                              included (--chamfer-jet-features: nn.MSELoss over (B, 4) is 1 / (4 B) with B the global batch); 0 = off */
 } lgn_net_desc;
+#define LGN_REAL_SUM 0        /* re + im */
+#define LGN_REAL_REAL 1       /* re (the reference's default --get-real-method) */
+#define LGN_REAL_IMAG 2       /* im */
+#define LGN_REAL_MEAN 3       /* (re + im) / 2 */
+#define LGN_REAL_NORM 4       /* sqrt(re^2 + im^2 + 1e-16) */
 /* latent pooling code: n = 1..4 poolings o0..o3 (LGN_POOL_MIN / MAX / MEAN), avg = 0: concatenated ('a&b'), 1: averaged ('a+b').
  * min / max pick ONE particle per (plane, channel) -- by the value itself (min) / its square (max) for scalars, by the Minkowski
  * square of the Cartesian vector for vectors (get_min_features / get_max_features, lgn_encoder.py:538-583); mean = torch.mean over

@@ -68,11 +68,13 @@ struct LevelArgs {
   T* z2 = nullptr;
   size_t z2n = 0;
   // Decoder, last level of a whole-step call (loss_wo1 != nullptr; separable form, N <= 40: level_fwd_carries_loss): the decoder
-  // output + get_real('sum') + Chamfer loss of the jet, forward and backward (net_dev.hpp: dec_output_loss_body), run as the tail
+  // output + get_real + Chamfer loss (+ jet-feature term) of the jet, forward and backward (net_dev.hpp: dec_output_loss_body), run as the tail
   // of this kernel on the v_out it has just written.
   const T* loss_wo1 = nullptr;     // mix_to_output weights of (1,1): [2][CO]
   const T* loss_target = nullptr;  // [B][N][4]
   T loss_scale = T(1);
+  int loss_real = 0;               // get_real method (LGN_REAL_* of include/lgn_amd.h)
+  T loss_jscale = T(0);            // weight of the jet-feature term (0: off)
   T* loss_recon = nullptr;         // [2][B][N][4]
   T* loss_part = nullptr;          // [B]
   T* loss_gv = nullptr;            // [2][B][N][CO][4] gradient w.r.t. v_out

@@ -557,8 +557,8 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   if constexpr (DEC) {
     if (a.loss_wo1) {      // (one workgroup of BLOCK threads per jet: checked on the host)
       __syncthreads();     // this jet's v_out is complete and visible to the workgroup; the level's LDS is free
-      dec_output_loss_body(B, N, CO, a.v_out, a.loss_wo1, a.loss_target, a.loss_scale, a.loss_recon, a.loss_part, a.loss_gv,
-                           a.loss_wpart, smem_raw);
+      dec_output_loss_body(B, N, CO, a.v_out, a.loss_wo1, a.loss_target, a.loss_scale, a.loss_real, a.loss_jscale, a.loss_recon,
+                           a.loss_part, a.loss_gv, a.loss_wpart, smem_raw);
     }
   }
 }

@@ -45,8 +45,9 @@ int dec_input_fwd(int B, int N, int C, int Tin, const double* lat_v, const doubl
 int dec_input_bwd(int B, int N, int C, int Tin, const double* lat_v, const double* wg1, const double* w1, const double* pdec,
                   const double* g_p, const double* g_s0, const double* g_v0, double* g_lat_v,
                   double* part /*[B][4C + 2 N Tin]*/, hipStream_t);
-int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, double* recon,
-                    double* loss_part /*[B]*/, double* g_v, double* part /*[B][2C]*/, hipStream_t);
+// method: get_real code (LGN_REAL_* of include/lgn_amd.h); jscale: weight of the jet-feature term (0: off)
+int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, int method,
+                    double jscale, double* recon, double* loss_part /*[B]*/, double* g_v, double* part /*[B][2C]*/, hipStream_t);
 // Chamfer loss per jet and its gradients (module API: lgn/losses.py); loss_part [B], gx [B][N][4], gy [B][M][4]
 int chamfer_fwd(int B, int N, int M, const double* x, const double* y, int jet_features, double* loss_part, double* gx, double* gy,
                 hipStream_t);

@@ -50,21 +50,42 @@ __device__ __forceinline__ cx<double> cart_from_canon_m(const double* c, int m) 
   return {-(c[5] + c[7]) * NET_RSQRT2, (c[1] + c[3]) * NET_RSQRT2};
 }
 
+// Jet momenta of two padded particle sets, as the reference's jet-feature MSE sums them (x.sum(-2), y.sum(-2): every row,
+// padding included, no mask): js[m] = sum_i x[i][m] (threads 0..3), js[4 + m] = sum_j y[j][m] (threads 4..7), in particle
+// order.  The caller synchronises before reading js.
+__device__ __forceinline__ void jet_sums(const double* x, int N, const double* y, int M, double* js) {
+  const int tid = threadIdx.x;
+  if (tid < 8) {
+    const int m = tid & 3;
+    double s = 0.0;
+    if (tid < 4) for (int i = 0; i < N; ++i) s += x[i * 4 + m];
+    else for (int j = 0; j < M; ++j) s += y[j * 4 + m];
+    js[tid] = s;
+  }
+}
+
+// get_real methods of the whole step (utils/utils.py:194-207; LGN_REAL_* of include/lgn_amd.h)
+enum : int { REAL_SUM = 0, REAL_RE = 1, REAL_IM = 2, REAL_MEAN = 3, REAL_NORM = 4 };
+constexpr double GET_REAL_NORM_EPS = 1e-16;
+
 // ============================================================================================
-// decoder output + get_real('sum') + Chamfer loss, forward and backward in one pass per jet
+// decoder output + get_real(., method) + Chamfer loss [+ jscale * sum_mu (sum_i x_i - sum_j t_j)_mu^2: the jet-feature term],
+// forward and backward in one pass per jet.  method and jscale are uniform: the branches on them cost the 'sum' path a few
+// scalar instructions
 //   recon [2][B][N][4]; loss_part [B]; g_v [2][B][N][C][4]; part row per jet: dWo1 [2][C]
 // LDS: x [N][4] | tg [N][4] | rmin [N] | cmin [N] | gx [N][4] | ycl [N][8] | vl [N*C][8] | tmp [N*C][2] | wol [2C] | rarg, carg [N] ints
+//      | js [8] (jet momenta of x and the target)
 // ============================================================================================
 __host__ __device__ inline size_t dec_out_loss_bytes(int N, int C) {
-  return sizeof(double) * ((size_t)N * 22 + (size_t)N * C * 10 + 2 * (size_t)C) + sizeof(int) * 2 * (size_t)N;
+  return sizeof(double) * ((size_t)N * 22 + (size_t)N * C * 10 + 2 * (size_t)C + 8) + sizeof(int) * 2 * (size_t)N;
 }
 // One workgroup of BLOCK threads per jet; lds = dec_out_loss_bytes(N, C) bytes of (dynamic) LDS.  A kernel of its own
 // (dec_output_loss_kernel), or the tail of the decoder's last level forward (level_fwd2.hip: LevelArgs::loss_wo1).
 __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const double* __restrict__ v,
                                                      const double* __restrict__ wo1, const double* __restrict__ target,
-                                                     double loss_scale, double* recon, double* loss_part, double* g_v,
-                                                     double* part, unsigned char* smem_raw) {
-  double* x = reinterpret_cast<double*>(smem_raw);       // [N][4] real reconstruction (re + im)
+                                                     double loss_scale, int method, double jscale, double* recon,
+                                                     double* loss_part, double* g_v, double* part, unsigned char* smem_raw) {
+  double* x = reinterpret_cast<double*>(smem_raw);       // [N][4] real reconstruction get_real(re, im)
   double* tg = x + N * 4;                                // [N][4] target
   double* rmin = tg + N * 4;                             // [N]
   double* cmin = rmin + N;                               // [N]
@@ -75,6 +96,7 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
   double* wol = tmp + N * C * 2;                         // [2C]
   int* rarg = reinterpret_cast<int*>(wol + 2 * C);       // [N]
   int* carg = rarg + N;                                  // [N]
+  double* js = reinterpret_cast<double*>(carg + N);      // [8] jet momenta of x (0..3) and of the target (4..7)
   __shared__ double red[4];
   const int b = blockIdx.x;
   const size_t plp = (size_t)B * N * 4, pl = (size_t)B * N * C, j4 = (size_t)b * N * 4, jc = (size_t)b * N * C;
@@ -102,9 +124,16 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
     const cx<double> pc = cart_from_canon_m(ycl + (e >> 2) * 8, e & 3);
     recon[j4 + e] = pc.r;
     recon[plp + j4 + e] = pc.i;
-    x[e] = pc.r + pc.i;                                  // get_real(., 'sum')
+    double xe;                                           // get_real(., method)
+    if (method == REAL_SUM) xe = pc.r + pc.i;
+    else if (method == REAL_RE) xe = pc.r;
+    else if (method == REAL_IM) xe = pc.i;
+    else if (method == REAL_MEAN) xe = (pc.r + pc.i) / 2;
+    else xe = sqrt(pc.r * pc.r + pc.i * pc.i + GET_REAL_NORM_EPS);
+    x[e] = xe;
   }
   __syncthreads();
+  if (jscale != 0.0) jet_sums(x, N, tg, N, js);          // (read after the block sum below: it synchronises)
   // squared Euclidean distances d(i,j) = |t_j - x_i|^2; row minima (over j) and column minima (over i), first occurrence:
   // four lanes per row / column scan a quarter of the range each, then meet on (distance, index)
   const int nq = (N + 3) / 4;
@@ -135,7 +164,11 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
   double lsum = 0;
   for (int n = threadIdx.x; n < N; n += BLOCK) lsum += (rmin[n] + cmin[n]) * 0.5;
   lsum = block_sum(lsum, red);
-  if (threadIdx.x == 0) loss_part[b] = lsum;
+  if (threadIdx.x == 0) {
+    if (jscale != 0.0)
+      for (int m = 0; m < 4; ++m) { const double dj = js[m] - js[4 + m]; lsum += dj * dj * jscale; }
+    loss_part[b] = lsum;
+  }
   // d loss / d x_i = (x_i - t_{j*(i)}) + sum_{j : i*(j) = i} (x_i - t_j)      (two lanes per (i, component): a half of the j range each)
   const int nh = (N + 1) / 2;
   for (int e = threadIdx.x; e < N * 8; e += BLOCK) {
@@ -145,15 +178,28 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
 #pragma unroll 5
     for (int j = h * nh; j < min(N, (h + 1) * nh); ++j) g += carg[j] == i ? xi - tg[j * 4 + m] : 0.0;
     g += __shfl_xor(g, 1, 2);
+    if (jscale != 0.0) g += h ? 0.0 : 2.0 * jscale * (js[m] - js[4 + m]);
     if (h == 0) gx[im] = g * loss_scale;
   }
   __syncthreads();
-  // back through get_real (both planes receive g), rep_to_p and mix_to_output; dWo1[c] = sum_n sum_m G_yc[n][m] conj(v[n][c][m])
+  // back through get_real (the planes' gradients: gx, 0 / 0, gx / gx, gx / gx/2, gx/2 / gx re/x, gx im/x), rep_to_p and
+  // mix_to_output; dWo1[c] = sum_n sum_m G_yc[n][m] conj(v[n][c][m])
   for (int e = threadIdx.x; e < N * C; e += BLOCK) {
     const int n = e / C, c = e - n * C;
     cx<double> g[4], gc[4], d = {0, 0};
 #pragma unroll
-    for (int m = 0; m < 4; ++m) g[m] = {gx[n * 4 + m], gx[n * 4 + m]};
+    for (int m = 0; m < 4; ++m) {
+      const double q = gx[n * 4 + m];
+      if (method == REAL_SUM) g[m] = {q, q};
+      else if (method == REAL_RE) g[m] = {q, 0.0};
+      else if (method == REAL_IM) g[m] = {0.0, q};
+      else if (method == REAL_MEAN) g[m] = {q / 2, q / 2};
+      else {                                             // re / im again from the canonical output, still in LDS
+        const cx<double> pc = cart_from_canon_m(ycl + n * 8, m);
+        const double r = q / x[n * 4 + m];
+        g[m] = {r * pc.r, r * pc.i};
+      }
+    }
     cart_from_canon_bwd(g, gc);
     const cx<double> w = {wol[c], wol[C + c]};
     const size_t base = jc + e;

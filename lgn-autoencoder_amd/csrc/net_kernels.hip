@@ -2,7 +2,7 @@
 //   encoder input   (lgn_encoder.py:284-298,376)   mass + canonical momenta + input_func_node MixReps
 //   encoder latent  (lgn_encoder.py:322-331,419-583) mix_reps MixReps + rep_to_p + 'min&max' pooling
 //   decoder input   (lgn_decoder.py:305-345,257-265) latent_to_graph + p_cplx_to_rep + input_func_node
-//   decoder output  (lgn_decoder.py:286-295) + get_real('sum') (utils/utils.py:194-207)
+//   decoder output  (lgn_decoder.py:286-295) + get_real(., method) (utils/utils.py:194-207)
 //                   + ChamferLoss (utils/losses/chamfer_loss/chamfer_loss.py:17-23) forward AND backward
 //   L1 + Adam       (utils/train.py:484-487, utils/initialize.py:156-158)
 // Each forward/backward pair is one workgroup per jet; weight-gradient partials are one row per jet.
@@ -900,16 +900,16 @@ __global__ __launch_bounds__(BLOCK) void junction_bwd_kernel(int B, int N, int C
 }
 
 // ============================================================================================
-// decoder output + get_real('sum') + Chamfer loss, forward and backward in one pass per jet
+// decoder output + get_real(., method) + Chamfer loss [+ jet-feature term], forward and backward in one pass per jet
 //   recon [2][B][N][4]; loss_part [B]; g_v [2][B][N][C][4]; part row per jet: dWo1 [2][C]
 // LDS: x [N][4] | tg [N][4] | rmin [N] | cmin [N] | gx [N][4] | ycl [N][8] | vl [N*C][8] | tmp [N*C][2] | wol [2C] | rarg, carg [N] ints
 // ============================================================================================
 __global__ __launch_bounds__(BLOCK) void dec_output_loss_kernel(int B, int N, int C, const double* __restrict__ v,
                                                                const double* __restrict__ wo1, const double* __restrict__ target,
-                                                               double loss_scale, double* recon, double* loss_part, double* g_v,
-                                                               double* part) {
+                                                               double loss_scale, int method, double jscale, double* recon,
+                                                               double* loss_part, double* g_v, double* part) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  dec_output_loss_body(B, N, C, v, wo1, target, loss_scale, recon, loss_part, g_v, part, smem_raw);
+  dec_output_loss_body(B, N, C, v, wo1, target, loss_scale, method, jscale, recon, loss_part, g_v, part, smem_raw);
 }
 
 // ============================================================================================
@@ -975,13 +975,7 @@ __global__ __launch_bounds__(BLOCK) void chamfer_kernel(int B, int N, int M, con
     }
     mine += 0.5 * best;
   }
-  if (jet_features && tid < 8) {                         // jet sums of x (tid 0..3) and y (4..7), component tid & 3
-    const int m = tid & 3;
-    double s = 0.0;
-    if (tid < 4) for (int i = 0; i < N; ++i) s += xl[i * 4 + m];
-    else for (int j = 0; j < M; ++j) s += yl[j * 4 + m];
-    red[BLOCK / 64 + tid] = s;
-  }
+  if (jet_features) jet_sums(xl, N, yl, M, red + BLOCK / 64);
   mine = group_sum<64>(mine);
   if ((tid & 63) == 0) red[tid >> 6] = mine;
   __syncthreads();
@@ -1220,12 +1214,12 @@ int dec_input_bwd(int B, int N, int C, int Tin, const double* lat_v, const doubl
   LGN_CHECK_LAUNCH();
   return 0;
 }
-int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, double* recon,
-                    double* loss_part, double* g_v, double* part, hipStream_t st) {
+int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, int method,
+                    double jscale, double* recon, double* loss_part, double* g_v, double* part, hipStream_t st) {
   const size_t smem = dec_out_loss_bytes(N, C);
   LGN_LDS_LAUNCH(dec_output_loss_kernel, "dec_output_loss", smem);
-  hipLaunchKernelGGL(dec_output_loss_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, loss_scale, recon, loss_part,
-                     g_v, part);
+  hipLaunchKernelGGL(dec_output_loss_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, loss_scale, method, jscale, recon,
+                     loss_part, g_v, part);
   LGN_CHECK_LAUNCH();
   return 0;
 }

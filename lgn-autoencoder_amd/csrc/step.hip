@@ -1,7 +1,7 @@
 // lgn-autoencoder_amd/csrc/step.hip -- one training step of the LGN autoencoder as a single native call.
 //
 // Counterpart of the inner loop of the reference's utils/train.py:283-343 (encoder -> decoder ->
-// get_real('sum') -> Chamfer -> backward) for the maxdim=2 path: ~80 kernel launches enqueued back to back
+// get_real -> Chamfer [+ jet-feature MSE] -> backward) for the maxdim=2 path: ~80 kernel launches enqueued back to back
 // on the caller's stream, no host synchronisation, every buffer caller-owned and static -> the call can be
 // captured into a HIP graph (the Python harness does so) and replayed.  Parameter gradients are written
 // straight into the caller's flat gradient buffer at the same offsets as the parameters.
@@ -215,6 +215,8 @@ struct InputStage {
 struct LossStage {
   const double *wo1, *target;
   double scale;
+  int method;      // get_real code
+  double jscale;   // jet-feature term weight (0: off)
   double *recon, *loss_part, *g_v, *wpart;
 };
 
@@ -233,7 +235,8 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       a.z1 = in0->z1; a.z1n = in0->z1n; a.z2 = in0->z2; a.z2n = in0->z2n;
     }
     if (l + 1 == d.n_levels && dec && loss) {
-      a.loss_wo1 = loss->wo1; a.loss_target = loss->target; a.loss_scale = loss->scale; a.loss_recon = loss->recon;
+      a.loss_wo1 = loss->wo1; a.loss_target = loss->target; a.loss_scale = loss->scale; a.loss_real = loss->method;
+      a.loss_jscale = loss->jscale; a.loss_recon = loss->recon;
       a.loss_part = loss->loss_part; a.loss_gv = loss->g_v; a.loss_wpart = loss->wpart;
     }
     a.flags = d.flags;
@@ -327,6 +330,14 @@ int check_desc(const lgn_net_desc* d) {
   for (int l = 0; l <= d->n_levels; ++l)
     LGN_CHECK_ARG(d->enc_channels[l] >= 1 && d->enc_channels[l] <= 8 && d->dec_channels[l] >= 1 && d->dec_channels[l] <= 8,
                   "step: channel counts must be in 1..8");
+  LGN_CHECK_ARG(d->get_real >= LGN_REAL_SUM && d->get_real <= LGN_REAL_NORM, "step: get_real=%d is not an LGN_REAL_* code", d->get_real);
+  LGN_CHECK_ARG(d->jet_loss_scale >= 0.0, "step: jet_loss_scale=%g must be >= 0", d->jet_loss_scale);
+  LGN_CHECK_ARG(d->dec_N >= 0, "step: dec_N=%d must be >= 0", d->dec_N);
+  if (d->dec_N > 0) {        // the whole step's decoder end stages are one workgroup per jet of dec_N particles
+    const int Tin = d->tau_v_in ? d->tau_v_in : pool_blocks(d->latent_pool) * d->tau_v;
+    const size_t need = decoder_end_lds_bytes(d->dec_N, d->dec_channels[0], Tin, d->dec_channels[d->n_levels]);
+    LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: dec_N=%d: the decoder end stages need %zu B of LDS (> %d)", d->dec_N, need, LGN_LDS_LIMIT);
+  }
   return 0;
 }
 
@@ -855,7 +866,8 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   RadFinJob fin{};
   {
     DQ_NEW(part, (size_t)B * 2 * CL);
-    LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, recon, loss_part, g.ds.gv, part, st));
+    LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part,
+                                    g.ds.gv, part, st));
     dq.add(part, B, 2 * CL, 0, 2 * CL, grads + dec_off[S.out0(true) + 1]);
   }
   std::vector<UnpackJob> post;
@@ -1235,10 +1247,11 @@ static int step_fwd_bwd_split(const lgn_net_desc& d, Work& w, const double* para
   int cur = 0;
   {
     DQ_NEW(part, (size_t)B * 2 * cd[L]);
-    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, recon, loss_part, w.gv[cur], part};
+    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, w.gv[cur], part};
     const bool rides = level_fwd_carries_loss(Nd, d.flags);
     LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr));
-    if (!rides) LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, recon, loss_part, w.gv[cur], part, st));
+    if (!rides)
+      LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
     dq.add(part, B, 2 * cd[L], 0, 2 * cd[L], grads + dec_off[S.out0(true) + 1]);
   }
   // ---------------- backward ----------------
@@ -1343,11 +1356,11 @@ static int step_fwd_bwd(const lgn_net_desc* d, const double* params, double* gra
   int cur = 0;
   {
     DQ_NEW(part, (size_t)B * 2 * cd[L]);
-    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, recon, loss_part, w.gv[cur], part};
+    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d->get_real, d->jet_loss_scale, recon, loss_part, w.gv[cur], part};
     const bool rides = level_fwd_carries_loss(N, d->flags);
     LGN_TRY(levels_fwd(*d, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr));
     if (!rides)
-      LGN_TRY(dec_output_loss(B, N, cd[L], w.dec.v[L], ls.wo1, target, 1.0, recon, loss_part, w.gv[cur], part, st));
+      LGN_TRY(dec_output_loss(B, N, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
     dq.add(part, B, 2 * cd[L], 0, 2 * cd[L], grads + dec_off[S.out0(true) + 1]);
   }
 

@@ -15,7 +15,7 @@ import torch  # imported before the .so so that the process-wide libamdhip64 is 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LGN_AMD_LIB") or os.path.join(_HERE, "_lib", "liblgn_amd.so")   # LGN_AMD_LIB: debug builds (tools/)
-ABI_VERSION = 17
+ABI_VERSION = 18
 FINALIZE_SCRATCH = 2048      # include/lgn_amd.h: LGN_FINALIZE_SCRATCH
 
 _lib: Optional[C.CDLL] = None
@@ -115,7 +115,8 @@ class NetDesc(C.Structure):
                 ("enc_tables", _tp * 4), ("dec_tables", _tp * 4),
                 ("enc_Q", C.c_int * 5), ("enc_qs", C.c_int * 5), ("enc_qv", C.c_int * 5),
                 ("dec_Q", C.c_int * 5), ("dec_qs", C.c_int * 5), ("dec_qv", C.c_int * 5), ("flags", C.c_int),
-                ("activation", C.c_int), ("n_in_scalars", C.c_int), ("latent_pool", C.c_int), ("dec_N", C.c_int)]
+                ("activation", C.c_int), ("n_in_scalars", C.c_int), ("latent_pool", C.c_int), ("dec_N", C.c_int),
+                ("get_real", C.c_int), ("jet_loss_scale", C.c_double)]
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)

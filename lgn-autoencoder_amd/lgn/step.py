@@ -1,5 +1,5 @@
 """
-Training-step harness for the accelerated path: encoder -> decoder -> get_real('sum') -> Chamfer
+Training-step harness for the accelerated path: encoder -> decoder -> get_real(., method) -> Chamfer [+ jet-feature MSE]
 + l1_lambda * L1 -> backward -> (gradient all-reduce) -> Adam, i.e. the inner loop of the reference's
 utils/train.py:280-343 with utils/initialize.py:153-173's optimisers, restated for one process per GPU.
 
@@ -174,6 +174,15 @@ class ReferenceLoopStep:
 from .ops import slot_tensors as _slot_tensors  # noqa: E402  (parameter slots of include/lgn_amd.h)
 
 
+def _capturing(graph, pool=None):
+    """torch.cuda.graph in the capture mode of every step graph here: thread_local.  Under the default 'global' mode a HIP call
+    that another thread makes during the capture is an error in that thread -- and with a process group alive, its watchdog thread
+    polls the events of finished collectives (the warm-up's eager all-reduce, any_rank's flag) at any moment: a poll that lands
+    inside the capture window makes the watchdog throw and abort the process.  thread_local still refuses unsafe calls made by the
+    capturing thread itself."""
+    return torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local")
+
+
 def any_rank(flag: bool, group, device) -> bool:
     """True on EVERY rank iff `flag` is true on ANY rank: one eager all-reduce(MAX) of a one-element tensor."""
     t = torch.tensor([1.0 if flag else 0.0], device=device, dtype=torch.float64)
@@ -216,15 +225,38 @@ def agree_in_graph(try_capture, replay_matches, reset, group, device, strict: bo
     return True
 
 
+# LGN_REAL_* of include/lgn_amd.h
+GET_REAL_CODES = {"sum": 0, "real": 1, "imag": 2, "mean": 3, "norm": 4}
+
+
+def get_real_code(method: str) -> int:
+    """The LGN_REAL_* code of a get_real method name; like utils/utils.py:194-207, case-insensitive, and an unknown name logs a
+    warning and means 'real'."""
+    code = GET_REAL_CODES.get(str(method).lower())
+    if code is None:
+        import logging
+        logging.warning(f"Invalid method of get_real: {method}. Using 'real' instead.")
+        code = GET_REAL_CODES["real"]
+    return code
+
+
 class NativeTrainStep:
     """Same step as TrainStep, executed by lgn_step_fwd_bwd_f64 / lgn_step_finalize_f64 (csrc/step.hip):
     no autograd graph, no PyTorch kernels, every buffer static.  With ``use_graph=True`` the two native calls
     are captured once into HIP graphs (torch.cuda.CUDAGraph around the ctypes calls -- the kernels are
-    enqueued on the capturing stream) and replayed; the gradient all-reduce sits between the two graphs."""
+    enqueued on the capturing stream) and replayed; the gradient all-reduce sits between the two graphs.
+
+    The loss options of the reference's main.py run inside the step's last kernel (lgn_net_desc.get_real / jet_loss_scale,
+    ABI 18): ``get_real_method`` ('real', 'imag', 'sum', 'mean', 'norm', any case; an unknown name warns and takes 'real', as
+    utils/utils.py:194-207) and ``chamfer_jet_features`` (--chamfer-jet-features: + nn.MSELoss() of the jets' summed momenta,
+    utils/losses/chamfer_loss/chamfer_loss.py:25-29).  The MSE is a mean over (global batch, 4): with data parallelism each rank
+    weighs its jets by 1 / (4 batch_size world), so the SUM all-reduce gives the step of one process on the whole batch.  The
+    defaults ('sum', no jet term) are the step of ABI 17."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, optimizer: bool = True, use_graph: bool = True,
-                 force_collective: bool = False, graph_collective: Optional[bool] = None):
+                 force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
+                 chamfer_jet_features: bool = False):
         import ctypes as C
         from . import _native as N
         self.N = N
@@ -285,6 +317,9 @@ class NativeTrainStep:
         d.activation = N.activation_id(encoder.activation)
         fused = native_kind(encoder) == "fused"
         d.dec_N = decoder.num_output_particles if self.split else 0
+        self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
+        d.get_real = get_real_code(get_real_method)
+        d.jet_loss_scale = 1.0 / (4.0 * batch_size * self.world) if self.chamfer_jet_features else 0.0
         if decoder.tau_latent_vectors != N.pool_blocks(d.latent_pool) * d.tau_v or \
                 decoder.num_output_particles != encoder.num_input_particles - int(bool(getattr(encoder, "jet_features", False))):
             raise ValueError(f"decoder latent size / particle count does not match the encoder (map_to_latent={encoder.map_to_latent!r} "
@@ -388,7 +423,7 @@ class NativeTrainStep:
             # collective does not reproduce the eager step -- on ANY rank -- every rank uses the three-launch form below
             # (agree_in_graph: the ranks exchange both outcomes, none decides from what it saw locally)
             def try_capture():
-                with torch.cuda.graph(self._g1):
+                with _capturing(self._g1):
                     self._fwd_bwd()
                     dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
                     self._finalize(self.optimizer)
@@ -401,12 +436,12 @@ class NativeTrainStep:
                                             self.flat.flat.device, strict=self.graph_collective is True)
         if self.collective and not self._in_graph:      # the gradient all-reduce sits between two graphs
             self._g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g1):
+            with _capturing(self._g1):
                 self._fwd_bwd()
-            with torch.cuda.graph(self._g2, pool=self._g1.pool()):
+            with _capturing(self._g2, pool=self._g1.pool()):
                 self._finalize(self.optimizer)
         elif not self.collective:     # single process: the whole step is ONE graph launch
-            with torch.cuda.graph(self._g1):
+            with _capturing(self._g1):
                 self._train(self.optimizer)
         self.launches_per_step = 3 if self._g2 is not None else 1
         with torch.no_grad():   # capture does not execute, but restore anyway in case a backend replays eagerly
@@ -477,7 +512,7 @@ class NativeTrainStep:
 
 class CapturedModuleStep:
     """The training step for every configuration the MODULES run but lgn_step_fwd_bwd_f64 refuses -- ``jet_features`` / extra
-    input scalars (the encoder has one node more than the decoder), ``--chamfer-jet-features``, mixed maxdim-2 / maxdim-3 networks,
+    input scalars of maxdim-3 networks, mixed maxdim-2 / maxdim-3 networks,
     ``map_to_latent='sum'``, levels without CGMLP: ``encoder(batch) -> decoder(latent) -> lgn.losses.ChamferLoss -> backward()``
     under autograd (one native call per network and direction where the configuration allows it, per operator otherwise), then
     lgn_step_finalize_f64 (L1 sub-gradient, loss assembly, Adam) -- all of it, input preparation included, captured ONCE into a
@@ -543,12 +578,12 @@ class CapturedModuleStep:
         self._g1 = torch.cuda.CUDAGraph()
         if self.world > 1:
             self._g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g1):
+            with _capturing(self._g1):
                 self._fwd_bwd()
-            with torch.cuda.graph(self._g2, pool=self._g1.pool()):
+            with _capturing(self._g2, pool=self._g1.pool()):
                 self._finalize(self.optimizer)
         else:
-            with torch.cuda.graph(self._g1):
+            with _capturing(self._g1):
                 self._fwd_bwd()
                 self._finalize(self.optimizer)
         self.launches_per_step = 3 if self._g2 is not None else 1
@@ -608,12 +643,10 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
         return {k: v for k, v in kw.items() if k in takes[cls]}
 
     # (extra_scalars: sizes CapturedModuleStep's buffers; NativeTrainStep reads the count off the encoder -- it does not force the module route)
-    needs_modules = bool(kw.get("chamfer_jet_features") or kw.get("get_real_method", "sum") != "sum")
-    if not needs_modules:
-        try:
-            return NativeTrainStep(encoder, decoder, batch_size, **only(NativeTrainStep))
-        except NotImplementedError:
-            pass
+    try:
+        return NativeTrainStep(encoder, decoder, batch_size, **only(NativeTrainStep))
+    except NotImplementedError:
+        pass
     dropped = sorted(k for k in kw if k not in takes[CapturedModuleStep])
     if dropped:
         warnings.warn(f"native_train_step: this configuration runs as CapturedModuleStep, which does not take {dropped}; ignored")
