@@ -341,6 +341,21 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
                        double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
                        int do_adam, double* loss_out, void* stream);
 
+/* ---- evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
+ * get_real(., d->get_real) -> Chamfer [+ d->jet_loss_scale * jet-feature term], forward only and without L1 (regularization =
+ * is_train, utils/train.py:308-314).  Takes every descriptor lgn_step_fwd_bwd_f64 takes and the same inputs; nothing is kept for a
+ * backward, so the workspace (lgn_eval_workspace_doubles) is smaller than the training step's.  Only enqueues work (no allocation,
+ * no host sync): capturable into a graph.  Refusals come before the first launch.
+ *   recon_real [B][Nd][4] = get_real(reconstruction): the training step's reconstruction through the same get_real, bit for bit;
+ *   lat_s [2][B][P tau_s], lat_v [2][B][P tau_v][4] (both or neither; NULL: not written) the pooled latent as lgn_encoder_fwd_f64
+ *   writes it; loss_part [B] the per-jet terms (a data-parallel caller reduces them); loss_out[0] = sum of loss_part over the jets
+ *   with at least one unmasked particle (a short last batch is padded with all-masked jets), in a fixed order. */
+long long lgn_eval_workspace_doubles(const lgn_net_desc* d);
+int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                      const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
+                      double* workspace, long long workspace_doubles, double* recon_real, double* lat_s /*nullable*/,
+                      double* lat_v /*nullable*/, double* loss_part, double* loss_out, void* stream);
+
 /* ---- one network at a time, maxdim = 2: what LGNEncoder.forward / LGNDecoder.forward (lgn/models/lgn_encoder.py:255-336,
  * lgn_decoder.py:218-303) and autograd's backward of them become under the module API.  Same parameter-slot layout as
  * above, but `params` / `grads` / `off` refer to ONE network's flat parameter block.  *_fwd writes the activations the

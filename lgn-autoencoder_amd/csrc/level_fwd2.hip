@@ -68,7 +68,9 @@ struct Fwd2 {
 //   A1_i = e0 sum_j v_j            A2_i = R1 (p_i sum_j s_j - sum_j s_j p_j)
 //   A4_i = e0 sum_j s_j            A3_i = R1 (<sum_j v_j, p_i> - sum_j <v_j, p_j>) / 2
 // O(N C) instead of O(N^2 C) work per jet, same values up to summation order.  SEP = false keeps the pair sweep.
-template <int C, bool DEC, bool SEP>
+// TRAIN = false (evaluation step, level_fwd_eval): the aggregate is not stored (nothing runs a backward) and the riding loss tail
+// is its forward-only form; the sweep, its summation order, CatMix and the riding input stage are the same code.
+template <int C, bool DEC, bool SEP, bool TRAIN>
 __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double> a, int chunk) {
   using F = Fwd2<C, DEC>;
   constexpr int NG = F::NG;
@@ -530,7 +532,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   STAMP(20);
 
   // ---- aggregate -> global (saved for the backward): ag0 [2][B][N][2C], ag1 [2][B][N][2C][4] -----------------------
-  {
+  if constexpr (TRAIN) {
     const size_t pl0 = (size_t)B * N * 2 * C;
     for (int e = tid; e < (c1 - c0) * 2 * C; e += nthr) {        // e = n * 2C + (blk * C + ch), blk 0: A3, 1: A4
       const int n = e / (2 * C), r = e - n * 2 * C, blk = r / C, ch = r - blk * C;
@@ -557,13 +559,13 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   if constexpr (DEC) {
     if (a.loss_wo1) {      // (one workgroup of BLOCK threads per jet: checked on the host)
       __syncthreads();     // this jet's v_out is complete and visible to the workgroup; the level's LDS is free
-      dec_output_loss_body(B, N, CO, a.v_out, a.loss_wo1, a.loss_target, a.loss_scale, a.loss_real, a.loss_jscale, a.loss_recon,
-                           a.loss_part, a.loss_gv, a.loss_wpart, smem_raw);
+      dec_output_loss_body<TRAIN>(B, N, CO, a.v_out, a.loss_wo1, a.loss_target, a.loss_scale, a.loss_real, a.loss_jscale,
+                                  a.loss_recon, a.loss_part, a.loss_gv, a.loss_wpart, smem_raw);
     }
   }
 }
 
-template <int C, bool DEC, bool SEP>
+template <int C, bool DEC, bool SEP, bool TRAIN>
 static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
   using F = Fwd2<C, DEC>;
   // aggregate rows kept in LDS: the whole jet if that still leaves room for two workgroups per CU (or nothing does),
@@ -582,12 +584,12 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
   }
   size_t smem = fixed + chunk * row;
   if (a.loss_wo1) {
-    LGN_CHECK_ARG(DEC && SEP && a.N <= 40 && !wide && a.loss_target && a.loss_recon && a.loss_part && a.loss_gv && a.loss_wpart,
+    LGN_CHECK_ARG(DEC && SEP && a.N <= 40 && !wide && a.loss_target && a.loss_recon && a.loss_part && (!TRAIN || (a.loss_gv && a.loss_wpart)),
                   "level_fwd: the loss rides on the separable decoder forward of jets of <= 40 particles only");
     if (smem < dec_out_loss_bytes(a.N, a.CO)) smem = dec_out_loss_bytes(a.N, a.CO);
   }
   LGN_CHECK_ARG(smem <= 160 * 1024, "level_fwd: N=%d C=%d needs %zu B of LDS (> 160 KiB)", a.N, a.C, smem);
-  auto kern = level_fwd2_kernel<C, DEC, SEP>;
+  auto kern = level_fwd2_kernel<C, DEC, SEP, TRAIN>;
   if (smem > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
@@ -603,16 +605,16 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
 
 bool level_fwd_carries_loss(int N, int flags) { return N <= 40 && !(flags & LVL_DEC_PAIRWISE); }
 
-template <>
-int level_fwd_dispatch<double>(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
+template <bool TRAIN>
+static int level_fwd_run(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
   LGN_CHECK_ARG(a.B > 0 && a.N > 0, "level_fwd: empty batch (B=%d N=%d)", a.B, a.N);
   LGN_CHECK_ARG(!a.in_w0 || (!decoder && a.in_w1 && a.in_s && a.in_v), "level_fwd: the input stage rides on encoder levels only");
   LGN_CHECK_ARG(a.CO >= 1 && a.CO <= 8, "level_fwd: C_out=%d unsupported (1..8)", a.CO);
   const bool pairwise = (a.flags & LVL_DEC_PAIRWISE) != 0;   // the decoder on the O(N^2) pair sweep (cross-check of the separable form)
 #define LGN_CASE(CC)                                                                                         \
   case CC:                                                                                                   \
-    if (!decoder) return launch_level_fwd2<CC, false, false>(a, stream);                                     \
-    return pairwise ? launch_level_fwd2<CC, true, false>(a, stream) : launch_level_fwd2<CC, true, true>(a, stream);
+    if (!decoder) return launch_level_fwd2<CC, false, false, TRAIN>(a, stream);                              \
+    return pairwise ? launch_level_fwd2<CC, true, false, TRAIN>(a, stream) : launch_level_fwd2<CC, true, true, TRAIN>(a, stream);
   switch (a.C) {
 #ifdef LGN_DEV_ONLY_C4      // development builds: one channel count (compile time)
     LGN_CASE(4)
@@ -625,5 +627,13 @@ int level_fwd_dispatch<double>(const LevelArgs<double>& a, int decoder, hipStrea
   }
 #undef LGN_CASE
 }
+
+template <>
+int level_fwd_dispatch<double>(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
+  return level_fwd_run<true>(a, decoder, stream);
+}
+
+// evaluation step: ag0 / ag1 are not read (may be null); a riding loss tail writes get_real(recon) [B][N][4] and loss_part only
+int level_fwd_eval(const LevelArgs<double>& a, int decoder, hipStream_t stream) { return level_fwd_run<false>(a, decoder, stream); }
 
 }  // namespace lgn

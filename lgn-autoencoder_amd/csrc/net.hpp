@@ -48,6 +48,11 @@ int dec_input_bwd(int B, int N, int C, int Tin, const double* lat_v, const doubl
 // method: get_real code (LGN_REAL_* of include/lgn_amd.h); jscale: weight of the jet-feature term (0: off)
 int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, int method,
                     double jscale, double* recon, double* loss_part /*[B]*/, double* g_v, double* part /*[B][2C]*/, hipStream_t);
+// forward-only form (evaluation step): recon_real [B][N][4] = get_real(recon, method), loss_part [B]; no gradient
+int dec_output_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, double jscale,
+                    double* recon_real, double* loss_part, hipStream_t);
+// loss_out[0] = sum of loss_part over the jets with an unmasked particle (mask [B][N]), in a fixed order
+int eval_loss_sum(int B, int N, const uint8_t* mask, const double* loss_part, double* loss_out, hipStream_t);
 // Chamfer loss per jet and its gradients (module API: lgn/losses.py); loss_part [B], gx [B][N][4], gy [B][M][4]
 int chamfer_fwd(int B, int N, int M, const double* x, const double* y, int jet_features, double* loss_part, double* gx, double* gy,
                 hipStream_t);

@@ -81,6 +81,10 @@ __host__ __device__ inline size_t dec_out_loss_bytes(int N, int C) {
 }
 // One workgroup of BLOCK threads per jet; lds = dec_out_loss_bytes(N, C) bytes of (dynamic) LDS.  A kernel of its own
 // (dec_output_loss_kernel), or the tail of the decoder's last level forward (level_fwd2.hip: LevelArgs::loss_wo1).
+// GRAD = false (evaluation step): recon receives get_real(., method) [B][N][4] instead of the two planes, loss_part the per-jet
+// terms, and nothing else is written (g_v, part unused): the forward arithmetic is the same code, so recon and loss_part are the
+// training step's bits.
+template <bool GRAD = true>
 __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const double* __restrict__ v,
                                                      const double* __restrict__ wo1, const double* __restrict__ target,
                                                      double loss_scale, int method, double jscale, double* recon,
@@ -122,8 +126,10 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
   __syncthreads();
   for (int e = threadIdx.x; e < N * 4; e += BLOCK) {
     const cx<double> pc = cart_from_canon_m(ycl + (e >> 2) * 8, e & 3);
-    recon[j4 + e] = pc.r;
-    recon[plp + j4 + e] = pc.i;
+    if (GRAD) {
+      recon[j4 + e] = pc.r;
+      recon[plp + j4 + e] = pc.i;
+    }
     double xe;                                           // get_real(., method)
     if (method == REAL_SUM) xe = pc.r + pc.i;
     else if (method == REAL_RE) xe = pc.r;
@@ -131,6 +137,7 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
     else if (method == REAL_MEAN) xe = (pc.r + pc.i) / 2;
     else xe = sqrt(pc.r * pc.r + pc.i * pc.i + GET_REAL_NORM_EPS);
     x[e] = xe;
+    if (!GRAD) recon[j4 + e] = xe;
   }
   __syncthreads();
   if (jscale != 0.0) jet_sums(x, N, tg, N, js);          // (read after the block sum below: it synchronises)
@@ -169,6 +176,7 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
       for (int m = 0; m < 4; ++m) { const double dj = js[m] - js[4 + m]; lsum += dj * dj * jscale; }
     loss_part[b] = lsum;
   }
+  if constexpr (!GRAD) return;
   // d loss / d x_i = (x_i - t_{j*(i)}) + sum_{j : i*(j) = i} (x_i - t_j)      (two lanes per (i, component): a half of the j range each)
   const int nh = (N + 1) / 2;
   for (int e = threadIdx.x; e < N * 8; e += BLOCK) {

@@ -912,6 +912,30 @@ __global__ __launch_bounds__(BLOCK) void dec_output_loss_kernel(int B, int N, in
   dec_output_loss_body(B, N, C, v, wo1, target, loss_scale, method, jscale, recon, loss_part, g_v, part, smem_raw);
 }
 
+// evaluation step: the forward-only form of the kernel above -- recon_real [B][N][4] = get_real(recon, method), loss_part [B]
+__global__ __launch_bounds__(BLOCK) void dec_output_eval_kernel(int B, int N, int C, const double* __restrict__ v,
+                                                               const double* __restrict__ wo1, const double* __restrict__ target,
+                                                               int method, double jscale, double* recon_real, double* loss_part) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  dec_output_loss_body<false>(B, N, C, v, wo1, target, 1.0, method, jscale, recon_real, loss_part, nullptr, nullptr, smem_raw);
+}
+
+// evaluation loss: sum of the per-jet terms of the jets with at least one unmasked particle (a partial last batch is padded with
+// mask-0 jets), one workgroup, the reduction order of l1_adam_kernel's loss sum -- a full batch gives the training step's Chamfer
+// sum bit for bit, and every replay the same bits
+__global__ __launch_bounds__(BLOCK) void eval_loss_sum_kernel(int B, int N, const uint8_t* __restrict__ mask,
+                                                             const double* __restrict__ loss_part, double* loss_out) {
+  __shared__ double red[4];
+  double l = 0.0;
+  for (int b = threadIdx.x; b < B; b += BLOCK) {
+    bool live = false;
+    for (int n = 0; n < N && !live; ++n) live = mask[(size_t)b * N + n] != 0;
+    if (live) l += loss_part[b];
+  }
+  l = block_sum(l, red);
+  if (threadIdx.x == 0) loss_out[0] = l;
+}
+
 // ============================================================================================
 // decoder output alone (module API: the loss is the caller's): mix_to_output on the (1,1) irrep + rep_to_p
 // (lgn_decoder.py:286-295) and its backward from an arbitrary upstream gradient g_recon [2][B][N][4].
@@ -1220,6 +1244,19 @@ int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, con
   LGN_LDS_LAUNCH(dec_output_loss_kernel, "dec_output_loss", smem);
   hipLaunchKernelGGL(dec_output_loss_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, loss_scale, method, jscale, recon,
                      loss_part, g_v, part);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+int dec_output_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, double jscale,
+                    double* recon_real, double* loss_part, hipStream_t st) {
+  const size_t smem = dec_out_loss_bytes(N, C);
+  LGN_LDS_LAUNCH(dec_output_eval_kernel, "dec_output_eval", smem);
+  hipLaunchKernelGGL(dec_output_eval_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, method, jscale, recon_real, loss_part);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+int eval_loss_sum(int B, int N, const uint8_t* mask, const double* loss_part, double* loss_out, hipStream_t st) {
+  hipLaunchKernelGGL(eval_loss_sum_kernel, dim3(1), dim3(BLOCK), 0, st, B, N, mask, loss_part, loss_out);
   LGN_CHECK_LAUNCH();
   return 0;
 }

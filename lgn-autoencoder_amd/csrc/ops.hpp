@@ -8,6 +8,8 @@ namespace lgn {
 
 // ---- level (level_fwd.hip / level_bwd.hip) ---------------------------------------------------------
 template <typename T> int level_fwd_dispatch(const LevelArgs<T>&, int decoder, hipStream_t);
+// the same level forward without the aggregate stores and with the forward-only loss tail (evaluation step)
+int level_fwd_eval(const LevelArgs<double>&, int decoder, hipStream_t);
 template <typename T> int level_bwd_dispatch(const LevelBwdArgs<T>&, int decoder, hipStream_t);
 template <typename T> int reduce_partials(const T* part, int rows, int n, T* out, int accumulate, hipStream_t);
 template <typename T> int reduce_partials_strided(const T* part, int rows, int stride, int col0, int n, T* out, hipStream_t);

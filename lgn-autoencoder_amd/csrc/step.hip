@@ -221,8 +221,10 @@ struct LossStage {
 };
 
 // forward of one network's level stack; returns via buffers
+// eval (evaluation step): the level kernels without the aggregate stores (level_fwd_eval; n.ag0 / ag1 unused), a riding loss
+// tail in its forward-only form, and no CGMLP after the decoder's last level (its scalars never reach the output)
 int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, const int64_t* off, NetBuf& n, const double* pos,
-               const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr) {
+               const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr, bool eval = false) {
   const Slots S{d.n_levels, d.mlp_nlin};
   for (int l = 0; l < d.n_levels; ++l) {
     auto p = [&](int slot) { return P + off[slot]; };
@@ -240,7 +242,8 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       a.loss_part = loss->loss_part; a.loss_gv = loss->g_v; a.loss_wpart = loss->wpart;
     }
     a.flags = d.flags;
-    LGN_TRY(level_fwd_dispatch<double>(a, dec, st));
+    LGN_TRY(eval ? level_fwd_eval(a, dec, st) : level_fwd_dispatch<double>(a, dec, st));
+    if (eval && dec && l + 1 == d.n_levels) break;
     MlpArgs<double> m{};
     m.M = d.B * d.N; m.C = ch[l + 1]; m.H = d.mlp_hidden_mul * 2 * ch[l + 1]; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
     for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = p(S.mlp(dec, l, 2 * q)); m.b[q] = p(S.mlp(dec, l, 2 * q + 1)); }
@@ -1440,6 +1443,167 @@ int lgn_step_finalize_f64(double* params, double* grads, long long n_params, con
   LGN_TRY(finalize_step(params, grads, (long)n_params, loss_part, n_loss, l1_lambda, adam_m, adam_v, reinterpret_cast<long*>(step_dev),
                         lr, beta1, beta2, eps, do_adam, loss_out, st));
   return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
+// get_real -> Chamfer [+ jet-feature term] forward only, no L1 (regularization = is_train, utils/train.py:308-314).  Nothing is
+// kept for a backward: two feature buffers per network used in turn, level kernels without the aggregate stores, the CGMLPs on
+// their no-save path, no CGMLP after the decoder's last level, a loss tail that writes no gradient.
+// ---------------------------------------------------------------------------------------------------------
+namespace lgn {
+namespace {
+
+struct EvalWork {
+  NetBuf enc, dec;                  // s / v of level l point to feature buffer l & 1 of the network; smix one buffer for all levels
+  double *lat_s, *lat_v, *pdec;
+  int* idx;
+  size_t total;
+};
+
+EvalWork carve_eval(const lgn_net_desc& d, double* base) {
+  EvalWork w{};
+  Bump b{base};
+  const int L = d.n_levels, Nd = dec_nodes(d);
+  const size_t BNe = (size_t)d.B * d.N, BNd = (size_t)d.B * Nd;
+  size_t smix = 0;
+  auto net = [&](NetBuf& n, const int* ch, size_t BN) {
+    int cmax = 0;
+    for (int l = 0; l <= L; ++l) cmax = cmax > ch[l] ? cmax : ch[l];
+    double *s[2], *v[2];
+    for (int q = 0; q < 2; ++q) {
+      s[q] = b.take(2 * BN * cmax);
+      v[q] = b.take(8 * BN * cmax);
+    }
+    for (int l = 0; l <= L; ++l) {
+      n.s[l] = s[l & 1];
+      n.v[l] = v[l & 1];
+    }
+    smix = std::max(smix, 2 * BN * cmax);
+  };
+  net(w.enc, d.enc_channels, BNe);
+  net(w.dec, d.dec_channels, BNd);
+  double* sm = b.take(smix);
+  for (int l = 0; l < L; ++l) w.enc.smix[l] = w.dec.smix[l] = sm;
+  const int PB = pool_blocks(d.latent_pool);
+  w.lat_s = b.take((size_t)2 * d.B * PB * d.tau_s);
+  w.lat_v = b.take((size_t)2 * d.B * PB * d.tau_v * 4);
+  w.pdec = b.take(8 * BNd);
+  w.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (d.tau_s + d.tau_v) * 2 + 1) / 2 + 8));
+  w.total = b.off;
+  return w;
+}
+
+// table-driven networks: the training forward (gen_encoder_fwd / gen_decoder_fwd) on activations of their own -- those kernels
+// store what their backward would read; no-keep forms of them are not part of the evaluation step yet
+struct GenEval {
+  GenAct ea, da;
+  double *lat_s, *lat_v;
+  size_t total;
+};
+GenEval carve_gen_eval(const lgn_net_desc& d, double* base) {
+  GenEval g{};
+  auto at = [&](size_t off) { return base ? base + off : nullptr; };
+  size_t off = 0;
+  g.ea = carve_gen_act(d, false, at(off)); off += (g.ea.total + 15) & ~size_t(15);
+  g.da = carve_gen_act(d, true, at(off)); off += (g.da.total + 15) & ~size_t(15);
+  const int P = pool_blocks(d.latent_pool);
+  g.lat_s = at(off); off += ((size_t)2 * d.B * P * d.tau_s + 15) & ~size_t(15);
+  g.lat_v = at(off); off += ((size_t)2 * d.B * P * d.tau_v * 4 + 15) & ~size_t(15);
+  g.total = off;
+  return g;
+}
+
+long long eval_workspace(const lgn_net_desc& d) {
+  if (is_generic(d, false) || is_generic(d, true)) {
+    if (check_generic(d, false) || check_generic(d, true)) return -1;
+    return (long long)carve_gen_eval(d, nullptr).total;
+  }
+  return (long long)carve_eval(d, nullptr).total;
+}
+
+int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
+              const double* target, const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
+              double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st) {
+  // every refusal comes before the first launch
+  if (int rc = check_desc(dp)) return rc;
+  const lgn_net_desc& d = *dp;
+  LGN_CHECK_ARG(params && enc_off && dec_off && p4 && target && mask && workspace && recon_real && loss_part && loss_out,
+                "step_eval: null pointer");
+  LGN_CHECK_ARG(d.n_in_scalars <= 1 || in_scalars, "step_eval: %d input scalars per node, but in_scalars is NULL", d.n_in_scalars);
+  LGN_CHECK_ARG(!lat_s_out == !lat_v_out, "step_eval: give both latent outputs or neither");
+  const int Tin = pool_blocks(d.latent_pool) * d.tau_v;
+  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step_eval: the decoder must consume the encoder's %d pooled latent vectors", Tin);
+  const long long need = eval_workspace(d);
+  if (need < 0) return -1;
+  LGN_CHECK_ARG(need <= workspace_doubles, "step_eval: workspace holds %lld doubles, this configuration needs %lld", workspace_doubles, need);
+  if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
+  if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dec_nodes(d), Ts = d.tau_s, Tv = d.tau_v;
+  const int* ce = d.enc_channels;
+  const int* cd = d.dec_channels;
+  const double* wl0 = params + enc_off[S.out0(false)];
+  const double* wl1 = params + enc_off[S.out0(false) + 1];
+  const double* wo1 = params + dec_off[S.out0(true) + 1];
+
+  if (is_generic(d, false) || is_generic(d, true)) {
+    LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step_eval: encoder and decoder must both be table-driven (or both fused)");
+    LGN_CHECK_ARG(!step_is_split(d), "step_eval: table-driven networks take the mass as the only input scalar and one node count for "
+                  "both networks (n_in_scalars=%d, N=%d, dec_N=%d)", d.n_in_scalars, d.N, d.dec_N);
+    GenEval g = carve_gen_eval(d, workspace);
+    double* ls = lat_s_out ? lat_s_out : g.lat_s;
+    double* lv = lat_v_out ? lat_v_out : g.lat_v;
+    LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, g.ea, ls, lv, st, nullptr, /*with_latent=*/false));
+    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, g.ea.sL, g.ea.vL, wl0, wl1, ls, lv, g.ea.idx, cd[0], params + dec_off[1],
+                         params + dec_off[2], params + dec_off[3], g.da.pdec, g.da.s0, g.da.v0, st));
+    LGN_TRY(gen_decoder_fwd(d, params, dec_off, lv, g.da, st, /*with_input=*/false));
+    LGN_TRY(dec_output_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+    return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
+  }
+
+  EvalWork w = carve_eval(d, workspace);
+  double* ls = lat_s_out ? lat_s_out : w.lat_s;
+  double* lv = lat_v_out ? lat_v_out : w.lat_v;
+  lgn_net_desc dd = d;
+  dd.N = Nd;
+  const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
+  const bool rides = level_fwd_carries_loss(Nd, d.flags);
+  if (step_is_split(d)) {            // the four end stages as launches of their own (step_fwd_bwd_split)
+    LGN_TRY(enc_input_fwd(B, Ne, ce[0], in_K(d), p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, /*eval=*/true));
+    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, ls, lv, w.idx, st));
+    LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, lv, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
+                          w.dec.v[0], st));
+  } else {                           // input stage riding on the first level, latent + decoder input stage as one junction kernel
+    const InputStage in0{params + enc_off[0], params + enc_off[1]};
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, /*eval=*/true));
+    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, ls, lv, w.idx, cd[0],
+                         params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
+  }
+  LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &loss : nullptr, /*eval=*/true));
+  if (!rides) LGN_TRY(dec_output_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+  return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
+}
+
+}  // namespace
+}  // namespace lgn
+
+extern "C" {
+
+long long lgn_eval_workspace_doubles(const lgn_net_desc* d) {
+  if (check_desc(d)) return -1;
+  return eval_workspace(*d);
+}
+
+int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                      const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
+                      double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
+                      double* loss_part, double* loss_out, void* stream) {
+  return step_eval(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real, lat_s,
+                   lat_v, loss_part, loss_out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -165,9 +165,11 @@ _SIGNATURES.update({
     "lgn_step_finalize_f64": [_vp, _vp, _ll, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp],
     "lgn_step_train_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i,
                            _vp, _vp],
+    "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
 })
 _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_step_workspace_doubles": [_dp],
+    "lgn_eval_workspace_doubles": [_dp],
     "lgn_net_workspace_doubles": [_dp, _i, _i],
     "lgn_moments_scratch_doubles": [_i, _i, _i, _i],
     "lgn_local_static_packed_doubles": [_i, _i, _i],

@@ -172,6 +172,7 @@ class ReferenceLoopStep:
 # ---------------------------------------------------------------------------------------------------
 
 from .ops import slot_tensors as _slot_tensors  # noqa: E402  (parameter slots of include/lgn_amd.h)
+from .ops import describe_network  # noqa: E402
 
 
 def _capturing(graph, pool=None):
@@ -240,6 +241,46 @@ def get_real_code(method: str) -> int:
     return code
 
 
+def _check_native_pair(encoder, decoder) -> bool:
+    """Plan-time refusals (NotImplementedError) shared by NativeTrainStep and NativeEvalStep: the configurations the whole-step
+    calls of csrc/step.hip do not cover.  Returns whether the step is the split form (jet_features / extra input scalars)."""
+    from . import _native as N
+    from .ops import native_kind as _kind
+    if _kind(encoder) is None or _kind(encoder) != _kind(decoder):
+        # lgn_step_fwd_bwd_f64 covers networks whose levels are all the fused maxdim=2 closed form or all table driven
+        # (maxdim=3), with 20 radial basis functions and 7-layer CGMLPs.  Anything else would be read with the wrong
+        # layout -> refuse instead of computing garbage.
+        raise NotImplementedError(
+            "the native step implements maxdim=2 / maxdim=3 networks (the same kind for encoder and decoder) with "
+            "map_to_latent = min / max / mean joined by '&' or '+', CGMLP levels (mlp_depth 3 .. 6), num_basis_fn <= 10 and <= 8 channels; got encoder "
+            f"maxdim={encoder.level_maxdim} map_to_latent={encoder.map_to_latent!r} mlp={encoder.mlp} mlp_depth="
+            f"{encoder.mlp_depth}, decoder maxdim={decoder.level_maxdim} mlp={decoder.mlp}")
+    # jet_features (the encoder works on one node more than the decoder reconstructs) and data['scalars']: the whole-step call
+    # takes them for maxdim = 2 networks (lgn_net_desc.dec_N / n_in_scalars, ABI 17), its four end stages then run as launches
+    # of their own; table-driven networks keep the module route
+    split = getattr(encoder, "tau_input_scalars", 1) != 1 or bool(getattr(encoder, "jet_features", False))
+    if split and (_kind(encoder) != "fused" or encoder.tau_input_scalars > 8):
+        raise NotImplementedError("the native step of table-driven (maxdim 3) networks takes the particle masses as the only input "
+                                  "scalars: jet_features / extra input scalars run through the module API there (CapturedModuleStep "
+                                  "/ native_train_step capture that step into one graph)")
+    encoder._require_gpu()
+    if not N.end_stages_fit(encoder, decoder, junction=not split):
+        # a jet's latent / junction stage is ONE workgroup: refused here, at plan time, so that native_train_step (and any caller
+        # catching NotImplementedError) takes the module route instead of failing at the first launch
+        raise NotImplementedError(
+            f"the per-jet latent stage of map_to_latent={encoder.map_to_latent!r} at {encoder.num_input_particles} particles needs "
+            "more than the 160 KiB of LDS of a CU; this configuration runs through the module API (per-operator path)")
+    return split
+
+
+def _check_latent_match(d, encoder, decoder):
+    from . import _native as N
+    if decoder.tau_latent_vectors != N.pool_blocks(d.latent_pool) * d.tau_v or \
+            decoder.num_output_particles != encoder.num_input_particles - int(bool(getattr(encoder, "jet_features", False))):
+        raise ValueError(f"decoder latent size / particle count does not match the encoder (map_to_latent={encoder.map_to_latent!r} "
+                         f"gives {N.pool_blocks(d.latent_pool)} x {d.tau_v} latent vectors, the decoder takes {decoder.tau_latent_vectors})")
+
+
 class NativeTrainStep:
     """Same step as TrainStep, executed by lgn_step_fwd_bwd_f64 / lgn_step_finalize_f64 (csrc/step.hip):
     no autograd graph, no PyTorch kernels, every buffer static.  With ``use_graph=True`` the two native calls
@@ -260,31 +301,7 @@ class NativeTrainStep:
         import ctypes as C
         from . import _native as N
         self.N = N
-        from .ops import native_kind as _kind
-        if _kind(encoder) is None or _kind(encoder) != _kind(decoder):
-            # lgn_step_fwd_bwd_f64 covers networks whose levels are all the fused maxdim=2 closed form or all table driven
-            # (maxdim=3), with 20 radial basis functions and 7-layer CGMLPs.  Anything else would be read with the wrong
-            # layout -> refuse instead of computing garbage.
-            raise NotImplementedError(
-                "the native step implements maxdim=2 / maxdim=3 networks (the same kind for encoder and decoder) with "
-                "map_to_latent = min / max / mean joined by '&' or '+', CGMLP levels (mlp_depth 3 .. 6), num_basis_fn <= 10 and <= 8 channels; got encoder "
-                f"maxdim={encoder.level_maxdim} map_to_latent={encoder.map_to_latent!r} mlp={encoder.mlp} mlp_depth="
-                f"{encoder.mlp_depth}, decoder maxdim={decoder.level_maxdim} mlp={decoder.mlp}")
-        # jet_features (the encoder works on one node more than the decoder reconstructs) and data['scalars']: the whole-step call
-        # takes them for maxdim = 2 networks (lgn_net_desc.dec_N / n_in_scalars, ABI 17), its four end stages then run as launches
-        # of their own; table-driven networks keep the module route
-        self.split = getattr(encoder, "tau_input_scalars", 1) != 1 or bool(getattr(encoder, "jet_features", False))
-        if self.split and (_kind(encoder) != "fused" or encoder.tau_input_scalars > 8):
-            raise NotImplementedError("the native step of table-driven (maxdim 3) networks takes the particle masses as the only input "
-                                      "scalars: jet_features / extra input scalars run through the module API there (CapturedModuleStep "
-                                      "/ native_train_step capture that step into one graph)")
-        encoder._require_gpu()
-        if not N.end_stages_fit(encoder, decoder, junction=not self.split):
-            # a jet's latent / junction stage is ONE workgroup: refused here, at plan time, so that native_train_step (and any caller
-            # catching NotImplementedError) takes the module route instead of failing at the first launch
-            raise NotImplementedError(
-                f"the per-jet latent stage of map_to_latent={encoder.map_to_latent!r} at {encoder.num_input_particles} particles needs "
-                "more than the 160 KiB of LDS of a CU; this configuration runs through the module API (per-operator path)")
+        self.split = _check_native_pair(encoder, decoder)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
         self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet Chamfer terms
@@ -320,10 +337,7 @@ class NativeTrainStep:
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
         d.get_real = get_real_code(get_real_method)
         d.jet_loss_scale = 1.0 / (4.0 * batch_size * self.world) if self.chamfer_jet_features else 0.0
-        if decoder.tau_latent_vectors != N.pool_blocks(d.latent_pool) * d.tau_v or \
-                decoder.num_output_particles != encoder.num_input_particles - int(bool(getattr(encoder, "jet_features", False))):
-            raise ValueError(f"decoder latent size / particle count does not match the encoder (map_to_latent={encoder.map_to_latent!r} "
-                             f"gives {N.pool_blocks(d.latent_pool)} x {d.tau_v} latent vectors, the decoder takes {decoder.tau_latent_vectors})")
+        _check_latent_match(d, encoder, decoder)
         self.desc = d
         lib = N.lib()
         base = self.flat.flat.data_ptr()
@@ -651,3 +665,200 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
     if dropped:
         warnings.warn(f"native_train_step: this configuration runs as CapturedModuleStep, which does not take {dropped}; ignored")
     return CapturedModuleStep(encoder, decoder, batch_size, **only(CapturedModuleStep))
+
+
+# ---------------------------------------------------------------------------------------------------
+# evaluation step: the reference's validate() / test.py loop (utils/train.py:390, under torch.no_grad()) as one native call
+# ---------------------------------------------------------------------------------------------------
+
+class NativeEvalStep:
+    """encoder -> decoder -> get_real -> Chamfer [+ jet-feature MSE] forward only, executed by lgn_step_eval_f64 (csrc/step.hip):
+    the reference's evaluation loss (no L1: regularization = is_train, utils/train.py:308-314), the reconstruction after get_real
+    (what validate() collects) and, with ``keep_latent``, the pooled latent (what test.py saves).  Nothing is kept for a backward.
+    With ``use_graph`` the call is captured once into a HIP graph and replayed.
+
+    The parameters are read where the modules hold them (their flat blocks, or the joint buffer a NativeTrainStep re-homed them
+    into), without a copy: an evaluation step built on the same modules as a training step sees every update.  If the blocks move,
+    the next ``run`` re-plans.  Same configurations and plan-time refusals (NotImplementedError) as NativeTrainStep.
+
+    A short last batch (B' < batch_size jets) is padded with all-masked jets; loss and outputs cover the B' real ones, and the
+    jet-feature MSE is the mean over those B' jets (nn.MSELoss on that batch)."""
+
+    def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
+                 keep_latent: bool = False, use_graph: bool = True):
+        from . import _native as N
+        self.N = N
+        self.split = _check_native_pair(encoder, decoder)
+        if N.activation_id(encoder.activation) != N.activation_id(decoder.activation):
+            raise NotImplementedError("the native step takes ONE activation for the CGMLPs of both networks (as --activation gives them); "
+                                      f"got {encoder.activation} / {decoder.activation}")
+        self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
+        self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
+        self.keep_latent, self.use_graph = bool(keep_latent), use_graph
+        self._plan()
+        d = self.desc
+        dev, dt = encoder.flat_params.device, encoder.flat_params.dtype
+        Nd = decoder.num_output_particles
+        self.workspace = torch.empty(self._ws, device=dev, dtype=dt)
+        self.recon = torch.empty(d.B, Nd, 4, device=dev, dtype=dt)
+        self.loss_part = torch.empty(d.B, device=dev, dtype=dt)
+        self.loss_out = torch.zeros(1, device=dev, dtype=dt)
+        self.loss = self.loss_out[0]
+        self.p4 = torch.zeros(d.B, d.N, 4, device=dev, dtype=dt)
+        self.target = torch.zeros(d.B, Nd, 4, device=dev, dtype=dt)
+        self.mask = torch.zeros(d.B, d.N, device=dev, dtype=torch.uint8)
+        K = max(1, encoder.tau_input_scalars)
+        self.in_scalars = torch.zeros(d.B, d.N, K - 1, device=dev, dtype=dt) if K > 1 else None
+        P = N.pool_blocks(d.latent_pool)
+        self.lat_s = torch.empty(2, d.B, 1, P * d.tau_s, 1, device=dev, dtype=dt) if self.keep_latent else None
+        self.lat_v = torch.empty(2, d.B, 1, P * d.tau_v, 4, device=dev, dtype=dt) if self.keep_latent else None
+        self._graph = None
+        self.n_real = d.B
+
+    def _plan(self):
+        """Descriptor and parameter offsets for where the two flat blocks are now (offsets count from the lower block)."""
+        import ctypes as C
+        N, enc, dec = self.N, self.encoder, self.decoder
+        enc._check_views()
+        dec._check_views()
+        L = enc.num_cg_levels
+        d = N.NetDesc()
+        d.B, d.N, d.n_levels = self.B, enc.num_input_particles, L
+        self._keep = describe_network(d, enc, False) + describe_network(d, dec, True)
+        d.mlp_hidden_mul, d.mlp_nlin = enc.mlp_width, enc.mlp_depth + 1
+        d.activation = N.activation_id(enc.activation)
+        d.dec_N = dec.num_output_particles if self.split else 0
+        d.get_real = get_real_code(self.get_real_method)
+        d.jet_loss_scale = 1.0 / (4.0 * self.B) if self.chamfer_jet_features else 0.0
+        _check_latent_match(d, enc, dec)
+        lib = N.lib()
+        self._ptrs = (enc.flat_params.data_ptr(), dec.flat_params.data_ptr())
+        self._base = min(self._ptrs)
+
+        def offsets(net, is_dec):
+            ts = _slot_tensors(net, is_dec)
+            want = lib.lgn_step_param_slots(C.byref(d), int(is_dec))
+            if want < 0:
+                raise RuntimeError(N.last_error())
+            assert len(ts) == want, (len(ts), want)
+            offs = [(t.data_ptr() - self._base) // 8 for t in ts]
+            assert all(o >= 0 for o in offs)
+            return (C.c_int64 * len(offs))(*offs)
+
+        self.enc_off, self.dec_off = offsets(enc, False), offsets(dec, True)
+        self._ws = lib.lgn_eval_workspace_doubles(C.byref(d))
+        if self._ws < 0:
+            raise RuntimeError(N.last_error())
+        self.desc = d
+
+    def _eval(self, desc=None):
+        import ctypes as C
+        N = self.N
+        rc = N.lib().lgn_step_eval_f64(C.byref(desc if desc is not None else self.desc), self._base, self.enc_off, self.dec_off,
+                                       N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask), N.ptr(self.in_scalars), N.ptr(self.workspace),
+                                       self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s), N.ptr(self.lat_v),
+                                       N.ptr(self.loss_part), N.ptr(self.loss_out), N.stream_ptr())
+        N._check(rc, "lgn_step_eval_f64")
+
+    def _capture(self):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):            # warm-up: lazy module loads, hipFuncSetAttribute
+            self._eval()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._graph = torch.cuda.CUDAGraph()
+        with _capturing(self._graph):
+            self._eval()
+
+    def load_batch(self, batch: Dict[str, torch.Tensor]):
+        """Stage a batch of B' <= batch_size jets into the static input buffers; rows B' .. batch_size - 1 become all-masked jets."""
+        p4 = batch["p4"]
+        n = p4.shape[0]
+        if n < 1 or n > self.B or tuple(p4.shape[1:]) != tuple(self.target.shape[1:]):
+            raise ValueError(f"NativeEvalStep was built for batches of up to {self.B} jets of shape {tuple(self.target.shape[1:])}, "
+                             f"got {tuple(p4.shape)}")
+        if self.split:
+            ps, mask, scalars = self.encoder._prepare_input(batch)
+        else:
+            ps = p4.to(self.p4.dtype) * self.encoder.scale if self.encoder.scale != 1.0 else p4
+            for key in ("labels", "masks", "mask"):
+                if key in batch:
+                    mask = batch[key]
+                    if tuple(mask.shape) != (n, self.mask.shape[1]):
+                        raise ValueError(f"mask shape {tuple(mask.shape)} != {(n, self.mask.shape[1])}")
+                    break
+            else:
+                mask = p4[..., 0] != 0
+            scalars = None
+        self.p4[:n].copy_(ps)
+        self.target[:n].copy_(p4)
+        self.mask[:n].copy_(mask.to(torch.uint8))
+        if self.in_scalars is not None:
+            self.in_scalars[:n].copy_(scalars)
+        if n < self.B:
+            self.p4[n:].zero_()
+            self.target[n:].zero_()
+            self.mask[n:].zero_()
+            if self.in_scalars is not None:
+                self.in_scalars[n:].zero_()
+        self.n_real = n
+
+    def run(self, batch: Optional[Dict[str, torch.Tensor]] = None):
+        """One evaluation step on `batch` (or on the staged buffers).  Returns {'loss': 0-d device tensor, 'recon': (B', N, 4)
+        get_real(reconstruction)} and, with keep_latent, 'latent': the GVec encoder(batch) returns.  The tensors are the step's
+        static buffers: the next run overwrites them."""
+        if batch is not None:
+            self.load_batch(batch)
+        if (self.encoder.flat_params.data_ptr(), self.decoder.flat_params.data_ptr()) != self._ptrs:
+            self._plan()                     # the blocks moved (e.g. a NativeTrainStep re-homed them): new offsets, new graph
+            if self._ws > self.workspace.numel():
+                self.workspace = torch.empty(self._ws, device=self.workspace.device, dtype=self.workspace.dtype)
+            self._graph = None
+        n = self.n_real
+        if n < self.B and self.chamfer_jet_features:
+            # nn.MSELoss over the B' real jets: a descriptor of its own, one call outside the graph
+            d = type(self.desc).from_buffer_copy(self.desc)
+            d.jet_loss_scale = 1.0 / (4.0 * n)
+            self._eval(d)
+        elif self.use_graph:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+        else:
+            self._eval()
+        out = {"loss": self.loss, "recon": self.recon[:n]}
+        if self.keep_latent:
+            from .g_lib import GVec
+            out["latent"] = GVec({(0, 0): self.lat_s[:, :n], (1, 1): self.lat_v[:, :n]})
+        return out
+
+
+class ModuleEvalStep:
+    """The evaluation step through the module API under torch.no_grad() (encoder(batch) -> decoder -> get_real -> ChamferLoss), for
+    the configurations NativeEvalStep refuses.  Same interface."""
+
+    def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
+                 keep_latent: bool = False, use_graph: bool = True):
+        from .losses import ChamferLoss
+        self.encoder, self.decoder, self.B = encoder, decoder, batch_size
+        self.get_real_method, self.chamfer_jet_features, self.keep_latent = get_real_method, chamfer_jet_features, keep_latent
+        self.loss_fn = ChamferLoss(device=encoder.device)
+
+    @torch.no_grad()
+    def run(self, batch: Dict[str, torch.Tensor]):
+        latent = self.encoder(batch)
+        recon = get_real(self.decoder(latent), self.get_real_method)
+        loss = self.loss_fn(recon, batch["p4"].to(recon.device), jet_features=self.chamfer_jet_features)
+        out = {"loss": loss, "recon": recon}
+        if self.keep_latent:
+            out["latent"] = latent
+        return out
+
+
+def native_eval_step(encoder, decoder, batch_size: int, **kw):
+    """NativeEvalStep where lgn_step_eval_f64 covers the configuration, else ModuleEvalStep (the module API under no_grad)."""
+    try:
+        return NativeEvalStep(encoder, decoder, batch_size, **kw)
+    except NotImplementedError:
+        return ModuleEvalStep(encoder, decoder, batch_size, **kw)
