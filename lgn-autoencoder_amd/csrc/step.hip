@@ -53,7 +53,7 @@ struct Deferred {
   double* parts;
   size_t off = 0, cap = 0;
   // nullptr when the slice does not fit: callers test it (DQ_TAKE) BEFORE enqueuing the kernel that would write there --
-  // the capacity is a hand-maintained mirror of the take sequence (carve*), a disagreement must not reach the device
+  // the capacity mirrors the take sequence (net_parts / gen_net_parts), a disagreement must not reach the device
   double* take(size_t n) {
     n = (n + 15) & ~size_t(15);
     if (off + n > cap) return nullptr;
@@ -93,10 +93,21 @@ int finish_reductions(Deferred& dq, const RadFinJob& fin, double* grads, long lo
   return rad_finalize_batch(fin, st);
 }
 
-// partial rows of level l's CGMLP weight gradients
-size_t mlp_part_rows(const lgn_net_desc& d, bool dec, int l) {
-  const int* ch = dec ? d.dec_channels : d.enc_channels;
-  return (size_t)mlp_partial_rows(d.B * (dec && d.dec_N > 0 ? d.dec_N : d.N), d.mlp_hidden_mul * 2 * ch[l + 1]);
+// The end of a whole step.  With `tail` (single process: nothing sits between the gradients and the optimiser) the deferred
+// reductions, the radial finalisation, L1 + Adam and the loss assembly are ONE launch (step_tail.hip); where that form does not fit
+// (-2), or with LGN_NET_SPLIT_TAIL, finish_reductions and then finalize_step.  Without `tail` (data-parallel step: the all-reduce
+// follows) finish_reductions alone, in one launch on `counters` where the caller has them.
+int end_step(Deferred& dq, const RadFinJob& fin, double* grads, long long n_params, double* counters, int flags, const StepTailArgs* tail,
+             hipStream_t st) {
+  if (tail && !(flags & LGN_NET_SPLIT_TAIL)) {
+    const int rc = step_tail(dq.segs, fin, *tail, st);
+    if (rc != -2) return rc;
+  }
+  if (int rc = finish_reductions(dq, fin, grads, n_params, tail ? nullptr : counters, flags, st)) return rc;
+  if (!tail) return 0;
+  const StepTailArgs& t = *tail;
+  return finalize_step(t.w, t.g, t.n, t.loss_part, t.nB, t.lambda, t.m, t.v, t.step_dev, t.lr, t.beta1, t.beta2, t.eps, t.do_adam,
+                       t.loss_out, st);
 }
 
 inline int in_K(const lgn_net_desc& d) { return d.n_in_scalars > 1 ? d.n_in_scalars : 1; }      // encoder input scalars per node
@@ -111,6 +122,73 @@ inline int dec_nodes(const lgn_net_desc& d) { return d.dec_N > 0 ? d.dec_N : d.N
 // the step takes the two-kernel junction and the riding input stage only when both networks work on the same nodes and the mass is
 // the only input scalar; otherwise the four end stages are launches of their own
 inline bool step_is_split(const lgn_net_desc& d) { return dec_nodes(d) != d.N || d.n_in_scalars > 1; }
+// latent vectors per jet the decoder's input stage reads: its own tau_v_in, or the encoder's pooled ones
+inline int dec_tin(const lgn_net_desc& d) { return d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v; }
+// a whole step's decoder consumes the encoder's pooled latent vectors
+int check_latent_match(const lgn_net_desc& d) {
+  const int Tin = pool_blocks(d.latent_pool) * d.tau_v;
+  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step: the decoder must consume the encoder's %d pooled latent vectors", Tin);
+  return 0;
+}
+
+struct Slots {                      // canonical parameter slot order shared with lgn/step.py
+  int L, nlin;
+  int in0(bool dec) const { return dec ? 2 : 0; }
+  int rad(bool dec, int l, int k) const { return in0(dec) + 2 + 7 * l + k; }
+  int mix(bool dec, int l, int k) const { return in0(dec) + 2 + 7 * L + 2 * l + k; }
+  int mlp(bool dec, int l, int k) const { return in0(dec) + 2 + 9 * L + 2 * nlin * l + k; }
+  int out0(bool dec) const { return in0(dec) + 2 + 9 * L + 2 * nlin * L; }
+  int count(bool dec) const { return out0(dec) + 2; }
+};
+
+// Partial-row layout of an end stage: its launch writes one row of `width` doubles per workgroup; columns [col, col + n) of the rows
+// reduce into the gradient of parameter slot `slot`.  Each layout below is stated here only: the sequencers register their
+// reductions with add(), the workspace carves size the rows with width.
+struct RowLayout {
+  int width, nseg, col[3], n[3], slot[3];
+  void add(Deferred& dq, const double* part, int rows, double* G, const int64_t* off) const {
+    for (int i = 0; i < nseg; ++i) dq.add(part, rows, width, col[i], n[i], G + off[slot[i]]);
+  }
+};
+// encoder latent stage (enc_latent_bwd / junction_bwd): dWl0 [2][Ts][KL] | dWl1 [2][Tv][KL]
+RowLayout enc_latent_rows(const lgn_net_desc& d, int N, int CL) {
+  const int KL = pool_mix_in(d.latent_pool, N, CL), o = Slots{d.n_levels, d.mlp_nlin}.out0(false);
+  return {2 * (d.tau_s + d.tau_v) * KL, 2, {0, 2 * d.tau_s * KL}, {2 * d.tau_s * KL, 2 * d.tau_v * KL}, {o, o + 1}};
+}
+// encoder input stage with K scalars (enc_input_bwd, or riding on the first level's backward with K = 1): dW00 [2][C0][K] | dW11 [2][C0]
+RowLayout enc_input_rows(int K, int C0) { return {(2 * K + 2) * C0, 2, {0, 2 * C0 * K}, {2 * C0 * K, 2 * C0}, {0, 1}}; }
+// decoder input stage (dec_input_bwd / junction_bwd): dW00 [2][C0] | dW11 [2][C0] | dWg1 [2][N][Tin]
+RowLayout dec_input_rows(int C0, int N, int Tin) {
+  return {4 * C0 + 2 * N * Tin, 3, {0, 2 * C0, 4 * C0}, {2 * C0, 2 * C0, 2 * N * Tin}, {2, 3, 1}};
+}
+// decoder output stage (dec_output_bwd / dec_output_loss): dWo1 [2][CL]
+RowLayout dec_output_rows(const lgn_net_desc& d, int CL) {
+  return {2 * CL, 1, {0}, {2 * CL}, {Slots{d.n_levels, d.mlp_nlin}.out0(true) + 1}};
+}
+
+inline size_t r16(size_t n) { return (n + 15) & ~size_t(15); }     // a Deferred::take of n doubles
+// partial rows of a network's two end stages on N nodes; in_rows: rows of the encoder's input stage
+size_t end_parts(const lgn_net_desc& d, bool dec, int N, int in_rows) {
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
+  const int L = d.n_levels;
+  if (dec) return r16((size_t)d.B * dec_output_rows(d, ch[L]).width) + r16((size_t)d.B * dec_input_rows(ch[0], N, dec_tin(d)).width);
+  return r16((size_t)d.B * enc_latent_rows(d, N, ch[L]).width) + r16((size_t)in_rows * enc_input_rows(in_K(d), ch[0]).width);
+}
+// partial-row capacity of one maxdim-2 network on N nodes: its level stack (levels_bwd) and its end stages.  (The decoder's CGMLP rows
+// are counted on dec_nodes(d) even for a per-network call, where the descriptor's dec_N is 0 -- as the layout has always been sized.)
+size_t net_parts(const lgn_net_desc& d, bool dec, int N) {
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
+  int rm, rr;
+  level_bwd_partial_rows(d.B, N, dec, d.flags, &rm, &rr);
+  size_t sum = 0;
+  for (int l = 0; l < d.n_levels; ++l) {
+    const int H = d.mlp_hidden_mul * 2 * ch[l + 1];
+    sum += r16((size_t)rm * 4 * ch[l + 1] * 5 * ch[l]) + r16((size_t)rr * rad_partial_size(ch[l], dec)) +
+           r16((size_t)mlp_partial_rows(d.B * (dec ? dec_nodes(d) : N), H) * mlp_psize(ch[l + 1], H, d.mlp_nlin));
+  }
+  // the encoder's input-stage rows: one per jet, or one per workgroup of the first level's backward when they ride on it
+  return sum + end_parts(d, dec, N, rm > d.B ? rm : d.B);
+}
 
 Work carve(const lgn_net_desc& d, double* base) {
   Work w{};
@@ -159,36 +237,15 @@ Work carve(const lgn_net_desc& d, double* base) {
     w.zero_doubles = b.off - z0;
   }
   w.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (Ts + Tv) * 2 + 1) / 2 + 8));
+  for (int dec = 0; dec < 2; ++dec)
+    for (int l = 0; l < L; ++l) w.tot[dec][l] = b.take(rad_partial_size((dec ? d.dec_channels : d.enc_channels)[l], dec != 0) + 16);
   // partial rows: every producer keeps its own slice until the deferred reduction at the end of the step
-  size_t psum = 0;
-  for (int dec = 0; dec < 2; ++dec) {
-    const int* ch = dec ? d.dec_channels : d.enc_channels;
-    for (int l = 0; l < L; ++l) {
-      int rm, rr;
-      level_bwd_partial_rows(d.B, dec ? Nd : d.N, dec, d.flags, &rm, &rr);
-      const size_t nmix = (size_t)4 * ch[l + 1] * 5 * ch[l], nrad = rad_partial_size(ch[l], dec != 0);
-      psum += ((rm * nmix + 15) & ~size_t(15)) + ((rr * nrad + 15) & ~size_t(15));
-      psum += (mlp_part_rows(d, dec, l) * mlp_psize(ch[l + 1], d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) + 15) & ~size_t(15);
-      w.tot[dec][l] = b.take(nrad + 16);
-    }
-  }
-  psum += 4 * (((size_t)d.B * (4 * cmax + 2 * (size_t)Nmax * PB * Tv + 2 * (size_t)(Ts + Tv) * pool_mix_in(d.latent_pool, Nmax, cmax)) + 15) & ~size_t(15));
-  psum += ((size_t)d.B * (2 * in_K(d) + 2) * cmax + 15) & ~size_t(15);                  // input stage with K scalars (split step)
+  const size_t psum = net_parts(d, false, d.N) + net_parts(d, true, Nd);
   w.parts = b.take(psum);
   w.parts_size = psum;
   w.total = b.off;
   return w;
 }
-
-struct Slots {                      // canonical parameter slot order shared with lgn/step.py
-  int L, nlin;
-  int in0(bool dec) const { return dec ? 2 : 0; }
-  int rad(bool dec, int l, int k) const { return in0(dec) + 2 + 7 * l + k; }
-  int mix(bool dec, int l, int k) const { return in0(dec) + 2 + 7 * L + 2 * l + k; }
-  int mlp(bool dec, int l, int k) const { return in0(dec) + 2 + 9 * L + 2 * nlin * l + k; }
-  int out0(bool dec) const { return in0(dec) + 2 + 9 * L + 2 * nlin * L; }
-  int count(bool dec) const { return out0(dec) + 2; }
-};
 
 #define HIPOK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { set_error("%s: %s", #e, hipGetErrorString(e_)); return (int)e_; } } while (0)
 #define DQ_NEW(var, n) double* var = nullptr; DQ_TAKE(var, n)
@@ -220,6 +277,16 @@ struct LossStage {
   double *recon, *loss_part, *g_v, *wpart;
 };
 
+// the arguments of level l's CGMLP every caller shares: shape (M = B N), activation, weights and biases
+MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const double* P, const int64_t* off) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int CO = (dec ? d.dec_channels : d.enc_channels)[l + 1];
+  MlpArgs<double> m{};
+  m.M = d.B * d.N; m.C = CO; m.H = d.mlp_hidden_mul * 2 * CO; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
+  for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = P + off[S.mlp(dec, l, 2 * q)]; m.b[q] = P + off[S.mlp(dec, l, 2 * q + 1)]; }
+  return m;
+}
+
 // forward of one network's level stack; returns via buffers
 // eval (evaluation step): the level kernels without the aggregate stores (level_fwd_eval; n.ag0 / ag1 unused), a riding loss
 // tail in its forward-only form, and no CGMLP after the decoder's last level (its scalars never reach the output)
@@ -244,9 +311,7 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
     a.flags = d.flags;
     LGN_TRY(eval ? level_fwd_eval(a, dec, st) : level_fwd_dispatch<double>(a, dec, st));
     if (eval && dec && l + 1 == d.n_levels) break;
-    MlpArgs<double> m{};
-    m.M = d.B * d.N; m.C = ch[l + 1]; m.H = d.mlp_hidden_mul * 2 * ch[l + 1]; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
-    for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = p(S.mlp(dec, l, 2 * q)); m.b[q] = p(S.mlp(dec, l, 2 * q + 1)); }
+    MlpArgs<double> m = level_mlp_args(d, dec, l, P, off);
     m.s_in = n.smix[l]; m.s_out = n.s[l + 1];
     m.h_saved = n.hsave[l]; m.h_rows = mlp_saved_rows(m.M);
     LGN_TRY(mlp_dispatch<double>(m, false, st));
@@ -257,12 +322,11 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
 // backward of one network's level stack.  On entry gs[cur]/gv[cur] hold the gradient w.r.t. (s[L], v[L]);
 // has_s_grad says whether gs is non-zero (false for both networks of the autoencoder: the last level's
 // scalars never reach the loss).  On exit gs[cur]/gv[cur] hold the gradient w.r.t. level 0.
-// in0_grads (encoder only, optional): gradient slots of input_func_node's two weights.  When the first level's backward is the
-// one-kernel form, the input stage's backward rides on it (LevelBwdArgs::part_in0) and *in0_done is set; otherwise the caller
-// launches enc_input_bwd.
+// in0_done (encoder only, optional): the input stage's backward (mass only) may ride on the first level's.  When that level's
+// backward is the one-kernel form, it does (LevelBwdArgs::part_in0) and *in0_done is set; otherwise the caller launches enc_input_bwd.
 int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, double* G, const int64_t* off, const NetBuf& n,
                const double* pos, const uint8_t* mask, Work& w, Deferred& dq, RadFinJob& fin, int& cur, bool has_s_grad,
-               hipStream_t st, double* const* in0_grads = nullptr, bool* in0_done = nullptr) {
+               hipStream_t st, bool* in0_done = nullptr) {
   const Slots S{d.n_levels, d.mlp_nlin};
   const int BN = d.B * d.N;
   for (int l = d.n_levels - 1; l >= 0; --l) {
@@ -271,9 +335,7 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
     const int C = ch[l], CO = ch[l + 1];
     const double* g_smix = w.zeros_s;
     if (has_s_grad) {
-      MlpArgs<double> m{};
-      m.M = BN; m.C = CO; m.H = d.mlp_hidden_mul * 2 * CO; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
-      for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = p(S.mlp(dec, l, 2 * q)); m.b[q] = p(S.mlp(dec, l, 2 * q + 1)); }
+      MlpArgs<double> m = level_mlp_args(d, dec, l, P, off);
       m.s_in = n.smix[l]; m.g_out = w.gs[cur]; m.g_in = w.gsmix;
       m.h_saved = n.hsave[l];
       m.h_rows = mlp_saved_rows(BN);
@@ -294,13 +356,13 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
                            p(S.rad(dec, l, 0)), p(S.rad(dec, l, 1)), p(S.rad(dec, l, 2)), p(S.rad(dec, l, 3)), p(S.rad(dec, l, 4)),
                            p(S.rad(dec, l, 5)), p(S.rad(dec, l, 6)), p(S.mix(dec, l, 0)), p(S.mix(dec, l, 1)), n.ag0[l], n.ag1[l],
                            g_smix, w.gv[cur], w.g_ag, w.gs[nxt], w.gv[nxt], dec ? w.g_p : nullptr, part_mix, part_rad};
-    const bool carry_in0 = !dec && l == 0 && in0_grads && level_bwd_carries_input(d.N, d.flags);
-    if (carry_in0) { DQ_TAKE(a.part_in0, (size_t)rm * 4 * C); }
+    const bool carry_in0 = !dec && l == 0 && in0_done && level_bwd_carries_input(d.N, d.flags);
+    const RowLayout rin = enc_input_rows(1, C);
+    if (carry_in0) { DQ_TAKE(a.part_in0, (size_t)rm * rin.width); }
     a.flags = d.flags;
     LGN_TRY(level_bwd_dispatch<double>(a, dec, st));
     if (carry_in0) {
-      dq.add(a.part_in0, rm, 4 * C, 0, 2 * C, in0_grads[0]);
-      dq.add(a.part_in0, rm, 4 * C, 2 * C, 2 * C, in0_grads[1]);
+      rin.add(dq, a.part_in0, rm, G, off);
       *in0_done = true;
     }
     // deferred reductions: CatMix weights (partial row = [wm0 | wm1]) + radial sums
@@ -337,8 +399,7 @@ int check_desc(const lgn_net_desc* d) {
   LGN_CHECK_ARG(d->jet_loss_scale >= 0.0, "step: jet_loss_scale=%g must be >= 0", d->jet_loss_scale);
   LGN_CHECK_ARG(d->dec_N >= 0, "step: dec_N=%d must be >= 0", d->dec_N);
   if (d->dec_N > 0) {        // the whole step's decoder end stages are one workgroup per jet of dec_N particles
-    const int Tin = d->tau_v_in ? d->tau_v_in : pool_blocks(d->latent_pool) * d->tau_v;
-    const size_t need = decoder_end_lds_bytes(d->dec_N, d->dec_channels[0], Tin, d->dec_channels[d->n_levels]);
+    const size_t need = decoder_end_lds_bytes(d->dec_N, d->dec_channels[0], dec_tin(*d), d->dec_channels[d->n_levels]);
     LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: dec_N=%d: the decoder end stages need %zu B of LDS (> %d)", d->dec_N, need, LGN_LDS_LIMIT);
   }
   return 0;
@@ -494,6 +555,22 @@ struct GenScratch {
   double* parts;
   size_t parts_size, total;
 };
+// partial-row capacity of one table-driven network: its level stack (gen_levels_bwd) and its end stages
+size_t gen_net_parts(const lgn_net_desc& d, bool dec) {
+  const GenGeom g = geom(d, dec);
+  const size_t BN = (size_t)d.B * d.N, tiles = (BN + 63) / 64;
+  const bool tb = is_static(d, dec), sep = is_sep_fused(d, dec);
+  size_t sum = 0;
+  for (int l = 0; l < d.n_levels; ++l) {
+    const int H = d.mlp_hidden_mul * 2 * g.ch[l + 1];
+    const size_t lrows = tb ? (sep ? (size_t)local_sep_part_rows(d.B) : tiles) * local_static_packed_doubles(g.tab[l]->static_kind, g.ch[l], g.ch[l + 1])
+                            : (size_t)local_partial_rows((int)BN) * 2 * g.tab[l]->n_w;
+    sum += r16(lrows) + r16((size_t)d.B * rad_partial_size(g.ch[l], dec)) +
+           r16((size_t)mlp_partial_rows((int)BN, H) * mlp_psize(g.ch[l + 1], H, d.mlp_nlin));
+  }
+  return sum + end_parts(d, dec, d.N, d.B);
+}
+
 GenScratch carve_gen_scratch(const lgn_net_desc& d, bool dec, double* base) {
   GenScratch s{};
   Bump b{base};
@@ -524,18 +601,8 @@ GenScratch carve_gen_scratch(const lgn_net_desc& d, bool dec, double* base) {
     s.gpb[l] = sep ? b.take((size_t)g.ch[l] * BN * 8) : nullptr;
   }
   s.gbuf = (!dec && d.N <= 32) ? b.take(moments2_gbuf_doubles(d.B, d.N, (int)cmax)) : nullptr;
-  size_t psum = 0;
-  for (int l = 0; l < L; ++l) {
-    const size_t nrad = rad_partial_size(g.ch[l], dec);
-    const size_t lrows = tb ? (sep ? (size_t)local_sep_part_rows(d.B) : tiles) * local_static_packed_doubles(g.tab[l]->static_kind, g.ch[l], g.ch[l + 1])
-                            : (size_t)local_partial_rows((int)BN) * 2 * g.tab[l]->n_w;
-    psum += ((lrows + 15) & ~size_t(15)) + (((size_t)d.B * nrad + 15) & ~size_t(15));
-    psum += ((size_t)mlp_partial_rows((int)BN, d.mlp_hidden_mul * 2 * g.ch[l + 1]) * mlp_psize(g.ch[l + 1], d.mlp_hidden_mul * 2 * g.ch[l + 1], d.mlp_nlin) + 15) & ~size_t(15);
-    s.tot[l] = b.take(nrad + 16);
-  }
-  const int Tin = d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v;
-  if (dec) psum += (((size_t)d.B * 2 * g.ch[L] + 15) & ~size_t(15)) + (((size_t)d.B * (4 * g.ch[0] + 2 * (size_t)d.N * Tin) + 15) & ~size_t(15));
-  else psum += (((size_t)d.B * 2 * (d.tau_s + d.tau_v) * pool_mix_in(d.latent_pool, d.N, g.ch[L]) + 15) & ~size_t(15)) + (((size_t)d.B * (2 * in_K(d) + 2) * g.ch[0] + 15) & ~size_t(15));
+  for (int l = 0; l < L; ++l) s.tot[l] = b.take(rad_partial_size(g.ch[l], dec) + 16);
+  const size_t psum = gen_net_parts(d, dec);
   s.parts = b.take(psum);
   s.parts_size = psum;
   s.total = b.off;
@@ -592,9 +659,7 @@ int gen_levels_fwd(const lgn_net_desc& d, bool dec, const double* P, const int64
       la.s_copy = a.smix[l]; la.q_s = g.qs[l + 1];
       LGN_TRY(local_fwd(la, st));
     }
-    MlpArgs<double> mm{};
-    mm.M = BN; mm.C = g.ch[l + 1]; mm.H = d.mlp_hidden_mul * 2 * g.ch[l + 1]; mm.nlin = d.mlp_nlin; mm.act = d.activation; mm.flags = d.flags;
-    for (int q = 0; q < d.mlp_nlin; ++q) { mm.w[q] = P + off[S.mlp(dec, l, 2 * q)]; mm.b[q] = P + off[S.mlp(dec, l, 2 * q + 1)]; }
+    MlpArgs<double> mm = level_mlp_args(d, dec, l, P, off);
     mm.s_in = a.smix[l];
     if (tb) { mm.s_out = a.X[l + 1] + (size_t)g.qs[l + 1] * 128; mm.tbQ = g.Q[l + 1]; }
     else { mm.s_out = a.X[l + 1] + g.qs[l + 1]; mm.ld = g.Q[l + 1]; }
@@ -621,9 +686,7 @@ int gen_levels_bwd(const lgn_net_desc& d, bool dec, const double* P, double* G, 
   for (int l = d.n_levels - 1; l >= 0; --l) {
     const int C = g.ch[l], CO = g.ch[l + 1];
     if (has_s_grad) {     // CGMLP backward, in place on the scalar column of the gradient
-      MlpArgs<double> m{};
-      m.M = BN; m.C = CO; m.H = d.mlp_hidden_mul * 2 * CO; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
-      for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = P + off[S.mlp(dec, l, 2 * q)]; m.b[q] = P + off[S.mlp(dec, l, 2 * q + 1)]; }
+      MlpArgs<double> m = level_mlp_args(d, dec, l, P, off);
       m.s_in = a.smix[l];
       if (tb) { m.g_out = sc.gX[cur] + (size_t)g.qs[l + 1] * 128; m.g_in = sc.gX[cur] + (size_t)g.qs[l + 1] * 128; m.tbQ = g.Q[l + 1]; }
       else { m.g_out = sc.gX[cur] + g.qs[l + 1]; m.g_in = sc.gX[cur] + g.qs[l + 1]; m.ld = g.Q[l + 1]; }
@@ -739,8 +802,9 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
   RadFinJob fin{};
   int cur = 0;
   {
-    const int CL = g.ch[L], KL = pool_mix_in(d.latent_pool, N, CL), rowe = 2 * (Ts + Tv) * KL;
-    DQ_NEW(parte, (size_t)B * rowe);
+    const int CL = g.ch[L];
+    const RowLayout rl = enc_latent_rows(d, N, CL);
+    DQ_NEW(parte, (size_t)B * rl.width);
     if (jb)       // whole step: the decoder's input stage backward and this latent stage backward of a jet in one launch
       LGN_TRY(junction_bwd(B, N, jb->C0, jb->Tin, jb->lat_v, jb->wg1, jb->w1, jb->pdec, jb->g_p, jb->g_s0, jb->g_v0, const_cast<double*>(g_lat_v),
                            jb->part_dec, CL, Ts, Tv, d.latent_pool, a.sL, a.vL, P + off[S.out0(false)], P + off[S.out0(false) + 1],
@@ -748,8 +812,7 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
     else
       LGN_TRY(enc_latent_bwd(B, N, CL, Ts, Tv, d.latent_pool, a.sL, a.vL, P + off[S.out0(false)], P + off[S.out0(false) + 1],
                              g_lat_s ? g_lat_s : sc.g_lat_s, g_lat_v, a.idx, sc.gs, sc.gv, parte, st));
-    dq.add(parte, B, rowe, 0, 2 * Ts * KL, G + off[S.out0(false)]);
-    dq.add(parte, B, rowe, 2 * Ts * KL, 2 * Tv * KL, G + off[S.out0(false) + 1]);
+    rl.add(dq, parte, B, G, off);
     LGN_TRY(net_pack(d, false, L, g_lat_s ? sc.gs : sc.zero0, sc.gv, sc.gX[cur], st));
   }
   std::vector<UnpackJob> post;
@@ -757,11 +820,10 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
   {
     const int C0 = g.ch[0];
     LGN_TRY(net_unpack(d, false, 0, sc.gX[cur], sc.gs, sc.gv, st));
-    const int K = in_K(d), row = (2 * K + 2) * C0;
-    DQ_NEW(part, (size_t)B * row);
-    LGN_TRY(enc_input_bwd(B, N, C0, K, p4, xs, sc.gs, sc.gv, part, st));
-    dq.add(part, B, row, 0, 2 * C0 * K, G + off[0]);
-    dq.add(part, B, row, 2 * C0 * K, 2 * C0, G + off[1]);
+    const RowLayout ri = enc_input_rows(in_K(d), C0);
+    DQ_NEW(part, (size_t)B * ri.width);
+    LGN_TRY(enc_input_bwd(B, N, C0, in_K(d), p4, xs, sc.gs, sc.gv, part, st));
+    ri.add(dq, part, B, G, off);
   }
   LGN_CHECK_ARG(dq.off <= dq.cap, "encoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
   if (hand_dq) {
@@ -780,8 +842,8 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
 int gen_decoder_fwd(const lgn_net_desc& d, const double* P, const int64_t* off, const double* lat_v, GenAct& a, hipStream_t st,
                     bool with_input = true) {
   const GenGeom g = geom(d, true);
-  const int L = d.n_levels, Tin = d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v;
-  if (with_input) LGN_TRY(dec_input_fwd(d.B, d.N, g.ch[0], Tin, lat_v, P + off[1], P + off[2], P + off[3], a.pdec, a.s0, a.v0, st));
+  const int L = d.n_levels;
+  if (with_input) LGN_TRY(dec_input_fwd(d.B, d.N, g.ch[0], dec_tin(d), lat_v, P + off[1], P + off[2], P + off[3], a.pdec, a.s0, a.v0, st));
   LGN_TRY(net_pack(d, true, 0, a.s0, a.v0, a.X[0], st));
   LGN_TRY(gen_levels_fwd(d, true, P, off, a, a.pdec, nullptr, st));
   LGN_TRY(net_unpack(d, true, L, a.X[L], a.sL, a.vL, st));
@@ -796,7 +858,7 @@ int gen_decoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
                     double* g_lat_v, GenScratch& sc, Deferred& dq, RadFinJob& fin, std::vector<UnpackJob>& post, hipStream_t st,
                     double** part_in = nullptr) {
   const GenGeom g = geom(d, true);
-  const int L = d.n_levels, B = d.B, N = d.N, Tin = d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v;
+  const int L = d.n_levels, B = d.B, N = d.N, Tin = dec_tin(d);
   int cur = 0;
   LGN_TRY(net_pack(d, true, L, sc.zero0, sc.gv, sc.gX[cur], st));
   LGN_TRY(gen_levels_bwd(d, true, P, G, off, a, a.pdec, nullptr, sc, dq, fin, post, cur, /*has_s_grad=*/false, st));
@@ -806,14 +868,13 @@ int gen_decoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
     for (int l = 0; l < L; ++l) { gpb[l] = sc.gpb[L - 1 - l]; cl[l] = g.ch[L - 1 - l]; }      // (the order the levels ran in)
     LGN_TRY(local_sep_gp_reduce(gpb, cl, L, B * N, sc.g_p, st));
   }
-  const int C0 = g.ch[0], row = 4 * C0 + 2 * N * Tin;
+  const int C0 = g.ch[0];
+  const RowLayout ri = dec_input_rows(C0, N, Tin);
   LGN_TRY(net_unpack(d, true, 0, sc.gX[cur], sc.gs, sc.gv, st));
-  DQ_NEW(part, (size_t)B * row);
+  DQ_NEW(part, (size_t)B * ri.width);
   if (part_in) *part_in = part;
   else LGN_TRY(dec_input_bwd(B, N, C0, Tin, lat_v, P + off[1], P + off[3], a.pdec, sc.g_p, sc.gs, sc.gv, g_lat_v, part, st));
-  dq.add(part, B, row, 0, 2 * C0, G + off[2]);
-  dq.add(part, B, row, 2 * C0, 2 * C0, G + off[3]);
-  dq.add(part, B, row, 4 * C0, 2 * N * Tin, G + off[1]);
+  ri.add(dq, part, B, G, off);
   return 0;
 }
 
@@ -832,7 +893,7 @@ GenStep carve_gen_step(const lgn_net_desc& d, double* base) {
   g.da = carve_gen_act(d, true, at(off)); off += (g.da.total + 15) & ~size_t(15);
   g.es = carve_gen_scratch(d, false, at(off)); off += (g.es.total + 15) & ~size_t(15);
   g.ds = carve_gen_scratch(d, true, at(off)); off += (g.ds.total + 15) & ~size_t(15);
-  const int Tin = d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v;
+  const int Tin = dec_tin(d);
   g.lat_s = at(off); off += ((size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s + 15) & ~size_t(15);
   g.lat_v = at(off); off += ((size_t)2 * d.B * Tin * 4 + 15) & ~size_t(15);
   g.g_lat_v = at(off); off += ((size_t)2 * d.B * Tin * 4 + 15) & ~size_t(15);
@@ -846,8 +907,6 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step: encoder and decoder must both be table-driven (or both fused)");
   if (int rc = check_generic(d, false)) return rc;
   if (int rc = check_generic(d, true)) return rc;
-  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == pool_blocks(d.latent_pool) * d.tau_v,
-                "step: the decoder must consume the encoder's %d pooled latent vectors", pool_blocks(d.latent_pool) * d.tau_v);
   GenStep g = carve_gen_step(d, workspace);
   LGN_CHECK_ARG((long long)g.total <= workspace_doubles, "step: workspace holds %lld doubles, this configuration needs %zu",
                 workspace_doubles, g.total);
@@ -857,7 +916,7 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   const int L = d.n_levels, B = d.B, N = d.N, CL = d.dec_channels[L];
   LGN_TRY(zero_ranges(grads, (size_t)n_params, g.es.zero0, g.es.zero_doubles, g.ds.zero0, g.ds.zero_doubles, st));
   // encoder latent stage + decoder input stage of a jet: ONE launch (the junction kernels of the maxdim-2 step), forward and backward
-  const int Tin = pool_blocks(d.latent_pool) * d.tau_v, CLe = d.enc_channels[d.n_levels], C0d = d.dec_channels[0];
+  const int Tin = dec_tin(d), CLe = d.enc_channels[d.n_levels], C0d = d.dec_channels[0];
   LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, g.ea, g.lat_s, g.lat_v, st, nullptr, /*with_latent=*/false));
   LGN_TRY(junction_fwd(B, N, CLe, d.tau_s, d.tau_v, d.latent_pool, g.ea.sL, g.ea.vL, params + enc_off[S.out0(false)],
                        params + enc_off[S.out0(false) + 1], g.lat_s, g.lat_v, g.ea.idx, C0d, params + dec_off[1], params + dec_off[2],
@@ -868,10 +927,11 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   dq.cap = g.ds.parts_size;
   RadFinJob fin{};
   {
-    DQ_NEW(part, (size_t)B * 2 * CL);
+    const RowLayout ro = dec_output_rows(d, CL);
+    DQ_NEW(part, (size_t)B * ro.width);
     LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part,
-                                    g.ds.gv, part, st));
-    dq.add(part, B, 2 * CL, 0, 2 * CL, grads + dec_off[S.out0(true) + 1]);
+                            g.ds.gv, part, st));
+    ro.add(dq, part, B, grads, dec_off);
   }
   std::vector<UnpackJob> post;
   double* part_in = nullptr;
@@ -896,17 +956,7 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
     return 0;
   }
   LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st, nullptr, &dq, &fin, &jb));
-  if (tail && !(d.flags & LGN_NET_SPLIT_TAIL)) {
-    const int rc = step_tail(dq.segs, fin, *tail, st);
-    if (rc == 0) return 0;
-    if (rc != -2) return rc;
-  }
-  LGN_TRY(dq.flush(st));
-  LGN_TRY(rad_finalize_batch(fin, st));
-  if (tail)
-    LGN_TRY(finalize_step(tail->w, tail->g, tail->n, tail->loss_part, tail->nB, tail->lambda, tail->m, tail->v, tail->step_dev, tail->lr,
-                          tail->beta1, tail->beta2, tail->eps, tail->do_adam, tail->loss_out, st));
-  return 0;
+  return end_step(dq, fin, grads, n_params, /*counters=*/nullptr, d.flags, tail, st);
 }
 
 }  // namespace
@@ -957,7 +1007,7 @@ NetScratch carve_scratch(const lgn_net_desc& d, bool dec, double* base) {
   Work& w = s.w;
   Bump b{base};
   const size_t BN = (size_t)d.B * d.N;
-  const int L = d.n_levels, Ts = d.tau_s, Tv = d.tau_v;
+  const int L = d.n_levels;
   const int* ch = dec ? d.dec_channels : d.enc_channels;
   int cmax = 0;
   for (int l = 0; l <= L; ++l) cmax = cmax > ch[l] ? cmax : ch[l];
@@ -966,7 +1016,7 @@ NetScratch carve_scratch(const lgn_net_desc& d, bool dec, double* base) {
     w.tail_cnt = b.take(8);
     w.zeros_s = b.take(2 * BN * cmax);
     w.g_p = b.take(dec ? 8 * BN : 0);
-    w.g_lat_s = b.take(dec ? 0 : (size_t)2 * d.B * pool_blocks(d.latent_pool) * Ts);
+    w.g_lat_s = b.take(dec ? 0 : (size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s);
     w.zero_doubles = b.off - z0;
   }
   for (int q = 0; q < 2; ++q) {
@@ -975,24 +1025,8 @@ NetScratch carve_scratch(const lgn_net_desc& d, bool dec, double* base) {
   }
   w.gsmix = b.take(2 * BN * cmax);
   w.g_ag = b.take(20 * BN * cmax);
-  size_t psum = 0;
-  for (int l = 0; l < L; ++l) {
-    int rm, rr;
-    level_bwd_partial_rows(d.B, d.N, dec, d.flags, &rm, &rr);
-    const size_t nmix = (size_t)4 * ch[l + 1] * 5 * ch[l], nrad = rad_partial_size(ch[l], dec);
-    psum += ((rm * nmix + 15) & ~size_t(15)) + ((rr * nrad + 15) & ~size_t(15));
-    psum += (mlp_part_rows(d, dec, l) * mlp_psize(ch[l + 1], d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) + 15) & ~size_t(15);
-    w.tot[dec ? 1 : 0][l] = b.take(nrad + 16);
-  }
-  // input / output ends: decoder  B x (2 C_L) + B x (4 C_0 + 2 N Tin);  encoder  B x 2 (Ts + Tv) C_L + B x 4 C_0
-  const int Tin = d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * Tv;
-  if (dec) psum += (((size_t)d.B * 2 * ch[L] + 15) & ~size_t(15)) + (((size_t)d.B * (4 * ch[0] + 2 * (size_t)d.N * Tin) + 15) & ~size_t(15));
-  else {
-    int rm0, rr0;                                          // input-stage partial rows: one per workgroup of the first level's backward
-    level_bwd_partial_rows(d.B, d.N, 0, d.flags, &rm0, &rr0);
-    if (rm0 < d.B) rm0 = d.B;
-    psum += (((size_t)d.B * 2 * (Ts + Tv) * pool_mix_in(d.latent_pool, d.N, ch[L]) + 15) & ~size_t(15)) + (((size_t)rm0 * (2 * in_K(d) + 2) * ch[0] + 15) & ~size_t(15));
-  }
+  for (int l = 0; l < L; ++l) w.tot[dec ? 1 : 0][l] = b.take(rad_partial_size(ch[l], dec) + 16);
+  const size_t psum = net_parts(d, dec, d.N);
   w.parts = b.take(psum);
   w.parts_size = psum;
   s.total = b.off;
@@ -1068,7 +1102,7 @@ int lgn_encoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
   hipStream_t st = (hipStream_t)stream;
   Work& w = sc.w;
   const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, B = d->B, N = d->N, Ts = d->tau_s, Tv = d->tau_v;
+  const int L = d->n_levels, B = d->B, N = d->N;
   const int* ce = d->enc_channels;
   LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, w.zero0(), w.zero_doubles, st));
   Deferred dq;
@@ -1077,25 +1111,22 @@ int lgn_encoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
   RadFinJob fin{};
   int cur = 0;
   {
-    const int CL = ce[L], KL = pool_mix_in(d->latent_pool, N, CL), rowe = 2 * (Ts + Tv) * KL;
-    DQ_NEW(parte, (size_t)B * rowe);
-    LGN_TRY(enc_latent_bwd(B, N, CL, Ts, Tv, d->latent_pool, a.n.s[L], a.n.v[L], params + off[S.out0(false)], params + off[S.out0(false) + 1],
-                           g_lat_s ? g_lat_s : w.g_lat_s, g_lat_v, a.idx, w.gs[cur], w.gv[cur], parte, st));
-    dq.add(parte, B, rowe, 0, 2 * Ts * KL, grads + off[S.out0(false)]);
-    dq.add(parte, B, rowe, 2 * Ts * KL, 2 * Tv * KL, grads + off[S.out0(false) + 1]);
+    const RowLayout rl = enc_latent_rows(*d, N, ce[L]);
+    DQ_NEW(parte, (size_t)B * rl.width);
+    LGN_TRY(enc_latent_bwd(B, N, ce[L], d->tau_s, d->tau_v, d->latent_pool, a.n.s[L], a.n.v[L], params + off[S.out0(false)],
+                           params + off[S.out0(false) + 1], g_lat_s ? g_lat_s : w.g_lat_s, g_lat_v, a.idx, w.gs[cur], w.gv[cur], parte, st));
+    rl.add(dq, parte, B, grads, off);
   }
   // without an upstream gradient on the latent scalars the last level's scalars (and its CGMLP) receive none
-  double* const in0_grads[2] = {grads + off[0], grads + off[1]};
   bool in0_done = false;
   const int K = in_K(*d);      // (several input scalars: the input stage's backward is its own launch, nothing rides)
   LGN_TRY(levels_bwd(*d, false, ce, params, grads, off, a.n, p4, mask, w, dq, fin, cur, /*has_s_grad=*/g_lat_s != nullptr, st,
-                     K > 1 ? nullptr : in0_grads, &in0_done));
+                     K > 1 ? nullptr : &in0_done));
   if (!in0_done) {
-    const int C0 = ce[0], row = (2 * K + 2) * C0;
-    DQ_NEW(part, (size_t)B * row);
-    LGN_TRY(enc_input_bwd(B, N, C0, K, p4, in_scalars, w.gs[cur], w.gv[cur], part, st));
-    dq.add(part, B, row, 0, 2 * C0 * K, grads + off[0]);
-    dq.add(part, B, row, 2 * C0 * K, 2 * C0, grads + off[1]);
+    const RowLayout ri = enc_input_rows(K, ce[0]);
+    DQ_NEW(part, (size_t)B * ri.width);
+    LGN_TRY(enc_input_bwd(B, N, ce[0], K, p4, in_scalars, w.gs[cur], w.gv[cur], part, st));
+    ri.add(dq, part, B, grads, off);
   }
   LGN_CHECK_ARG(dq.off <= dq.cap, "encoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
   // (measured at cfg2, captured module step: the one-launch form is 3 us SLOWER for the encoder alone -- 0.5966 against 0.5937 ms)
@@ -1119,9 +1150,9 @@ int lgn_decoder_fwd_f64(const lgn_net_desc* d, const double* params, const int64
   LGN_CHECK_ARG((long long)a.total <= act_doubles, "decoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, a.total);
   hipStream_t st = (hipStream_t)stream;
   const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, Tin = d->tau_v_in > 0 ? d->tau_v_in : pool_blocks(d->latent_pool) * d->tau_v;
+  const int L = d->n_levels;
   const int* cd = d->dec_channels;
-  LGN_TRY(dec_input_fwd(d->B, d->N, cd[0], Tin, lat_v, params + off[1], params + off[2], params + off[3], a.pdec, a.n.s[0], a.n.v[0], st));
+  LGN_TRY(dec_input_fwd(d->B, d->N, cd[0], dec_tin(*d), lat_v, params + off[1], params + off[2], params + off[3], a.pdec, a.n.s[0], a.n.v[0], st));
   LGN_TRY(levels_fwd(*d, true, cd, params, off, a.n, a.pdec, nullptr, st));
   LGN_TRY(dec_output_fwd(d->B, d->N, cd[L], a.n.v[L], params + off[S.out0(true) + 1], recon, st));
   return 0;
@@ -1147,9 +1178,10 @@ int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
     dq.parts = gs.parts;
     dq.cap = gs.parts_size;
     RadFinJob fin{};
-    DQ_NEW(part, (size_t)d->B * 2 * CL);
+    const RowLayout ro = dec_output_rows(*d, CL);
+    DQ_NEW(part, (size_t)d->B * ro.width);
     LGN_TRY(dec_output_bwd(d->B, d->N, CL, ga.vL, params + off[Sg.out0(true) + 1], g_recon, gs.gv, part, gst));
-    dq.add(part, d->B, 2 * CL, 0, 2 * CL, grads + off[Sg.out0(true) + 1]);
+    ro.add(dq, part, d->B, grads, off);
     std::vector<UnpackJob> post;
     LGN_TRY(gen_decoder_bwd(*d, params, grads, off, lat_v, ga, g_lat_v, gs, dq, fin, post, gst));
     LGN_CHECK_ARG(dq.off <= dq.cap, "decoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
@@ -1164,7 +1196,7 @@ int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
   hipStream_t st = (hipStream_t)stream;
   Work& w = sc.w;
   const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, B = d->B, N = d->N, Tin = d->tau_v_in > 0 ? d->tau_v_in : pool_blocks(d->latent_pool) * d->tau_v;
+  const int L = d->n_levels, B = d->B, N = d->N, Tin = dec_tin(*d);
   const int* cd = d->dec_channels;
   LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, w.zero0(), w.zero_doubles, st));
   Deferred dq;
@@ -1173,23 +1205,20 @@ int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
   RadFinJob fin{};
   int cur = 0;
   {
-    DQ_NEW(part, (size_t)B * 2 * cd[L]);
+    const RowLayout ro = dec_output_rows(*d, cd[L]);
+    DQ_NEW(part, (size_t)B * ro.width);
     LGN_TRY(dec_output_bwd(B, N, cd[L], a.n.v[L], params + off[S.out0(true) + 1], g_recon, w.gv[cur], part, st));
-    dq.add(part, B, 2 * cd[L], 0, 2 * cd[L], grads + off[S.out0(true) + 1]);
+    ro.add(dq, part, B, grads, off);
   }
   LGN_TRY(levels_bwd(*d, true, cd, params, grads, off, a.n, a.pdec, nullptr, w, dq, fin, cur, /*has_s_grad=*/false, st));
   {
-    const int C0 = cd[0], row = 4 * C0 + 2 * N * Tin;
-    DQ_NEW(part, (size_t)B * row);
-    LGN_TRY(dec_input_bwd(B, N, C0, Tin, lat_v, params + off[1], params + off[3], a.pdec, w.g_p, w.gs[cur], w.gv[cur], g_lat_v, part, st));
-    dq.add(part, B, row, 0, 2 * C0, grads + off[2]);
-    dq.add(part, B, row, 2 * C0, 2 * C0, grads + off[3]);
-    dq.add(part, B, row, 4 * C0, 2 * N * Tin, grads + off[1]);
+    const RowLayout ri = dec_input_rows(cd[0], N, Tin);
+    DQ_NEW(part, (size_t)B * ri.width);
+    LGN_TRY(dec_input_bwd(B, N, cd[0], Tin, lat_v, params + off[1], params + off[3], a.pdec, w.g_p, w.gs[cur], w.gv[cur], g_lat_v, part, st));
+    ri.add(dq, part, B, grads, off);
   }
   LGN_CHECK_ARG(dq.off <= dq.cap, "decoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-  LGN_TRY(dq.flush(st));
-  LGN_TRY(rad_finalize_batch(fin, st));
-  return 0;
+  return finish_reductions(dq, fin, grads, n_params, /*counters=*/nullptr, d->flags, st);
 }
 
 }  // extern "C"
@@ -1210,7 +1239,7 @@ long long lgn_junction_lds_bytes(int N, int CL, int Ts, int Tv, int pool, int C0
 }
 
 long long lgn_step_workspace_doubles(const lgn_net_desc* d) {
-  if (check_desc(d)) return -1;
+  if (check_desc(d) || check_latent_match(*d)) return -1;
   if (is_generic(*d, false) || is_generic(*d, true)) {
     if (check_generic(*d, false) || check_generic(*d, true)) return -1;
     return (long long)carve_gen_step(*d, nullptr).total;
@@ -1219,196 +1248,114 @@ long long lgn_step_workspace_doubles(const lgn_net_desc* d) {
 }
 
 }  // extern "C"
-// The step of networks that do not share their nodes or take more input scalars than the mass (jet_features: the encoder works on
-// N + 1 nodes, lgn/models/lgn_encoder.py:372-411; data['scalars']): the same level stacks, the four end stages as launches of their
-// own (no junction kernels, no riding input stage) -- every one of them takes its network's node count.
-static int step_fwd_bwd_split(const lgn_net_desc& d, Work& w, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                              const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                              double* recon, double* loss_part, hipStream_t st, const StepTailArgs* tail) {
+// forward + backward of a training step, ended by end_step.  Two forms of the same level stacks:
+//   fused: both networks on the same N nodes, the mass the only input scalar -- the encoder's input stage (and the clearing of the
+//          gradients and the zero block) rides on its first level's kernel, the latent stage and the decoder's input stage are one
+//          junction kernel in each direction, the input stage's backward may ride on the first level's backward;
+//   split (step_is_split: jet_features gives the encoder N + 1 nodes, lgn/models/lgn_encoder.py:372-411; data['scalars'] more input
+//          scalars): the four end stages are launches of their own, each on its network's node count, and nothing rides.
+static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, long long n_params, const int64_t* enc_off,
+                        const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
+                        const StepTailArgs* tail) {
+  if (int rc = check_desc(dp)) return rc;
+  const lgn_net_desc& d = *dp;
+  LGN_CHECK_ARG(params && grads && enc_off && dec_off && p4 && target && mask && workspace && recon && loss_part && n_params > 0,
+                "step_fwd_bwd: null pointer");
+  LGN_CHECK_ARG(d.n_in_scalars <= 1 || in_scalars, "step_fwd_bwd: %d input scalars per node, but in_scalars is NULL", d.n_in_scalars);
+  if (int rc = check_latent_match(d)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool split = step_is_split(d);
+  if (is_generic(d, false) || is_generic(d, true)) {
+    LGN_CHECK_ARG(!split, "step_fwd_bwd: table-driven networks take the mass as the only input scalar and one node count "
+                  "for both networks (n_in_scalars=%d, N=%d, dec_N=%d): use the per-network calls", d.n_in_scalars, d.N, d.dec_N);
+    return gen_step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, workspace, workspace_doubles, recon,
+                            loss_part, st, tail);
+  }
+  Work w = carve(d, workspace);
+  // the layout depends on run-time switches (LGN_AMD_DEC_PAIRWISE / LGN_AMD_LEVEL_V2 change the partial-row counts):
+  // refuse before anything is enqueued if the caller sized the workspace under different settings
+  LGN_CHECK_ARG((long long)w.total <= workspace_doubles, "step: workspace holds %lld doubles, this configuration needs %zu",
+                workspace_doubles, w.total);
+  // MLP parameter blocks must be contiguous (W_0, b_0, W_1, b_1, ...) for the single-reduce path
   if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
   if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
-  lgn_net_desc de = d, dd = d;                   // per-network views of the descriptor: the level sequencers read B, N, flags, MLP shape
+  lgn_net_desc dd = d;               // the decoder's view of the descriptor: the level sequencers read B, N, flags, MLP shape
   dd.N = dec_nodes(d);
   const Slots S{d.n_levels, d.mlp_nlin};
-  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dd.N, Ts = d.tau_s, Tv = d.tau_v, K = in_K(d);
+  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dd.N, Ts = d.tau_s, Tv = d.tau_v, K = in_K(d), Tin = dec_tin(d);
   const int* ce = d.enc_channels;
   const int* cd = d.dec_channels;
-  const int Tin = pool_blocks(d.latent_pool) * Tv;
-  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step: the decoder must consume the encoder's %d pooled latent vectors", Tin);
+  const double* wl0 = params + enc_off[S.out0(false)];
+  const double* wl1 = params + enc_off[S.out0(false) + 1];
   Deferred dq;
   dq.parts = w.parts;
   dq.cap = w.parts_size;
   RadFinJob fin{};
-  LGN_TRY(zero_ranges(grads, (size_t)n_params, w.zero0(), w.zero_doubles, nullptr, 0, st));
+
   // ---------------- forward ----------------
-  LGN_TRY(enc_input_fwd(B, Ne, ce[0], K, p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
-  LGN_TRY(levels_fwd(de, false, ce, params, enc_off, w.enc, p4, mask, st));
-  LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], params + enc_off[S.out0(false)],
-                         params + enc_off[S.out0(false) + 1], w.lat_s, w.lat_v, w.idx, st));
-  LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
-                        w.dec.v[0], st));
+  if (split) {
+    LGN_TRY(zero_ranges(grads, (size_t)n_params, w.zero0(), w.zero_doubles, nullptr, 0, st));
+    LGN_TRY(enc_input_fwd(B, Ne, ce[0], K, p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st));
+    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, st));
+    LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
+                          w.dec.v[0], st));
+  } else {
+    // the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s
+    // (the encoder's input stage and the two clears ride on the first level's kernel: levels_fwd / InputStage)
+    const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, w.zeros_s, w.zero_doubles};
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0));
+    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, cd[0],
+                         params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
+  }
+  // ---------------- loss (and its backward), on the last decoder level's kernel when that is one workgroup per jet ----------
   int cur = 0;
   {
-    DQ_NEW(part, (size_t)B * 2 * cd[L]);
+    const RowLayout ro = dec_output_rows(d, cd[L]);
+    DQ_NEW(part, (size_t)B * ro.width);
     const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, w.gv[cur], part};
     const bool rides = level_fwd_carries_loss(Nd, d.flags);
     LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr));
     if (!rides)
       LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
-    dq.add(part, B, 2 * cd[L], 0, 2 * cd[L], grads + dec_off[S.out0(true) + 1]);
+    ro.add(dq, part, B, grads, dec_off);
   }
+
   // ---------------- backward ----------------
   LGN_TRY(levels_bwd(dd, true, cd, params, grads, dec_off, w.dec, w.pdec, nullptr, w, dq, fin, cur, /*has_s_grad=*/false, st));
   {
-    const int C0 = cd[0], row = 4 * C0 + 2 * Nd * Tin;
-    const int CL = ce[L], KL = pool_mix_in(d.latent_pool, Ne, CL), rowe = 2 * (Ts + Tv) * KL;
-    DQ_NEW(part, (size_t)B * row);
-    DQ_NEW(parte, (size_t)B * rowe);
-    const int rd = cur, wr = cur ^ 1;
-    cur = wr;
-    LGN_TRY(dec_input_bwd(B, Nd, C0, Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd], w.g_lat_v,
-                          part, st));
-    // the decoder never reads the latent scalars (SURVEY fact 7): their gradient is the zero block's g_lat_s
-    LGN_TRY(enc_latent_bwd(B, Ne, CL, Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], params + enc_off[S.out0(false)],
-                           params + enc_off[S.out0(false) + 1], w.g_lat_s, w.g_lat_v, w.idx, w.gs[wr], w.gv[wr], parte, st));
-    dq.add(part, B, row, 0, 2 * C0, grads + dec_off[2]);
-    dq.add(part, B, row, 2 * C0, 2 * C0, grads + dec_off[3]);
-    dq.add(part, B, row, 4 * C0, 2 * Nd * Tin, grads + dec_off[1]);
-    dq.add(parte, B, rowe, 0, 2 * Ts * KL, grads + enc_off[S.out0(false)]);
-    dq.add(parte, B, rowe, 2 * Ts * KL, 2 * Tv * KL, grads + enc_off[S.out0(false) + 1]);
-  }
-  LGN_TRY(levels_bwd(de, false, ce, params, grads, enc_off, w.enc, p4, mask, w, dq, fin, cur, /*has_s_grad=*/false, st));
-  {
-    const int C0 = ce[0], row = (2 * K + 2) * C0;
-    DQ_NEW(part, (size_t)B * row);
-    LGN_TRY(enc_input_bwd(B, Ne, C0, K, p4, in_scalars, w.gs[cur], w.gv[cur], part, st));
-    dq.add(part, B, row, 0, 2 * C0 * K, grads + enc_off[0]);
-    dq.add(part, B, row, 2 * C0 * K, 2 * C0, grads + enc_off[1]);
-  }
-  LGN_CHECK_ARG(dq.off <= dq.cap, "step: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-  if (tail && !(d.flags & LGN_NET_SPLIT_TAIL)) {
-    const int rc = step_tail(dq.segs, fin, *tail, st);
-    if (rc == 0) return 0;
-    if (rc != -2) return rc;
-  }
-  LGN_TRY(finish_reductions(dq, fin, grads, n_params, tail ? nullptr : w.tail_cnt, d.flags, st));
-  if (tail)
-    LGN_TRY(finalize_step(tail->w, tail->g, tail->n, tail->loss_part, tail->nB, tail->lambda, tail->m, tail->v, tail->step_dev, tail->lr,
-                          tail->beta1, tail->beta2, tail->eps, tail->do_adam, tail->loss_out, st));
-  return 0;
-}
-
-// forward + backward of a training step; with `tail` (single process: nothing sits between the gradients and the optimiser) the
-// deferred reductions, the radial finalisation, L1 + Adam and the loss assembly are ONE launch (step_tail.hip) instead of three
-static int step_fwd_bwd(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                        const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
-                        const StepTailArgs* tail) {
-  if (int rc = check_desc(d)) return rc;
-  LGN_CHECK_ARG(params && grads && enc_off && dec_off && p4 && target && mask && workspace && recon && loss_part && n_params > 0,
-                "step_fwd_bwd: null pointer");
-  LGN_CHECK_ARG(d->n_in_scalars <= 1 || in_scalars, "step_fwd_bwd: %d input scalars per node, but in_scalars is NULL", d->n_in_scalars);
-  hipStream_t st = (hipStream_t)stream;
-  if (is_generic(*d, false) || is_generic(*d, true)) {
-    LGN_CHECK_ARG(!step_is_split(*d), "step_fwd_bwd: table-driven networks take the mass as the only input scalar and one node count "
-                  "for both networks (n_in_scalars=%d, N=%d, dec_N=%d): use the per-network calls", d->n_in_scalars, d->N, d->dec_N);
-    return gen_step_fwd_bwd(*d, params, grads, n_params, enc_off, dec_off, p4, target, mask, workspace, workspace_doubles, recon,
-                            loss_part, st, tail);
-  }
-  Work w = carve(*d, workspace);
-  // the layout depends on run-time switches (LGN_AMD_DEC_PAIRWISE / LGN_AMD_LEVEL_V2 change the partial-row counts):
-  // refuse before anything is enqueued if the caller sized the workspace under different settings
-  LGN_CHECK_ARG((long long)w.total <= workspace_doubles, "step: workspace holds %lld doubles, this configuration needs %zu",
-                workspace_doubles, w.total);
-  const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, B = d->B, N = d->N, Ts = d->tau_s, Tv = d->tau_v;
-  const int* ce = d->enc_channels;
-  const int* cd = d->dec_channels;
-  if (step_is_split(*d))
-    return step_fwd_bwd_split(*d, w, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, recon, loss_part, st, tail);
-  // MLP parameter blocks must be contiguous (W_0, b_0, W_1, b_1, ...) for the single-reduce path
-  for (int dec = 0; dec < 2; ++dec) {
-    const int64_t* off = dec ? dec_off : enc_off;
-    const int* ch = dec ? cd : ce;
-    for (int l = 0; l < L; ++l) {
-      const int D = 2 * ch[l + 1], H = d->mlp_hidden_mul * D;
-      int64_t expect = off[S.mlp(dec, l, 0)];
-      for (int q = 0; q < d->mlp_nlin; ++q) {
-        const int hin = q == 0 ? D : H, hout = q == d->mlp_nlin - 1 ? D : H;
-        LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q)] == expect, "step: MLP weights are not contiguous in the flat parameter buffer");
-        expect += (int64_t)hin * hout;
-        LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q + 1)] == expect, "step: MLP biases are not contiguous in the flat parameter buffer");
-        expect += hout;
-      }
-    }
-  }
-  Deferred dq;
-  dq.parts = w.parts;
-  dq.cap = w.parts_size;
-  RadFinJob fin{};
-
-  // ---------------- forward ----------------
-  // the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s
-  // (the encoder's input stage and the two clears ride on the first level's kernel: levels_fwd / InputStage)
-  const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, w.zeros_s, w.zero_doubles};
-  LGN_TRY(levels_fwd(*d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0));
-  LGN_TRY(junction_fwd(B, N, ce[L], Ts, Tv, d->latent_pool, w.enc.s[L], w.enc.v[L], params + enc_off[S.out0(false)],
-                       params + enc_off[S.out0(false) + 1], w.lat_s, w.lat_v, w.idx, cd[0], params + dec_off[1], params + dec_off[2],
-                       params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
-  // ---------------- loss (and its backward), on the last decoder level's kernel when that is one workgroup per jet ----------
-  int cur = 0;
-  {
-    DQ_NEW(part, (size_t)B * 2 * cd[L]);
-    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d->get_real, d->jet_loss_scale, recon, loss_part, w.gv[cur], part};
-    const bool rides = level_fwd_carries_loss(N, d->flags);
-    LGN_TRY(levels_fwd(*d, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr));
-    if (!rides)
-      LGN_TRY(dec_output_loss(B, N, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
-    dq.add(part, B, 2 * cd[L], 0, 2 * cd[L], grads + dec_off[S.out0(true) + 1]);
-  }
-
-  // ---------------- backward ----------------
-  LGN_TRY(levels_bwd(*d, true, cd, params, grads, dec_off, w.dec, w.pdec, nullptr, w, dq, fin, cur, /*has_s_grad=*/false, st));
-  {
-    const int C0 = cd[0], Tin = pool_blocks(d->latent_pool) * Tv, row = 4 * C0 + 2 * N * Tin;
-    const int CL = ce[L], KL = pool_mix_in(d->latent_pool, N, CL), rowe = 2 * (Ts + Tv) * KL;
-    DQ_NEW(part, (size_t)B * row);
-    DQ_NEW(parte, (size_t)B * rowe);
+    const RowLayout ri = dec_input_rows(cd[0], Nd, Tin), rl = enc_latent_rows(d, Ne, ce[L]);
+    DQ_NEW(part, (size_t)B * ri.width);
+    DQ_NEW(parte, (size_t)B * rl.width);
     // reads the gradient w.r.t. the decoder's level-0 features, writes the one w.r.t. the encoder's last level into the
     // other buffer pair (jets do not occupy the same slices when the two channel counts differ)
     const int rd = cur, wr = cur ^ 1;
     cur = wr;
-    LGN_TRY(junction_bwd(B, N, C0, Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd], w.g_lat_v, part,
-                         CL, Ts, Tv, d->latent_pool, w.enc.s[L], w.enc.v[L], params + enc_off[S.out0(false)], params + enc_off[S.out0(false) + 1],
-                         w.g_lat_s, w.idx, w.gs[wr], w.gv[wr], parte, st));
-    dq.add(part, B, row, 0, 2 * C0, grads + dec_off[2]);
-    dq.add(part, B, row, 2 * C0, 2 * C0, grads + dec_off[3]);
-    dq.add(part, B, row, 4 * C0, 2 * N * Tin, grads + dec_off[1]);
-    dq.add(parte, B, rowe, 0, 2 * Ts * KL, grads + enc_off[S.out0(false)]);
-    dq.add(parte, B, rowe, 2 * Ts * KL, 2 * Tv * KL, grads + enc_off[S.out0(false) + 1]);
+    // the decoder never reads the latent scalars (SURVEY fact 7): their gradient is the zero block's g_lat_s
+    if (split) {
+      LGN_TRY(dec_input_bwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd],
+                            w.g_lat_v, part, st));
+      LGN_TRY(enc_latent_bwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.g_lat_s, w.g_lat_v, w.idx, w.gs[wr],
+                             w.gv[wr], parte, st));
+    } else {
+      LGN_TRY(junction_bwd(B, Ne, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd], w.g_lat_v,
+                           part, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.g_lat_s, w.idx, w.gs[wr], w.gv[wr], parte, st));
+    }
+    ri.add(dq, part, B, grads, dec_off);
+    rl.add(dq, parte, B, grads, enc_off);
   }
-  double* const in0_grads[2] = {grads + enc_off[0], grads + enc_off[1]};
+  // the input stage's backward rides on the first level's where it can -- fused form only (split: its own launch, even with K = 1)
   bool in0_done = false;
-  LGN_TRY(levels_bwd(*d, false, ce, params, grads, enc_off, w.enc, p4, mask, w, dq, fin, cur, /*has_s_grad=*/false, st, in0_grads, &in0_done));
-  if (!in0_done) {      // (three-kernel level backward: N > 40, LGN_AMD_LEVEL_V2)
-    const int C0 = ce[0];
-    DQ_NEW(part, (size_t)B * 4 * C0);
-    LGN_TRY(enc_input_bwd(B, N, C0, 1, p4, nullptr, w.gs[cur], w.gv[cur], part, st));
-    dq.add(part, B, 4 * C0, 0, 2 * C0, grads + enc_off[0]);
-    dq.add(part, B, 4 * C0, 2 * C0, 2 * C0, grads + enc_off[1]);
+  LGN_TRY(levels_bwd(d, false, ce, params, grads, enc_off, w.enc, p4, mask, w, dq, fin, cur, /*has_s_grad=*/false, st,
+                     split ? nullptr : &in0_done));
+  if (!in0_done) {      // (split, or the three-kernel level backward: N > 40, LGN_AMD_LEVEL_V2)
+    const RowLayout ri = enc_input_rows(K, ce[0]);
+    DQ_NEW(part, (size_t)B * ri.width);
+    LGN_TRY(enc_input_bwd(B, Ne, ce[0], K, p4, split ? in_scalars : nullptr, w.gs[cur], w.gv[cur], part, st));
+    ri.add(dq, part, B, grads, enc_off);
   }
-  LGN_CHECK_ARG(dq.off <= dq.cap, "step: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-  if (tail && !(d->flags & LGN_NET_SPLIT_TAIL)) {
-    const int rc = step_tail(dq.segs, fin, *tail, st);
-    if (rc == 0) return 0;
-    if (rc != -2) return rc;                   // -2: does not fit the fused form -> the separate launches below
-  }
-  // (data-parallel step: the all-reduce follows -- reductions + radial finalisation as one launch where that fits)
-  LGN_TRY(finish_reductions(dq, fin, grads, n_params, tail ? nullptr : w.tail_cnt, d->flags, st));
-  if (tail)
-    LGN_TRY(finalize_step(tail->w, tail->g, tail->n, tail->loss_part, tail->nB, tail->lambda, tail->m, tail->v, tail->step_dev, tail->lr,
-                          tail->beta1, tail->beta2, tail->eps, tail->do_adam, tail->loss_out, st));
-  return 0;
+  return end_step(dq, fin, grads, n_params, w.tail_cnt, d.flags, tail, st);
 }
 extern "C" {
 
@@ -1534,15 +1481,14 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
                 "step_eval: null pointer");
   LGN_CHECK_ARG(d.n_in_scalars <= 1 || in_scalars, "step_eval: %d input scalars per node, but in_scalars is NULL", d.n_in_scalars);
   LGN_CHECK_ARG(!lat_s_out == !lat_v_out, "step_eval: give both latent outputs or neither");
-  const int Tin = pool_blocks(d.latent_pool) * d.tau_v;
-  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step_eval: the decoder must consume the encoder's %d pooled latent vectors", Tin);
+  if (int rc = check_latent_match(d)) return rc;
   const long long need = eval_workspace(d);
   if (need < 0) return -1;
   LGN_CHECK_ARG(need <= workspace_doubles, "step_eval: workspace holds %lld doubles, this configuration needs %lld", workspace_doubles, need);
   if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
   if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
   const Slots S{d.n_levels, d.mlp_nlin};
-  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dec_nodes(d), Ts = d.tau_s, Tv = d.tau_v;
+  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dec_nodes(d), Ts = d.tau_s, Tv = d.tau_v, Tin = dec_tin(d);
   const int* ce = d.enc_channels;
   const int* cd = d.dec_channels;
   const double* wl0 = params + enc_off[S.out0(false)];
@@ -1571,7 +1517,7 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
   dd.N = Nd;
   const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
   const bool rides = level_fwd_carries_loss(Nd, d.flags);
-  if (step_is_split(d)) {            // the four end stages as launches of their own (step_fwd_bwd_split)
+  if (step_is_split(d)) {            // the four end stages as launches of their own (as in step_fwd_bwd)
     LGN_TRY(enc_input_fwd(B, Ne, ce[0], in_K(d), p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
     LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, /*eval=*/true));
     LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, ls, lv, w.idx, st));

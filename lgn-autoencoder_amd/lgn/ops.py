@@ -328,6 +328,28 @@ def slot_tensors(net, decoder: bool):
     return out
 
 
+def param_offsets(net, decoder: bool, desc, base: int, limit=None):
+    """Slot offsets of a network's parameters for the C ABI (lgn_step_param_slots / include/lgn_amd.h), in doubles from the device
+    address `base`, as a ctypes int64 array; every offset is >= 0 and, given `limit`, below it.  Checks the slot count against the
+    library and the per-level slot sizes the kernels assume."""
+    import ctypes as C
+    ts = slot_tensors(net, decoder)
+    want = N.lib().lgn_step_param_slots(C.byref(desc), int(decoder))
+    if want < 0:
+        raise RuntimeError(N.last_error())
+    assert len(ts) == want, (len(ts), want)
+    L, ch, fused, first = net.num_cg_levels, net.num_channels, native_kind(net) == "fused", 2 if decoder else 0
+    for l in range(L):
+        mix0 = ts[first + 2 + 7 * L + 2 * l]
+        assert not fused or mix0.numel() == 2 * ch[l + 1] * 5 * ch[l], "CatMix weight is not [2][CO][5C]: not a maxdim=2 level"
+        rf = net.rad_funcs.rad_funcs[l]      # (num_basis_fn < 10: stored 20 wide, zero padded -- lgn/nn: RadPolyTrig._kernel_pad)
+        assert rf.kernel_params()[0].numel() == 20 and rf.kernel_params()[0].data_ptr() == ts[first + 2 + 7 * l].data_ptr(), \
+            "the radial parameters must be stored 20 bells wide"
+    offs = [(t.data_ptr() - base) // 8 for t in ts]
+    assert all(0 <= o and (limit is None or o < limit) for o in offs)
+    return (C.c_int64 * len(offs))(*offs)
+
+
 def flat_level_tables(net, lvl: int):
     """Device tables of a table-driven level whose CatMix weight offsets point into the network's flat parameter block
     (relative to the level's lowest-addressed CatMix weight); cached until the block moves."""
@@ -389,16 +411,8 @@ class NetHandle:
         d.mlp_hidden_mul, d.mlp_nlin = net.mlp_width, net.mlp_depth + 1
         d.activation = N.activation_id(net.activation)
         lib = N.lib()
-        slots = slot_tensors(net, decoder)
-        want = lib.lgn_step_param_slots(C.byref(d), int(decoder))
-        if want < 0:
-            raise RuntimeError(N.last_error())
-        assert len(slots) == want, (len(slots), want)
-        base = net.flat_params.data_ptr()
-        offs = [(t.data_ptr() - base) // 8 for t in slots]
-        assert all(0 <= o < net.flat_params.numel() for o in offs)
+        self.off = param_offsets(net, decoder, d, net.flat_params.data_ptr(), net.flat_params.numel())
         self.desc, self.ref = d, C.byref(d)
-        self.off = (C.c_int64 * len(offs))(*offs)
         self.n_act = lib.lgn_net_workspace_doubles(self.ref, int(decoder), 0)
         self.n_scratch = lib.lgn_net_workspace_doubles(self.ref, int(decoder), 1)
         if self.n_act < 0 or self.n_scratch < 0:

@@ -171,8 +171,7 @@ class ReferenceLoopStep:
 # fully native step: one C call for encoder -> decoder -> loss -> backward, captured in a HIP graph
 # ---------------------------------------------------------------------------------------------------
 
-from .ops import slot_tensors as _slot_tensors  # noqa: E402  (parameter slots of include/lgn_amd.h)
-from .ops import describe_network  # noqa: E402
+from .ops import describe_network, param_offsets  # noqa: E402  (descriptor and parameter slots of include/lgn_amd.h)
 
 
 def _capturing(graph, pool=None):
@@ -281,6 +280,25 @@ def _check_latent_match(d, encoder, decoder):
                          f"gives {N.pool_blocks(d.latent_pool)} x {d.tau_v} latent vectors, the decoder takes {decoder.tau_latent_vectors})")
 
 
+def _step_desc(encoder, decoder, B: int, split: bool, get_real_method: str, jet_loss_scale: float):
+    """The lgn_net_desc of a whole step (training or evaluation) on the two networks where their parameters are now, and the
+    objects it points into (keep them alive as long as the descriptor is used)."""
+    from . import _native as N
+    if N.activation_id(encoder.activation) != N.activation_id(decoder.activation):
+        raise NotImplementedError("the native step takes ONE activation for the CGMLPs of both networks (as --activation gives them); "
+                                  f"got {encoder.activation} / {decoder.activation}")
+    d = N.NetDesc()
+    d.B, d.N, d.n_levels = B, encoder.num_input_particles, encoder.num_cg_levels   # (num_input_particles counts the jet node of jet_features)
+    keep = describe_network(d, encoder, False) + describe_network(d, decoder, True)
+    d.mlp_hidden_mul, d.mlp_nlin = encoder.mlp_width, encoder.mlp_depth + 1
+    d.activation = N.activation_id(encoder.activation)
+    d.dec_N = decoder.num_output_particles if split else 0
+    d.get_real = get_real_code(get_real_method)
+    d.jet_loss_scale = jet_loss_scale
+    _check_latent_match(d, encoder, decoder)
+    return d, keep
+
+
 class NativeTrainStep:
     """Same step as TrainStep, executed by lgn_step_fwd_bwd_f64 / lgn_step_finalize_f64 (csrc/step.hip):
     no autograd graph, no PyTorch kernels, every buffer static.  With ``use_graph=True`` the two native calls
@@ -322,44 +340,14 @@ class NativeTrainStep:
         self.launches_per_step = None
         self.optimizer = optimizer
         dev, dt = self.flat.flat.device, self.flat.flat.dtype
-        L = encoder.num_cg_levels
-        d = N.NetDesc()
-        from .ops import describe_network, native_kind
-        d.B, d.N, d.n_levels = batch_size, encoder.num_input_particles, L       # (num_input_particles counts the jet node of jet_features)
-        self._keep = describe_network(d, encoder, False) + describe_network(d, decoder, True)    # (after FlatParams re-homed the blocks)
-        d.mlp_hidden_mul, d.mlp_nlin = encoder.mlp_width, encoder.mlp_depth + 1
-        if N.activation_id(encoder.activation) != N.activation_id(decoder.activation):
-            raise NotImplementedError("the native step takes ONE activation for the CGMLPs of both networks (as --activation gives them); "
-                                      f"got {encoder.activation} / {decoder.activation}")
-        d.activation = N.activation_id(encoder.activation)
-        fused = native_kind(encoder) == "fused"
-        d.dec_N = decoder.num_output_particles if self.split else 0
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
-        d.get_real = get_real_code(get_real_method)
-        d.jet_loss_scale = 1.0 / (4.0 * batch_size * self.world) if self.chamfer_jet_features else 0.0
-        _check_latent_match(d, encoder, decoder)
+        jscale = 1.0 / (4.0 * batch_size * self.world) if self.chamfer_jet_features else 0.0
+        # (after FlatParams re-homed the blocks)
+        d, self._keep = _step_desc(encoder, decoder, batch_size, self.split, get_real_method, jscale)
         self.desc = d
         lib = N.lib()
-        base = self.flat.flat.data_ptr()
-
-        def offsets(net, dec):
-            ts = _slot_tensors(net, dec)
-            want = lib.lgn_step_param_slots(C.byref(d), int(dec))
-            if want < 0:
-                raise RuntimeError(N.last_error())
-            assert len(ts) == want, (len(ts), want)
-            ch = net.num_channels
-            for l in range(L):                   # sizes the kernels assume for the per-level slots
-                mix0 = ts[(2 if dec else 0) + 2 + 7 * L + 2 * l]
-                assert not fused or mix0.numel() == 2 * ch[l + 1] * 5 * ch[l], "CatMix weight is not [2][CO][5C]: not a maxdim=2 level"
-                rf = net.rad_funcs.rad_funcs[l]      # (num_basis_fn < 10: stored 20 wide, zero padded -- lgn/nn: RadPolyTrig._kernel_pad)
-                assert rf.kernel_params()[0].numel() == 20 and rf.kernel_params()[0].data_ptr() == ts[(2 if dec else 0) + 2 + 7 * l].data_ptr(), \
-                    "the radial parameters must be stored 20 bells wide"
-            offs = [(t.data_ptr() - base) // 8 for t in ts]
-            assert all(0 <= o < self.flat.flat.numel() for o in offs)
-            return (C.c_int64 * len(offs))(*offs)
-
-        self.enc_off, self.dec_off = offsets(encoder, False), offsets(decoder, True)
+        base, n = self.flat.flat.data_ptr(), self.flat.flat.numel()
+        self.enc_off, self.dec_off = param_offsets(encoder, False, d, base, n), param_offsets(decoder, True, d, base, n)
         nws = lib.lgn_step_workspace_doubles(C.byref(d))
         if nws < 0:
             raise RuntimeError(N.last_error())
@@ -689,9 +677,6 @@ class NativeEvalStep:
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
-        if N.activation_id(encoder.activation) != N.activation_id(decoder.activation):
-            raise NotImplementedError("the native step takes ONE activation for the CGMLPs of both networks (as --activation gives them); "
-                                      f"got {encoder.activation} / {decoder.activation}")
         self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
         self.keep_latent, self.use_graph = bool(keep_latent), use_graph
@@ -721,32 +706,12 @@ class NativeEvalStep:
         N, enc, dec = self.N, self.encoder, self.decoder
         enc._check_views()
         dec._check_views()
-        L = enc.num_cg_levels
-        d = N.NetDesc()
-        d.B, d.N, d.n_levels = self.B, enc.num_input_particles, L
-        self._keep = describe_network(d, enc, False) + describe_network(d, dec, True)
-        d.mlp_hidden_mul, d.mlp_nlin = enc.mlp_width, enc.mlp_depth + 1
-        d.activation = N.activation_id(enc.activation)
-        d.dec_N = dec.num_output_particles if self.split else 0
-        d.get_real = get_real_code(self.get_real_method)
-        d.jet_loss_scale = 1.0 / (4.0 * self.B) if self.chamfer_jet_features else 0.0
-        _check_latent_match(d, enc, dec)
-        lib = N.lib()
+        d, self._keep = _step_desc(enc, dec, self.B, self.split, self.get_real_method,
+                                   1.0 / (4.0 * self.B) if self.chamfer_jet_features else 0.0)
         self._ptrs = (enc.flat_params.data_ptr(), dec.flat_params.data_ptr())
         self._base = min(self._ptrs)
-
-        def offsets(net, is_dec):
-            ts = _slot_tensors(net, is_dec)
-            want = lib.lgn_step_param_slots(C.byref(d), int(is_dec))
-            if want < 0:
-                raise RuntimeError(N.last_error())
-            assert len(ts) == want, (len(ts), want)
-            offs = [(t.data_ptr() - self._base) // 8 for t in ts]
-            assert all(o >= 0 for o in offs)
-            return (C.c_int64 * len(offs))(*offs)
-
-        self.enc_off, self.dec_off = offsets(enc, False), offsets(dec, True)
-        self._ws = lib.lgn_eval_workspace_doubles(C.byref(d))
+        self.enc_off, self.dec_off = param_offsets(enc, False, d, self._base), param_offsets(dec, True, d, self._base)
+        self._ws = N.lib().lgn_eval_workspace_doubles(C.byref(d))
         if self._ws < 0:
             raise RuntimeError(N.last_error())
         self.desc = d

@@ -75,3 +75,18 @@ def test_eval_refuses_an_unknown_get_real_code(code):
     d, _keep = _desc("cfg1", get_real=code)
     assert _call(d) != 0
     assert "get_real" in N.last_error()
+
+
+@pytest.mark.parametrize("tau_v_in", [5, 32])
+def test_training_step_refuses_a_decoder_that_does_not_take_the_pooled_latent(tau_v_in):
+    """The fused maxdim-2 training step (one node count, the mass the only input scalar) refuses a decoder whose tau_v_in is not the
+    encoder's pool_blocks * tau_v, before any launch (placeholder pointers), as the split, table-driven and evaluation steps do; the
+    workspace query refuses it too."""
+    d, _keep = _desc("cfg1", tau_v_in=tau_v_in)
+    lib = N.lib()
+    assert lib.lgn_step_workspace_doubles(C.byref(d)) == -1
+    assert "pooled latent" in N.last_error()
+    off = (C.c_int64 * 64)()
+    p = 8
+    assert lib.lgn_step_fwd_bwd_f64(C.byref(d), p, p, 1000, off, off, p, p, p, None, p, 1 << 40, p, p, None) != 0
+    assert "pooled latent" in N.last_error()
