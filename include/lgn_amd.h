@@ -390,6 +390,34 @@ int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* gra
 int lgn_chamfer_f64(int B, int N, int M, const double* x, const double* y, int jet_features, double* loss_part, double* gx, double* gy,
                     void* stream);
 
+/* ---- anomaly scores (the reference's anomaly_scores(), utils/jet_analysis/anomaly_detection.py, with include_emd=False) ---------
+ * recons, target, recons_n, target_n [B][N][4] real Cartesian (E, px, py, pz) 4-vectors (recons_n / target_n: the normalized
+ * jets).  One workgroup per jet; nothing is allocated, nothing waits on the host: capturable into a graph.  1 <= N <= LGN_ANOMALY_NMAX.
+ *   scores [B][LGN_ANOMALY_NSCORES] in the reference's key order (lgn/anomaly.py: SCORE_KEYS):
+ *      0..4 Chamfer, 5..9 Hungarian, 10..14 MSE in the Cartesian, polar, normalized Cartesian, normalized polar and relative polar
+ *      frames; 15 jet Cartesian; 16 jet "polar" (the reference scores it on the Cartesian jets: equal to 15); 17 Chamfer, 18 Hungarian,
+ *      19 MSE and 20 jet with the Minkowski square diag(+,-,-,-).  Nothing is masked: zero-padded rows take part, as in the reference.
+ *      Hungarian: col_ind = scipy's linear_sum_assignment of C[i][j] = |p_i - q_j| (Lorentz: the signed Minkowski square), and the
+ *      score is the reference's mean_r sum_c (p[col_ind[r]]_c - q[r]_c)^2 (Lorentz: on the Cartesian frame).
+ *   score_mask: bit k asks for score k (LGN_ANOMALY_ALL: every score); a score not asked for is written as NaN, and a Hungarian
+ *      variant not asked for is not solved (its col4row row is -1).  LGN_ANOMALY_NO_HUNGARIAN skips the six assignments.
+ *   col4row [6][B][N] (nullable) int32: col_ind of the Hungarian variants in score order (5..9, 18).
+ *   status [B] int32: bit v (v = 0..5) -- variant v has a NaN or -inf cost (scipy: "matrix contains invalid numeric entries");
+ *      bit 8 + v -- variant v is infeasible.  Either way its score is NaN and its col4row row -1.
+ * Replaces: anomaly_scores() and its helpers chamfer / hungarian / mse / *_lorentz / get_p4_polar / get_polar_rel. */
+#define LGN_ANOMALY_NMAX 192
+#define LGN_ANOMALY_NSCORES 21
+#define LGN_ANOMALY_ALL 0x1FFFFF
+#define LGN_ANOMALY_HUNGARIAN 0x403E0        /* bits 5..9 and 18 */
+#define LGN_ANOMALY_NO_HUNGARIAN (LGN_ANOMALY_ALL & ~LGN_ANOMALY_HUNGARIAN)
+int lgn_anomaly_scores_f64(const double* recons, const double* target, const double* recons_n, const double* target_n, int B, int N,
+                           int score_mask, double* scores, int* col4row /*nullable*/, int* status, void* stream);
+
+/* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
+ * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.
+ *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */
+int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,4 +191,24 @@ int lgn_local_bwd_f64(int nodes, int C, int CO, int Q, int Qout, const lgn_local
   return local_bwd(a, (hipStream_t)stream);
 }
 
+int lgn_anomaly_scores_f64(const double* recons, const double* target, const double* recons_n, const double* target_n, int B, int N,
+                           int score_mask, double* scores, int* col4row, int* status, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "anomaly_scores: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(N >= 1 && N <= LGN_ANOMALY_NMAX, "anomaly_scores: N = %d outside 1 .. %d", N, LGN_ANOMALY_NMAX);
+  LGN_CHECK_ARG(recons && target && recons_n && target_n, "anomaly_scores: null input pointer (recons, target, recons_n, target_n)");
+  LGN_CHECK_ARG(scores, "anomaly_scores: null scores");
+  LGN_CHECK_ARG(status, "anomaly_scores: null status");
+  LGN_CHECK_ARG((score_mask & ~LGN_ANOMALY_ALL) == 0, "anomaly_scores: unknown score_mask bits 0x%x", score_mask & ~LGN_ANOMALY_ALL);
+  return anomaly_scores(recons, target, recons_n, target_n, B, N, score_mask, scores, col4row, status, (hipStream_t)stream);
+}
+
+int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row, int* status, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "linear_sum_assignment: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(n >= 1 && n <= LGN_ANOMALY_NMAX, "linear_sum_assignment: n = %d outside 1 .. %d", n, LGN_ANOMALY_NMAX);
+  LGN_CHECK_ARG(cost, "linear_sum_assignment: null cost");
+  LGN_CHECK_ARG(col4row, "linear_sum_assignment: null col4row");
+  LGN_CHECK_ARG(status, "linear_sum_assignment: null status");
+  return linear_sum_assignment(cost, B, n, col4row, status, (hipStream_t)stream);
+}
+
 }  // extern "C"

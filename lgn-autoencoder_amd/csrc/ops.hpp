@@ -216,6 +216,10 @@ int local_sep_gp_reduce(const double* const* gpb, const int* C, int n, int M, do
 struct StaticPackJob { int kind, C, CO; int w0[5]; const double* src; double* dst; };
 int local_static_pack_batch(const StaticPackJob* jobs, int n, bool unpack, hipStream_t st);
 // packed X [2][nodes][C][Q] <-> s [2][nodes][C] (component q_s) + v [2][nodes][C][4] (components q_v..q_v+3); pack zero-fills the rest
+// anomaly scores and the batched assignment solver (anomaly.hip)
+int anomaly_scores(const double* rec, const double* tgt, const double* rec_n, const double* tgt_n, int B, int N, int mask, double* scores,
+                   int* col4row, int* status, hipStream_t st);
+int linear_sum_assignment(const double* cost, int B, int n, int* col4row, int* status, hipStream_t st);
 int gen_pack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* s, const double* v, double* X, hipStream_t st);
 int gen_unpack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* X, double* s, double* v, hipStream_t st);
 // the same with the packed tensor tile-blocked: XT [tile][C][Q][2][64]  (M nodes; whole tiles are written, padding lanes zero)

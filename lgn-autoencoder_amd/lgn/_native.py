@@ -166,6 +166,8 @@ _SIGNATURES.update({
     "lgn_step_train_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i,
                            _vp, _vp],
     "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+    "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
+    "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
 })
 _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_step_workspace_doubles": [_dp],
