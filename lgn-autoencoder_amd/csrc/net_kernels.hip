@@ -173,20 +173,25 @@ __host__ __device__ inline size_t lat_y_doubles(int N, int Ts, int Tv, int pool 
 __host__ __device__ inline size_t lat_fwd_doubles(int N, int C, int Ts, int Tv, int pool = 0) {
   return lat_y_doubles(N, Ts, Tv, pool) + (size_t)N * C * 10 + 2 * (size_t)(Ts + Tv) * pool_mix_in(pool, N, C);
 }
-// node features of the jet -> sv [N][C][10] (s re, im, v re[4], im[4]) and the two mixing weights; zero_y: y / gy starts at zero
+// node features of the jet -> sv [N][C][10] (s re, im, v re[4], im[4]) and the two mixing weights; zero_y: y / gy starts at zero.
+// s == nullptr (a step that neither returns the latent scalars nor runs the encoder's last CGMLP, which would produce s): the
+// scalars read as zero.  The latent vectors and the vector channels' arg-indices do not depend on s.  The scalar channels'
+// arg-indices (t < Ts) then all tie at particle 0 and mean nothing: every such caller passes the zero block as g_lat_s, so they
+// route only a zero gradient.
 struct LatentStage {
   StageRegs<2> sr, si;
   StageRegs<4> vr, vi;
   StageRegs<1> w0, w1;
   const double *s0, *s1, *v0, *v1, *wl0, *wl1;
-  int N, C, Ts, Tv, K, NY;                              // K: input channels of the two weights (C; N C under 'mix'); NY: y block
+  int N, C, Ts, Tv, K, NY, NS;                          // K: input channels of the two weights (C; N C under 'mix'); NY: y block
   __device__ __forceinline__ void issue(int B, int N_, int C_, int Ts_, int Tv_, const double* __restrict__ s, const double* __restrict__ v,
                                         const double* __restrict__ wl0_, const double* __restrict__ wl1_, int pool = 0) {
     N = N_; C = C_; Ts = Ts_; Tv = Tv_; wl0 = wl0_; wl1 = wl1_; K = pool_mix_in(pool, N_, C_); NY = (int)lat_y_doubles(N_, Ts_, Tv_, pool);
     const size_t pl = (size_t)B * N * C, j0 = (size_t)blockIdx.x * N * C;
-    s0 = s + j0; s1 = s + pl + j0; v0 = v + j0 * 4; v1 = v + (pl + j0) * 4;
+    NS = s ? N * C : 0;
+    s0 = s ? s + j0 : nullptr; s1 = s ? s + pl + j0 : nullptr; v0 = v + j0 * 4; v1 = v + (pl + j0) * 4;
     vr.issue(v0, N * C * 4); vi.issue(v1, N * C * 4);
-    sr.issue(s0, N * C); si.issue(s1, N * C);
+    sr.issue(s0, NS); si.issue(s1, NS);
     w0.issue(wl0, 2 * Ts * K); w1.issue(wl1, 2 * Tv * K);
   }
   __device__ __forceinline__ void commit(double* lds, bool zero_y) const {
@@ -197,8 +202,12 @@ struct LatentStage {
       for (int e = threadIdx.x; e < NY; e += BLOCK) lds[e] = 0.0;
     vr.commit(v0, N * C * 4, [&](int e, double x) { sv[(e >> 2) * 10 + 2 + (e & 3)] = x; });
     vi.commit(v1, N * C * 4, [&](int e, double x) { sv[(e >> 2) * 10 + 6 + (e & 3)] = x; });
-    sr.commit(s0, N * C, [&](int e, double x) { sv[e * 10] = x; });
-    si.commit(s1, N * C, [&](int e, double x) { sv[e * 10 + 1] = x; });
+    if (NS) {
+      sr.commit(s0, NS, [&](int e, double x) { sv[e * 10] = x; });
+      si.commit(s1, NS, [&](int e, double x) { sv[e * 10 + 1] = x; });
+    } else {
+      for (int e = threadIdx.x; e < N * C; e += BLOCK) sv[e * 10] = sv[e * 10 + 1] = 0.0;
+    }
     w0.commit(wl0, 2 * Ts * K, [&](int e, double x) { w0l[e] = x; });
     w1.commit(wl1, 2 * Tv * K, [&](int e, double x) { w1l[e] = x; });
   }

@@ -290,8 +290,13 @@ MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const dou
 // forward of one network's level stack; returns via buffers
 // eval (evaluation step): the level kernels without the aggregate stores (level_fwd_eval; n.ag0 / ag1 unused), a riding loss
 // tail in its forward-only form, and no CGMLP after the decoder's last level (its scalars never reach the output)
+// last_scalars = false: the caller consumes no output of the last level's CGMLP (the last level's scalars n.s[L]), which is then
+// not launched and leaves n.s[L] unwritten -- a step that returns no latent scalars, for either network (the decoder's output
+// and loss read only its last level's vectors; the latent vectors only the encoder's, and the latent scalars, which then mean
+// nothing, carry no gradient: LatentStage).
 int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, const int64_t* off, NetBuf& n, const double* pos,
-               const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr, bool eval = false) {
+               const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr, bool eval = false,
+               bool last_scalars = true) {
   const Slots S{d.n_levels, d.mlp_nlin};
   for (int l = 0; l < d.n_levels; ++l) {
     auto p = [&](int slot) { return P + off[slot]; };
@@ -310,7 +315,7 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
     }
     a.flags = d.flags;
     LGN_TRY(eval ? level_fwd_eval(a, dec, st) : level_fwd_dispatch<double>(a, dec, st));
-    if (eval && dec && l + 1 == d.n_levels) break;
+    if (l + 1 == d.n_levels && (!last_scalars || (eval && dec))) break;
     MlpArgs<double> m = level_mlp_args(d, dec, l, P, off);
     m.s_in = n.smix[l]; m.s_out = n.s[l + 1];
     m.h_saved = n.hsave[l]; m.h_rows = mlp_saved_rows(m.M);
@@ -1294,19 +1299,21 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
   RadFinJob fin{};
 
   // ---------------- forward ----------------
+  // the step returns no latent scalars and the decoder never reads them: neither network's last CGMLP runs, and
+  // the latent stage takes the encoder's last-level scalars as zero (LatentStage)
   if (split) {
     LGN_TRY(zero_ranges(grads, (size_t)n_params, w.zero0(), w.zero_doubles, nullptr, 0, st));
     LGN_TRY(enc_input_fwd(B, Ne, ce[0], K, p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st));
-    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, st));
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, false, /*last_scalars=*/false));
+    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, st));
     LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
                           w.dec.v[0], st));
   } else {
     // the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s
     // (the encoder's input stage and the two clears ride on the first level's kernel: levels_fwd / InputStage)
     const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, w.zeros_s, w.zero_doubles};
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0));
-    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, cd[0],
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, false, /*last_scalars=*/false));
+    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, cd[0],
                          params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
   }
   // ---------------- loss (and its backward), on the last decoder level's kernel when that is one workgroup per jet ----------
@@ -1316,7 +1323,8 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
     DQ_NEW(part, (size_t)B * ro.width);
     const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, w.gv[cur], part};
     const bool rides = level_fwd_carries_loss(Nd, d.flags);
-    LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr));
+    LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr, false,
+                       /*last_scalars=*/false));
     if (!rides)
       LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
     ro.add(dq, part, B, grads, dec_off);
@@ -1336,11 +1344,11 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
     if (split) {
       LGN_TRY(dec_input_bwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd],
                             w.g_lat_v, part, st));
-      LGN_TRY(enc_latent_bwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.g_lat_s, w.g_lat_v, w.idx, w.gs[wr],
+      LGN_TRY(enc_latent_bwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.g_lat_s, w.g_lat_v, w.idx, w.gs[wr],
                              w.gv[wr], parte, st));
     } else {
       LGN_TRY(junction_bwd(B, Ne, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd], w.g_lat_v,
-                           part, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, w.g_lat_s, w.idx, w.gs[wr], w.gv[wr], parte, st));
+                           part, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.g_lat_s, w.idx, w.gs[wr], w.gv[wr], parte, st));
     }
     ri.add(dq, part, B, grads, dec_off);
     rl.add(dq, parte, B, grads, enc_off);
@@ -1517,16 +1525,19 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
   dd.N = Nd;
   const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
   const bool rides = level_fwd_carries_loss(Nd, d.flags);
+  // the latent scalars (the encoder's last CGMLP and what the latent stage makes of its output) only when they are returned
+  const bool keep_s = lat_s_out != nullptr;
+  const double* sL = keep_s ? w.enc.s[L] : nullptr;
   if (step_is_split(d)) {            // the four end stages as launches of their own (as in step_fwd_bwd)
     LGN_TRY(enc_input_fwd(B, Ne, ce[0], in_K(d), p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, /*eval=*/true));
-    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, ls, lv, w.idx, st));
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, /*eval=*/true, keep_s));
+    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, sL, w.enc.v[L], wl0, wl1, ls, lv, w.idx, st));
     LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, lv, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
                           w.dec.v[0], st));
   } else {                           // input stage riding on the first level, latent + decoder input stage as one junction kernel
     const InputStage in0{params + enc_off[0], params + enc_off[1]};
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, /*eval=*/true));
-    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, w.enc.s[L], w.enc.v[L], wl0, wl1, ls, lv, w.idx, cd[0],
+    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, /*eval=*/true, keep_s));
+    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, sL, w.enc.v[L], wl0, wl1, ls, lv, w.idx, cd[0],
                          params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
   }
   LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &loss : nullptr, /*eval=*/true));
