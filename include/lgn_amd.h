@@ -418,6 +418,59 @@ int lgn_anomaly_scores_f64(const double* recons, const double* target, const dou
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */
 int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row, int* status, void* stream);
 
+/* ---- assignment losses: --loss-choice mse / hungarian (utils/train.py:416-480: get_loss) --------------------------------------
+ * The whole-step calls above with the loss as an argument.  loss == NULL or kind == LGN_LOSS_CHAMFER IS the plain call (same code
+ * path, same bits; assignment and status are then not touched).  Otherwise, with x = get_real(reconstruction) and t = target:
+ *   LGN_LOSS_MSE        nn.MSELoss()(x, t) (utils/train.py:460-462): the identity assignment on the (E, px, py, pz) columns;
+ *   LGN_LOSS_HUNGARIAN  HungarianMSELoss (utils/losses/hungarian_mse/hungarian_mse.py:46-84 and utils.py next to it) in the frame
+ *                       abs_coord / polar_coord select (main.py:324-334: --hungarian-abs-coord True, --hungarian-polar-coord False):
+ *       abs Cartesian (E, px, py, pz), D = 4;  abs polar (pt, eta, phi) of get_p_polar, D = 3;  relative polar (pt / Jpt, eta - Jeta,
+ *       phi - Jphi) with J the polar form of the TARGET's summed momenta for both sides;  relative Cartesian (pt cos phi, pt cos phi,
+ *       pt sinh eta) of the relative polar frame, as get_p_cartesian has it.
+ *     col = scipy.optimize.linear_sum_assignment of the Euclidean distances |p_i - q_j| (ties as scipy breaks them; no gradient
+ *     through it), solved by one wavefront per jet on the device instead of the reference's copy to the host and Python loop.
+ *   loss_part[b] = scale * sum_r sum_c (p[col[r]][c] - q[r][c])^2 -- the reference pairs p[col[r]] with q[r] -- and the gradient
+ *   goes through the frame, get_real and the output mix like the Chamfer gradient.  scale = 1 / (global batch * N * D): the mean of
+ *   nn.MSELoss.  Nothing is masked.  d->jet_loss_scale must be 0 (--chamfer-jet-features is a Chamfer option).  The loss stage is a
+ *   launch of its own (csrc/assign_loss.hip); 1 <= Nd <= LGN_ANOMALY_NMAX and its LDS must fit LGN_LDS_LIMIT: refused before any launch.
+ *   assignment [B][Nd] int32 (nullable): col; status [B] int32 (nullable): 1 -- a cost is NaN or -inf, 256 -- infeasible matrix;
+ *   loss_part[b] is then NaN, its assignment row is -1, and the stage hands on exact zeros for the jet (d loss / d x, the gradient
+ *   into the last level's vectors and its dWo1 partial row); where the jet's activations themselves are NaN, the level backwards
+ *   after the stage still turn 0 * NaN into NaN parameter gradients.
+ * Workspace sizes are those of the plain calls. */
+#define LGN_LOSS_CHAMFER 0
+#define LGN_LOSS_MSE 1
+#define LGN_LOSS_HUNGARIAN 2
+typedef struct lgn_loss_desc {
+  int kind;                /* LGN_LOSS_* */
+  int abs_coord;           /* Hungarian: --hungarian-abs-coord */
+  int polar_coord;         /* Hungarian: --hungarian-polar-coord */
+  double scale;            /* 1 / (global batch * N * D), D = 4 (MSE, abs Cartesian) or 3 */
+} lgn_loss_desc;
+int lgn_step_fwd_bwd_loss_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params,
+                              const int64_t* enc_off, const int64_t* dec_off, const double* p4, const double* target,
+                              const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
+                              double* recon, double* loss_part, const lgn_loss_desc* loss, int* assignment /* [B][Nd], nullable */,
+                              int* status /* [B], nullable */, void* stream);
+int lgn_step_train_loss_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
+                            const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
+                            double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
+                            int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment /* [B][Nd], nullable */,
+                            int* status /* [B], nullable */, void* stream);
+int lgn_step_eval_loss_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                           const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
+                           double* workspace, long long workspace_doubles, double* recon_real, double* lat_s /*nullable*/,
+                           double* lat_v /*nullable*/, double* loss_part, double* loss_out, const lgn_loss_desc* loss,
+                           int* assignment /* [B][Nd], nullable */, int* status /* [B], nullable */, void* stream);
+/* The loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the same device code
+ * without the output mix): x, y [B][N][4] real 4-vectors -> loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */
+int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int kind, int abs_coord, int polar_coord, double scale,
+                          double* loss_part, double* gx, int* assignment /* [B][N], nullable */, int* status /* [B], nullable */,
+                          void* stream);
+/* Plan-time fit query: bytes of LDS of the step's assignment-loss stage at N particles and C channels of the last decoder level. */
+long long lgn_assign_loss_lds_bytes(int N, int C);
+
 #ifdef __cplusplus
 }
 #endif

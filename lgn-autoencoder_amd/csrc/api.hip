@@ -211,4 +211,14 @@ int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row
   return linear_sum_assignment(cost, B, n, col4row, status, (hipStream_t)stream);
 }
 
+int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int kind, int abs_coord, int polar_coord, double scale,
+                          double* loss_part, double* gx, int* assignment, int* status, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "hungarian_mse: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(x && y && loss_part && gx, "hungarian_mse: null pointer");
+  const AssignLoss al{kind, abs_coord, polar_coord, scale, assignment, status};
+  return hungarian_mse(B, N, x, y, al, loss_part, gx, (hipStream_t)stream);
+}
+
+long long lgn_assign_loss_lds_bytes(int N, int C) { return N >= 1 && C >= 1 ? (long long)assign_loss_lds_bytes(N, C) : -1; }
+
 }  // extern "C"

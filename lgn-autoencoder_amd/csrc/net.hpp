@@ -51,6 +51,21 @@ int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, con
 // forward-only form (evaluation step): recon_real [B][N][4] = get_real(recon, method), loss_part [B]; no gradient
 int dec_output_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, double jscale,
                     double* recon_real, double* loss_part, hipStream_t);
+// The assignment losses (assign_loss.hip): nn.MSELoss (identity assignment) and the reference's HungarianMSELoss in its four frames, as
+// the step's last stage in place of dec_output_loss / dec_output_eval, and on their own (module API).  kind: LGN_LOSS_MSE /
+// LGN_LOSS_HUNGARIAN; scale = 1 / (global batch * N * D); assignment [B][N], status [B] nullable
+struct AssignLoss {
+  int kind, abs_coord, polar_coord;
+  double scale;
+  int *assignment, *status;
+};
+int check_assign_loss(const AssignLoss& al, int N);
+int dec_output_assign_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, const AssignLoss& al,
+                           double* recon, double* loss_part /*[B]*/, double* g_v, double* part /*[B][2C]*/, hipStream_t);
+int dec_output_assign_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, const AssignLoss& al,
+                           double* recon_real, double* loss_part, hipStream_t);
+int hungarian_mse(int B, int N, const double* x, const double* y, const AssignLoss& al, double* loss_part, double* gx, hipStream_t);
+size_t assign_loss_lds_bytes(int N, int C);
 // loss_out[0] = sum of loss_part over the jets with an unmasked particle (mask [B][N]), in a fixed order
 int eval_loss_sum(int B, int N, const uint8_t* mask, const double* loss_part, double* loss_out, hipStream_t);
 // Chamfer loss per jet and its gradients (module API: lgn/losses.py); loss_part [B], gx [B][N][4], gy [B][M][4]

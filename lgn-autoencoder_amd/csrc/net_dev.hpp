@@ -231,5 +231,102 @@ __device__ __forceinline__ void dec_output_loss_body(int B, int N, int C, const 
   }
 }
 
+// The output mix, get_real and their backward as stages of their own, for the per-jet loss kernels that are not Chamfer's
+// (assign_loss.hip).  The same statements as in dec_output_loss_body above, which stays one piece: the level kernels that carry it as
+// their tail keep their code and register counts.  THE TWO COPIES MUST CHANGE TOGETHER: the forward copy is pinned against the original by
+// the bit-for-bit reconstruction test, the backward copy by the gradient tests of both losses against the same oracle.  The LDS blocks they work on (each caller carves its own layout around them):
+struct DecOutLds {
+  double *x, *tg, *gx, *ycl, *vl, *tmp, *wol;    // [N][4] get_real(re, im) | [N][4] target | [N][4] d loss / d x | [N][8] | [N*C][8] | [N*C][2] | [2C]
+};
+// mix_to_output on the last level's vectors -> Cartesian -> get_real(., method): stages v, the target and Wo1, leaves x and tg in LDS
+// (synchronised).  GRAD: recon [2][B][N][4] receives the two planes; else recon [B][N][4] receives x.
+template <bool GRAD>
+__device__ __forceinline__ void dec_out_forward(int B, int N, int C, const double* __restrict__ v, const double* __restrict__ wo1,
+                                                const double* __restrict__ target, int method, double* recon, const DecOutLds& s) {
+  double *x = s.x, *tg = s.tg, *ycl = s.ycl, *vl = s.vl, *wol = s.wol;
+  const int b = blockIdx.x;
+  const size_t plp = (size_t)B * N * 4, pl = (size_t)B * N * C, j4 = (size_t)b * N * 4, jc = (size_t)b * N * C;
+  {
+    StageRegs<4> vr, vi;
+    StageRegs<1> tr, wr;
+    vr.issue(v + jc * 4, N * C * 4); vi.issue(v + (pl + jc) * 4, N * C * 4); tr.issue(target + j4, N * 4); wr.issue(wo1, 2 * C);
+    vr.commit(v + jc * 4, N * C * 4, [&](int e, double q) { vl[(e >> 2) * 8 + (e & 3)] = q; });
+    vi.commit(v + (pl + jc) * 4, N * C * 4, [&](int e, double q) { vl[(e >> 2) * 8 + 4 + (e & 3)] = q; });
+    tr.commit(target + j4, N * 4, [&](int e, double q) { tg[e] = q; });
+    wr.commit(wo1, 2 * C, [&](int e, double q) { wol[e] = q; });
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < N * 4; e += BLOCK) {     // (node, component): mix_to_output on the (1,1) irrep
+    const int n = e >> 2, m = e & 3;
+    cx<double> yc = {0, 0};
+#pragma unroll 4
+    for (int c = 0; c < C; ++c)
+      cfma(yc, cx<double>{wol[c], wol[C + c]}, cx<double>{vl[(n * C + c) * 8 + m], vl[(n * C + c) * 8 + 4 + m]});
+    ycl[n * 8 + m] = yc.r;
+    ycl[n * 8 + 4 + m] = yc.i;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < N * 4; e += BLOCK) {
+    const cx<double> pc = cart_from_canon_m(ycl + (e >> 2) * 8, e & 3);
+    if (GRAD) {
+      recon[j4 + e] = pc.r;
+      recon[plp + j4 + e] = pc.i;
+    }
+    double xe;                                           // get_real(., method)
+    if (method == REAL_SUM) xe = pc.r + pc.i;
+    else if (method == REAL_RE) xe = pc.r;
+    else if (method == REAL_IM) xe = pc.i;
+    else if (method == REAL_MEAN) xe = (pc.r + pc.i) / 2;
+    else xe = sqrt(pc.r * pc.r + pc.i * pc.i + GET_REAL_NORM_EPS);
+    x[e] = xe;
+    if (!GRAD) recon[j4 + e] = xe;
+  }
+  __syncthreads();
+}
+// gx [N][4] = d loss / d x (in LDS, synchronised) -> g_v [2][B][N][C][4] and the jet's dWo1 partial row [2][C]
+__device__ __forceinline__ void dec_out_backward(int B, int N, int C, int method, double* g_v, double* part, const DecOutLds& s) {
+  double *x = s.x, *gx = s.gx, *ycl = s.ycl, *vl = s.vl, *tmp = s.tmp, *wol = s.wol;
+  const int b = blockIdx.x;
+  const size_t pl = (size_t)B * N * C, jc = (size_t)b * N * C;
+  // back through get_real (the planes' gradients: gx, 0 / 0, gx / gx, gx / gx/2, gx/2 / gx re/x, gx im/x), rep_to_p and
+  // mix_to_output; dWo1[c] = sum_n sum_m G_yc[n][m] conj(v[n][c][m])
+  for (int e = threadIdx.x; e < N * C; e += BLOCK) {
+    const int n = e / C, c = e - n * C;
+    cx<double> g[4], gc[4], d = {0, 0};
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const double q = gx[n * 4 + m];
+      if (method == REAL_SUM) g[m] = {q, q};
+      else if (method == REAL_RE) g[m] = {q, 0.0};
+      else if (method == REAL_IM) g[m] = {0.0, q};
+      else if (method == REAL_MEAN) g[m] = {q / 2, q / 2};
+      else {                                             // re / im again from the canonical output, still in LDS
+        const cx<double> pc = cart_from_canon_m(ycl + n * 8, m);
+        const double r = q / x[n * 4 + m];
+        g[m] = {r * pc.r, r * pc.i};
+      }
+    }
+    cart_from_canon_bwd(g, gc);
+    const cx<double> w = {wol[c], wol[C + c]};
+    const size_t base = jc + e;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      cx<double> r = cmulc(gc[m], w);
+      g_v[base * 4 + m] = r.r;
+      g_v[pl * 4 + base * 4 + m] = r.i;
+      cfmac(d, gc[m], cx<double>{vl[e * 8 + m], vl[e * 8 + 4 + m]});
+    }
+    tmp[e * 2] = d.r;
+    tmp[e * 2 + 1] = d.i;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C) {
+    const int k = threadIdx.x / C, c = threadIdx.x - k * C;
+    double acc = 0.0;
+#pragma unroll 6
+    for (int n = 0; n < N; ++n) acc += tmp[(n * C + c) * 2 + k];
+    part[(size_t)b * 2 * C + k * C + c] = acc;
+  }
+}
 
 }  // namespace lgn

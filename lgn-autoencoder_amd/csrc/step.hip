@@ -410,6 +410,23 @@ int check_desc(const lgn_net_desc* d) {
   return 0;
 }
 
+// The loss argument of the *_loss_f64 calls: nullptr for Chamfer (the plain call), else the assignment loss the step's last stage
+// runs (net.hpp: AssignLoss).  Every refusal is made here, before anything is enqueued.
+int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, AssignLoss& al, const AssignLoss** out) {
+  *out = nullptr;
+  if (!loss || loss->kind == LGN_LOSS_CHAMFER) return 0;
+  if (int rc = check_desc(d)) return rc;
+  al = AssignLoss{loss->kind, loss->abs_coord, loss->polar_coord, loss->scale, assignment, status};
+  const int Nd = dec_nodes(*d), CL = d->dec_channels[d->n_levels];
+  if (int rc = check_assign_loss(al, Nd)) return rc;
+  LGN_CHECK_ARG(d->jet_loss_scale == 0.0, "step: jet_loss_scale=%g with loss kind %d: the jet-feature term is a Chamfer option "
+                "(--chamfer-jet-features)", d->jet_loss_scale, loss->kind);
+  const size_t need = assign_loss_lds_bytes(Nd, CL);
+  LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the assignment-loss stage at N=%d needs %zu B of LDS (> %d)", Nd, need, LGN_LDS_LIMIT);
+  *out = &al;
+  return 0;
+}
+
 }  // namespace
 
 }  // namespace lgn
@@ -908,7 +925,8 @@ GenStep carve_gen_step(const lgn_net_desc& d, double* base) {
 
 int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                      const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, double* workspace,
-                     long long workspace_doubles, double* recon, double* loss_part, hipStream_t st, const StepTailArgs* tail) {
+                     long long workspace_doubles, double* recon, double* loss_part, hipStream_t st, const StepTailArgs* tail,
+                     const AssignLoss* al) {
   LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step: encoder and decoder must both be table-driven (or both fused)");
   if (int rc = check_generic(d, false)) return rc;
   if (int rc = check_generic(d, true)) return rc;
@@ -934,8 +952,12 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   {
     const RowLayout ro = dec_output_rows(d, CL);
     DQ_NEW(part, (size_t)B * ro.width);
-    LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part,
-                            g.ds.gv, part, st));
+    if (al)
+      LGN_TRY(dec_output_assign_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, d.get_real, *al, recon, loss_part,
+                                     g.ds.gv, part, st));
+    else
+      LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon,
+                              loss_part, g.ds.gv, part, st));
     ro.add(dq, part, B, grads, dec_off);
   }
   std::vector<UnpackJob> post;
@@ -1262,7 +1284,7 @@ long long lgn_step_workspace_doubles(const lgn_net_desc* d) {
 static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                         const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                         double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
-                        const StepTailArgs* tail) {
+                        const StepTailArgs* tail, const AssignLoss* al = nullptr) {
   if (int rc = check_desc(dp)) return rc;
   const lgn_net_desc& d = *dp;
   LGN_CHECK_ARG(params && grads && enc_off && dec_off && p4 && target && mask && workspace && recon && loss_part && n_params > 0,
@@ -1275,7 +1297,7 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
     LGN_CHECK_ARG(!split, "step_fwd_bwd: table-driven networks take the mass as the only input scalar and one node count "
                   "for both networks (n_in_scalars=%d, N=%d, dec_N=%d): use the per-network calls", d.n_in_scalars, d.N, d.dec_N);
     return gen_step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, workspace, workspace_doubles, recon,
-                            loss_part, st, tail);
+                            loss_part, st, tail, al);
   }
   Work w = carve(d, workspace);
   // the layout depends on run-time switches (LGN_AMD_DEC_PAIRWISE / LGN_AMD_LEVEL_V2 change the partial-row counts):
@@ -1322,10 +1344,12 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
     const RowLayout ro = dec_output_rows(d, cd[L]);
     DQ_NEW(part, (size_t)B * ro.width);
     const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, w.gv[cur], part};
-    const bool rides = level_fwd_carries_loss(Nd, d.flags);
+    const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);      // (an assignment loss is a launch of its own in every regime)
     LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr, false,
                        /*last_scalars=*/false));
-    if (!rides)
+    if (al)
+      LGN_TRY(dec_output_assign_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, ls.method, *al, recon, loss_part, w.gv[cur], part, st));
+    else if (!rides)
       LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
     ro.add(dq, part, B, grads, dec_off);
   }
@@ -1367,11 +1391,22 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
 }
 extern "C" {
 
+int lgn_step_fwd_bwd_loss_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
+                              const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                              double* workspace, long long workspace_doubles, double* recon, double* loss_part, const lgn_loss_desc* loss,
+                              int* assignment, int* status, void* stream) {
+  AssignLoss al;
+  const AssignLoss* alp;
+  if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
+  return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
+                      loss_part, stream, nullptr, alp);
+}
+
 int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                          const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                          double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream) {
-  return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
-                      loss_part, stream, nullptr);
+  return lgn_step_fwd_bwd_loss_f64(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles,
+                                   recon, loss_part, nullptr, nullptr, nullptr, stream);
 }
 
 int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
@@ -1379,6 +1414,19 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda, double* adam_m,
                        double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps, int do_adam,
                        double* loss_out, void* stream) {
+  return lgn_step_train_loss_f64(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
+                                 loss_part, n_loss, l1_lambda, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, do_adam, loss_out, nullptr,
+                                 nullptr, nullptr, stream);
+}
+
+int lgn_step_train_loss_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
+                            const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
+                            double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
+                            int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
+  AssignLoss al;
+  const AssignLoss* alp;
+  if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   LGN_CHECK_ARG(loss_out && n_loss > 0, "step_train: null pointer");
   LGN_CHECK_ARG(!do_adam || (adam_m && adam_v && step_dev), "step_train: Adam state missing");
   const StepTailArgs tail{params, grads, (long)n_params, adam_m, adam_v, reinterpret_cast<long*>(step_dev), l1_lambda, lr, beta1, beta2,
@@ -1386,7 +1434,7 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
   // LGN_NET_SPLIT_TAIL (frozen into the descriptor): the three separate launches (reduce_segments, rad_finalize_batch, l1_adam) -- the
   // A/B switch of the fused tail
   return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
-                      loss_part, stream, &tail);
+                      loss_part, stream, &tail, alp);
 }
 
 int lgn_step_finalize_f64(double* params, double* grads, long long n_params, const double* loss_part, int n_loss, double l1_lambda,
@@ -1481,7 +1529,8 @@ long long eval_workspace(const lgn_net_desc& d) {
 
 int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
               const double* target, const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
-              double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st) {
+              double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st,
+              const AssignLoss* al) {
   // every refusal comes before the first launch
   if (int rc = check_desc(dp)) return rc;
   const lgn_net_desc& d = *dp;
@@ -1514,7 +1563,8 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
     LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, g.ea.sL, g.ea.vL, wl0, wl1, ls, lv, g.ea.idx, cd[0], params + dec_off[1],
                          params + dec_off[2], params + dec_off[3], g.da.pdec, g.da.s0, g.da.v0, st));
     LGN_TRY(gen_decoder_fwd(d, params, dec_off, lv, g.da, st, /*with_input=*/false));
-    LGN_TRY(dec_output_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+    if (al) LGN_TRY(dec_output_assign_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, *al, recon_real, loss_part, st));
+    else LGN_TRY(dec_output_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
     return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
   }
 
@@ -1524,7 +1574,7 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
   lgn_net_desc dd = d;
   dd.N = Nd;
   const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
-  const bool rides = level_fwd_carries_loss(Nd, d.flags);
+  const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);
   // the latent scalars (the encoder's last CGMLP and what the latent stage makes of its output) only when they are returned
   const bool keep_s = lat_s_out != nullptr;
   const double* sL = keep_s ? w.enc.s[L] : nullptr;
@@ -1541,7 +1591,8 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
                          params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
   }
   LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &loss : nullptr, /*eval=*/true));
-  if (!rides) LGN_TRY(dec_output_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+  if (al) LGN_TRY(dec_output_assign_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, *al, recon_real, loss_part, st));
+  else if (!rides) LGN_TRY(dec_output_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
   return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
 }
 
@@ -1555,12 +1606,23 @@ long long lgn_eval_workspace_doubles(const lgn_net_desc* d) {
   return eval_workspace(*d);
 }
 
+int lgn_step_eval_loss_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                           const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
+                           double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
+                           double* loss_part, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
+  AssignLoss al;
+  const AssignLoss* alp;
+  if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
+  return step_eval(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real, lat_s,
+                   lat_v, loss_part, loss_out, (hipStream_t)stream, alp);
+}
+
 int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
                       const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
                       double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
                       double* loss_part, double* loss_out, void* stream) {
-  return step_eval(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real, lat_s,
-                   lat_v, loss_part, loss_out, (hipStream_t)stream);
+  return lgn_step_eval_loss_f64(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real,
+                                lat_s, lat_v, loss_part, loss_out, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

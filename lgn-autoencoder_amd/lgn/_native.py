@@ -169,6 +169,23 @@ _SIGNATURES.update({
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
 })
+
+
+class LossDesc(C.Structure):
+    """lgn_loss_desc of include/lgn_amd.h."""
+    _fields_ = [("kind", C.c_int), ("abs_coord", C.c_int), ("polar_coord", C.c_int), ("scale", C.c_double)]
+
+
+LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
+ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
+_lp = C.POINTER(LossDesc)
+# the whole-step calls with a loss descriptor: the arguments of the plain calls, then (loss, assignment, status) before the stream
+_SIGNATURES.update({
+    "lgn_step_fwd_bwd_loss_f64": _SIGNATURES["lgn_step_fwd_bwd_f64"][:-1] + [_lp, _vp, _vp, _vp],
+    "lgn_step_train_loss_f64": _SIGNATURES["lgn_step_train_f64"][:-1] + [_lp, _vp, _vp, _vp],
+    "lgn_step_eval_loss_f64": _SIGNATURES["lgn_step_eval_f64"][:-1] + [_lp, _vp, _vp, _vp],
+    "lgn_hungarian_mse_f64": [_i, _i, _vp, _vp, _i, _i, _i, _d] + [_vp] * 5,
+})
 _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_step_workspace_doubles": [_dp],
     "lgn_eval_workspace_doubles": [_dp],
@@ -178,6 +195,7 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_encoder_end_lds_bytes": [_i] * 7,
     "lgn_decoder_end_lds_bytes": [_i] * 4,
     "lgn_junction_lds_bytes": [_i] * 6,
+    "lgn_assign_loss_lds_bytes": [_i, _i],
 }
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
 EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)
@@ -353,6 +371,22 @@ def chamfer(x, y, jet_features=False):
     _check(lib().lgn_chamfer_f64(B, Np, M, ptr(x), ptr(y), int(bool(jet_features)), ptr(part), ptr(gx), ptr(gy), stream_ptr()),
            "lgn_chamfer_f64")
     return part, gx, gy
+
+
+def hungarian_mse(x, y, kind=LOSS_HUNGARIAN, abs_coord=True, polar_coord=False, scale=None):
+    """x, y (B,N,4) real 4-vectors -> per-jet loss terms (B,), d loss / d x, assignment (B,N) int32, status (B,) int32
+    (lgn_hungarian_mse_f64).  scale: 1 / (B N D) -- the reference's mean over the batch -- when None."""
+    x, y = f64(x), f64(y)
+    B, Np = x.shape[0], x.shape[1]
+    if scale is None:
+        scale = 1.0 / (B * Np * (4 if kind == LOSS_MSE or (abs_coord and not polar_coord) else 3))
+    out = torch.empty(B + 4 * B * Np, device=x.device, dtype=x.dtype)              # one allocation: [loss_part | gx]
+    ints = torch.empty(B * Np + B, device=x.device, dtype=torch.int32)             # [assignment | status]
+    part, gx = out[:B], out[B:].view(B, Np, 4)
+    assignment, status = ints[:B * Np].view(B, Np), ints[B * Np:]
+    _check(lib().lgn_hungarian_mse_f64(B, Np, ptr(x), ptr(y), int(kind), int(bool(abs_coord)), int(bool(polar_coord)), float(scale),
+                                       ptr(part), ptr(gx), ptr(assignment), ptr(status), stream_ptr()), "lgn_hungarian_mse_f64")
+    return part, gx, assignment, status
 
 
 def mixreps_fwd(w, x):

@@ -4,7 +4,12 @@
 cdist of distance_sq.py:263-304 with its default even p: the plain sum of squared component differences): same constructor, same
 ``forward(x, y, jet_features=False)``, one HIP kernel (csrc/net_kernels.hip: chamfer_kernel) for the loss and both gradients
 instead of ~25 elementwise / reduction launches.  ``lgn.step.NativeTrainStep`` does not use it -- there the loss is the tail of the
-decoder's last kernel."""
+decoder's last kernel.
+
+``HungarianMSELoss`` is the drop-in of ``utils.losses.HungarianMSELoss`` (utils/losses/hungarian_mse/hungarian_mse.py:8-84): the four
+coordinate frames, the assignment (scipy's ``linear_sum_assignment``, ties included, solved by one wavefront per jet), the MSE of the
+paired rows and its gradient in one HIP kernel (csrc/assign_loss.hip) -- no copy of the cost matrices to the host, no Python loop
+over the jets, capturable into a graph."""
 from typing import Optional
 
 import torch
@@ -55,3 +60,69 @@ class ChamferLoss(nn.Module):
             raise RuntimeError(f"The size of tensor a ({x.shape[-2]}) must match the size of tensor b ({y.shape[-2]}) at non-singleton "
                                "dimension 1 (the reference's ChamferLoss takes sets of equal size)")
         return ChamferFn.apply(x.reshape(-1, x.shape[-2], 4), y.reshape(-1, y.shape[-2], 4), jet_features)
+
+
+def loss_kind(loss_choice: str) -> int:
+    """LGN_LOSS_* of a --loss-choice string, matched as get_loss() matches it (utils/train.py:416-480: lower-cased, tests in the
+    reference's order).  EMD and the hybrid loss need jetnet / energyflow, which this build does not have: refused by name."""
+    c = str(loss_choice).lower()
+    if "chamfer" in c:
+        return N.LOSS_CHAMFER
+    if "emd" in c or c in ("hybrid", "combined", "mix"):
+        raise NotImplementedError(f"loss choice ({loss_choice}): the EMD and hybrid losses are not implemented in this build. "
+                                  "The available options are ('chamfer', 'mse', 'hungarian')")
+    if "mse" in c:
+        return N.LOSS_MSE
+    if "jet" in c or "hungarian" in c:
+        return N.LOSS_HUNGARIAN
+    raise NotImplementedError(f"Current loss choice ({loss_choice}) is not implemented. "
+                              "The available options are ('chamfer', 'mse', 'hungarian')")
+
+
+def loss_columns(kind: int, abs_coord: bool = True, polar_coord: bool = False) -> int:
+    """D: columns the mean of the loss runs over (4: MSE and the absolute Cartesian frame; 3: the (pt, eta, phi)-derived frames)."""
+    return 4 if kind == N.LOSS_MSE or (abs_coord and not polar_coord) else 3
+
+
+class HungarianMSEFn(torch.autograd.Function):
+    """(recons (B,N,4), target (B,N,4), abs_coord, polar_coord, owner) -> scalar loss; the assignment carries no gradient, and
+    neither does the target (as in the reference, whose target is data)."""
+
+    @staticmethod
+    def forward(ctx, x, y, abs_coord, polar_coord, owner):
+        part, gx, assignment, status = N.hungarian_mse(x.detach(), y.detach(), N.LOSS_HUNGARIAN, abs_coord, polar_coord)
+        ctx.save_for_backward(gx)
+        owner._assignment, owner.status = assignment, status
+        return part.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        (gx,) = ctx.saved_tensors
+        return (gx * g if ctx.needs_input_grad[0] else None), None, None, None, None
+
+
+class HungarianMSELoss(nn.Module):
+    """utils/losses/hungarian_mse/hungarian_mse.py:8-44.  recons, target: real 4-vectors (B, N, 4); returns the mean over
+    (B, N, D) of (p[col[r]] - q[r])^2 in the chosen frame.  After a forward, ``assignment`` (B, N) int64 -- col of every jet -- and
+    ``status`` (B,) int32 (non-zero: that jet's cost matrix held NaN / -inf or was infeasible; its term is NaN) are readable."""
+
+    def __init__(self):
+        super().__init__()
+        self._assignment = self.status = None
+
+    @property
+    def assignment(self):
+        return None if self._assignment is None else self._assignment.long()
+
+    def forward(self, recons: torch.Tensor, target: torch.Tensor, abs_coord: bool = True, polar_coord: bool = False):
+        self.abs_coord, self.polar_coord, self.device = abs_coord, polar_coord, recons.device
+        target = target.to(recons.device)
+        if recons.shape[-1] != 4 or target.shape[-1] != 4:
+            raise ValueError(f"Wrong last dimension of p. Should be 4 but found: {recons.shape[-1]} / {target.shape[-1]} "
+                             "(3-vectors: reference only).")
+        if recons.device.type != "cuda":
+            raise RuntimeError("lgn (MI355X build): HungarianMSELoss runs only in the HIP kernels of liblgn_amd.so on a GPU device; "
+                               f"got tensors on '{recons.device}'. There is no CPU fallback.")
+        if recons.dim() != 3 or recons.shape != target.shape:
+            raise ValueError(f"recons {tuple(recons.shape)} and target {tuple(target.shape)} must both be (batch, particles, 4)")
+        return HungarianMSEFn.apply(recons, target, bool(abs_coord), bool(polar_coord), self)

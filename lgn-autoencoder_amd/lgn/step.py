@@ -126,19 +126,22 @@ class ReferenceLoopStep:
     Nothing is re-homed or captured: this is what a user who only swaps the ``lgn`` package gets.  Under data
     parallelism the two flat gradients are all-reduced (SUM) and the L1 term is weighted 1/world per rank.
     ``native_loss``: ``lgn.losses.ChamferLoss`` (one kernel, the drop-in of utils.losses.ChamferLoss) instead of the torch
-    restatement of the reference's loss (~25 launches)."""
+    restatement of the reference's loss (~25 launches).  ``loss_choice`` as get_loss() takes it: 'mse' (nn.MSELoss) and 'hungarian'
+    (lgn.losses.HungarianMSELoss) are means over the batch, so under data parallelism a rank's loss is weighted 1/world as well; the
+    value returned is the rank's own loss (its share of the batch) plus the L1 term."""
 
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
-                 process_group=None, optimizer: bool = True, native_loss: bool = True):
+                 process_group=None, optimizer: bool = True, native_loss: bool = True, loss_choice: str = "chamfer",
+                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False):
         self.encoder, self.decoder = encoder, decoder
-        if native_loss:
-            from .losses import ChamferLoss
-            self.loss_fn = ChamferLoss(device=encoder.device)
-        else:
-            self.loss_fn = chamfer_loss
+        self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
+                                    None if native_loss else chamfer_loss)
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.group = process_group
+        # Chamfer is a SUM over the jets: the ranks' gradients add up to the step of one process on the whole batch.  mse / hungarian
+        # are MEANS over the batch: a rank's term is weighted 1 / world before the SUM all-reduce (ranks hold equal shares)
+        self._loss_weight = 1.0 if "chamfer" in str(loss_choice).lower() else 1.0 / self.world
         self.opt_enc = torch.optim.Adam(encoder.parameters(), lr) if optimizer else None
         self.opt_dec = torch.optim.Adam(decoder.parameters(), lr) if optimizer else None
 
@@ -149,7 +152,7 @@ class ReferenceLoopStep:
         target = batch["p4"].to(device=real.device, dtype=real.dtype)
         chamfer = self.loss_fn(real, target)
         l1 = self.encoder.l1_norm() + self.decoder.l1_norm()
-        loss = chamfer + (self.l1_lambda / self.world) * l1
+        loss = self._loss_weight * chamfer + (self.l1_lambda / self.world) * l1
         if self.opt_enc is not None:         # utils/train.py:324-325
             self.opt_enc.zero_grad()
             self.opt_dec.zero_grad()
@@ -165,6 +168,27 @@ class ReferenceLoopStep:
             self.opt_enc.step()
             self.opt_dec.step()
         return (chamfer + self.l1_lambda * l1).detach(), recon
+
+
+def _module_loss(loss_choice, abs_coord, polar_coord, device, chamfer=None, jet_features=False):
+    """The loss of the module-API steps as a function (x, target) -> scalar, chosen as get_loss() chooses it (utils/train.py:416-480):
+    lgn.losses.ChamferLoss (or `chamfer`, a restatement), nn.MSELoss, lgn.losses.HungarianMSELoss."""
+    from . import _native as N
+    from .losses import ChamferLoss, HungarianMSELoss, loss_kind
+    kind = loss_kind(loss_choice)
+    if kind == N.LOSS_CHAMFER:
+        if chamfer is not None:
+            return chamfer
+        fn = ChamferLoss(device=device)
+        return (lambda x, t: fn(x, t, jet_features=True)) if jet_features else fn
+    if jet_features:
+        raise ValueError("chamfer_jet_features is an option of the Chamfer loss")
+    if kind == N.LOSS_MSE:
+        return torch.nn.MSELoss()
+    fn = HungarianMSELoss()
+    loss = lambda x, t: fn(x, t, abs_coord=abs_coord, polar_coord=polar_coord)     # noqa: E731
+    loss.module = fn
+    return loss
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -299,6 +323,32 @@ def _step_desc(encoder, decoder, B: int, split: bool, get_real_method: str, jet_
     return d, keep
 
 
+def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, n_particles):
+    """(kind, lgn_loss_desc or None) of a whole step: None for Chamfer -- the step then issues the plain calls, as it always has.
+    scale = 1 / (n_jets N D), n_jets the GLOBAL batch (the mean of nn.MSELoss over everything the ranks hold together)."""
+    from . import _native as N
+    from .losses import loss_kind, loss_columns
+    kind = loss_kind(loss_choice)
+    if kind == N.LOSS_CHAMFER:
+        return kind, None
+    if jet_features:
+        raise ValueError("chamfer_jet_features is an option of the Chamfer loss; it cannot be combined with "
+                         f"loss_choice={loss_choice!r}")
+    ld = N.LossDesc()
+    ld.kind, ld.abs_coord, ld.polar_coord = kind, int(bool(abs_coord)), int(bool(polar_coord))
+    ld.scale = 1.0 / (n_jets * n_particles * loss_columns(kind, abs_coord, polar_coord))
+    return kind, ld
+
+
+def _check_assign_fit(decoder):
+    from . import _native as N
+    Nd, CL = decoder.num_output_particles, decoder.num_channels[-1]
+    need = N.lib().lgn_assign_loss_lds_bytes(Nd, CL)
+    if Nd > N.ASSIGN_NMAX or not 0 <= need <= N.LDS_LIMIT:
+        raise NotImplementedError(f"the native mse / hungarian loss stage at {Nd} particles needs {need} B of LDS (limit {N.LDS_LIMIT}, "
+                                  f"at most {N.ASSIGN_NMAX} particles); this configuration runs through the module API")
+
+
 class NativeTrainStep:
     """Same step as TrainStep, executed by lgn_step_fwd_bwd_f64 / lgn_step_finalize_f64 (csrc/step.hip):
     no autograd graph, no PyTorch kernels, every buffer static.  With ``use_graph=True`` the two native calls
@@ -310,20 +360,32 @@ class NativeTrainStep:
     utils/utils.py:194-207) and ``chamfer_jet_features`` (--chamfer-jet-features: + nn.MSELoss() of the jets' summed momenta,
     utils/losses/chamfer_loss/chamfer_loss.py:25-29).  The MSE is a mean over (global batch, 4): with data parallelism each rank
     weighs its jets by 1 / (4 batch_size world), so the SUM all-reduce gives the step of one process on the whole batch.  The
-    defaults ('sum', no jet term) are the step of ABI 17."""
+    defaults ('sum', no jet term) are the step of ABI 17.
+
+    ``loss_choice`` (--loss-choice, matched as utils/train.py:416-480 matches it): 'chamfer', 'mse' or 'hungarian' / 'jet' with
+    ``hungarian_abs_coord`` / ``hungarian_polar_coord`` (main.py:324-334); 'emd' and 'hybrid' raise NotImplementedError.  The mse and
+    Hungarian losses run as the step's loss stage (lgn_step_*_loss_f64, csrc/assign_loss.hip); they are means over (global batch, N,
+    D), so each rank scales by 1 / (batch_size world N D).  ``assignment`` is the (B, N) int32 buffer the last step filled with every
+    jet's col (static: graph replays keep filling it), ``status`` its (B,) int32 companion."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
-                 chamfer_jet_features: bool = False):
+                 chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
+                 hungarian_polar_coord: bool = False):
         import ctypes as C
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
+        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.loss_choice = loss_choice
+        self.loss_kind, self.loss_desc = _loss_desc(loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features,
+                                                    batch_size * self.world, decoder.num_output_particles)
+        if self.loss_desc is not None:
+            _check_assign_fit(decoder)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
-        self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet Chamfer terms
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet loss terms
         self.group = process_group
         # force_collective: take the two-graph + all-reduce branch even with one rank (exercises the capture boundaries and
         # the RCCL call on the flat buffer on a single GPU; a 1-rank SUM leaves the buffer unchanged)
@@ -368,11 +430,23 @@ class NativeTrainStep:
         self.in_scalars = torch.empty(d.B, d.N, K - 1, device=dev, dtype=dt) if K > 1 else None     # jet mass term, data['scalars']
         self.use_graph = use_graph
         self._g1 = self._g2 = None
+        self.assignment = self.status = None
+        if self.loss_desc is not None:
+            self.assignment = torch.full((d.B, Nd), -1, device=dev, dtype=torch.int32)
+            self.status = torch.zeros(d.B, device=dev, dtype=torch.int32)
 
     # -- raw native calls on the current stream
     def _fwd_bwd(self):
         import ctypes as C
         N = self.N
+        if self.loss_desc is not None:
+            rc = N.lib().lgn_step_fwd_bwd_loss_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
+                                                   self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
+                                                   N.ptr(self.in_scalars) if self.in_scalars is not None else None,
+                                                   N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
+                                                   C.byref(self.loss_desc), N.ptr(self.assignment), N.ptr(self.status), N.stream_ptr())
+            N._check(rc, "lgn_step_fwd_bwd_loss_f64")
+            return
         rc = N.lib().lgn_step_fwd_bwd_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
                                           self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
                                           N.ptr(self.in_scalars) if self.in_scalars is not None else None,
@@ -394,6 +468,17 @@ class NativeTrainStep:
         instead of three; same results bit for bit (LGN_AMD_SPLIT_TAIL=1 when the step is built: the separate launches)."""
         import ctypes as C
         N = self.N
+        if self.loss_desc is not None:
+            rc = N.lib().lgn_step_train_loss_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
+                                                 self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
+                                                 N.ptr(self.in_scalars) if self.in_scalars is not None else None,
+                                                 N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
+                                                 self.loss_part.numel(), float(self.l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v),
+                                                 N.ptr(self.step_dev), float(self.lr), float(self.betas[0]), float(self.betas[1]),
+                                                 float(self.eps), int(do_adam), N.ptr(self._loss_buf), C.byref(self.loss_desc),
+                                                 N.ptr(self.assignment), N.ptr(self.status), N.stream_ptr())
+            N._check(rc, "lgn_step_train_loss_f64")
+            return
         rc = N.lib().lgn_step_train_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
                                         self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
                                         N.ptr(self.in_scalars) if self.in_scalars is not None else None,
@@ -524,9 +609,9 @@ class CapturedModuleStep:
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8, betas=(0.9, 0.999),
                  eps: float = 1e-8, process_group=None, optimizer: bool = True, use_graph: bool = True, get_real_method: str = "sum",
-                 chamfer_jet_features: bool = False, extra_scalars: int = 0):
+                 chamfer_jet_features: bool = False, extra_scalars: int = 0, loss_choice: str = "chamfer",
+                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False):
         from . import _native as N
-        from .losses import ChamferLoss
         self.N = N
         encoder._require_gpu()
         self.encoder, self.decoder = encoder, decoder
@@ -541,7 +626,9 @@ class CapturedModuleStep:
                       "labels": torch.zeros(batch_size, n_in, device=dev, dtype=torch.uint8)}
         if extra_scalars:
             self.batch["scalars"] = torch.zeros(batch_size, encoder.num_input_particles, extra_scalars, device=dev, dtype=dt)
-        self.loss_fn = ChamferLoss(device=dev)
+        # (mse / hungarian are means over the GLOBAL batch: a rank's term is weighted 1 / world before the SUM all-reduce)
+        self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, dev, jet_features=chamfer_jet_features)
+        self._loss_weight = 1.0 if "chamfer" in str(loss_choice).lower() else 1.0 / self.world
         self.loss_part = self.flat.tail
         self._loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=dev, dtype=dt)
         self.loss_out = self._loss_buf[:3]
@@ -554,7 +641,9 @@ class CapturedModuleStep:
     def _fwd_bwd(self):
         self.flat.grad_buf.zero_()
         recon = self.decoder(self.encoder(self.batch))
-        loss = self.loss_fn(get_real(recon, self.get_real_method), self.batch["p4"], jet_features=self.chamfer_jet_features)
+        loss = self.loss_fn(get_real(recon, self.get_real_method), self.batch["p4"])
+        if self._loss_weight != 1.0:
+            loss = loss * self._loss_weight
         loss.backward()                                   # accumulates into the views of flat.grad the parameters hold
         self.loss_part.copy_(loss.detach().reshape(1))
         self.recon = recon.detach()
@@ -660,7 +749,9 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
 # ---------------------------------------------------------------------------------------------------
 
 class NativeEvalStep:
-    """encoder -> decoder -> get_real -> Chamfer [+ jet-feature MSE] forward only, executed by lgn_step_eval_f64 (csrc/step.hip):
+    """encoder -> decoder -> get_real -> loss forward only -- Chamfer [+ jet-feature MSE], or with ``loss_choice`` 'mse' / 'hungarian'
+    (``hungarian_abs_coord``, ``hungarian_polar_coord``) the assignment losses, whose ``assignment`` (B, N) / ``status`` (B,) int32
+    buffers the run fills -- executed by lgn_step_eval_f64 / lgn_step_eval_loss_f64 (csrc/step.hip):
     the reference's evaluation loss (no L1: regularization = is_train, utils/train.py:308-314), the reconstruction after get_real
     (what validate() collects) and, with ``keep_latent``, the pooled latent (what test.py saves).  Nothing is kept for a backward.
     With ``use_graph`` the call is captured once into a HIP graph and replayed.
@@ -670,14 +761,19 @@ class NativeEvalStep:
     the next ``run`` re-plans.  Same configurations and plan-time refusals (NotImplementedError) as NativeTrainStep.
 
     A short last batch (B' < batch_size jets) is padded with all-masked jets; loss and outputs cover the B' real ones, and the
-    jet-feature MSE is the mean over those B' jets (nn.MSELoss on that batch)."""
+    jet-feature MSE, like the mse / hungarian loss, is the mean over those B' jets (nn.MSELoss on that batch)."""
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
-                 keep_latent: bool = False, use_graph: bool = True):
+                 keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
+                 hungarian_polar_coord: bool = False):
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
         self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
+        self._loss_args = (loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features)
+        self.loss_kind, self.loss_desc = _loss_desc(*self._loss_args, self.B, decoder.num_output_particles)
+        if self.loss_desc is not None:
+            _check_assign_fit(decoder)
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
         self.keep_latent, self.use_graph = bool(keep_latent), use_graph
         self._plan()
@@ -699,6 +795,10 @@ class NativeEvalStep:
         self.lat_v = torch.empty(2, d.B, 1, P * d.tau_v, 4, device=dev, dtype=dt) if self.keep_latent else None
         self._graph = None
         self.n_real = d.B
+        self.assignment = self.status = None
+        if self.loss_desc is not None:
+            self.assignment = torch.full((d.B, Nd), -1, device=dev, dtype=torch.int32)
+            self.status = torch.zeros(d.B, device=dev, dtype=torch.int32)
 
     def _plan(self):
         """Descriptor and parameter offsets for where the two flat blocks are now (offsets count from the lower block)."""
@@ -716,9 +816,18 @@ class NativeEvalStep:
             raise RuntimeError(N.last_error())
         self.desc = d
 
-    def _eval(self, desc=None):
+    def _eval(self, desc=None, loss_desc=None):
         import ctypes as C
         N = self.N
+        if self.loss_desc is not None:
+            ld = loss_desc if loss_desc is not None else self.loss_desc
+            rc = N.lib().lgn_step_eval_loss_f64(C.byref(self.desc), self._base, self.enc_off, self.dec_off, N.ptr(self.p4),
+                                                N.ptr(self.target), N.ptr(self.mask), N.ptr(self.in_scalars), N.ptr(self.workspace),
+                                                self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s), N.ptr(self.lat_v),
+                                                N.ptr(self.loss_part), N.ptr(self.loss_out), C.byref(ld), N.ptr(self.assignment),
+                                                N.ptr(self.status), N.stream_ptr())
+            N._check(rc, "lgn_step_eval_loss_f64")
+            return
         rc = N.lib().lgn_step_eval_f64(C.byref(desc if desc is not None else self.desc), self._base, self.enc_off, self.dec_off,
                                        N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask), N.ptr(self.in_scalars), N.ptr(self.workspace),
                                        self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s), N.ptr(self.lat_v),
@@ -786,6 +895,9 @@ class NativeEvalStep:
             d = type(self.desc).from_buffer_copy(self.desc)
             d.jet_loss_scale = 1.0 / (4.0 * n)
             self._eval(d)
+        elif n < self.B and self.loss_desc is not None:
+            # the mean over the B' real jets: a loss descriptor of its own, one call outside the graph
+            self._eval(loss_desc=_loss_desc(*self._loss_args, n, self.decoder.num_output_particles)[1])
         elif self.use_graph:
             if self._graph is None:
                 self._capture()
@@ -804,17 +916,18 @@ class ModuleEvalStep:
     the configurations NativeEvalStep refuses.  Same interface."""
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
-                 keep_latent: bool = False, use_graph: bool = True):
-        from .losses import ChamferLoss
+                 keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
+                 hungarian_polar_coord: bool = False):
         self.encoder, self.decoder, self.B = encoder, decoder, batch_size
         self.get_real_method, self.chamfer_jet_features, self.keep_latent = get_real_method, chamfer_jet_features, keep_latent
-        self.loss_fn = ChamferLoss(device=encoder.device)
+        self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
+                                    jet_features=chamfer_jet_features)
 
     @torch.no_grad()
     def run(self, batch: Dict[str, torch.Tensor]):
         latent = self.encoder(batch)
         recon = get_real(self.decoder(latent), self.get_real_method)
-        loss = self.loss_fn(recon, batch["p4"].to(recon.device), jet_features=self.chamfer_jet_features)
+        loss = self.loss_fn(recon, batch["p4"].to(recon.device))
         out = {"loss": loss, "recon": recon}
         if self.keep_latent:
             out["latent"] = latent
