@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define LGN_AMD_ABI_VERSION 18   /* bump on ANY struct or signature change (lgn/_native.py: ABI_VERSION) */
+#define LGN_AMD_ABI_VERSION 19   /* bump on ANY struct or signature change (lgn/_native.py: ABI_VERSION) */
 
 int lgn_abi_version(void);
 const char* lgn_last_error(void);
@@ -255,6 +255,35 @@ typedef struct lgn_net_desc {
 #define LGN_REAL_IMAG 2       /* im */
 #define LGN_REAL_MEAN 3       /* (re + im) / 2 */
 #define LGN_REAL_NORM 4       /* sqrt(re^2 + im^2 + 1e-16) */
+/* The loss of the whole-step calls (--loss-choice, utils/train.py:416-480: get_loss): their `loss` argument.  NULL or kind ==
+ * LGN_LOSS_CHAMFER: Chamfer [+ the jet-feature term of d->jet_loss_scale] inside the decoder's last kernel; assignment and status are
+ * then not touched.  Otherwise, with x = get_real(reconstruction) and t = target:
+ *   LGN_LOSS_MSE        nn.MSELoss()(x, t) (utils/train.py:460-462): the identity assignment on the (E, px, py, pz) columns;
+ *   LGN_LOSS_HUNGARIAN  HungarianMSELoss (utils/losses/hungarian_mse/hungarian_mse.py:46-84 and utils.py next to it) in the frame
+ *                       abs_coord / polar_coord select (main.py:324-334: --hungarian-abs-coord True, --hungarian-polar-coord False):
+ *       abs Cartesian (E, px, py, pz), D = 4;  abs polar (pt, eta, phi) of get_p_polar, D = 3;  relative polar (pt / Jpt, eta - Jeta,
+ *       phi - Jphi) with J the polar form of the TARGET's summed momenta for both sides;  relative Cartesian (pt cos phi, pt cos phi,
+ *       pt sinh eta) of the relative polar frame, as get_p_cartesian has it.
+ *     col = scipy.optimize.linear_sum_assignment of the Euclidean distances |p_i - q_j| (ties as scipy breaks them; no gradient
+ *     through it), solved by one wavefront per jet on the device instead of the reference's copy to the host and Python loop.
+ *   loss_part[b] = scale * sum_r sum_c (p[col[r]][c] - q[r][c])^2 -- the reference pairs p[col[r]] with q[r] -- and the gradient
+ *   goes through the frame, get_real and the output mix like the Chamfer gradient.  scale = 1 / (global batch * N * D): the mean of
+ *   nn.MSELoss.  Nothing is masked.  d->jet_loss_scale must be 0 (--chamfer-jet-features is a Chamfer option).  The loss stage is a
+ *   launch of its own (csrc/assign_loss.hip); 1 <= Nd <= LGN_ANOMALY_NMAX and its LDS must fit LGN_LDS_LIMIT: refused before any launch.
+ *   assignment [B][Nd] int32 (nullable): col; status [B] int32 (nullable): 1 -- a cost is NaN or -inf, 256 -- infeasible matrix;
+ *   loss_part[b] is then NaN, its assignment row is -1, and the stage hands on exact zeros for the jet (d loss / d x, the gradient
+ *   into the last level's vectors and its dWo1 partial row); where the jet's activations themselves are NaN, the level backwards
+ *   after the stage still turn 0 * NaN into NaN parameter gradients.
+ * Workspace sizes do not depend on the loss. */
+#define LGN_LOSS_CHAMFER 0
+#define LGN_LOSS_MSE 1
+#define LGN_LOSS_HUNGARIAN 2
+typedef struct lgn_loss_desc {
+  int kind;                /* LGN_LOSS_* */
+  int abs_coord;           /* Hungarian: --hungarian-abs-coord */
+  int polar_coord;         /* Hungarian: --hungarian-polar-coord */
+  double scale;            /* 1 / (global batch * N * D), D = 4 (MSE, abs Cartesian) or 3 */
+} lgn_loss_desc;
 /* latent pooling code: n = 1..4 poolings o0..o3 (LGN_POOL_MIN / MAX / MEAN), avg = 0: concatenated ('a&b'), 1: averaged ('a+b').
  * min / max pick ONE particle per (plane, channel) -- by the value itself (min) / its square (max) for scalars, by the Minkowski
  * square of the Cartesian vector for vectors (get_min_features / get_max_features, lgn_encoder.py:538-583); mean = torch.mean over
@@ -308,11 +337,14 @@ long long lgn_step_workspace_doubles(const lgn_net_desc* d);
  * p4 when scale == 1 and Nd == N), Nd = d->dec_N or N; mask [B][N]; in_scalars [B][N][K - 1] or NULL (d->n_in_scalars <= 1);
  * recon [2][B][Nd][4]; loss_part [B].  workspace_doubles = capacity of `workspace`: the call
  * fails before enqueuing anything if the current configuration needs more (lgn_step_workspace_doubles).
- * (ABI 16: the side_stream argument of the forked gradient reductions is gone with that path -- measured slower in every regime.) */
+ * loss, assignment [B][Nd], status [B]: the lgn_loss_desc above and what its stage writes; all three NULL = Chamfer.
+ * (ABI 16: the side_stream argument of the forked gradient reductions is gone with that path -- measured slower in every regime.)
+ * (ABI 19: the three whole-step calls take (loss, assignment, status) themselves; their *_loss_f64 twins are gone.) */
 int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params,
                          const int64_t* enc_off, const int64_t* dec_off, const double* p4, const double* target,
                          const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
-                         double* recon, double* loss_part, void* stream);
+                         double* recon, double* loss_part, const lgn_loss_desc* loss, int* assignment /* nullable */,
+                         int* status /* nullable */, void* stream);
 /* grads += l1_lambda*sign(params) (utils/train.py:484-487); loss_out[0..2] = total, chamfer, sum|w|; optional Adam
  * (torch.optim.Adam defaults; the step counter lives on the device so that graph replays stay correct).
  * loss_out must hold 3 + LGN_FINALIZE_SCRATCH doubles: the results, then scratch -- the per-workgroup |w| partials, the cached
@@ -339,10 +371,11 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
                        const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
                        double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
-                       int do_adam, double* loss_out, void* stream);
+                       int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment /* nullable */,
+                       int* status /* nullable */, void* stream);
 
 /* ---- evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
- * get_real(., d->get_real) -> Chamfer [+ d->jet_loss_scale * jet-feature term], forward only and without L1 (regularization =
+ * get_real(., d->get_real) -> Chamfer [+ d->jet_loss_scale * jet-feature term] or the assignment loss of `loss`, forward only and without L1 (regularization =
  * is_train, utils/train.py:308-314).  Takes every descriptor lgn_step_fwd_bwd_f64 takes and the same inputs; nothing is kept for a
  * backward, so the workspace (lgn_eval_workspace_doubles) is smaller than the training step's.  Only enqueues work (no allocation,
  * no host sync): capturable into a graph.  Refusals come before the first launch.
@@ -354,7 +387,8 @@ long long lgn_eval_workspace_doubles(const lgn_net_desc* d);
 int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
                       const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
                       double* workspace, long long workspace_doubles, double* recon_real, double* lat_s /*nullable*/,
-                      double* lat_v /*nullable*/, double* loss_part, double* loss_out, void* stream);
+                      double* lat_v /*nullable*/, double* loss_part, double* loss_out, const lgn_loss_desc* loss,
+                      int* assignment /* [B][Nd], nullable */, int* status /* [B], nullable */, void* stream);
 
 /* ---- one network at a time, maxdim = 2: what LGNEncoder.forward / LGNDecoder.forward (lgn/models/lgn_encoder.py:255-336,
  * lgn_decoder.py:218-303) and autograd's backward of them become under the module API.  Same parameter-slot layout as
@@ -418,53 +452,9 @@ int lgn_anomaly_scores_f64(const double* recons, const double* target, const dou
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */
 int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row, int* status, void* stream);
 
-/* ---- assignment losses: --loss-choice mse / hungarian (utils/train.py:416-480: get_loss) --------------------------------------
- * The whole-step calls above with the loss as an argument.  loss == NULL or kind == LGN_LOSS_CHAMFER IS the plain call (same code
- * path, same bits; assignment and status are then not touched).  Otherwise, with x = get_real(reconstruction) and t = target:
- *   LGN_LOSS_MSE        nn.MSELoss()(x, t) (utils/train.py:460-462): the identity assignment on the (E, px, py, pz) columns;
- *   LGN_LOSS_HUNGARIAN  HungarianMSELoss (utils/losses/hungarian_mse/hungarian_mse.py:46-84 and utils.py next to it) in the frame
- *                       abs_coord / polar_coord select (main.py:324-334: --hungarian-abs-coord True, --hungarian-polar-coord False):
- *       abs Cartesian (E, px, py, pz), D = 4;  abs polar (pt, eta, phi) of get_p_polar, D = 3;  relative polar (pt / Jpt, eta - Jeta,
- *       phi - Jphi) with J the polar form of the TARGET's summed momenta for both sides;  relative Cartesian (pt cos phi, pt cos phi,
- *       pt sinh eta) of the relative polar frame, as get_p_cartesian has it.
- *     col = scipy.optimize.linear_sum_assignment of the Euclidean distances |p_i - q_j| (ties as scipy breaks them; no gradient
- *     through it), solved by one wavefront per jet on the device instead of the reference's copy to the host and Python loop.
- *   loss_part[b] = scale * sum_r sum_c (p[col[r]][c] - q[r][c])^2 -- the reference pairs p[col[r]] with q[r] -- and the gradient
- *   goes through the frame, get_real and the output mix like the Chamfer gradient.  scale = 1 / (global batch * N * D): the mean of
- *   nn.MSELoss.  Nothing is masked.  d->jet_loss_scale must be 0 (--chamfer-jet-features is a Chamfer option).  The loss stage is a
- *   launch of its own (csrc/assign_loss.hip); 1 <= Nd <= LGN_ANOMALY_NMAX and its LDS must fit LGN_LDS_LIMIT: refused before any launch.
- *   assignment [B][Nd] int32 (nullable): col; status [B] int32 (nullable): 1 -- a cost is NaN or -inf, 256 -- infeasible matrix;
- *   loss_part[b] is then NaN, its assignment row is -1, and the stage hands on exact zeros for the jet (d loss / d x, the gradient
- *   into the last level's vectors and its dWo1 partial row); where the jet's activations themselves are NaN, the level backwards
- *   after the stage still turn 0 * NaN into NaN parameter gradients.
- * Workspace sizes are those of the plain calls. */
-#define LGN_LOSS_CHAMFER 0
-#define LGN_LOSS_MSE 1
-#define LGN_LOSS_HUNGARIAN 2
-typedef struct lgn_loss_desc {
-  int kind;                /* LGN_LOSS_* */
-  int abs_coord;           /* Hungarian: --hungarian-abs-coord */
-  int polar_coord;         /* Hungarian: --hungarian-polar-coord */
-  double scale;            /* 1 / (global batch * N * D), D = 4 (MSE, abs Cartesian) or 3 */
-} lgn_loss_desc;
-int lgn_step_fwd_bwd_loss_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params,
-                              const int64_t* enc_off, const int64_t* dec_off, const double* p4, const double* target,
-                              const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
-                              double* recon, double* loss_part, const lgn_loss_desc* loss, int* assignment /* [B][Nd], nullable */,
-                              int* status /* [B], nullable */, void* stream);
-int lgn_step_train_loss_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
-                            const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
-                            double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
-                            int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment /* [B][Nd], nullable */,
-                            int* status /* [B], nullable */, void* stream);
-int lgn_step_eval_loss_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
-                           const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
-                           double* workspace, long long workspace_doubles, double* recon_real, double* lat_s /*nullable*/,
-                           double* lat_v /*nullable*/, double* loss_part, double* loss_out, const lgn_loss_desc* loss,
-                           int* assignment /* [B][Nd], nullable */, int* status /* [B], nullable */, void* stream);
-/* The loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the same device code
- * without the output mix): x, y [B][N][4] real 4-vectors -> loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */
+/* ---- the assignment loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the device
+ * code of the whole-step calls' loss stage -- lgn_loss_desc above -- without the output mix): x, y [B][N][4] real 4-vectors ->
+ * loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */
 int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int kind, int abs_coord, int polar_coord, double scale,
                           double* loss_part, double* gx, int* assignment /* [B][N], nullable */, int* status /* [B], nullable */,
                           void* stream);

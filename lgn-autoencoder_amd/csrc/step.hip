@@ -410,7 +410,7 @@ int check_desc(const lgn_net_desc* d) {
   return 0;
 }
 
-// The loss argument of the *_loss_f64 calls: nullptr for Chamfer (the plain call), else the assignment loss the step's last stage
+// The loss argument of the whole-step calls: nullptr for Chamfer, else the assignment loss the step's last stage
 // runs (net.hpp: AssignLoss).  Every refusal is made here, before anything is enqueued.
 int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, AssignLoss& al, const AssignLoss** out) {
   *out = nullptr;
@@ -1391,10 +1391,10 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
 }
 extern "C" {
 
-int lgn_step_fwd_bwd_loss_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                              const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                              double* workspace, long long workspace_doubles, double* recon, double* loss_part, const lgn_loss_desc* loss,
-                              int* assignment, int* status, void* stream) {
+int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
+                         const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                         double* workspace, long long workspace_doubles, double* recon, double* loss_part, const lgn_loss_desc* loss,
+                         int* assignment, int* status, void* stream) {
   AssignLoss al;
   const AssignLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
@@ -1402,28 +1402,11 @@ int lgn_step_fwd_bwd_loss_f64(const lgn_net_desc* d, const double* params, doubl
                       loss_part, stream, nullptr, alp);
 }
 
-int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                         const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                         double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream) {
-  return lgn_step_fwd_bwd_loss_f64(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles,
-                                   recon, loss_part, nullptr, nullptr, nullptr, stream);
-}
-
 int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
                        const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                       double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda, double* adam_m,
-                       double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps, int do_adam,
-                       double* loss_out, void* stream) {
-  return lgn_step_train_loss_f64(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
-                                 loss_part, n_loss, l1_lambda, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, do_adam, loss_out, nullptr,
-                                 nullptr, nullptr, stream);
-}
-
-int lgn_step_train_loss_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
-                            const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
-                            double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
-                            int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
+                       double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
+                       double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
+                       int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
   AssignLoss al;
   const AssignLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
@@ -1606,23 +1589,15 @@ long long lgn_eval_workspace_doubles(const lgn_net_desc* d) {
   return eval_workspace(*d);
 }
 
-int lgn_step_eval_loss_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
-                           const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
-                           double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
-                           double* loss_part, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
+int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                      const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
+                      double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
+                      double* loss_part, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
   AssignLoss al;
   const AssignLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   return step_eval(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real, lat_s,
                    lat_v, loss_part, loss_out, (hipStream_t)stream, alp);
-}
-
-int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t* enc_off, const int64_t* dec_off,
-                      const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
-                      double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
-                      double* loss_part, double* loss_out, void* stream) {
-  return lgn_step_eval_loss_f64(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real,
-                                lat_s, lat_v, loss_part, loss_out, nullptr, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

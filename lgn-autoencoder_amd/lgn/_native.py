@@ -15,7 +15,7 @@ import torch  # imported before the .so so that the process-wide libamdhip64 is 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LGN_AMD_LIB") or os.path.join(_HERE, "_lib", "liblgn_amd.so")   # LGN_AMD_LIB: debug builds (tools/)
-ABI_VERSION = 18
+ABI_VERSION = 19
 FINALIZE_SCRATCH = 2048      # include/lgn_amd.h: LGN_FINALIZE_SCRATCH
 
 _lib: Optional[C.CDLL] = None
@@ -145,7 +145,15 @@ def net_flags() -> int:
     return sum(bit for name, bit in _NET_FLAG_ENV.items() if os.environ.get(name, "") == "1")
 
 
+class LossDesc(C.Structure):
+    """lgn_loss_desc of include/lgn_amd.h."""
+    _fields_ = [("kind", C.c_int), ("abs_coord", C.c_int), ("polar_coord", C.c_int), ("scale", C.c_double)]
+
+
+LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
+ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
 _dp = C.POINTER(NetDesc)
+_lp = C.POINTER(LossDesc)
 _ll = C.c_longlong
 _d = C.c_double
 _SIGNATURES.update({
@@ -157,35 +165,22 @@ _SIGNATURES.update({
     "lgn_local_bwd_static_f64": [_i] * 4 + [_vp] * 3 + [_ip] + [_vp] * 8,
     "lgn_local_bwd_f64": [_i] * 5 + [_tp] + [_vp] * 8,
     "lgn_step_param_slots": [_dp, _i],
-    "lgn_step_fwd_bwd_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp],
+    # (the whole-step calls end in loss, assignment, status, stream)
+    "lgn_step_fwd_bwd_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _lp, _vp, _vp, _vp],
     "lgn_encoder_fwd_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp],
     "lgn_encoder_bwd_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _ll, _vp],
     "lgn_decoder_fwd_f64": [_dp, _vp, _vp, _vp, _vp, _ll, _vp, _vp],
     "lgn_decoder_bwd_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _ll, _vp],
     "lgn_step_finalize_f64": [_vp, _vp, _ll, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp],
     "lgn_step_train_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i,
-                           _vp, _vp],
-    "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp],
+                           _vp, _lp, _vp, _vp, _vp],
+    "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _lp, _vp, _vp, _vp],
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
-})
-
-
-class LossDesc(C.Structure):
-    """lgn_loss_desc of include/lgn_amd.h."""
-    _fields_ = [("kind", C.c_int), ("abs_coord", C.c_int), ("polar_coord", C.c_int), ("scale", C.c_double)]
-
-
-LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
-ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
-_lp = C.POINTER(LossDesc)
-# the whole-step calls with a loss descriptor: the arguments of the plain calls, then (loss, assignment, status) before the stream
-_SIGNATURES.update({
-    "lgn_step_fwd_bwd_loss_f64": _SIGNATURES["lgn_step_fwd_bwd_f64"][:-1] + [_lp, _vp, _vp, _vp],
-    "lgn_step_train_loss_f64": _SIGNATURES["lgn_step_train_f64"][:-1] + [_lp, _vp, _vp, _vp],
-    "lgn_step_eval_loss_f64": _SIGNATURES["lgn_step_eval_f64"][:-1] + [_lp, _vp, _vp, _vp],
     "lgn_hungarian_mse_f64": [_i, _i, _vp, _vp, _i, _i, _i, _d] + [_vp] * 5,
 })
+
+
 _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_step_workspace_doubles": [_dp],
     "lgn_eval_workspace_doubles": [_dp],

@@ -12,6 +12,7 @@ MI355X-first choices (none of them exist in the reference, which is single-devic
     gradients reproduces the single-GPU step on the concatenated batch exactly; the L1 sub-gradient
     l1_lambda * sign(w) is batch independent and is added once, after the all-reduce.
 """
+import inspect
 from typing import Dict, Optional
 
 import torch
@@ -45,6 +46,10 @@ def chamfer_loss(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 def normalize_p4(p4: torch.Tensor) -> torch.Tensor:
     """'overall_max' normalisation (utils/normalize_p4.py:39-52)."""
     return p4 / (torch.abs(p4).amax(dim=-1, keepdim=True).amax(dim=-2, keepdim=True) + 1e-16)
+
+
+def _world_size(group) -> int:
+    return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
 
 
 class FlatParams:
@@ -86,7 +91,7 @@ class TrainStep:
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
         self.flat = FlatParams(encoder, decoder)
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.world = _world_size(process_group)
         self.group = process_group
         # two Adam optimisers with identical hyper-parameters act on disjoint parameters (initialize.py:156-158);
         # one Adam over the flat buffer performs the same element-wise update.
@@ -137,11 +142,9 @@ class ReferenceLoopStep:
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
                                     None if native_loss else chamfer_loss)
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.world = _world_size(process_group)
         self.group = process_group
-        # Chamfer is a SUM over the jets: the ranks' gradients add up to the step of one process on the whole batch.  mse / hungarian
-        # are MEANS over the batch: a rank's term is weighted 1 / world before the SUM all-reduce (ranks hold equal shares)
-        self._loss_weight = 1.0 if "chamfer" in str(loss_choice).lower() else 1.0 / self.world
+        self._loss_weight = _loss_weight(loss_choice, self.world)
         self.opt_enc = torch.optim.Adam(encoder.parameters(), lr) if optimizer else None
         self.opt_dec = torch.optim.Adam(decoder.parameters(), lr) if optimizer else None
 
@@ -189,6 +192,15 @@ def _module_loss(loss_choice, abs_coord, polar_coord, device, chamfer=None, jet_
     loss = lambda x, t: fn(x, t, abs_coord=abs_coord, polar_coord=polar_coord)     # noqa: E731
     loss.module = fn
     return loss
+
+
+def _loss_weight(loss_choice, world: int) -> float:
+    """The weight of a rank's loss term in the module-API steps.  Chamfer is a SUM over the jets: the ranks' gradients add up to the
+    step of one process on the whole batch.  mse / hungarian are MEANS over the batch: a rank's term is weighted 1 / world before the
+    SUM all-reduce (ranks hold equal shares)."""
+    from . import _native as N
+    from .losses import loss_kind
+    return 1.0 if loss_kind(loss_choice) == N.LOSS_CHAMFER else 1.0 / world
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -323,9 +335,10 @@ def _step_desc(encoder, decoder, B: int, split: bool, get_real_method: str, jet_
     return d, keep
 
 
-def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, n_particles):
-    """(kind, lgn_loss_desc or None) of a whole step: None for Chamfer -- the step then issues the plain calls, as it always has.
-    scale = 1 / (n_jets N D), n_jets the GLOBAL batch (the mean of nn.MSELoss over everything the ranks hold together)."""
+def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, decoder):
+    """(kind, lgn_loss_desc or None) of a whole step: None for Chamfer -- the native calls then take NULL for it.
+    scale = 1 / (n_jets N D), n_jets the GLOBAL batch (the mean of nn.MSELoss over everything the ranks hold together).  Refuses
+    (NotImplementedError) a decoder whose loss stage does not fit a CU's LDS: that configuration runs through the module API."""
     from . import _native as N
     from .losses import loss_kind, loss_columns
     kind = loss_kind(loss_choice)
@@ -334,19 +347,111 @@ def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, n_part
     if jet_features:
         raise ValueError("chamfer_jet_features is an option of the Chamfer loss; it cannot be combined with "
                          f"loss_choice={loss_choice!r}")
-    ld = N.LossDesc()
-    ld.kind, ld.abs_coord, ld.polar_coord = kind, int(bool(abs_coord)), int(bool(polar_coord))
-    ld.scale = 1.0 / (n_jets * n_particles * loss_columns(kind, abs_coord, polar_coord))
-    return kind, ld
-
-
-def _check_assign_fit(decoder):
-    from . import _native as N
-    Nd, CL = decoder.num_output_particles, decoder.num_channels[-1]
-    need = N.lib().lgn_assign_loss_lds_bytes(Nd, CL)
+    Nd = decoder.num_output_particles
+    need = N.lib().lgn_assign_loss_lds_bytes(Nd, decoder.num_channels[-1])
     if Nd > N.ASSIGN_NMAX or not 0 <= need <= N.LDS_LIMIT:
         raise NotImplementedError(f"the native mse / hungarian loss stage at {Nd} particles needs {need} B of LDS (limit {N.LDS_LIMIT}, "
                                   f"at most {N.ASSIGN_NMAX} particles); this configuration runs through the module API")
+    ld = N.LossDesc()
+    ld.kind, ld.abs_coord, ld.polar_coord = kind, int(bool(abs_coord)), int(bool(polar_coord))
+    ld.scale = 1.0 / (n_jets * Nd * loss_columns(kind, abs_coord, polar_coord))
+    return kind, ld
+
+
+def _warm_up(fn):
+    """Run fn() once on a side stream before a capture (lazy module loads, hipFuncSetAttribute, allocator state), and wait for it."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+
+
+def _node_mask(batch, p4, shape):
+    """The uint8 node mask of a batch: its labels / masks / mask entry (of `shape`), else p4[..., 0] != 0, as in
+    LGNEncoder._prepare_input (lgn/models/lgn_encoder.py:386-398)."""
+    for key in ("labels", "masks", "mask"):
+        if key in batch:
+            if tuple(batch[key].shape) != tuple(shape):
+                raise ValueError(f"mask shape {tuple(batch[key].shape)} != {tuple(shape)}")
+            return batch[key].to(torch.uint8)
+    return (p4[..., 0] != 0).to(torch.uint8)
+
+
+class _OptimState:
+    """What lgn_step_finalize_f64 (and the tail of lgn_step_train_f64) works on besides the FlatParams: the Adam moments, the step
+    counter on the device, the loss block (results | scratch), the hyper-parameters -- and the call itself."""
+
+    def __init__(self, flat: FlatParams, l1_lambda, lr, betas, eps):
+        from . import _native as N
+        self.N, self.flat = N, flat
+        self.adam_m, self.adam_v = torch.zeros_like(flat.flat), torch.zeros_like(flat.flat)
+        self.step_dev = torch.zeros(1, device=flat.flat.device, dtype=torch.int64)
+        self.loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=flat.flat.device, dtype=flat.flat.dtype)
+        self.loss_out = self.loss_buf[:3]
+        self._state = (flat.flat, self.adam_m, self.adam_v, self.step_dev)          # what a step changes: snapshot() / restore()
+        self._head = (N.ptr(flat.flat), N.ptr(flat.grad), flat.flat.numel(), N.ptr(flat.tail))
+        self._hyper = (flat.tail.numel(), float(l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v), N.ptr(self.step_dev), float(lr),
+                       float(betas[0]), float(betas[1]), float(eps))
+
+    def tail_args(self, do_adam: bool):
+        """(n_loss, l1_lambda, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, do_adam, loss_out) of both calls."""
+        return self._hyper + (int(do_adam), self.N.ptr(self.loss_buf))
+
+    def finalize(self, do_adam: bool):
+        N = self.N
+        N._check(N.lib().lgn_step_finalize_f64(*self._head, *self.tail_args(do_adam), N.stream_ptr()), "lgn_step_finalize_f64")
+
+    def snapshot(self):
+        return tuple(t.clone() for t in self._state)
+
+    def restore(self, snap):
+        with torch.no_grad():
+            for t, s in zip(self._state, snap):
+                t.copy_(s)
+
+
+class _StaticInputs:
+    """The static input buffers of a whole step -- p4 (the encoder's input: scaled, with jet_features + the jet node), target (the
+    UNscaled batch the reconstruction is compared with, utils/train.py:285-292), mask, in_scalars (jet mass term, data['scalars'];
+    None without them) and, for an assignment loss, the assignment / status it fills -- and the staging of a batch into them."""
+
+    def __init__(self, encoder, decoder, B: int, split: bool, assignment: bool, alias_target: bool = False):
+        dev, dt = encoder.flat_params.device, encoder.flat_params.dtype
+        N, Nd, K = encoder.num_input_particles, decoder.num_output_particles, max(1, encoder.tau_input_scalars)
+        self.encoder, self.split, self.B = encoder, split, B
+        self.p4 = torch.zeros(B, N, 4, device=dev, dtype=dt)
+        # alias_target (training): the target IS the input when scale == 1 and the nodes are the same -- one copy per step
+        self.target = self.p4 if alias_target and encoder.scale == 1.0 and not split else torch.zeros(B, Nd, 4, device=dev, dtype=dt)
+        self.mask = torch.zeros(B, N, device=dev, dtype=torch.uint8)
+        self.in_scalars = torch.zeros(B, N, K - 1, device=dev, dtype=dt) if K > 1 else None
+        self.assignment = torch.full((B, Nd), -1, device=dev, dtype=torch.int32) if assignment else None
+        self.status = torch.zeros(B, device=dev, dtype=torch.int32) if assignment else None
+
+    def stage(self, batch: Dict[str, torch.Tensor], n: Optional[int] = None):
+        """Device-to-device copies of a batch of n jets (None: all B) into rows 0 .. n - 1; rows n .. B - 1 become all-masked jets."""
+        p4 = batch["p4"]
+        p4_in, target, mask = self.p4[:n], self.target[:n], self.mask[:n]
+        if self.split:
+            # jet node, jet-mass scalar, data['scalars']: the encoder's own input preparation (lgn_encoder.py:372-411), on the device
+            ps, m, scalars = self.encoder._prepare_input(batch)
+            p4_in.copy_(ps)
+            mask.copy_(m)
+            if self.in_scalars is not None:
+                self.in_scalars[:n].copy_(scalars)
+            target.copy_(p4)
+        else:
+            if self.target is self.p4:
+                p4_in.copy_(p4)
+            else:
+                target.copy_(p4)
+                torch.mul(target, self.encoder.scale, out=p4_in)
+            mask.copy_(_node_mask(batch, p4, mask.shape))
+        if n is not None and n < self.B:
+            for t in (self.p4, self.target, self.mask, self.in_scalars):
+                if t is not None:
+                    t[n:].zero_()
 
 
 class NativeTrainStep:
@@ -364,7 +469,7 @@ class NativeTrainStep:
 
     ``loss_choice`` (--loss-choice, matched as utils/train.py:416-480 matches it): 'chamfer', 'mse' or 'hungarian' / 'jet' with
     ``hungarian_abs_coord`` / ``hungarian_polar_coord`` (main.py:324-334); 'emd' and 'hybrid' raise NotImplementedError.  The mse and
-    Hungarian losses run as the step's loss stage (lgn_step_*_loss_f64, csrc/assign_loss.hip); they are means over (global batch, N,
+    Hungarian losses run as the step's loss stage (the `loss` argument of the native calls, csrc/assign_loss.hip); they are means over (global batch, N,
     D), so each rank scales by 1 / (batch_size world N D).  ``assignment`` is the (B, N) int32 buffer the last step filled with every
     jet's col (static: graph replays keep filling it), ``status`` its (B,) int32 companion."""
 
@@ -377,12 +482,10 @@ class NativeTrainStep:
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.world = _world_size(process_group)
         self.loss_choice = loss_choice
         self.loss_kind, self.loss_desc = _loss_desc(loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features,
-                                                    batch_size * self.world, decoder.num_output_particles)
-        if self.loss_desc is not None:
-            _check_assign_fit(decoder)
+                                                    batch_size * self.world, decoder)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
         self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet loss terms
@@ -414,94 +517,44 @@ class NativeTrainStep:
         if nws < 0:
             raise RuntimeError(N.last_error())
         self.workspace = torch.empty(nws, device=dev, dtype=dt)
-        Nd = decoder.num_output_particles
-        self.recon = torch.empty(2, d.B, Nd, 4, device=dev, dtype=dt)
+        self.recon = torch.empty(2, d.B, decoder.num_output_particles, 4, device=dev, dtype=dt)
         self.loss_part = self.flat.tail
-        self._loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=dev, dtype=dt)   # results | scratch
-        self.loss_out = self._loss_buf[:3]
-        self.adam_m = torch.zeros_like(self.flat.flat)
-        self.adam_v = torch.zeros_like(self.flat.flat)
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int64)
-        self.p4 = torch.empty(d.B, d.N, 4, device=dev, dtype=dt)           # encoder input (p4 * scale; with jet_features + the jet node)
-        # Chamfer target = the UNscaled batch (utils/train.py:285-292); aliases the input when scale == 1 and the nodes are the same
-        self.target = self.p4 if encoder.scale == 1.0 and not self.split else torch.empty(d.B, Nd, 4, device=dev, dtype=dt)
-        self.mask = torch.empty(d.B, d.N, device=dev, dtype=torch.uint8)
-        K = max(1, encoder.tau_input_scalars)
-        self.in_scalars = torch.empty(d.B, d.N, K - 1, device=dev, dtype=dt) if K > 1 else None     # jet mass term, data['scalars']
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps)
+        self.adam_m, self.adam_v, self.step_dev, self._loss_buf, self.loss_out = o.adam_m, o.adam_v, o.step_dev, o.loss_buf, o.loss_out
+        self._finalize = o.finalize                       # (do_adam): lgn_step_finalize_f64 on the current stream
+        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True)
+        self.p4, self.target, self.mask, self.in_scalars, self.assignment, self.status = \
+            i.p4, i.target, i.mask, i.in_scalars, i.assignment, i.status
         self.use_graph = use_graph
         self._g1 = self._g2 = None
-        self.assignment = self.status = None
-        if self.loss_desc is not None:
-            self.assignment = torch.full((d.B, Nd), -1, device=dev, dtype=torch.int32)
-            self.status = torch.zeros(d.B, device=dev, dtype=torch.int32)
+        # the arguments of the native calls: every pointer is static (self.desc / self.loss_desc stay alive with the step)
+        self._net_args = (C.byref(d), N.ptr(self.flat.flat), N.ptr(self.flat.grad), n, self.enc_off, self.dec_off, N.ptr(i.p4),
+                          N.ptr(i.target), N.ptr(i.mask), N.ptr(i.in_scalars), N.ptr(self.workspace), nws, N.ptr(self.recon),
+                          N.ptr(self.loss_part))
+        self._loss_args = (C.byref(self.loss_desc) if self.loss_desc is not None else None, N.ptr(i.assignment), N.ptr(i.status))
 
     # -- raw native calls on the current stream
     def _fwd_bwd(self):
-        import ctypes as C
         N = self.N
-        if self.loss_desc is not None:
-            rc = N.lib().lgn_step_fwd_bwd_loss_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
-                                                   self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
-                                                   N.ptr(self.in_scalars) if self.in_scalars is not None else None,
-                                                   N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
-                                                   C.byref(self.loss_desc), N.ptr(self.assignment), N.ptr(self.status), N.stream_ptr())
-            N._check(rc, "lgn_step_fwd_bwd_loss_f64")
-            return
-        rc = N.lib().lgn_step_fwd_bwd_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
-                                          self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
-                                          N.ptr(self.in_scalars) if self.in_scalars is not None else None,
-                                          N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
-                                          N.stream_ptr())
-        N._check(rc, "lgn_step_fwd_bwd_f64")
-
-    def _finalize(self, do_adam: bool):
-        N = self.N
-        rc = N.lib().lgn_step_finalize_f64(N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(), N.ptr(self.loss_part),
-                                           self.loss_part.numel(), float(self.l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v),
-                                           N.ptr(self.step_dev), float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                           float(self.eps), int(do_adam), N.ptr(self._loss_buf), N.stream_ptr())
-        N._check(rc, "lgn_step_finalize_f64")
+        N._check(N.lib().lgn_step_fwd_bwd_f64(*self._net_args, *self._loss_args, N.stream_ptr()), "lgn_step_fwd_bwd_f64")
 
     def _train(self, do_adam: bool):
         """Single process: the whole step in ONE native call (lgn_step_train_f64) -- with no all-reduce between the gradients and the
         optimiser, the reductions, the radial finalisation, L1 + Adam and the loss assembly are one launch (csrc/step_tail.hip)
         instead of three; same results bit for bit (LGN_AMD_SPLIT_TAIL=1 when the step is built: the separate launches)."""
-        import ctypes as C
         N = self.N
-        if self.loss_desc is not None:
-            rc = N.lib().lgn_step_train_loss_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
-                                                 self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
-                                                 N.ptr(self.in_scalars) if self.in_scalars is not None else None,
-                                                 N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
-                                                 self.loss_part.numel(), float(self.l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v),
-                                                 N.ptr(self.step_dev), float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                                 float(self.eps), int(do_adam), N.ptr(self._loss_buf), C.byref(self.loss_desc),
-                                                 N.ptr(self.assignment), N.ptr(self.status), N.stream_ptr())
-            N._check(rc, "lgn_step_train_loss_f64")
-            return
-        rc = N.lib().lgn_step_train_f64(C.byref(self.desc), N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(),
-                                        self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
-                                        N.ptr(self.in_scalars) if self.in_scalars is not None else None,
-                                        N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.loss_part),
-                                        self.loss_part.numel(), float(self.l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v),
-                                        N.ptr(self.step_dev), float(self.lr), float(self.betas[0]), float(self.betas[1]),
-                                        float(self.eps), int(do_adam), N.ptr(self._loss_buf), N.stream_ptr())
-        N._check(rc, "lgn_step_train_f64")
+        N._check(N.lib().lgn_step_train_f64(*self._net_args, *self.opt_state.tail_args(do_adam), *self._loss_args, N.stream_ptr()),
+                 "lgn_step_train_f64")
+
+    def _eager_collective(self, do_adam: bool):
+        self._fwd_bwd()
+        dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
+        self._finalize(do_adam)
 
     def _capture(self):
-        # warm up on a side stream (lazy module loads, hipFuncSetAttribute), then capture
-        snap = (self.flat.flat.clone(), self.adam_m.clone(), self.adam_v.clone(), self.step_dev.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            if self.collective:       # communicator / algorithm set-up of this message size happens outside the capture
-                self._fwd_bwd()
-                dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
-                self._finalize(False)
-            else:
-                self._train(False)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        snap = self.opt_state.snapshot()
+        # (with a collective, the communicator / algorithm set-up of this message size happens here, outside the capture)
+        _warm_up(lambda: self._eager_collective(False) if self.collective else self._train(False))
         ref = (self.flat.grad_buf.clone(), self._loss_buf[:3].clone())     # the eager step's reduced gradients | loss terms, loss
         self._g1, self._g2, self._in_graph = torch.cuda.CUDAGraph(), None, False
         if self.collective and self.graph_collective is not False:
@@ -511,9 +564,7 @@ class NativeTrainStep:
             # (agree_in_graph: the ranks exchange both outcomes, none decides from what it saw locally)
             def try_capture():
                 with _capturing(self._g1):
-                    self._fwd_bwd()
-                    dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
-                    self._finalize(self.optimizer)
+                    self._eager_collective(self.optimizer)
 
             def reset():
                 torch.cuda.synchronize()
@@ -531,50 +582,25 @@ class NativeTrainStep:
             with _capturing(self._g1):
                 self._train(self.optimizer)
         self.launches_per_step = 3 if self._g2 is not None else 1
-        with torch.no_grad():   # capture does not execute, but restore anyway in case a backend replays eagerly
-            self.flat.flat.copy_(snap[0]); self.adam_m.copy_(snap[1]); self.adam_v.copy_(snap[2]); self.step_dev.copy_(snap[3])
+        self.opt_state.restore(snap)   # capture does not execute, but restore anyway in case a backend replays eagerly
 
     def _captured_collective_matches(self, snap, ref) -> bool:
         """One replay of the freshly captured [fwd+bwd | all-reduce | L1 + Adam] graph from the snapshotted state: the reduced
         gradient buffer (gradients + L1 sub-gradient | per-jet loss terms of ALL ranks) and the loss must be what the eager
         warm-up step produced from the same state -- a capture that silently dropped the collective would leave the local sums.
         LOCAL verdict; agree_in_graph makes it every rank's."""
-        with torch.no_grad():
-            self.flat.flat.copy_(snap[0]); self.adam_m.copy_(snap[1]); self.adam_v.copy_(snap[2]); self.step_dev.copy_(snap[3])
+        self.opt_state.restore(snap)
         self._g1.replay()
         torch.cuda.synchronize()
         tol = dict(rtol=1e-11, atol=1e-300)       # same kernels; only the reduction order inside RCCL may differ
         return bool(torch.allclose(self.flat.grad_buf, ref[0], **tol) and torch.allclose(self._loss_buf[:3], ref[1], **tol))
 
     def load_batch(self, batch: Dict[str, torch.Tensor]):
-        """Stage a batch into the static input buffers (device-to-device copy; labels/masks as in
-        LGNEncoder._prepare_input, lgn/models/lgn_encoder.py:386-398)."""
-        p4 = batch["p4"]
-        if tuple(p4.shape) != tuple(self.target.shape):
-            raise ValueError(f"NativeTrainStep was built for batches of shape {tuple(self.target.shape)}, got {tuple(p4.shape)} "
+        """Stage a batch into the static input buffers (_StaticInputs.stage)."""
+        if tuple(batch["p4"].shape) != tuple(self.target.shape):
+            raise ValueError(f"NativeTrainStep was built for batches of shape {tuple(self.target.shape)}, got {tuple(batch['p4'].shape)} "
                              "(static buffers / captured graph: pad or drop the last short batch)")
-        if self.split:
-            # jet node, jet-mass scalar, data['scalars']: the encoder's own input preparation (lgn_encoder.py:372-411), on the device
-            ps, mask, scalars = self.encoder._prepare_input(batch)
-            self.p4.copy_(ps)
-            self.mask.copy_(mask)
-            if self.in_scalars is not None:
-                self.in_scalars.copy_(scalars)
-            self.target.copy_(p4)
-            return
-        if self.target is not self.p4:
-            self.target.copy_(p4)
-            torch.mul(self.target, self.encoder.scale, out=self.p4)
-        else:
-            self.p4.copy_(p4)
-        for key in ("labels", "masks", "mask"):
-            if key in batch:
-                if tuple(batch[key].shape) != tuple(self.mask.shape):
-                    raise ValueError(f"mask shape {tuple(batch[key].shape)} != {tuple(self.mask.shape)}")
-                self.mask.copy_(batch[key].to(torch.uint8))
-                break
-        else:
-            self.mask.copy_((p4[..., 0] != 0).to(torch.uint8))
+        self.inputs.stage(batch)
 
     def step(self, batch: Optional[Dict[str, torch.Tensor]] = None):
         """Runs one step on `batch` (or on the already staged static buffers when batch is None).
@@ -589,9 +615,7 @@ class NativeTrainStep:
                 dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
                 self._g2.replay()
         elif self.collective:
-            self._fwd_bwd()
-            dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
-            self._finalize(self.optimizer)
+            self._eager_collective(self.optimizer)
         else:
             self._train(self.optimizer)
         return self.loss_out[0], self.recon
@@ -618,7 +642,7 @@ class CapturedModuleStep:
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
         self.get_real_method, self.chamfer_jet_features = get_real_method, chamfer_jet_features
         self.flat = FlatParams(encoder, decoder, grad_tail=1)             # gradients | this rank's Chamfer term
-        self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
+        self.world = _world_size(process_group)
         self.group, self.optimizer, self.use_graph = process_group, optimizer, use_graph
         dev, dt = self.flat.flat.device, self.flat.flat.dtype
         n_in = encoder.num_input_particles - (1 if getattr(encoder, "jet_features", False) else 0)    # particles per jet in the batch
@@ -626,14 +650,12 @@ class CapturedModuleStep:
                       "labels": torch.zeros(batch_size, n_in, device=dev, dtype=torch.uint8)}
         if extra_scalars:
             self.batch["scalars"] = torch.zeros(batch_size, encoder.num_input_particles, extra_scalars, device=dev, dtype=dt)
-        # (mse / hungarian are means over the GLOBAL batch: a rank's term is weighted 1 / world before the SUM all-reduce)
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, dev, jet_features=chamfer_jet_features)
-        self._loss_weight = 1.0 if "chamfer" in str(loss_choice).lower() else 1.0 / self.world
+        self._loss_weight = _loss_weight(loss_choice, self.world)
         self.loss_part = self.flat.tail
-        self._loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=dev, dtype=dt)
-        self.loss_out = self._loss_buf[:3]
-        self.adam_m, self.adam_v = torch.zeros_like(self.flat.flat), torch.zeros_like(self.flat.flat)
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int64)
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps)
+        self.adam_m, self.adam_v, self.step_dev, self._loss_buf, self.loss_out = o.adam_m, o.adam_v, o.step_dev, o.loss_buf, o.loss_out
+        self._finalize = o.finalize                       # (do_adam): lgn_step_finalize_f64 on the current stream
         self.recon = None
         self._g1 = self._g2 = None
         self.launches_per_step = None
@@ -648,24 +670,15 @@ class CapturedModuleStep:
         self.loss_part.copy_(loss.detach().reshape(1))
         self.recon = recon.detach()
 
-    def _finalize(self, do_adam: bool):
-        N = self.N
-        rc = N.lib().lgn_step_finalize_f64(N.ptr(self.flat.flat), N.ptr(self.flat.grad), self.flat.flat.numel(), N.ptr(self.loss_part), 1,
-                                           float(self.l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v), N.ptr(self.step_dev),
-                                           float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), int(do_adam),
-                                           N.ptr(self._loss_buf), N.stream_ptr())
-        N._check(rc, "lgn_step_finalize_f64")
-
     def _capture(self):
-        snap = (self.flat.flat.clone(), self.adam_m.clone(), self.adam_v.clone(), self.step_dev.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                        # warm-up: lazy loads, autograd's first-use set-up, allocator state
+        snap = self.opt_state.snapshot()
+
+        def twice():                                      # autograd's first-use set-up, allocator state
             for _ in range(2):
                 self._fwd_bwd()
                 self._finalize(False)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+
+        _warm_up(twice)
         self._g1 = torch.cuda.CUDAGraph()
         if self.world > 1:
             self._g2 = torch.cuda.CUDAGraph()
@@ -678,8 +691,7 @@ class CapturedModuleStep:
                 self._fwd_bwd()
                 self._finalize(self.optimizer)
         self.launches_per_step = 3 if self._g2 is not None else 1
-        with torch.no_grad():
-            self.flat.flat.copy_(snap[0]); self.adam_m.copy_(snap[1]); self.adam_v.copy_(snap[2]); self.step_dev.copy_(snap[3])
+        self.opt_state.restore(snap)
 
     def load_batch(self, batch: Dict[str, torch.Tensor]):
         """Stage a batch into the static input tensors the captured graph reads (the encoder's own input preparation -- scale,
@@ -688,14 +700,7 @@ class CapturedModuleStep:
         if tuple(p4.shape) != tuple(self.batch["p4"].shape):
             raise ValueError(f"CapturedModuleStep was built for batches of shape {tuple(self.batch['p4'].shape)}, got {tuple(p4.shape)}")
         self.batch["p4"].copy_(p4)
-        for key in ("labels", "masks", "mask"):
-            if key in batch:
-                if tuple(batch[key].shape) != tuple(self.batch["labels"].shape):
-                    raise ValueError(f"mask shape {tuple(batch[key].shape)} != {tuple(self.batch['labels'].shape)}")
-                self.batch["labels"].copy_(batch[key].to(torch.uint8))
-                break
-        else:
-            self.batch["labels"].copy_((p4[..., 0] != 0).to(torch.uint8))
+        self.batch["labels"].copy_(_node_mask(batch, p4, self.batch["labels"].shape))
         if ("scalars" in batch) != ("scalars" in self.batch):
             raise ValueError("CapturedModuleStep: data['scalars'] must be present exactly when the step was built with extra_scalars")
         if "scalars" in batch:
@@ -720,12 +725,14 @@ class CapturedModuleStep:
         return self.loss_out[0], self.recon
 
 
+_STEP_KEYWORDS = {cls: set(inspect.signature(cls.__init__).parameters) - {"self"} for cls in (NativeTrainStep, CapturedModuleStep)}
+
+
 def native_train_step(encoder, decoder, batch_size: int, **kw):
     """NativeTrainStep where lgn_step_fwd_bwd_f64 covers the configuration (one native call per step), else CapturedModuleStep
     (the module-API step captured into one graph).  Keyword arguments the two do not share go to the one that takes them."""
-    import inspect
     import warnings
-    takes = {cls: set(inspect.signature(cls.__init__).parameters) - {"self"} for cls in (NativeTrainStep, CapturedModuleStep)}
+    takes = _STEP_KEYWORDS
     unknown = set(kw) - takes[NativeTrainStep] - takes[CapturedModuleStep]
     if unknown:
         raise TypeError(f"native_train_step: unknown keyword argument(s) {sorted(unknown)}")
@@ -751,7 +758,7 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
 class NativeEvalStep:
     """encoder -> decoder -> get_real -> loss forward only -- Chamfer [+ jet-feature MSE], or with ``loss_choice`` 'mse' / 'hungarian'
     (``hungarian_abs_coord``, ``hungarian_polar_coord``) the assignment losses, whose ``assignment`` (B, N) / ``status`` (B,) int32
-    buffers the run fills -- executed by lgn_step_eval_f64 / lgn_step_eval_loss_f64 (csrc/step.hip):
+    buffers the run fills -- executed by lgn_step_eval_f64 (csrc/step.hip):
     the reference's evaluation loss (no L1: regularization = is_train, utils/train.py:308-314), the reconstruction after get_real
     (what validate() collects) and, with ``keep_latent``, the pooled latent (what test.py saves).  Nothing is kept for a backward.
     With ``use_graph`` the call is captured once into a HIP graph and replayed.
@@ -770,35 +777,27 @@ class NativeEvalStep:
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
         self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
-        self._loss_args = (loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features)
-        self.loss_kind, self.loss_desc = _loss_desc(*self._loss_args, self.B, decoder.num_output_particles)
-        if self.loss_desc is not None:
-            _check_assign_fit(decoder)
+        self._loss_opts = (loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features)
+        self.loss_kind, self.loss_desc = _loss_desc(*self._loss_opts, self.B, decoder)
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
         self.keep_latent, self.use_graph = bool(keep_latent), use_graph
         self._plan()
         d = self.desc
         dev, dt = encoder.flat_params.device, encoder.flat_params.dtype
-        Nd = decoder.num_output_particles
         self.workspace = torch.empty(self._ws, device=dev, dtype=dt)
-        self.recon = torch.empty(d.B, Nd, 4, device=dev, dtype=dt)
+        self.recon = torch.empty(d.B, decoder.num_output_particles, 4, device=dev, dtype=dt)
         self.loss_part = torch.empty(d.B, device=dev, dtype=dt)
         self.loss_out = torch.zeros(1, device=dev, dtype=dt)
         self.loss = self.loss_out[0]
-        self.p4 = torch.zeros(d.B, d.N, 4, device=dev, dtype=dt)
-        self.target = torch.zeros(d.B, Nd, 4, device=dev, dtype=dt)
-        self.mask = torch.zeros(d.B, d.N, device=dev, dtype=torch.uint8)
-        K = max(1, encoder.tau_input_scalars)
-        self.in_scalars = torch.zeros(d.B, d.N, K - 1, device=dev, dtype=dt) if K > 1 else None
+        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None)
+        self.p4, self.target, self.mask, self.in_scalars, self.assignment, self.status = \
+            i.p4, i.target, i.mask, i.in_scalars, i.assignment, i.status
         P = N.pool_blocks(d.latent_pool)
         self.lat_s = torch.empty(2, d.B, 1, P * d.tau_s, 1, device=dev, dtype=dt) if self.keep_latent else None
         self.lat_v = torch.empty(2, d.B, 1, P * d.tau_v, 4, device=dev, dtype=dt) if self.keep_latent else None
         self._graph = None
         self.n_real = d.B
-        self.assignment = self.status = None
-        if self.loss_desc is not None:
-            self.assignment = torch.full((d.B, Nd), -1, device=dev, dtype=torch.int32)
-            self.status = torch.zeros(d.B, device=dev, dtype=torch.int32)
+        self._bind()
 
     def _plan(self):
         """Descriptor and parameter offsets for where the two flat blocks are now (offsets count from the lower block)."""
@@ -816,31 +815,28 @@ class NativeEvalStep:
             raise RuntimeError(N.last_error())
         self.desc = d
 
-    def _eval(self, desc=None, loss_desc=None):
+    def _bind(self):
+        """The arguments of lgn_step_eval_f64 for the current plan and workspace: every pointer is static until the next _plan
+        (self.desc / self.loss_desc stay alive with the step)."""
         import ctypes as C
         N = self.N
-        if self.loss_desc is not None:
-            ld = loss_desc if loss_desc is not None else self.loss_desc
-            rc = N.lib().lgn_step_eval_loss_f64(C.byref(self.desc), self._base, self.enc_off, self.dec_off, N.ptr(self.p4),
-                                                N.ptr(self.target), N.ptr(self.mask), N.ptr(self.in_scalars), N.ptr(self.workspace),
-                                                self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s), N.ptr(self.lat_v),
-                                                N.ptr(self.loss_part), N.ptr(self.loss_out), C.byref(ld), N.ptr(self.assignment),
-                                                N.ptr(self.status), N.stream_ptr())
-            N._check(rc, "lgn_step_eval_loss_f64")
-            return
-        rc = N.lib().lgn_step_eval_f64(C.byref(desc if desc is not None else self.desc), self._base, self.enc_off, self.dec_off,
-                                       N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask), N.ptr(self.in_scalars), N.ptr(self.workspace),
-                                       self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s), N.ptr(self.lat_v),
-                                       N.ptr(self.loss_part), N.ptr(self.loss_out), N.stream_ptr())
-        N._check(rc, "lgn_step_eval_f64")
+        self._args = (C.byref(self.desc), self._base, self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
+                      N.ptr(self.in_scalars), N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s),
+                      N.ptr(self.lat_v), N.ptr(self.loss_part), N.ptr(self.loss_out),
+                      C.byref(self.loss_desc) if self.loss_desc is not None else None, N.ptr(self.assignment), N.ptr(self.status))
+
+    def _eval(self, desc=None, loss_desc=None):
+        """The native call on the current stream; desc / loss_desc: descriptors of the caller's for this call (a short batch)."""
+        import ctypes as C
+        N, args = self.N, list(self._args)
+        if desc is not None:
+            args[0] = C.byref(desc)
+        if loss_desc is not None:
+            args[-3] = C.byref(loss_desc)
+        N._check(N.lib().lgn_step_eval_f64(*args, N.stream_ptr()), "lgn_step_eval_f64")
 
     def _capture(self):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):            # warm-up: lazy module loads, hipFuncSetAttribute
-            self._eval()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        _warm_up(self._eval)
         self._graph = torch.cuda.CUDAGraph()
         with _capturing(self._graph):
             self._eval()
@@ -852,30 +848,7 @@ class NativeEvalStep:
         if n < 1 or n > self.B or tuple(p4.shape[1:]) != tuple(self.target.shape[1:]):
             raise ValueError(f"NativeEvalStep was built for batches of up to {self.B} jets of shape {tuple(self.target.shape[1:])}, "
                              f"got {tuple(p4.shape)}")
-        if self.split:
-            ps, mask, scalars = self.encoder._prepare_input(batch)
-        else:
-            ps = p4.to(self.p4.dtype) * self.encoder.scale if self.encoder.scale != 1.0 else p4
-            for key in ("labels", "masks", "mask"):
-                if key in batch:
-                    mask = batch[key]
-                    if tuple(mask.shape) != (n, self.mask.shape[1]):
-                        raise ValueError(f"mask shape {tuple(mask.shape)} != {(n, self.mask.shape[1])}")
-                    break
-            else:
-                mask = p4[..., 0] != 0
-            scalars = None
-        self.p4[:n].copy_(ps)
-        self.target[:n].copy_(p4)
-        self.mask[:n].copy_(mask.to(torch.uint8))
-        if self.in_scalars is not None:
-            self.in_scalars[:n].copy_(scalars)
-        if n < self.B:
-            self.p4[n:].zero_()
-            self.target[n:].zero_()
-            self.mask[n:].zero_()
-            if self.in_scalars is not None:
-                self.in_scalars[n:].zero_()
+        self.inputs.stage(batch, n)
         self.n_real = n
 
     def run(self, batch: Optional[Dict[str, torch.Tensor]] = None):
@@ -888,16 +861,15 @@ class NativeEvalStep:
             self._plan()                     # the blocks moved (e.g. a NativeTrainStep re-homed them): new offsets, new graph
             if self._ws > self.workspace.numel():
                 self.workspace = torch.empty(self._ws, device=self.workspace.device, dtype=self.workspace.dtype)
+            self._bind()
             self._graph = None
         n = self.n_real
-        if n < self.B and self.chamfer_jet_features:
-            # nn.MSELoss over the B' real jets: a descriptor of its own, one call outside the graph
+        if n < self.B and (self.chamfer_jet_features or self.loss_desc is not None):
+            # the means (nn.MSELoss of the jet features; mse / hungarian) run over the B' real jets: descriptors of this call's own,
+            # one call outside the graph
             d = type(self.desc).from_buffer_copy(self.desc)
-            d.jet_loss_scale = 1.0 / (4.0 * n)
-            self._eval(d)
-        elif n < self.B and self.loss_desc is not None:
-            # the mean over the B' real jets: a loss descriptor of its own, one call outside the graph
-            self._eval(loss_desc=_loss_desc(*self._loss_args, n, self.decoder.num_output_particles)[1])
+            d.jet_loss_scale = 1.0 / (4.0 * n) if self.chamfer_jet_features else 0.0
+            self._eval(d, _loss_desc(*self._loss_opts, n, self.decoder)[1])
         elif self.use_graph:
             if self._graph is None:
                 self._capture()

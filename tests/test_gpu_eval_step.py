@@ -268,7 +268,7 @@ def test_refused_call_leaves_the_outputs_untouched():
     ev.loss_out.fill_(7.0)
     rc = N.lib().lgn_step_eval_f64(C.byref(ev.desc), ev._base, ev.enc_off, ev.dec_off, N.ptr(ev.p4), N.ptr(ev.target), N.ptr(ev.mask),
                                    None, N.ptr(ev.workspace), ev._ws - 1, N.ptr(ev.recon), None, None, N.ptr(ev.loss_part),
-                                   N.ptr(ev.loss_out), N.stream_ptr())
+                                   N.ptr(ev.loss_out), None, None, None, N.stream_ptr())
     torch.cuda.synchronize()
     assert rc != 0 and "workspace" in N.last_error()
     assert bool((ev.recon == 7.0).all()) and ev.loss_out.item() == 7.0

@@ -324,8 +324,8 @@ def test_split_step_matches_captured_module_step(loss):
 
 
 def test_two_call_form_equals_the_single_call():
-    """lgn_step_fwd_bwd_loss_f64 + lgn_step_finalize_f64 (the data-parallel form: the all-reduce sits between them) against the
-    single call lgn_step_train_loss_f64."""
+    """lgn_step_fwd_bwd_f64 + lgn_step_finalize_f64 (the data-parallel form: the all-reduce sits between them) against the
+    single call lgn_step_train_f64, both with a loss descriptor."""
     from lgn.step import NativeTrainStep
     p4, labels = _batch("md2_n12")
     batch = {"p4": p4.to(DEV), "labels": labels.to(DEV)}

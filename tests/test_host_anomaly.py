@@ -68,7 +68,7 @@ def test_anomaly_symbols_are_exported():
     for name in ("lgn_anomaly_scores_f64", "lgn_linear_sum_assignment_f64"):
         assert name in N.EXPORTED_SYMBOLS
         assert hasattr(lib, name)
-    assert lib.lgn_abi_version() == 18
+    assert lib.lgn_abi_version() == 19
 
 
 ALL = (1 << 21) - 1

@@ -31,7 +31,7 @@ def test_eval_symbols_are_exported():
     for name in ("lgn_eval_workspace_doubles", "lgn_step_eval_f64"):
         assert name in N.EXPORTED_SYMBOLS
         assert hasattr(lib, name)
-    assert N.lib().lgn_abi_version() == 18
+    assert N.lib().lgn_abi_version() == 19
 
 
 @pytest.mark.parametrize("cfg", sorted(CONFIGS))
@@ -54,7 +54,7 @@ def _call(d, target=8, workspace_doubles=None):
     off = (C.c_int64 * 64)()
     ws = lib.lgn_eval_workspace_doubles(C.byref(d)) if workspace_doubles is None else workspace_doubles
     p = 8
-    return lib.lgn_step_eval_f64(C.byref(d), p, off, off, p, target, p, None, p, ws, p, None, None, p, p, None)
+    return lib.lgn_step_eval_f64(C.byref(d), p, off, off, p, target, p, None, p, ws, p, None, None, p, p, None, None, None, None)
 
 
 def test_eval_refuses_a_null_target():
@@ -88,5 +88,5 @@ def test_training_step_refuses_a_decoder_that_does_not_take_the_pooled_latent(ta
     assert "pooled latent" in N.last_error()
     off = (C.c_int64 * 64)()
     p = 8
-    assert lib.lgn_step_fwd_bwd_f64(C.byref(d), p, p, 1000, off, off, p, p, p, None, p, 1 << 40, p, p, None) != 0
+    assert lib.lgn_step_fwd_bwd_f64(C.byref(d), p, p, 1000, off, off, p, p, p, None, p, 1 << 40, p, p, None, None, None, None) != 0
     assert "pooled latent" in N.last_error()

@@ -59,10 +59,12 @@ def test_mse_fixture_is_the_identity_assignment():
 
 def test_new_symbols_and_unchanged_abi():
     lib = N.lib()
-    assert lib.lgn_abi_version() == 18
-    for name in ("lgn_step_fwd_bwd_loss_f64", "lgn_step_train_loss_f64", "lgn_step_eval_loss_f64", "lgn_hungarian_mse_f64",
+    assert lib.lgn_abi_version() == 19
+    for name in ("lgn_step_fwd_bwd_f64", "lgn_step_train_f64", "lgn_step_eval_f64", "lgn_hungarian_mse_f64",
                  "lgn_assign_loss_lds_bytes"):
         assert hasattr(lib, name) and name in N.EXPORTED_SYMBOLS
+    for name in ("lgn_step_fwd_bwd_loss_f64", "lgn_step_train_loss_f64", "lgn_step_eval_loss_f64"):     # merged into the calls above
+        assert not hasattr(lib, name) and name not in N.EXPORTED_SYMBOLS
     assert 0 < lib.lgn_assign_loss_lds_bytes(30, 4) < lib.lgn_assign_loss_lds_bytes(150, 4) <= N.LDS_LIMIT
     assert lib.lgn_assign_loss_lds_bytes(192, 8) > N.LDS_LIMIT
     assert lib.lgn_assign_loss_lds_bytes(0, 4) < 0
@@ -82,8 +84,8 @@ def _call(d, ld, which="train"):
     lib = N.lib()
     ldp = C.byref(ld) if ld is not None else None
     if which == "eval":
-        return lib.lgn_step_eval_loss_f64(C.byref(d), *([None] * 8), 0, *([None] * 5), ldp, None, None, None)
-    return lib.lgn_step_fwd_bwd_loss_f64(C.byref(d), None, None, 0, *([None] * 7), 0, None, None, ldp, None, None, None)
+        return lib.lgn_step_eval_f64(C.byref(d), *([None] * 8), 0, *([None] * 5), ldp, None, None, None)
+    return lib.lgn_step_fwd_bwd_f64(C.byref(d), None, None, 0, *([None] * 7), 0, None, None, ldp, None, None, None)
 
 
 def _loss(kind, scale=1e-3, a=1, p=0):

@@ -24,7 +24,7 @@ def _slots(d):
 
 
 def test_abi_18_descriptor_carries_the_loss_options():
-    assert N.ABI_VERSION == 18 and N.lib().lgn_abi_version() == 18
+    assert N.ABI_VERSION == 19 and N.lib().lgn_abi_version() == 19
     d = N.NetDesc()
     assert d.get_real == 0 and d.jet_loss_scale == 0.0        # zero-initialised: the 'sum' step without the jet term
     assert _slots(_desc()) > 0
