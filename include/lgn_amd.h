@@ -374,6 +374,50 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
                        int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment /* nullable */,
                        int* status /* nullable */, void* stream);
 
+/* ---- the same two calls with an optimiser descriptor in place of the scalar hyper-parameter list: --optimizer rmsprop
+ * (utils/initialize.py:153-173: torch.optim.RMSprop(params, lr, eps=get_eps(dtype), momentum=0.9)) and --l2-lambda
+ * (utils/train.py:489-492: + l2_lambda * (encoder.l2_norm() + decoder.l2_norm()), l2_norm = sum w^2).  Per parameter, with g the
+ * reduced loss gradient and w the weight BEFORE the update:
+ *     g += l1_lambda * sign(w) + 2 * l2_lambda * w                  (a lambda of 0 switches its term off)
+ *     LGN_OPT_ADAM:    lgn_step_finalize_f64's update on that g (l2_lambda == 0: its bits -- weights, moments, gradients, counter)
+ *     LGN_OPT_RMSPROP: v = alpha v + (1 - alpha) g^2;  avg = sqrt(v) + eps;
+ *                      momentum > 0:  buf = momentum buf + g / avg,  w -= lr buf;      momentum == 0:  w -= lr g / avg
+ *                      (torch.optim.RMSprop, centered=False, weight_decay=0; torch's default alpha is 0.99, the reference passes
+ *                      momentum 0.9 and eps 1e-16).  state_v carries square_avg, state_m the momentum buffer (untouched when
+ *                      momentum == 0); no bias-correction powers; the device step counter advances by one per applied step.
+ * do_step == 0: gradients and loss only, for both kinds.
+ * loss_out must hold 4 + LGN_FINALIZE_OPT_SCRATCH doubles: loss_out[0..3] = total (= data + l1_lambda sum|w| + l2_lambda sum w^2),
+ * data loss, sum|w|, sum w^2 (both norms of the weights before the update), then scratch of these calls' own -- NOT the block of the
+ * calls above: TWO arrays of (LGN_FINALIZE_OPT_SCRATCH - 12) / 2 partial sums (|w|, then w^2; the fused tail of
+ * lgn_step_train_opt_f64 needs a slot per tile in each, and a step with more tiles than that takes the separate launches), then, as
+ * in the block above, four per-level counters (slots -11 .. -8), the cached powers of LGN_OPT_ADAM (-7 .. -2) and the
+ * finished-workgroup counter (-1).  The same rule holds: the caller zero-fills the block ONCE, at allocation; every launch leaves
+ * counters and partial-sum slots at zero (the fused tail reads "zero = not yet written in this launch": both sums are
+ * non-negative and travel with the sign bit set), so the two calls -- and both kinds -- may be mixed on one block; after a launch
+ * that died part-way, zero the block again before reusing it.
+ * Both calls only enqueue (capturable) and refuse before the first launch with a negative code and lgn_last_error(). */
+#define LGN_OPT_ADAM 0
+#define LGN_OPT_RMSPROP 1
+typedef struct {
+  int kind;               /* LGN_OPT_ADAM | LGN_OPT_RMSPROP */
+  double l1_lambda, l2_lambda, lr, eps;
+  double beta1, beta2;    /* LGN_OPT_ADAM */
+  double alpha, momentum; /* LGN_OPT_RMSPROP */
+} lgn_optim_desc;
+#define LGN_FINALIZE_OPT_SCRATCH 4096
+/* lgn_step_finalize_f64 with a descriptor: the data-parallel and module-step form, called after the all-reduce */
+int lgn_step_finalize_opt_f64(double* params, double* grads, long long n_params, const double* loss_part, int n_loss,
+                              const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
+                              double* loss_out, void* stream);
+/* lgn_step_train_f64 with a descriptor: the single-process form, ONE fused tail launch where lgn_step_train_f64 has one (same
+ * gradients, state and weights as lgn_step_fwd_bwd_f64 + lgn_step_finalize_opt_f64 bit for bit, the loss value to rounding) */
+int lgn_step_train_opt_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
+                           const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask,
+                           const double* in_scalars, double* workspace, long long workspace_doubles, double* recon,
+                           double* loss_part, int n_loss, const lgn_optim_desc* opt, double* state_m, double* state_v,
+                           long long* step_dev, int do_step, double* loss_out, const lgn_loss_desc* loss,
+                           int* assignment /* nullable */, int* status /* nullable */, void* stream);
+
 /* ---- evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
  * get_real(., d->get_real) -> Chamfer [+ d->jet_loss_scale * jet-feature term] or the assignment loss of `loss`, forward only and without L1 (regularization =
  * is_train, utils/train.py:308-314).  Takes every descriptor lgn_step_fwd_bwd_f64 takes and the same inputs; nothing is kept for a

@@ -80,6 +80,8 @@ size_t decoder_end_lds_bytes(int N, int C0, int Tin, int CL);
 size_t junction_lds_bytes(int N, int CL, int Ts, int Tv, int pool, int C0);
 int finalize_step(double* w, double* g, long n, const double* loss_part, int nB, double lambda, double* m, double* v, long* step_dev,
                   double lr, double beta1, double beta2, double eps, int do_adam, double* loss_out, hipStream_t st);
+// the same launch for a tail with an optimiser descriptor (t.opt_form: kind, L2; loss_out = 4 results + LGN_FINALIZE_OPT_SCRATCH)
+int finalize_step_opt(const StepTailArgs& t, hipStream_t st);
 // LocalArgs from the C-ABI table struct (shared by api.hip and step.hip)
 inline int local_args(LocalArgs& a, int nodes, int C, int CO, int Q, int Qout, const lgn_local_tables* t) {
   LGN_CHECK_ARG(t && t->row_ptr && t->t_type && t->t_a && t->t_b && t->t_coef && t->out_dim && t->out_nblk && t->out_row0 &&

@@ -1101,16 +1101,25 @@ __global__ __launch_bounds__(BLOCK) void dec_output_bwd_kernel(int B, int N, int
 // see its own launch's update), and falls back to pow() when the slot does not name this step (first step, restored counter);
 // four parameters per thread, a quarter of the workgroups at the counter.
 constexpr int ADAM_PER_THREAD = 4;
+// The lgn_optim_desc calls (include/lgn_amd.h) run the same kernel with two compile-time choices -- the update rule (OPT: TAIL_ADAM /
+// TAIL_RMSPROP of tail_dev.hpp) and L2, the descriptor form: + 2 l2 w on the gradient, a second partial sum (w^2 before the update,
+// same hand-off as the |w| sums) and loss_out[3].  <TAIL_ADAM, false> is the kernel of the calls without a descriptor: the extra
+// argument block (OptExtra, the pack X) exists for L2 only, so its argument list is what it was.  RMSprop keeps no powers: its
+// thread 0 has nothing to fetch, the counter still advances by one.
+struct OptExtra { double l2, alpha, mu; double* l2_part; };
+template <typename T> __device__ __forceinline__ const T& first_of(const T& t) { return t; }
+template <int OPT, bool L2, typename... X>
 __global__ __launch_bounds__(BLOCK) void l1_adam_kernel(long n, double* w, double* g, double* m, double* v, double lambda, double lr,
                                                        double beta1, double beta2, double eps, long* step_dev, int do_adam,
                                                        double* l1_part, double* powers, unsigned long long* done,
-                                                       const double* __restrict__ loss_part, int nB, double* loss_out) {
+                                                       const double* __restrict__ loss_part, int nB, double* loss_out, X... xs) {
+  static_assert(sizeof...(X) == (L2 ? 1 : 0), "l1_adam_kernel: one OptExtra for the descriptor form, none otherwise");
   __shared__ double red[4];
   __shared__ double bc[4];
   __shared__ int last;
   if (threadIdx.x == 0) {
     bc[0] = bc[1] = bc[2] = bc[3] = 1.0;
-    if (do_adam) {
+    if (OPT == TAIL_ADAM && do_adam) {
       // counter and BOTH slots in one memory round trip (counter, then its slot, was two -- with every other thread at the barrier)
       double pw[6];
 #pragma unroll
@@ -1131,10 +1140,20 @@ __global__ __launch_bounds__(BLOCK) void l1_adam_kernel(long n, double* w, doubl
   __syncthreads();
   const double bc1 = bc[0], bc2_sqrt = bc[1];
   double l1 = 0.0;
+  [[maybe_unused]] double l2s = 0.0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const double wi = w[i];
     l1 += fabs(wi);
-    const AdamOut o = l1_adam_one(wi, g[i], do_adam ? m[i] : 0.0, do_adam ? v[i] : 0.0, lambda, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+    AdamOut o;
+    if constexpr (!L2) {
+      o = l1_adam_one(wi, g[i], do_adam ? m[i] : 0.0, do_adam ? v[i] : 0.0, lambda, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+    } else {
+      const OptExtra& x = first_of(xs...);
+      l2s = __builtin_fma(wi, wi, l2s);
+      const double mi = do_adam ? m[i] : 0.0, vi = do_adam ? v[i] : 0.0;
+      if constexpr (OPT == TAIL_ADAM) o = l1_l2_adam_one(wi, g[i], mi, vi, lambda, x.l2, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+      else o = l1_l2_rmsprop_one(wi, g[i], mi, vi, lambda, x.l2, lr, x.alpha, x.mu, eps);
+    }
     g[i] = o.g;
     if (do_adam) {
       m[i] = o.m;
@@ -1143,6 +1162,7 @@ __global__ __launch_bounds__(BLOCK) void l1_adam_kernel(long n, double* w, doubl
     }
   }
   l1 = block_sum(l1, red);
+  if constexpr (L2) l2s = block_sum(l2s, red);
   if (threadIdx.x == 0) {
     // The partial goes out as a device-scope atomic exchange (performed at the coherent level; its return is awaited, so it is
     // complete before the count below is issued) and the last workgroup reads the partials back with device-scope atomic loads:
@@ -1150,32 +1170,52 @@ __global__ __launch_bounds__(BLOCK) void l1_adam_kernel(long n, double* w, doubl
     // the XCD, 3.5 of this kernel's 9 us.
     unsigned long long old = __hip_atomic_exchange(reinterpret_cast<unsigned long long*>(l1_part) + blockIdx.x,
                                                    (unsigned long long)__double_as_longlong(l1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (L2) {
+      unsigned long long old2 = __hip_atomic_exchange(reinterpret_cast<unsigned long long*>(first_of(xs...).l2_part) + blockIdx.x,
+                                                      (unsigned long long)__double_as_longlong(l2s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(old2) : : "memory");
+    }
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(old) : : "memory");       // the exchange has been performed before the count is issued
     last = __hip_atomic_fetch_add(done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)gridDim.x - 1;
   }
   __syncthreads();
   if (!last) return;
   double a = 0, l = 0;
+  [[maybe_unused]] double a2 = 0;
   for (int i = threadIdx.x; i < (int)gridDim.x; i += BLOCK) {
     a += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(l1_part) + i, __ATOMIC_RELAXED,
                                                            __HIP_MEMORY_SCOPE_AGENT));
     // the slots go back to zero: step_tail.hip shares them and reads "zero = not yet written in this launch" (lgn_amd.h: the scratch
     // block is zero between calls, whichever of the two kernels ran last)
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(l1_part) + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (L2) {
+      const OptExtra& x = first_of(xs...);
+      a2 += __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<unsigned long long*>(x.l2_part) + i, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT));
+      __hip_atomic_store(reinterpret_cast<unsigned long long*>(x.l2_part) + i, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
   }
   for (int i = threadIdx.x; i < nB; i += BLOCK) l += loss_part[i];
   a = block_sum(a, red);
   l = block_sum(l, red);
+  if constexpr (L2) a2 = block_sum(a2, red);
   if (threadIdx.x == 0) {
-    loss_out[0] = l + lambda * a;
+    if constexpr (L2) {
+      loss_out[0] = __builtin_fma(first_of(xs...).l2, a2, l + lambda * a);
+      loss_out[3] = a2;
+    } else {
+      loss_out[0] = l + lambda * a;
+    }
     loss_out[1] = l;
     loss_out[2] = a;
     if (do_adam) {
-      const long tn = *step_dev + 2;                       // the NEXT step's number and powers, into the slot it will read
-      double* slot = powers + 3 * (tn & 1);
-      slot[1] = bc[2] * beta1;
-      slot[2] = bc[3] * beta2;
-      slot[0] = (double)tn;
+      if constexpr (OPT == TAIL_ADAM) {
+        const long tn = *step_dev + 2;                       // the NEXT step's number and powers, into the slot it will read
+        double* slot = powers + 3 * (tn & 1);
+        slot[1] = bc[2] * beta1;
+        slot[2] = bc[3] * beta2;
+        slot[0] = (double)tn;
+      }
       *step_dev += 1;
     }
     *done = 0ull;
@@ -1368,8 +1408,28 @@ int finalize_step(double* w, double* g, long n, const double* loss_part, int nB,
   double* l1_part = loss_out + 3;
   double* powers = loss_out + 3 + LGN_FINALIZE_SCRATCH - 7;
   unsigned long long* done = reinterpret_cast<unsigned long long*>(loss_out + 3 + LGN_FINALIZE_SCRATCH - 1);
-  hipLaunchKernelGGL(l1_adam_kernel, dim3(nblk), dim3(BLOCK), 0, st, n, w, g, m, v, lambda, lr, beta1, beta2, eps, step_dev, do_adam,
-                     l1_part, powers, done, loss_part, nB, loss_out);
+  hipLaunchKernelGGL((l1_adam_kernel<TAIL_ADAM, false>), dim3(nblk), dim3(BLOCK), 0, st, n, w, g, m, v, lambda, lr, beta1, beta2, eps,
+                     step_dev, do_adam, l1_part, powers, done, loss_part, nB, loss_out);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+// loss_out: 4 results followed by LGN_FINALIZE_OPT_SCRATCH doubles (include/lgn_amd.h): [0, half) |w| partials, [half, 2 half) w^2
+// partials, then the twelve slots of finalize_step's block
+int finalize_step_opt(const StepTailArgs& t, hipStream_t st) {
+  constexpr int half = (LGN_FINALIZE_OPT_SCRATCH - 12) / 2;
+  int nblk = grid_for(((size_t)t.n + ADAM_PER_THREAD - 1) / ADAM_PER_THREAD);
+  if (nblk > half) nblk = half;
+  double* scratch = t.loss_out + 4;
+  double* powers = scratch + LGN_FINALIZE_OPT_SCRATCH - 7;
+  unsigned long long* done = reinterpret_cast<unsigned long long*>(scratch + LGN_FINALIZE_OPT_SCRATCH - 1);
+  const OptExtra x{t.l2, t.alpha, t.mu, scratch + half};
+  if (t.kind == LGN_OPT_ADAM)
+    hipLaunchKernelGGL((l1_adam_kernel<TAIL_ADAM, true, OptExtra>), dim3(nblk), dim3(BLOCK), 0, st, t.n, t.w, t.g, t.m, t.v, t.lambda, t.lr, t.beta1,
+                       t.beta2, t.eps, t.step_dev, t.do_adam, scratch, powers, done, t.loss_part, t.nB, t.loss_out, x);
+  else
+    hipLaunchKernelGGL((l1_adam_kernel<TAIL_RMSPROP, true, OptExtra>), dim3(nblk), dim3(BLOCK), 0, st, t.n, t.w, t.g, t.m, t.v, t.lambda, t.lr,
+                       t.beta1, t.beta2, t.eps, t.step_dev, t.do_adam, scratch, powers, done, t.loss_part, t.nB, t.loss_out, x);
   LGN_CHECK_LAUNCH();
   return 0;
 }

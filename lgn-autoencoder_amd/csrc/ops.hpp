@@ -48,6 +48,12 @@ struct StepTailArgs {
   // describe the gradient buffer, `counters` are 4 64-bit words that are zero before the first launch (the kernel leaves them zero)
   int reduce_only;
   unsigned long long* counters;
+  // the lgn_optim_desc calls (lgn_step_train_opt_f64 / lgn_step_finalize_opt_f64): kind = LGN_OPT_*, the L2 weight, RMSprop's alpha and
+  // momentum (m carries the momentum buffer, v square_avg; beta1 / beta2 are Adam's), and loss_out = 4 results +
+  // LGN_FINALIZE_OPT_SCRATCH doubles.  opt_form == 0: the calls without a descriptor -- L1 + Adam on the 3-result block.
+  int opt_form = 0;
+  int kind = 0;
+  double l2 = 0.0, alpha = 0.0, mu = 0.0;
 };
 int step_tail(const std::vector<RedSeg<double>>& segs, const RadFinJob& fin, const StepTailArgs& ta, hipStream_t st);
 void level_bwd_partial_rows(int B, int N, int decoder, int flags, int* rows_mix, int* rows_rad);

@@ -93,6 +93,13 @@ int finish_reductions(Deferred& dq, const RadFinJob& fin, double* grads, long lo
   return rad_finalize_batch(fin, st);
 }
 
+// L1 [+ L2] + optimiser + loss assembly as a launch of its own: l1_adam_kernel of the tail's form (net_kernels.hip)
+int finalize_tail(const StepTailArgs& t, hipStream_t st) {
+  if (t.opt_form) return finalize_step_opt(t, st);
+  return finalize_step(t.w, t.g, t.n, t.loss_part, t.nB, t.lambda, t.m, t.v, t.step_dev, t.lr, t.beta1, t.beta2, t.eps, t.do_adam,
+                       t.loss_out, st);
+}
+
 // The end of a whole step.  With `tail` (single process: nothing sits between the gradients and the optimiser) the deferred
 // reductions, the radial finalisation, L1 + Adam and the loss assembly are ONE launch (step_tail.hip); where that form does not fit
 // (-2), or with LGN_NET_SPLIT_TAIL, finish_reductions and then finalize_step.  Without `tail` (data-parallel step: the all-reduce
@@ -105,9 +112,7 @@ int end_step(Deferred& dq, const RadFinJob& fin, double* grads, long long n_para
   }
   if (int rc = finish_reductions(dq, fin, grads, n_params, tail ? nullptr : counters, flags, st)) return rc;
   if (!tail) return 0;
-  const StepTailArgs& t = *tail;
-  return finalize_step(t.w, t.g, t.n, t.loss_part, t.nB, t.lambda, t.m, t.v, t.step_dev, t.lr, t.beta1, t.beta2, t.eps, t.do_adam,
-                       t.loss_out, st);
+  return finalize_tail(*tail, st);
 }
 
 inline int in_K(const lgn_net_desc& d) { return d.n_in_scalars > 1 ? d.n_in_scalars : 1; }      // encoder input scalars per node
@@ -977,9 +982,7 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
     LGN_TRY(run_unpack_jobs(post, st));
     // the decoder never reads the latent scalars: no gradient on them
     LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st));
-    if (tail)
-      LGN_TRY(finalize_step(tail->w, tail->g, tail->n, tail->loss_part, tail->nB, tail->lambda, tail->m, tail->v, tail->step_dev, tail->lr,
-                            tail->beta1, tail->beta2, tail->eps, tail->do_adam, tail->loss_out, st));
+    if (tail) LGN_TRY(finalize_tail(*tail, st));
     return 0;
   }
   LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st, nullptr, &dq, &fin, &jb));
@@ -1429,6 +1432,60 @@ int lgn_step_finalize_f64(double* params, double* grads, long long n_params, con
   LGN_TRY(finalize_step(params, grads, (long)n_params, loss_part, n_loss, l1_lambda, adam_m, adam_v, reinterpret_cast<long*>(step_dev),
                         lr, beta1, beta2, eps, do_adam, loss_out, st));
   return 0;
+}
+
+}  // extern "C"
+
+namespace lgn {
+namespace {
+// the tail of a call with an optimiser descriptor; refuses what no kernel implements before anything is enqueued
+int optim_tail(const lgn_optim_desc* o, double* params, double* grads, long long n_params, double* state_m, double* state_v,
+               long long* step_dev, int do_step, const double* loss_part, int n_loss, double* loss_out, StepTailArgs& t) {
+  LGN_CHECK_ARG(o, "optimiser descriptor: null pointer");
+  LGN_CHECK_ARG(o->kind == LGN_OPT_ADAM || o->kind == LGN_OPT_RMSPROP, "optimiser descriptor: kind %d is neither LGN_OPT_ADAM nor "
+                "LGN_OPT_RMSPROP", o->kind);
+  LGN_CHECK_ARG(!do_step || (state_m && state_v && step_dev), "optimiser state missing");
+  LGN_CHECK_ARG(o->l2_lambda >= 0.0 && o->eps >= 0.0, "optimiser descriptor: negative l2_lambda or eps");
+  LGN_CHECK_ARG(o->kind != LGN_OPT_RMSPROP || (o->alpha >= 0.0 && o->alpha <= 1.0 && o->momentum >= 0.0),
+                "optimiser descriptor: RMSprop takes 0 <= alpha <= 1 and momentum >= 0");
+  t = StepTailArgs{params, grads, (long)n_params, state_m, state_v, reinterpret_cast<long*>(step_dev), o->l1_lambda, o->lr, o->beta1,
+                   o->beta2, o->eps, do_step, loss_part, n_loss, loss_out, 0, nullptr};
+  t.opt_form = 1;
+  t.kind = o->kind;
+  t.l2 = o->l2_lambda;
+  t.alpha = o->alpha;
+  t.mu = o->momentum;
+  return 0;
+}
+}  // namespace
+}  // namespace lgn
+
+extern "C" {
+
+int lgn_step_train_opt_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
+                           const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                           double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss,
+                           const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
+                           double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
+  lgn::AssignLoss al;
+  const lgn::AssignLoss* alp;
+  if (int rc = lgn::plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
+  LGN_CHECK_ARG(loss_out && n_loss > 0, "step_train_opt: null pointer");
+  lgn::StepTailArgs tail{};
+  if (int rc = lgn::optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
+    return rc;
+  return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles,
+                           recon, loss_part, stream, &tail, alp);
+}
+
+int lgn_step_finalize_opt_f64(double* params, double* grads, long long n_params, const double* loss_part, int n_loss,
+                              const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
+                              double* loss_out, void* stream) {
+  LGN_CHECK_ARG(params && grads && loss_part && loss_out && n_params > 0 && n_loss > 0, "step_finalize_opt: null pointer");
+  lgn::StepTailArgs tail{};
+  if (int rc = lgn::optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
+    return rc;
+  return lgn::finalize_step_opt(tail, (hipStream_t)stream);
 }
 
 }  // extern "C"

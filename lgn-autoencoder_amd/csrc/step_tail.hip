@@ -57,7 +57,17 @@ struct TailDev {
   RadFinJob fin;
 };
 
-static_assert(sizeof(RedJob<double>) + sizeof(TailDev) <= 4096, "step_tail_kernel: both argument blocks travel by value (4 KB of kernel arguments)");
+// The tail of the lgn_optim_desc calls (include/lgn_amd.h) is the same kernel with two compile-time choices: the update rule (OPT:
+// TAIL_ADAM / TAIL_RMSPROP of tail_dev.hpp) and L2, the descriptor form -- + 2 l2 w on the gradient, w^2 partial sums next to the |w|
+// ones (same slots, same sign-bit marker: both sums are non-negative) and loss_out[3].  <TAIL_ADAM, false> is the kernel of the calls
+// without a descriptor (and of reduce_only): its argument block is TailDev itself, its code what it was.
+template <bool L2> struct TailX : TailDev {
+  double l2, alpha, mu;
+  double* l2_part;                           // [ntiles + nlev] w^2 sums, laid out like l1_part
+};
+template <> struct TailX<false> : TailDev {};
+
+static_assert(sizeof(RedJob<double>) + sizeof(TailX<true>) <= 4096, "step_tail_kernel: both argument blocks travel by value (4 KB of kernel arguments)");
 
 __device__ __forceinline__ void put_shared(double* p, double x) {        // visible to every XCD once the return value is there
   unsigned long long old = __hip_atomic_exchange(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(x),
@@ -99,9 +109,13 @@ __device__ __forceinline__ double tail_block_sum(double v, double* red) {
 }
 // L1 sub-gradient + Adam of one parameter (weight wi, moments mi / vi) whose loss gradient is `gsum` -- the arithmetic of
 // l1_adam_kernel, operation for operation; returns |w| before the update
-__device__ __forceinline__ double finish_param(const TailDev& t, long i, double gsum, double wi, double mi0, double vi0, double bc1,
+template <int OPT, bool L2>
+__device__ __forceinline__ double finish_param(const TailX<L2>& t, long i, double gsum, double wi, double mi0, double vi0, double bc1,
                                                double bc2_sqrt) {
-  const AdamOut o = l1_adam_one(wi, gsum, mi0, vi0, t.lambda, t.lr, t.beta1, t.beta2, t.eps, bc1, bc2_sqrt);
+  AdamOut o;
+  if constexpr (!L2) o = l1_adam_one(wi, gsum, mi0, vi0, t.lambda, t.lr, t.beta1, t.beta2, t.eps, bc1, bc2_sqrt);
+  else if constexpr (OPT == TAIL_ADAM) o = l1_l2_adam_one(wi, gsum, mi0, vi0, t.lambda, t.l2, t.lr, t.beta1, t.beta2, t.eps, bc1, bc2_sqrt);
+  else o = l1_l2_rmsprop_one(wi, gsum, mi0, vi0, t.lambda, t.l2, t.lr, t.alpha, t.mu, t.eps);
   t.g[i] = o.g;
   if (t.do_adam) {
     t.m[i] = o.m;
@@ -110,11 +124,9 @@ __device__ __forceinline__ double finish_param(const TailDev& t, long i, double 
   }
   return fabs(wi);
 }
-__device__ __forceinline__ double finish_param(const TailDev& t, long i, double gsum, double bc1, double bc2_sqrt) {
-  return finish_param(t, i, gsum, t.w[i], t.do_adam ? t.m[i] : 0.0, t.do_adam ? t.v[i] : 0.0, bc1, bc2_sqrt);
-}
 
-__global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> job, TailDev t) {
+template <int OPT, bool L2>
+__global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> job, TailX<L2> t) {
   __shared__ double red[TAIL_CP][TAIL_RG][64];
   __shared__ double sred[TAIL_RG];
   __shared__ double bc[4];
@@ -148,7 +160,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
   // held every workgroup at its first barrier for two more memory round trips)
   long ti_prev = 0;
   double pw[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  if (tid == 0 && t.do_adam) {
+  if (OPT == TAIL_ADAM && tid == 0 && t.do_adam) {
     ti_prev = *t.step_dev;
 #pragma unroll
     for (int q = 0; q < 6; ++q) pw[q] = t.powers[q];
@@ -174,7 +186,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
   }
   if (tid == 0) {
     bc[0] = bc[1] = bc[2] = bc[3] = 1.0;
-    if (t.do_adam) {
+    if (OPT == TAIL_ADAM && t.do_adam) {
       const long ti = ti_prev + 1;
       const double tt = (double)ti;
       const int odd = (int)(ti & 1);
@@ -194,6 +206,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
   __syncthreads();
   const double bc1 = bc[0], bc2_sqrt = bc[1];
   double l1 = 0.0;
+  [[maybe_unused]] double l2s = 0.0;
   if (owner) {
     double s = g0;
     if (sg.rows > 0) {
@@ -202,7 +215,10 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
       for (int q = 0; q < TAIL_RG; ++q) s += red[rg][q][cl];
     }
     if (is_param && t.reduce_only) t.g[pidx] = s;
-    else if (is_param) l1 = finish_param(t, pidx, s, wi, mi, vi, bc1, bc2_sqrt);
+    else if (is_param) {
+      l1 = finish_param<OPT, L2>(t, pidx, s, wi, mi, vi, bc1, bc2_sqrt);
+      if constexpr (L2) l2s = wi * wi;
+    }
     else if (lev >= 0) put_shared(sg.out + mycol, s);
     else sg.out[mycol] = s;
   }
@@ -254,6 +270,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
       const double* rb = rabc + NB;
       const double* rc = rabc + 2 * NB;
       double l1r = 0.0;
+      [[maybe_unused]] double l2r = 0.0;
       if (gp) {                                // (rad_finalize_batch_kernel's arithmetic)
         double gsum;
         if (which == -1) gsum = radfin_weight(rb[kk], T1[tid], ra[kk], S[r]);
@@ -264,39 +281,59 @@ __global__ __launch_bounds__(TAIL_THREADS) void step_tail_kernel(RedJob<double> 
           gsum = which == 2 ? radfin_c(rb[kk], rc[kk], d) : d;
         }
         if (t.reduce_only) t.g[pi] = gsum;
-        else l1r = finish_param(t, pi, gsum, pw_, pm_, pv_, bc1, bc2_sqrt);
+        else {
+          l1r = finish_param<OPT, L2>(t, pi, gsum, pw_, pm_, pv_, bc1, bc2_sqrt);
+          if constexpr (L2) l2r = pw_ * pw_;
+        }
       }
       // the level's counter back to zero for the next launch (nobody counts on it again in this one)
       if (tid == 0) __hip_atomic_store(t.lev_done + lev, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (t.reduce_only) return;
       l1r = tail_block_sum(l1r, sred);
       if (tid == 0) post_sum(t.l1_part + t.ntiles + lev, l1r);
+      if constexpr (L2) {
+        l2r = tail_block_sum(l2r, sred);
+        if (tid == 0) post_sum(t.l2_part + t.ntiles + lev, l2r);
+      }
     }
   }
   if (t.reduce_only) return;
   // ---- |w| of this tile; the last workgroup assembles the loss ----
   l1 = tail_block_sum(l1, sred);
+  if constexpr (L2) l2s = tail_block_sum(l2s, sred);
   if (tid == 0) {
     post_sum(t.l1_part + blockIdx.x, l1);
+    if constexpr (L2) post_sum(t.l2_part + blockIdx.x, l2s);
     flag = __hip_atomic_fetch_add(t.done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)gridDim.x - 1;
   }
   __syncthreads();
   if (!flag) return;
   double a = 0.0, l = 0.0;
+  [[maybe_unused]] double a2 = 0.0;
   for (int i = tid; i < t.ntiles + t.nlev; i += TAIL_THREADS) a += take_sum(t.l1_part + i);
+  if constexpr (L2)
+    for (int i = tid; i < t.ntiles + t.nlev; i += TAIL_THREADS) a2 += take_sum(t.l2_part + i);
   for (int i = tid; i < t.nB; i += TAIL_THREADS) l += t.loss_part[i];
   a = tail_block_sum(a, sred);
   l = tail_block_sum(l, sred);
+  if constexpr (L2) a2 = tail_block_sum(a2, sred);
   if (tid == 0) {
-    t.loss_out[0] = l + t.lambda * a;
+    if constexpr (L2) {
+      t.loss_out[0] = __builtin_fma(t.l2, a2, l + t.lambda * a);
+      t.loss_out[3] = a2;
+    } else {
+      t.loss_out[0] = l + t.lambda * a;
+    }
     t.loss_out[1] = l;
     t.loss_out[2] = a;
     if (t.do_adam) {
-      const long tn = *t.step_dev + 2;
-      double* slot = t.powers + 3 * (tn & 1);
-      slot[1] = bc[2] * t.beta1;
-      slot[2] = bc[3] * t.beta2;
-      slot[0] = (double)tn;
+      if constexpr (OPT == TAIL_ADAM) {
+        const long tn = *t.step_dev + 2;
+        double* slot = t.powers + 3 * (tn & 1);
+        slot[1] = bc[2] * t.beta1;
+        slot[2] = bc[3] * t.beta2;
+        slot[0] = (double)tn;
+      }
       *t.step_dev += 1;
     }
     *t.done = 0ull;
@@ -369,6 +406,25 @@ int step_tail(const std::vector<RedSeg<double>>& segs, const RadFinJob& fin, con
   if (ta.reduce_only) {
     if (!ta.counters) return -2;
     t.lev_done = ta.counters;
+  } else if (ta.opt_form) {
+    // the descriptor form: 4 results, then two partial-sum arrays -- each tile and level needs a slot in both (lgn_amd.h)
+    constexpr int half = (LGN_FINALIZE_OPT_SCRATCH - 12) / 2;
+    if (tiles + fin.n > half) return -2;
+    double* scratch = ta.loss_out + 4;
+    TailX<true> x{};
+    t.l1_part = scratch;
+    t.lev_done = reinterpret_cast<unsigned long long*>(scratch + LGN_FINALIZE_OPT_SCRATCH - 11);
+    t.powers = scratch + LGN_FINALIZE_OPT_SCRATCH - 7;
+    t.done = reinterpret_cast<unsigned long long*>(scratch + LGN_FINALIZE_OPT_SCRATCH - 1);
+    static_cast<TailDev&>(x) = t;
+    x.l2 = ta.l2; x.alpha = ta.alpha; x.mu = ta.mu;
+    x.l2_part = scratch + half;
+    if (ta.kind == LGN_OPT_ADAM)
+      hipLaunchKernelGGL((step_tail_kernel<TAIL_ADAM, true>), dim3(tiles), dim3(TAIL_THREADS), 0, st, job, x);
+    else
+      hipLaunchKernelGGL((step_tail_kernel<TAIL_RMSPROP, true>), dim3(tiles), dim3(TAIL_THREADS), 0, st, job, x);
+    LGN_CHECK_LAUNCH();
+    return 0;
   } else {
     if (tiles + fin.n > LGN_FINALIZE_SCRATCH - 12) return -2;
     double* scratch = ta.loss_out + 3;
@@ -377,7 +433,9 @@ int step_tail(const std::vector<RedSeg<double>>& segs, const RadFinJob& fin, con
     t.powers = scratch + LGN_FINALIZE_SCRATCH - 7;
     t.done = reinterpret_cast<unsigned long long*>(scratch + LGN_FINALIZE_SCRATCH - 1);
   }
-  hipLaunchKernelGGL(step_tail_kernel, dim3(tiles), dim3(TAIL_THREADS), 0, st, job, t);
+  TailX<false> x0{};
+  static_cast<TailDev&>(x0) = t;
+  hipLaunchKernelGGL((step_tail_kernel<TAIL_ADAM, false>), dim3(tiles), dim3(TAIL_THREADS), 0, st, job, x0);
   LGN_CHECK_LAUNCH();
   return 0;
 }

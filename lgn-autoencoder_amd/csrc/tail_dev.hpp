@@ -1,7 +1,7 @@
 // lgn-autoencoder_amd/csrc/tail_dev.hpp -- the arithmetic of a step's tail with every multiply-add spelled out, shared by the
 // kernels that run it as separate launches (rad_finalize_batch_kernel in level_bwd.hip, l1_adam_kernel in net_kernels.hip) and
 // by the fused launch (step_tail.hip): which products the compiler contracts into fused multiply-adds may differ from one kernel to
-// the next, and the two routes are tested to agree bit for bit.
+// the next, and the two routes are tested to agree bit for bit.  The same holds for the update rules of the lgn_optim_desc calls below.
 #pragma once
 #include "common.hpp"
 
@@ -28,6 +28,35 @@ __device__ __forceinline__ AdamOut l1_adam_one(double w, double gsum, double m, 
   o.v = __builtin_fma((1.0 - beta2) * o.g, o.g, v * beta2);
   const double denom = sqrt(o.v) / bc2_sqrt + eps;
   o.w = w - (lr / bc1) * (o.m / denom);
+  return o;
+}
+
+// The optimiser kinds of the lgn_optim_desc calls (LGN_OPT_* of include/lgn_amd.h) as template arguments of the tail kernels.  The
+// second template argument of those kernels, L2, is "the lgn_optim_desc form": the L2 term, the w^2 partial sums and the fourth
+// result.  <TAIL_ADAM, false> is the kernel of the calls without a descriptor and stays the code it was.
+constexpr int TAIL_ADAM = 0, TAIL_RMSPROP = 1;
+
+// loss gradient + the L2 term 2 l2 w, from the weight BEFORE the update; l2 == 0 switches the term off (no "+ 0 w": the gradient
+// keeps its bits).  The L1 term is added to this sum, by l1_adam_one for Adam and in its words for RMSprop.
+__device__ __forceinline__ double l2_grad(double w, double gsum, double l2) {
+  return l2 != 0.0 ? __builtin_fma(2.0 * l2, w, gsum) : gsum;
+}
+// Adam with both regularisers: l1_adam_one on the gradient that holds the L2 term (l2 == 0: l1_adam_one's bits)
+__device__ __forceinline__ AdamOut l1_l2_adam_one(double w, double gsum, double m, double v, double l1, double l2, double lr, double beta1,
+                                                  double beta2, double eps, double bc1, double bc2_sqrt) {
+  return l1_adam_one(w, l2_grad(w, gsum, l2), m, v, l1, lr, beta1, beta2, eps, bc1, bc2_sqrt);
+}
+// RMSprop of one parameter in the arithmetic of torch.optim.RMSprop(centered=False, weight_decay=0) (utils/initialize.py:153-173):
+// v = alpha v + (1 - alpha) g^2;  avg = sqrt(v) + eps (eps OUTSIDE the root);  mu > 0: buf = mu buf + g / avg, w -= lr buf (lr on
+// the buffer);  mu == 0: w -= lr g / avg and the buffer is left alone.  AdamOut::m carries the momentum buffer, ::v square_avg.
+__device__ __forceinline__ AdamOut l1_l2_rmsprop_one(double w, double gsum, double buf, double v, double l1, double l2, double lr,
+                                                     double alpha, double mu, double eps) {
+  AdamOut o;
+  o.g = l2_grad(w, gsum, l2) + l1 * (double)((w > 0.0) - (w < 0.0));
+  o.v = __builtin_fma((1.0 - alpha) * o.g, o.g, v * alpha);
+  const double q = o.g / (sqrt(o.v) + eps);
+  o.m = mu > 0.0 ? __builtin_fma(mu, buf, q) : buf;
+  o.w = __builtin_fma(-lr, mu > 0.0 ? o.m : q, w);
   return o;
 }
 

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LGN_AMD_LIB") or os.path.join(_HERE, "_lib", "liblgn_amd.so")   # LGN_AMD_LIB: debug builds (tools/)
 ABI_VERSION = 19
 FINALIZE_SCRATCH = 2048      # include/lgn_amd.h: LGN_FINALIZE_SCRATCH
+FINALIZE_OPT_SCRATCH = 4096  # LGN_FINALIZE_OPT_SCRATCH: the scratch behind the 4 results of the lgn_optim_desc calls
 
 _lib: Optional[C.CDLL] = None
 
@@ -150,10 +151,18 @@ class LossDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("abs_coord", C.c_int), ("polar_coord", C.c_int), ("scale", C.c_double)]
 
 
+class OptimDesc(C.Structure):
+    """lgn_optim_desc of include/lgn_amd.h."""
+    _fields_ = [("kind", C.c_int), ("l1_lambda", C.c_double), ("l2_lambda", C.c_double), ("lr", C.c_double), ("eps", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("alpha", C.c_double), ("momentum", C.c_double)]
+
+
+OPT_ADAM, OPT_RMSPROP = 0, 1
 LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
 ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
 _dp = C.POINTER(NetDesc)
 _lp = C.POINTER(LossDesc)
+_op = C.POINTER(OptimDesc)
 _ll = C.c_longlong
 _d = C.c_double
 _SIGNATURES.update({
@@ -174,6 +183,10 @@ _SIGNATURES.update({
     "lgn_step_finalize_f64": [_vp, _vp, _ll, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp],
     "lgn_step_train_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _d, _vp, _vp, _vp, _d, _d, _d, _d, _i,
                            _vp, _lp, _vp, _vp, _vp],
+    # (the lgn_optim_desc twins: the descriptor where the scalar hyper-parameters were)
+    "lgn_step_finalize_opt_f64": [_vp, _vp, _ll, _vp, _i, _op, _vp, _vp, _vp, _i, _vp, _vp],
+    "lgn_step_train_opt_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _op, _vp, _vp, _vp, _i, _vp, _lp,
+                               _vp, _vp, _vp],
     "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _lp, _vp, _vp, _vp],
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],

@@ -83,13 +83,53 @@ class FlatParams:
         self.grad.zero_()
 
 
+OPTIMIZER_CHOICES = ("adam", "rmsprop")
+
+
+def optimizer_kind(optimizer_choice) -> str:
+    """--optimizer as utils/initialize.py:153-173 matches it: lower-cased, 'adam' or 'rmsprop'; anything else is not implemented."""
+    kind = str(optimizer_choice).lower()
+    if kind not in OPTIMIZER_CHOICES:
+        raise NotImplementedError("Other choices of optimizer are not implemented. Available choices are 'Adam' and 'RMSprop'. "
+                                  f"Found: {optimizer_choice}.")
+    return kind
+
+
+def optimizer_eps(optimizer_choice, eps=None, dtype=torch.float64) -> float:
+    """An explicit eps wins; None follows the choice: torch.optim.Adam's 1e-8, and for RMSprop what the reference passes,
+    get_eps(dtype) = 1e-16 for fp64, else 1e-12 (utils/utils.py:122-123)."""
+    if eps is not None:
+        return float(eps)
+    if optimizer_kind(optimizer_choice) == "adam":
+        return 1e-8
+    return 1e-16 if dtype == torch.float64 else 1e-12
+
+
+def l2_weight(l2_lambda) -> float:
+    """--l2-lambda as utils/train.py:489-492 tests it: None or <= 0 is off (0.0)."""
+    return float(l2_lambda) if l2_lambda is not None and l2_lambda > 0 else 0.0
+
+
+def torch_optimizer(params, optimizer_choice: str = "adam", lr: float = 5e-4, eps=None, betas=(0.9, 0.999), momentum: float = 0.9,
+                    rms_alpha: float = 0.99, dtype=torch.float64):
+    """The torch optimiser of the comparator steps, built as utils/initialize.py:153-173 builds it: torch.optim.Adam(params, lr), or
+    torch.optim.RMSprop(params, lr, eps=get_eps(dtype), momentum=0.9) -- with the hyper-parameters the native steps take."""
+    eps = optimizer_eps(optimizer_choice, eps, dtype)
+    if optimizer_kind(optimizer_choice) == "adam":
+        return torch.optim.Adam(params, lr, betas=tuple(betas), eps=eps)
+    return torch.optim.RMSprop(params, lr=lr, eps=eps, momentum=momentum, alpha=rms_alpha)
+
+
 class TrainStep:
-    """One data-parallel training step of the autoencoder (see module docstring)."""
+    """One data-parallel training step of the autoencoder (see module docstring).  ``optimizer_choice`` / ``l2_lambda`` /
+    ``rms_alpha`` / ``momentum``: --optimizer and --l2-lambda of the reference, as NativeTrainStep takes them."""
 
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
-                 process_group: Optional["dist.ProcessGroup"] = None, optimizer: bool = True):
+                 process_group: Optional["dist.ProcessGroup"] = None, optimizer: bool = True, optimizer_choice: str = "adam",
+                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None):
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
+        self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.flat = FlatParams(encoder, decoder)
         self.world = _world_size(process_group)
         self.group = process_group
@@ -97,7 +137,8 @@ class TrainStep:
         # one Adam over the flat buffer performs the same element-wise update.
         self.flat_param = torch.nn.Parameter(self.flat.flat)
         self.flat_param.grad = self.flat.grad
-        self.opt = torch.optim.Adam([self.flat_param], lr=lr) if optimizer else None
+        self.opt = torch_optimizer([self.flat_param], optimizer_choice, lr, eps, momentum=momentum, rms_alpha=rms_alpha,
+                                   dtype=self.flat.flat.dtype) if optimizer else None
 
     def forward_backward(self, batch: Dict[str, torch.Tensor]):
         """Returns (total loss as the reference logs it, reconstruction)."""
@@ -115,6 +156,10 @@ class TrainStep:
             # d/dw lambda*|w| = lambda*sign(w)  (utils/train.py:484-487; torch's abs backward uses sign, sign(0)=0)
             self.flat.grad.add_(torch.sign(self.flat.flat), alpha=self.l1_lambda)
             total = total + self.l1_lambda * self.flat.flat.abs().sum()
+        if self.l2_lambda:
+            # d/dw lambda*w^2 = 2*lambda*w  (utils/train.py:489-492)
+            total = total + self.l2_lambda * self.flat.flat.pow(2).sum()
+            self.flat.grad.add_(self.flat.flat, alpha=2.0 * self.l2_lambda)
         return total, recon
 
     def step(self, batch):
@@ -137,16 +182,24 @@ class ReferenceLoopStep:
 
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
                  process_group=None, optimizer: bool = True, native_loss: bool = True, loss_choice: str = "chamfer",
-                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False):
+                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam",
+                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None):
         self.encoder, self.decoder = encoder, decoder
+        self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
                                     None if native_loss else chamfer_loss)
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
         self.world = _world_size(process_group)
         self.group = process_group
         self._loss_weight = _loss_weight(loss_choice, self.world)
-        self.opt_enc = torch.optim.Adam(encoder.parameters(), lr) if optimizer else None
-        self.opt_dec = torch.optim.Adam(decoder.parameters(), lr) if optimizer else None
+        if self.optimizer_choice == "adam" and eps is None:      # (utils/initialize.py:156-158, untouched)
+            make = lambda m: torch.optim.Adam(m.parameters(), lr)                                          # noqa: E731
+        else:
+            dt = next(encoder.parameters()).dtype
+            make = lambda m: torch_optimizer(m.parameters(), optimizer_choice, lr, eps, momentum=momentum,  # noqa: E731
+                                             rms_alpha=rms_alpha, dtype=dt)
+        self.opt_enc = make(encoder) if optimizer else None
+        self.opt_dec = make(decoder) if optimizer else None
 
     def step(self, batch):
         latent = self.encoder(batch)
@@ -156,6 +209,11 @@ class ReferenceLoopStep:
         chamfer = self.loss_fn(real, target)
         l1 = self.encoder.l1_norm() + self.decoder.l1_norm()
         loss = self._loss_weight * chamfer + (self.l1_lambda / self.world) * l1
+        total = chamfer + self.l1_lambda * l1
+        if self.l2_lambda:                   # utils/train.py:489-492
+            l2 = self.encoder.l2_norm() + self.decoder.l2_norm()
+            loss = loss + (self.l2_lambda / self.world) * l2
+            total = total + self.l2_lambda * l2
         if self.opt_enc is not None:         # utils/train.py:324-325
             self.opt_enc.zero_grad()
             self.opt_dec.zero_grad()
@@ -170,7 +228,7 @@ class ReferenceLoopStep:
         if self.opt_enc is not None:
             self.opt_enc.step()
             self.opt_dec.step()
-        return (chamfer + self.l1_lambda * l1).detach(), recon
+        return total.detach(), recon
 
 
 def _module_loss(loss_choice, abs_coord, polar_coord, device, chamfer=None, jet_features=False):
@@ -380,28 +438,60 @@ def _node_mask(batch, p4, shape):
 
 
 class _OptimState:
-    """What lgn_step_finalize_f64 (and the tail of lgn_step_train_f64) works on besides the FlatParams: the Adam moments, the step
-    counter on the device, the loss block (results | scratch), the hyper-parameters -- and the call itself."""
+    """What the tail of a step works on besides the FlatParams -- the two state tensors of the optimiser (Adam: first / second moment;
+    RMSprop: momentum buffer / square_avg, also reachable as ``momentum_buf`` / ``square_avg``), the step counter on the device,
+    the loss block (results | scratch), the hyper-parameters -- and the calls themselves.  It owns the choice of optimiser: Adam
+    without L2 goes through lgn_step_finalize_f64 / lgn_step_train_f64 exactly as before, everything else (``optimizer_choice=
+    'rmsprop'``, ``l2_lambda > 0``) through their lgn_optim_desc twins, whose block has a fourth result, ``l2_out`` = sum w^2."""
 
-    def __init__(self, flat: FlatParams, l1_lambda, lr, betas, eps):
+    _force_opt = False      # tests: Adam without L2 through the lgn_optim_desc calls as well (same bits)
+
+    def __init__(self, flat: FlatParams, l1_lambda, lr, betas, eps, optimizer_choice: str = "adam", l2_lambda=0.0,
+                 rms_alpha: float = 0.99, momentum: float = 0.9):
         from . import _native as N
         self.N, self.flat = N, flat
+        self.kind, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
+        self.eps = optimizer_eps(self.kind, eps, flat.flat.dtype)
         self.adam_m, self.adam_v = torch.zeros_like(flat.flat), torch.zeros_like(flat.flat)
+        self.momentum_buf, self.square_avg = self.adam_m, self.adam_v
         self.step_dev = torch.zeros(1, device=flat.flat.device, dtype=torch.int64)
-        self.loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=flat.flat.device, dtype=flat.flat.dtype)
+        self.opt_form = self._force_opt or self.kind != "adam" or self.l2_lambda > 0.0
+        dev, dt = flat.flat.device, flat.flat.dtype
+        if self.opt_form:
+            self.loss_buf = torch.zeros(4 + N.FINALIZE_OPT_SCRATCH, device=dev, dtype=dt)
+            self.l2_out = self.loss_buf[3:4]
+            self.desc = d = N.OptimDesc()
+            d.kind = N.OPT_ADAM if self.kind == "adam" else N.OPT_RMSPROP
+            d.l1_lambda, d.l2_lambda, d.lr, d.eps = float(l1_lambda), self.l2_lambda, float(lr), self.eps
+            d.beta1, d.beta2, d.alpha, d.momentum = float(betas[0]), float(betas[1]), float(rms_alpha), float(momentum)
+        else:
+            self.loss_buf = torch.zeros(3 + N.FINALIZE_SCRATCH, device=dev, dtype=dt)
+            self.l2_out = torch.zeros(1, device=dev, dtype=dt)        # (no L2 term: nothing writes it)
+            self.desc = None
         self.loss_out = self.loss_buf[:3]
         self._state = (flat.flat, self.adam_m, self.adam_v, self.step_dev)          # what a step changes: snapshot() / restore()
         self._head = (N.ptr(flat.flat), N.ptr(flat.grad), flat.flat.numel(), N.ptr(flat.tail))
         self._hyper = (flat.tail.numel(), float(l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v), N.ptr(self.step_dev), float(lr),
-                       float(betas[0]), float(betas[1]), float(eps))
+                       float(betas[0]), float(betas[1]), self.eps)
 
     def tail_args(self, do_adam: bool):
-        """(n_loss, l1_lambda, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, do_adam, loss_out) of both calls."""
+        """(n_loss, l1_lambda, adam_m, adam_v, step_dev, lr, beta1, beta2, eps, do_adam, loss_out) of lgn_step_finalize_f64 /
+        lgn_step_train_f64; with a descriptor (n_loss, opt, state_m, state_v, step_dev, do_step, loss_out) of their twins."""
+        if self.opt_form:
+            import ctypes as C
+            return (self._hyper[0], C.byref(self.desc)) + self._hyper[2:5] + (int(do_adam), self.N.ptr(self.loss_buf))
         return self._hyper + (int(do_adam), self.N.ptr(self.loss_buf))
 
     def finalize(self, do_adam: bool):
         N = self.N
-        N._check(N.lib().lgn_step_finalize_f64(*self._head, *self.tail_args(do_adam), N.stream_ptr()), "lgn_step_finalize_f64")
+        name = "lgn_step_finalize_opt_f64" if self.opt_form else "lgn_step_finalize_f64"
+        N._check(getattr(N.lib(), name)(*self._head, *self.tail_args(do_adam), N.stream_ptr()), name)
+
+    def train(self, net_args, loss_args, do_adam: bool):
+        """The whole single-process step in one native call: lgn_step_train_f64, or its twin with the descriptor."""
+        N = self.N
+        name = "lgn_step_train_opt_f64" if self.opt_form else "lgn_step_train_f64"
+        N._check(getattr(N.lib(), name)(*net_args, *self.tail_args(do_adam), *loss_args, N.stream_ptr()), name)
 
     def snapshot(self):
         return tuple(t.clone() for t in self._state)
@@ -410,6 +500,15 @@ class _OptimState:
         with torch.no_grad():
             for t, s in zip(self._state, snap):
                 t.copy_(s)
+
+
+def _adopt_optim_state(step, o: _OptimState):
+    """The attributes a step class shows of its _OptimState: state tensors, counter, loss block and results, the options as they
+    were understood, and ``_finalize(do_adam)`` -- the finalize call of the state's form on the current stream."""
+    step.adam_m, step.adam_v, step.step_dev, step._loss_buf, step.loss_out = o.adam_m, o.adam_v, o.step_dev, o.loss_buf, o.loss_out
+    step.square_avg, step.momentum_buf, step.l2_out = o.square_avg, o.momentum_buf, o.l2_out
+    step.optimizer_choice, step.l2_lambda, step.eps = o.kind, o.l2_lambda, o.eps
+    step._finalize = o.finalize
 
 
 class _StaticInputs:
@@ -471,16 +570,25 @@ class NativeTrainStep:
     ``hungarian_abs_coord`` / ``hungarian_polar_coord`` (main.py:324-334); 'emd' and 'hybrid' raise NotImplementedError.  The mse and
     Hungarian losses run as the step's loss stage (the `loss` argument of the native calls, csrc/assign_loss.hip); they are means over (global batch, N,
     D), so each rank scales by 1 / (batch_size world N D).  ``assignment`` is the (B, N) int32 buffer the last step filled with every
-    jet's col (static: graph replays keep filling it), ``status`` its (B,) int32 companion."""
+    jet's col (static: graph replays keep filling it), ``status`` its (B,) int32 companion.
+
+    ``optimizer_choice`` (--optimizer, matched as utils/initialize.py:153-173 matches it: 'adam' or 'rmsprop' in any case, anything
+    else raises NotImplementedError) and ``l2_lambda`` (--l2-lambda: + l2_lambda * sum w^2 on the loss, utils/train.py:489-492; None
+    or <= 0 is off) run in the step's tail as L1 + Adam do, same launch count (include/lgn_amd.h: lgn_optim_desc).  RMSprop takes
+    ``rms_alpha`` (torch's 0.99) and ``momentum`` (the reference's 0.9); ``eps`` left at None follows the choice -- 1e-8 for Adam,
+    get_eps(dtype) = 1e-16 for RMSprop.  ``square_avg`` / ``momentum_buf`` alias the two state tensors, ``l2_out`` is sum w^2 of the
+    weights before the last step.  The defaults make exactly the native calls they made without these options."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
-                 betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, optimizer: bool = True, use_graph: bool = True,
+                 betas=(0.9, 0.999), eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
-                 hungarian_polar_coord: bool = False):
+                 hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
+                 momentum: float = 0.9):
         import ctypes as C
         from . import _native as N
         self.N = N
+        optimizer_kind(optimizer_choice)
         self.split = _check_native_pair(encoder, decoder)
         self.world = _world_size(process_group)
         self.loss_choice = loss_choice
@@ -519,9 +627,8 @@ class NativeTrainStep:
         self.workspace = torch.empty(nws, device=dev, dtype=dt)
         self.recon = torch.empty(2, d.B, decoder.num_output_particles, 4, device=dev, dtype=dt)
         self.loss_part = self.flat.tail
-        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps)
-        self.adam_m, self.adam_v, self.step_dev, self._loss_buf, self.loss_out = o.adam_m, o.adam_v, o.step_dev, o.loss_buf, o.loss_out
-        self._finalize = o.finalize                       # (do_adam): lgn_step_finalize_f64 on the current stream
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum)
+        _adopt_optim_state(self, o)
         self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True)
         self.p4, self.target, self.mask, self.in_scalars, self.assignment, self.status = \
             i.p4, i.target, i.mask, i.in_scalars, i.assignment, i.status
@@ -542,9 +649,7 @@ class NativeTrainStep:
         """Single process: the whole step in ONE native call (lgn_step_train_f64) -- with no all-reduce between the gradients and the
         optimiser, the reductions, the radial finalisation, L1 + Adam and the loss assembly are one launch (csrc/step_tail.hip)
         instead of three; same results bit for bit (LGN_AMD_SPLIT_TAIL=1 when the step is built: the separate launches)."""
-        N = self.N
-        N._check(N.lib().lgn_step_train_f64(*self._net_args, *self.opt_state.tail_args(do_adam), *self._loss_args, N.stream_ptr()),
-                 "lgn_step_train_f64")
+        self.opt_state.train(self._net_args, self._loss_args, do_adam)
 
     def _eager_collective(self, do_adam: bool):
         self._fwd_bwd()
@@ -632,11 +737,13 @@ class CapturedModuleStep:
     (gradients | this rank's Chamfer term) is all-reduced between two graphs."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8, betas=(0.9, 0.999),
-                 eps: float = 1e-8, process_group=None, optimizer: bool = True, use_graph: bool = True, get_real_method: str = "sum",
-                 chamfer_jet_features: bool = False, extra_scalars: int = 0, loss_choice: str = "chamfer",
-                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False):
+                 eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
+                 get_real_method: str = "sum", chamfer_jet_features: bool = False, extra_scalars: int = 0, loss_choice: str = "chamfer",
+                 hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0,
+                 rms_alpha: float = 0.99, momentum: float = 0.9):
         from . import _native as N
         self.N = N
+        optimizer_kind(optimizer_choice)
         encoder._require_gpu()
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
@@ -653,9 +760,8 @@ class CapturedModuleStep:
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, dev, jet_features=chamfer_jet_features)
         self._loss_weight = _loss_weight(loss_choice, self.world)
         self.loss_part = self.flat.tail
-        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps)
-        self.adam_m, self.adam_v, self.step_dev, self._loss_buf, self.loss_out = o.adam_m, o.adam_v, o.step_dev, o.loss_buf, o.loss_out
-        self._finalize = o.finalize                       # (do_adam): lgn_step_finalize_f64 on the current stream
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum)
+        _adopt_optim_state(self, o)
         self.recon = None
         self._g1 = self._g2 = None
         self.launches_per_step = None
