@@ -505,6 +505,35 @@ int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int ki
 /* Plan-time fit query: bytes of LDS of the step's assignment-loss stage at N particles and C channels of the last decoder level. */
 long long lgn_assign_loss_lds_bytes(int N, int C);
 
+/* ---- staging of a batch with the reference's --normalize / --normalize-method (utils/train.py:281-297, utils/normalize_p4.py) ------
+ * One launch does what a step's load_batch does: per jet the factor, target = p4 / factor (the UNscaled normalised batch the loss
+ * compares with), p4_in = target * scale (the encoder's input), the node mask, and with jet_features the jet node and the input
+ * scalars of Encoder._prepare_input.  One wavefront per jet; nothing is allocated, nothing waits on the host.  Any N >= 1.
+ *   method       LGN_NORM_NONE (factor 1), COMPONENT_MAX (max_i |p_i^mu| + 1e-16 per component), OVERALL_MAX (max over (i, mu) + 1e-16),
+ *                JET_E (sum_i E_i + 1e-16, summed in a fixed order).  The max keeps a NaN, as torch.amax does: a NaN or inf poisons
+ *                its own jet only.  The 1e-16 is added, not clamped: an all-zero jet has factor 1e-16 and stays zero.
+ *   p4           [B][N][4], 16-byte aligned;  labels [B][N] uint8, nullable: without it mask = target[..][0] != 0 (after the division)
+ *   scalars      [B][N + jet_features][K] data['scalars'], NULL when K = 0
+ *   p4_in        [B_pad][N + jet_features][4]; with jet_features row N is the jet node sum_i p4_in[i] (row order), its mask 1
+ *   target       [B_pad][N][4]; may BE p4_in when scale = 1 and there is no jet node
+ *   mask         [B_pad][N + jet_features] uint8
+ *   in_scalars   [B_pad][N + jet_features][jet_features + K], required when jet_features or K > 0: column 0 = normsq4(sum over all
+ *                N + 1 nodes) for every node (lgn_encoder.py:377-390), then the K columns of `scalars`
+ *   factor       [B_pad][4]: always four doubles per jet (the scalar methods write theirs four times)
+ * Jets B .. B_pad - 1 (the all-masked padding jets of a short batch) are written as zeros in every output. */
+#define LGN_NORM_NONE 0
+#define LGN_NORM_COMPONENT_MAX 1
+#define LGN_NORM_OVERALL_MAX 2
+#define LGN_NORM_JET_E 3
+int lgn_stage_batch_f64(const double* p4, const uint8_t* labels /*nullable*/, const double* scalars /*nullable*/, int B, int B_pad, int N,
+                        int method, double scale, int jet_features, int K, double* p4_in, double* target, uint8_t* mask,
+                        double* in_scalars /*nullable*/, double* factor, void* stream);
+/* out0[b][i][mu] = x0[b][i][mu] * factor[b][mu], and the same for x1 -> out1 (both NULL: one tensor only) in the same launch: what
+ * validate() collects under --normalize (p4_recons * norm_factor, p4_target * norm_factor).  x, out [B][N][4]; factor [B][4] as
+ * lgn_stage_batch_f64 writes it; all 16-byte aligned.  Static pointers: capturable behind lgn_step_eval_f64. */
+int lgn_denormalize_f64(const double* x0, const double* x1 /*nullable*/, const double* factor, int B, int N, double* out0,
+                        double* out1 /*nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

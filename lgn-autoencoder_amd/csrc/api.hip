@@ -221,4 +221,35 @@ int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int ki
 
 long long lgn_assign_loss_lds_bytes(int N, int C) { return N >= 1 && C >= 1 ? (long long)assign_loss_lds_bytes(N, C) : -1; }
 
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+int lgn_stage_batch_f64(const double* p4, const uint8_t* labels, const double* scalars, int B, int B_pad, int N, int method, double scale,
+                        int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,
+                        void* stream) {
+  LGN_CHECK_ARG(method >= LGN_NORM_NONE && method <= LGN_NORM_JET_E, "stage_batch: unknown method code %d", method);
+  LGN_CHECK_ARG(B >= 1, "stage_batch: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(B_pad >= B, "stage_batch: B_pad = %d < B = %d", B_pad, B);
+  LGN_CHECK_ARG(N >= 1, "stage_batch: N = %d (need N >= 1)", N);
+  LGN_CHECK_ARG(K >= 0, "stage_batch: K = %d (need K >= 0)", K);
+  LGN_CHECK_ARG(p4, "stage_batch: null p4");
+  LGN_CHECK_ARG(p4_in && target && mask && factor, "stage_batch: null output pointer (p4_in, target, mask, factor)");
+  LGN_CHECK_ARG(in_scalars || !(jet_features || K > 0), "stage_batch: in_scalars missing (jet_features = %d, K = %d)", jet_features, K);
+  LGN_CHECK_ARG(scalars || K == 0, "stage_batch: null scalars with K = %d", K);
+  LGN_CHECK_ARG(p4_in != target || (scale == 1.0 && !jet_features), "stage_batch: target may be p4_in only with scale 1 and no jet node");
+  LGN_CHECK_ARG(aligned16(p4) && aligned16(p4_in) && aligned16(target) && aligned16(factor),
+                "stage_batch: p4, p4_in, target and factor must be 16-byte aligned");
+  return stage_batch(p4, labels, scalars, B, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars, factor,
+                     (hipStream_t)stream);
+}
+
+int lgn_denormalize_f64(const double* x0, const double* x1, const double* factor, int B, int N, double* out0, double* out1, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "denormalize: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(N >= 1, "denormalize: N = %d (need N >= 1)", N);
+  LGN_CHECK_ARG(x0 && out0 && factor, "denormalize: null pointer (x0, out0, factor)");
+  LGN_CHECK_ARG((x1 == nullptr) == (out1 == nullptr), "denormalize: x1 and out1 go together");
+  LGN_CHECK_ARG(aligned16(x0) && aligned16(x1) && aligned16(factor) && aligned16(out0) && aligned16(out1),
+                "denormalize: every pointer must be 16-byte aligned");
+  return denormalize(x0, x1, factor, B, N, out0, out1, (hipStream_t)stream);
+}
+
 }  // extern "C"

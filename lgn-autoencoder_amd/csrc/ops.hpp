@@ -226,6 +226,11 @@ int local_static_pack_batch(const StaticPackJob* jobs, int n, bool unpack, hipSt
 int anomaly_scores(const double* rec, const double* tgt, const double* rec_n, const double* tgt_n, int B, int N, int mask, double* scores,
                    int* col4row, int* status, hipStream_t st);
 int linear_sum_assignment(const double* cost, int B, int n, int* col4row, int* status, hipStream_t st);
+// staging of a batch with the per-jet --normalize, and the de-normalisation of reconstruction and target (stage.hip)
+int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, int B, int B_pad, int N, int method, double scale,
+                int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,
+                hipStream_t st);
+int denormalize(const double* x0, const double* x1, const double* factor, int B, int N, double* out0, double* out1, hipStream_t st);
 int gen_pack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* s, const double* v, double* X, hipStream_t st);
 int gen_unpack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* X, double* s, double* v, hipStream_t st);
 // the same with the packed tensor tile-blocked: XT [tile][C][Q][2][64]  (M nodes; whole tiles are written, padding lanes zero)

@@ -1,0 +1,179 @@
+// lgn-autoencoder_amd/csrc/stage.hip -- staging of a batch into a step's static input buffers in one launch, with the reference's
+// per-jet --normalize (utils/normalize_p4.py, utils/train.py:281-297), and the de-normalisation of reconstruction and target that
+// validate() / test.py collect.
+//
+// stage_batch_kernel: one wavefront per jet, four jets per workgroup, lanes stride the particles; a row is 32 B = two 16-byte
+// vectors.  No LDS: the reductions (the jet's factor, the jet node of jet_features) run over wave shuffles.
+//   pass 1   per-lane max_i |p_i^mu| (NaN kept, as torch.amax keeps it: fmax would drop it) and sum_i E_i in row order, then the
+//            butterflies -> the jet's factor (+ 1e-16, added, not clamped: an all-zero jet has factor 1e-16 and stays zero)
+//   pass 2   target = p / factor, p4_in = target * scale, mask (labels, else target[.., 0] != 0: the reference's encoder sees the
+//            normalised batch), per-lane sums of p4_in in row order for the jet node
+//   pass 3   (jet_features) the jet node, the scalar normsq4(sum over all N + 1 nodes) in column 0 of in_scalars, data['scalars']
+// Jets b >= B (the all-masked padding jets of a short batch) are written as zeros in every output.
+//
+// Contraction is off: p / f * scale, the products of normsq4 and the sums round one operation at a time, as torch's do.
+#pragma clang fp contract(off)
+
+#include "common.hpp"
+#include "../../include/lgn_amd.h"
+#include "ops.hpp"
+#include "wave_sum.hpp"
+
+namespace lgn {
+namespace {
+
+constexpr double NORM_EPS = 1e-16;     // EPS of utils/normalize_p4.py
+constexpr int STAGE_WAVES = 4;
+
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+
+// max that keeps a NaN on either side (torch.amax); device fmax returns the other operand
+__device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
+__device__ __forceinline__ double wave_nan_max(double v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = nan_max(v, shfl_xor(v, m));
+  return v;
+}
+
+struct StageArgs {
+  const double* p4;          // [B][N][4]
+  const uint8_t* labels;     // [B][N] or null
+  const double* scalars;     // [B][Nn][K] or null (K == 0)
+  int B, B_pad, N, method, jet, K;
+  double scale;
+  double* p4_in;             // [B_pad][Nn][4]   Nn = N + jet
+  double* target;            // [B_pad][N][4]    (may be p4_in: scale == 1, no jet node)
+  uint8_t* mask;             // [B_pad][Nn]
+  double* in_scalars;        // [B_pad][Nn][jet + K] or null
+  double* factor;            // [B_pad][4]
+};
+
+__global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const StageArgs a) {
+  const int lane = threadIdx.x & 63;
+  const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
+  if (b >= a.B_pad) return;            // whole waves leave; nothing below waits on the workgroup
+  const int N = a.N, Nn = N + a.jet, S = a.jet + a.K;
+  dbl2* __restrict__ tg = reinterpret_cast<dbl2*>(a.target + (size_t)b * N * 4);
+  dbl2* __restrict__ pin = reinterpret_cast<dbl2*>(a.p4_in + (size_t)b * Nn * 4);
+  uint8_t* __restrict__ mk = a.mask + (size_t)b * Nn;
+  double* __restrict__ sc = a.in_scalars ? a.in_scalars + (size_t)b * Nn * S : nullptr;
+  const bool aliased = a.p4_in == a.target;
+  const dbl2 zero2 = {0.0, 0.0};
+
+  if (b >= a.B) {                      // padding jet: zeros everywhere
+    for (int i = lane; i < N; i += 64) { tg[2 * i] = zero2; tg[2 * i + 1] = zero2; }
+    if (!aliased)
+      for (int i = lane; i < Nn; i += 64) { pin[2 * i] = zero2; pin[2 * i + 1] = zero2; }
+    for (int i = lane; i < Nn; i += 64) mk[i] = 0;
+    if (sc)
+      for (int e = lane; e < Nn * S; e += 64) sc[e] = 0.0;
+    if (lane < 2) reinterpret_cast<dbl2*>(a.factor + (size_t)b * 4)[lane] = zero2;
+    return;
+  }
+
+  const dbl2* __restrict__ src = reinterpret_cast<const dbl2*>(a.p4 + (size_t)b * N * 4);
+  // ---- pass 1: the factor
+  double f[4] = {1.0, 1.0, 1.0, 1.0};
+  if (a.method != LGN_NORM_NONE) {
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, e = 0.0;
+    for (int i = lane; i < N; i += 64) {
+      const dbl2 lo = src[2 * i], hi = src[2 * i + 1];
+      m0 = nan_max(m0, fabs(lo.x)); m1 = nan_max(m1, fabs(lo.y));
+      m2 = nan_max(m2, fabs(hi.x)); m3 = nan_max(m3, fabs(hi.y));
+      e += lo.x;
+    }
+    if (a.method == LGN_NORM_JET_E) {
+      const double v[8] = {e, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      double s[8];
+      wave_allsum<8>(v, s, lane);
+      f[0] = f[1] = f[2] = f[3] = s[0] + NORM_EPS;
+    } else if (a.method == LGN_NORM_OVERALL_MAX) {
+      const double m = wave_nan_max(nan_max(nan_max(m0, m1), nan_max(m2, m3)));
+      f[0] = f[1] = f[2] = f[3] = m + NORM_EPS;
+    } else {
+      f[0] = wave_nan_max(m0) + NORM_EPS; f[1] = wave_nan_max(m1) + NORM_EPS;
+      f[2] = wave_nan_max(m2) + NORM_EPS; f[3] = wave_nan_max(m3) + NORM_EPS;
+    }
+  }
+  if (lane < 2) {
+    const dbl2 fv = {lane ? f[2] : f[0], lane ? f[3] : f[1]};       // (no run-time index: the array stays in registers)
+    reinterpret_cast<dbl2*>(a.factor + (size_t)b * 4)[lane] = fv;
+  }
+
+  // ---- pass 2: target, encoder input, mask; per-lane sums of the encoder input in row order
+  const uint8_t* __restrict__ lab = a.labels ? a.labels + (size_t)b * N : nullptr;
+  double j[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = lane; i < N; i += 64) {
+    const dbl2 lo = src[2 * i], hi = src[2 * i + 1];
+    const dbl2 tlo = {lo.x / f[0], lo.y / f[1]}, thi = {hi.x / f[2], hi.y / f[3]};
+    const dbl2 qlo = {tlo.x * a.scale, tlo.y * a.scale}, qhi = {thi.x * a.scale, thi.y * a.scale};
+    tg[2 * i] = tlo; tg[2 * i + 1] = thi;
+    if (!aliased) { pin[2 * i] = qlo; pin[2 * i + 1] = qhi; }
+    mk[i] = lab ? lab[i] : (uint8_t)(tlo.x != 0.0);
+    j[0] += qlo.x; j[1] += qlo.y; j[2] += qhi.x; j[3] += qhi.y;
+  }
+
+  // ---- pass 3: jet node, jet-mass scalar, data['scalars']  (Encoder._prepare_input)
+  if (a.jet) {
+    double s[8];
+    wave_allsum<8>(j, s, lane);
+    if (lane < 2) {
+      const dbl2 jv = {lane ? s[2] : s[0], lane ? s[3] : s[1]};
+      pin[2 * N + lane] = jv;
+    }
+    if (lane == 0) mk[N] = 1;
+    // normsq4 of the sum over ALL N + 1 nodes = particles + jet node: twice the jet (lgn_encoder.py:377-390), 2 E^2 - sum p^2
+    const double t0 = s[0] + s[0], t1 = s[1] + s[1], t2 = s[2] + s[2], t3 = s[3] + s[3];
+    const double q0 = t0 * t0, q1 = t1 * t1, q2 = t2 * t2, q3 = t3 * t3;
+    const double mass = 2.0 * q0 - (((q0 + q1) + q2) + q3);
+    for (int i = lane; i < Nn; i += 64) sc[(size_t)i * S] = mass;
+  }
+  if (a.K > 0) {
+    const double* __restrict__ xs = a.scalars + (size_t)b * Nn * a.K;
+    for (int e = lane; e < Nn * a.K; e += 64) {
+      const int i = e / a.K, k = e - i * a.K;
+      sc[(size_t)i * S + a.jet + k] = xs[e];
+    }
+  }
+}
+
+// out[b][i][mu] = x[b][i][mu] * factor[b][mu] for reconstruction and target at once: one thread per row of each tensor
+__global__ __launch_bounds__(BLOCK) void denormalize_kernel(const double* __restrict__ x0, const double* __restrict__ x1,
+                                                            const double* __restrict__ factor, long rows, int N,
+                                                            double* __restrict__ out0, double* __restrict__ out1) {
+  const long r = (long)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= rows) return;
+  const dbl2* f = reinterpret_cast<const dbl2*>(factor + (r / N) * 4);
+  const dbl2 flo = f[0], fhi = f[1];
+  {
+    const dbl2 lo = reinterpret_cast<const dbl2*>(x0)[2 * r], hi = reinterpret_cast<const dbl2*>(x0)[2 * r + 1];
+    reinterpret_cast<dbl2*>(out0)[2 * r] = lo * flo;
+    reinterpret_cast<dbl2*>(out0)[2 * r + 1] = hi * fhi;
+  }
+  if (x1) {
+    const dbl2 lo = reinterpret_cast<const dbl2*>(x1)[2 * r], hi = reinterpret_cast<const dbl2*>(x1)[2 * r + 1];
+    reinterpret_cast<dbl2*>(out1)[2 * r] = lo * flo;
+    reinterpret_cast<dbl2*>(out1)[2 * r + 1] = hi * fhi;
+  }
+}
+
+}  // namespace
+
+int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, int B, int B_pad, int N, int method, double scale,
+                int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,
+                hipStream_t st) {
+  const StageArgs a{p4, labels, scalars, B, B_pad, N, method, jet_features ? 1 : 0, K, scale, p4_in, target, mask, in_scalars, factor};
+  stage_batch_kernel<<<cdiv(B_pad, STAGE_WAVES), 64 * STAGE_WAVES, 0, st>>>(a);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int denormalize(const double* x0, const double* x1, const double* factor, int B, int N, double* out0, double* out1, hipStream_t st) {
+  const long rows = (long)B * N;
+  denormalize_kernel<<<(unsigned)((rows + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>(x0, x1, factor, rows, N, out0, out1);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace lgn

@@ -191,7 +191,12 @@ _SIGNATURES.update({
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
     "lgn_hungarian_mse_f64": [_i, _i, _vp, _vp, _i, _i, _i, _d] + [_vp] * 5,
+    # (p4, labels, scalars, B, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars, factor, stream)
+    "lgn_stage_batch_f64": [_vp] * 3 + [_i] * 4 + [_d, _i, _i] + [_vp] * 6,
+    "lgn_denormalize_f64": [_vp] * 3 + [_i, _i] + [_vp] * 3,
 })
+# LGN_NORM_* of include/lgn_amd.h
+NORM_NONE, NORM_COMPONENT_MAX, NORM_OVERALL_MAX, NORM_JET_E = 0, 1, 2, 3
 
 
 _LL_SIGNATURES = {          # entry points that return a long long

@@ -541,3 +541,82 @@ class L1Fn(torch.autograd.Function):
     def backward(ctx, g):
         (flat,) = ctx.saved_tensors
         return torch.sign(flat.detach()).mul_(g)
+
+
+# ---------------------------------------------------------------------------------------------
+# --normalize: per-jet normalisation and the staging of a batch (csrc/stage.hip)
+# ---------------------------------------------------------------------------------------------
+
+NORMALIZE_CODES = {"component_max": N.NORM_COMPONENT_MAX, "overall_max": N.NORM_OVERALL_MAX, "jet_e": N.NORM_JET_E}
+
+
+def normalize_code(method: str) -> int:
+    """The LGN_NORM_* code of a --normalize-method name as utils/normalize_p4.py:12-22 matches it: lower-cased, ' ' and '-' read as
+    '_'.  An unknown name logs the reference's warning -- whose text says component_max -- and takes what the reference then calls:
+    overall_max."""
+    code = NORMALIZE_CODES.get(str(method).lower().replace(" ", "_").replace("-", "_"))
+    if code is None:
+        import logging
+        logging.warning(f"Normalization method {method} not recognized. Using component_max.")
+        code = N.NORM_OVERALL_MAX
+    return code
+
+
+def _stage_source(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """A batch entry where the kernel can read it: on the device of the buffers, fp64, contiguous, 16-byte aligned."""
+    t = t.to(device=like.device, dtype=torch.float64).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def stage_batch(p4, code: int, p4_in, target, mask, factor, in_scalars=None, labels=None, scalars=None, scale: float = 1.0,
+                jet_features: bool = False):
+    """lgn_stage_batch_f64 on the current stream: the n = p4.shape[0] jets of a batch into rows 0 .. n - 1 of the (B_pad, ...) buffers
+    p4_in / target / mask / in_scalars / factor, zeros into the rest.  ``target`` may be ``p4_in`` (scale 1, no jet node)."""
+    p4 = _stage_source(p4, target)
+    n, Np = p4.shape[0], p4.shape[1]
+    if labels is not None:
+        labels = labels.to(device=target.device)
+        labels = (labels.view(torch.uint8) if labels.dtype == torch.bool else labels.to(torch.uint8)).contiguous()
+        if tuple(labels.shape) != (n, Np):
+            raise ValueError(f"mask shape {tuple(labels.shape)} != {(n, Np)}")
+    K = 0
+    if scalars is not None:
+        scalars = _stage_source(scalars, target)
+        K = scalars.shape[-1]
+        if tuple(scalars.shape) != (n, Np + int(jet_features), K):
+            raise ValueError(f"data['scalars'] of shape {tuple(scalars.shape)}; the encoder's nodes are {(n, Np + int(jet_features))}")
+    if in_scalars is not None and in_scalars.shape[-1] != int(jet_features) + K:
+        raise ValueError(f"the encoder was built for {1 + in_scalars.shape[-1]} input scalars per particle, the batch gives "
+                         f"{1 + int(jet_features) + K}")
+    N._check(N.lib().lgn_stage_batch_f64(N.ptr(p4), N.ptr(labels), N.ptr(scalars), n, target.shape[0], Np, int(code), float(scale),
+                                         int(bool(jet_features)), K, N.ptr(p4_in), N.ptr(target), N.ptr(mask), N.ptr(in_scalars),
+                                         N.ptr(factor), N.stream_ptr()), "lgn_stage_batch_f64")
+
+
+def factor_view(factor: torch.Tensor, code: int) -> torch.Tensor:
+    """The (B, 4) factors of lgn_stage_batch_f64 in the reference's shape: (B, 1, 4) for component_max, (B, 1, 1) otherwise."""
+    return factor.unsqueeze(1) if code == N.NORM_COMPONENT_MAX else factor[:, :1].unsqueeze(1)
+
+
+def normalize_p4(p4: torch.Tensor, method: str = "overall_max"):
+    """Drop-in of utils.normalize_p4.normalize_p4 on the GPU (one launch): (p4 / factor, factor) with factor of shape (..., 1, 4) for
+    'component_max' and (..., 1, 1) for 'overall_max' / 'jet_E'.  p4 (..., N, 4) fp64 on the device; there is no CPU fallback."""
+    code = normalize_code(method)
+    x = N.f64(p4)
+    lead, (Np, D) = tuple(x.shape[:-2]), x.shape[-2:]
+    if D != 4:
+        raise ValueError(f"normalize_p4 takes 4-momenta (..., N, 4); got {tuple(p4.shape)}")
+    x = x.reshape(-1, Np, 4)
+    B = x.shape[0]
+    out = torch.empty(B, Np, 4, device=x.device, dtype=x.dtype)
+    mask = torch.empty(B, Np, device=x.device, dtype=torch.uint8)
+    factor = torch.empty(B, 4, device=x.device, dtype=x.dtype)
+    stage_batch(x, code, out, out, mask, factor)
+    f = factor_view(factor, code)
+    return out.reshape(lead + (Np, 4)), f.reshape(lead + tuple(f.shape[1:]))
+
+
+def denormalize(factor, x0, out0, x1=None, out1=None):
+    """lgn_denormalize_f64 on the current stream: out = x * factor[:, None, :] for one or two (B, N, 4) tensors."""
+    N._check(N.lib().lgn_denormalize_f64(N.ptr(x0), N.ptr(x1), N.ptr(factor), x0.shape[0], x0.shape[1], N.ptr(out0), N.ptr(out1),
+                                         N.stream_ptr()), "lgn_denormalize_f64")

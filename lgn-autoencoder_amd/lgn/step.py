@@ -122,12 +122,15 @@ def torch_optimizer(params, optimizer_choice: str = "adam", lr: float = 5e-4, ep
 
 class TrainStep:
     """One data-parallel training step of the autoencoder (see module docstring).  ``optimizer_choice`` / ``l2_lambda`` /
-    ``rms_alpha`` / ``momentum``: --optimizer and --l2-lambda of the reference, as NativeTrainStep takes them."""
+    ``rms_alpha`` / ``momentum``: --optimizer and --l2-lambda of the reference, as NativeTrainStep takes them; ``normalize`` /
+    ``normalize_method``: --normalize, the batch is normalised per jet before the encoder sees it (one native launch)."""
 
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
                  process_group: Optional["dist.ProcessGroup"] = None, optimizer: bool = True, optimizer_choice: str = "adam",
-                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None):
+                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None, normalize: bool = False,
+                 normalize_method: str = "overall_max"):
         self.encoder, self.decoder = encoder, decoder
+        self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
         self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.flat = FlatParams(encoder, decoder)
@@ -142,6 +145,8 @@ class TrainStep:
 
     def forward_backward(self, batch: Dict[str, torch.Tensor]):
         """Returns (total loss as the reference logs it, reconstruction)."""
+        if self.normalize:
+            batch, self.norm_factor = _normalized_batch(batch, self.norm_code, self.flat.flat.device)
         self.flat.zero_grad()
         latent = self.encoder(batch)
         recon = self.decoder(latent)
@@ -183,8 +188,10 @@ class ReferenceLoopStep:
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
                  process_group=None, optimizer: bool = True, native_loss: bool = True, loss_choice: str = "chamfer",
                  hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam",
-                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None):
+                 l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None, normalize: bool = False,
+                 normalize_method: str = "overall_max"):
         self.encoder, self.decoder = encoder, decoder
+        self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
                                     None if native_loss else chamfer_loss)
@@ -202,6 +209,8 @@ class ReferenceLoopStep:
         self.opt_dec = make(decoder) if optimizer else None
 
     def step(self, batch):
+        if self.normalize:                   # utils/train.py:281-283
+            batch, self.norm_factor = _normalized_batch(batch, self.norm_code, self.encoder.device)
         latent = self.encoder(batch)
         recon = self.decoder(latent)
         real = get_real(recon, self.get_real_method)
@@ -266,6 +275,8 @@ def _loss_weight(loss_choice, world: int) -> float:
 # ---------------------------------------------------------------------------------------------------
 
 from .ops import describe_network, param_offsets  # noqa: E402  (descriptor and parameter slots of include/lgn_amd.h)
+from .ops import factor_view, normalize_code, stage_batch  # noqa: E402  (--normalize: csrc/stage.hip)
+from .ops import denormalize as _denormalize  # noqa: E402
 
 
 def _capturing(graph, pool=None):
@@ -437,6 +448,28 @@ def _node_mask(batch, p4, shape):
     return (p4[..., 0] != 0).to(torch.uint8)
 
 
+def _given_mask(batch):
+    """The labels / masks / mask entry of a batch, or None."""
+    for key in ("labels", "masks", "mask"):
+        if key in batch:
+            return batch[key]
+    return None
+
+
+def _normalized_batch(batch, code: int, device):
+    """The batch a module-API step feeds its encoder under --normalize (utils/train.py:281-283), made from freshly staged buffers --
+    p4 = batch['p4'] / factor, labels = the batch's mask or p4[..., 0] != 0 taken after the division, data['scalars'] as given -- and
+    the (n, 4) factors.  One native launch (lgn_stage_batch_f64); the encoder applies its own scale and jet features."""
+    n, Np = batch["p4"].shape[0], batch["p4"].shape[1]
+    p4 = torch.empty(n, Np, 4, device=device, dtype=torch.float64)
+    mask = torch.empty(n, Np, device=device, dtype=torch.uint8)
+    factor = torch.empty(n, 4, device=device, dtype=torch.float64)
+    stage_batch(batch["p4"], code, p4, p4, mask, factor, labels=_given_mask(batch))
+    out = {k: v for k, v in batch.items() if k not in ("p4", "labels", "masks", "mask")}
+    out["p4"], out["labels"] = p4, mask
+    return out, factor
+
+
 class _OptimState:
     """What the tail of a step works on besides the FlatParams -- the two state tensors of the optimiser (Adam: first / second moment;
     RMSprop: momentum buffer / square_avg, also reachable as ``momentum_buf`` / ``square_avg``), the step counter on the device,
@@ -514,9 +547,12 @@ def _adopt_optim_state(step, o: _OptimState):
 class _StaticInputs:
     """The static input buffers of a whole step -- p4 (the encoder's input: scaled, with jet_features + the jet node), target (the
     UNscaled batch the reconstruction is compared with, utils/train.py:285-292), mask, in_scalars (jet mass term, data['scalars'];
-    None without them) and, for an assignment loss, the assignment / status it fills -- and the staging of a batch into them."""
+    None without them) and, for an assignment loss, the assignment / status it fills -- and the staging of a batch into them.
+    ``normalize`` (--normalize / --normalize-method): the batch is divided per jet before anything else sees it, the target is the
+    normalised batch, ``norm_factor`` (B, 4) holds the factors (ones without it); the staging is then ONE native launch."""
 
-    def __init__(self, encoder, decoder, B: int, split: bool, assignment: bool, alias_target: bool = False):
+    def __init__(self, encoder, decoder, B: int, split: bool, assignment: bool, alias_target: bool = False, normalize: bool = False,
+                 normalize_method: str = "overall_max"):
         dev, dt = encoder.flat_params.device, encoder.flat_params.dtype
         N, Nd, K = encoder.num_input_particles, decoder.num_output_particles, max(1, encoder.tau_input_scalars)
         self.encoder, self.split, self.B = encoder, split, B
@@ -527,9 +563,21 @@ class _StaticInputs:
         self.in_scalars = torch.zeros(B, N, K - 1, device=dev, dtype=dt) if K > 1 else None
         self.assignment = torch.full((B, Nd), -1, device=dev, dtype=torch.int32) if assignment else None
         self.status = torch.zeros(B, device=dev, dtype=torch.int32) if assignment else None
+        self.normalize, self.norm_code = bool(normalize), normalize_code(normalize_method)
+        self.norm_factor = torch.ones(B, 4, device=dev, dtype=dt)
+
+    def _stage_normalized(self, batch: Dict[str, torch.Tensor]):
+        """lgn_stage_batch_f64: factor, target = p4 / factor, p4 = target * scale, mask, jet node and input scalars, zeros in the rows
+        behind the batch -- one launch, outside the step's graph (the batch's pointer changes from step to step)."""
+        jet = self.split and bool(getattr(self.encoder, "jet_features", False))
+        stage_batch(batch["p4"], self.norm_code, self.p4, self.target, self.mask, self.norm_factor, self.in_scalars,
+                    labels=_given_mask(batch), scalars=batch.get("scalars") if self.split else None, scale=self.encoder.scale,
+                    jet_features=jet)
 
     def stage(self, batch: Dict[str, torch.Tensor], n: Optional[int] = None):
         """Device-to-device copies of a batch of n jets (None: all B) into rows 0 .. n - 1; rows n .. B - 1 become all-masked jets."""
+        if self.normalize:
+            return self._stage_normalized(batch)
         p4 = batch["p4"]
         p4_in, target, mask = self.p4[:n], self.target[:n], self.mask[:n]
         if self.split:
@@ -577,14 +625,19 @@ class NativeTrainStep:
     or <= 0 is off) run in the step's tail as L1 + Adam do, same launch count (include/lgn_amd.h: lgn_optim_desc).  RMSprop takes
     ``rms_alpha`` (torch's 0.99) and ``momentum`` (the reference's 0.9); ``eps`` left at None follows the choice -- 1e-8 for Adam,
     get_eps(dtype) = 1e-16 for RMSprop.  ``square_avg`` / ``momentum_buf`` alias the two state tensors, ``l2_out`` is sum w^2 of the
-    weights before the last step.  The defaults make exactly the native calls they made without these options."""
+    weights before the last step.  The defaults make exactly the native calls they made without these options.
+
+    ``normalize`` / ``normalize_method`` (--normalize / --normalize-method, utils/train.py:281-283): every batch is divided per jet
+    -- by 'component_max', 'overall_max' or 'jet_E', names matched as utils/normalize_p4.py matches them -- before the encoder's
+    scale and jet features, and the loss is taken against the normalised batch.  load_batch is then one native launch
+    (lgn_stage_batch_f64) in place of the torch copies; ``norm_factor`` (B, 4) holds the last batch's factors."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
                  betas=(0.9, 0.999), eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
-                 momentum: float = 0.9):
+                 momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max"):
         import ctypes as C
         from . import _native as N
         self.N = N
@@ -629,9 +682,11 @@ class NativeTrainStep:
         self.loss_part = self.flat.tail
         self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum)
         _adopt_optim_state(self, o)
-        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True)
+        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True,
+                                        normalize=normalize, normalize_method=normalize_method)
         self.p4, self.target, self.mask, self.in_scalars, self.assignment, self.status = \
             i.p4, i.target, i.mask, i.in_scalars, i.assignment, i.status
+        self.normalize, self.norm_factor = i.normalize, i.norm_factor
         self.use_graph = use_graph
         self._g1 = self._g2 = None
         # the arguments of the native calls: every pointer is static (self.desc / self.loss_desc stay alive with the step)
@@ -740,11 +795,12 @@ class CapturedModuleStep:
                  eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  get_real_method: str = "sum", chamfer_jet_features: bool = False, extra_scalars: int = 0, loss_choice: str = "chamfer",
                  hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0,
-                 rms_alpha: float = 0.99, momentum: float = 0.9):
+                 rms_alpha: float = 0.99, momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max"):
         from . import _native as N
         self.N = N
         optimizer_kind(optimizer_choice)
         encoder._require_gpu()
+        self.normalize, self.norm_code = bool(normalize), normalize_code(normalize_method)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
         self.get_real_method, self.chamfer_jet_features = get_real_method, chamfer_jet_features
@@ -757,6 +813,7 @@ class CapturedModuleStep:
                       "labels": torch.zeros(batch_size, n_in, device=dev, dtype=torch.uint8)}
         if extra_scalars:
             self.batch["scalars"] = torch.zeros(batch_size, encoder.num_input_particles, extra_scalars, device=dev, dtype=dt)
+        self.norm_factor = torch.ones(batch_size, 4, device=dev, dtype=dt)
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, dev, jet_features=chamfer_jet_features)
         self._loss_weight = _loss_weight(loss_choice, self.world)
         self.loss_part = self.flat.tail
@@ -805,8 +862,12 @@ class CapturedModuleStep:
         p4 = batch["p4"]
         if tuple(p4.shape) != tuple(self.batch["p4"].shape):
             raise ValueError(f"CapturedModuleStep was built for batches of shape {tuple(self.batch['p4'].shape)}, got {tuple(p4.shape)}")
-        self.batch["p4"].copy_(p4)
-        self.batch["labels"].copy_(_node_mask(batch, p4, self.batch["labels"].shape))
+        if self.normalize:      # (--normalize: the static batch IS the normalised one, its labels taken after the division)
+            stage_batch(p4, self.norm_code, self.batch["p4"], self.batch["p4"], self.batch["labels"], self.norm_factor,
+                        labels=_given_mask(batch))
+        else:
+            self.batch["p4"].copy_(p4)
+            self.batch["labels"].copy_(_node_mask(batch, p4, self.batch["labels"].shape))
         if ("scalars" in batch) != ("scalars" in self.batch):
             raise ValueError("CapturedModuleStep: data['scalars'] must be present exactly when the step was built with extra_scalars")
         if "scalars" in batch:
@@ -874,11 +935,16 @@ class NativeEvalStep:
     the next ``run`` re-plans.  Same configurations and plan-time refusals (NotImplementedError) as NativeTrainStep.
 
     A short last batch (B' < batch_size jets) is padded with all-masked jets; loss and outputs cover the B' real ones, and the
-    jet-feature MSE, like the mse / hungarian loss, is the mean over those B' jets (nn.MSELoss on that batch)."""
+    jet-feature MSE, like the mse / hungarian loss, is the mean over those B' jets (nn.MSELoss on that batch).
+
+    ``normalize`` / ``normalize_method`` (--normalize): the batch is normalised per jet while it is staged (one native launch), the
+    loss is taken in the normalised space, and one more kernel right behind lgn_step_eval_f64 -- inside the graph -- multiplies
+    reconstruction and target back: ``run`` then also returns 'recon_denorm' and 'target_denorm' (what validate() collects,
+    utils/train.py:294-297) and 'norm_factors' in the reference's shape, (B', 1, 4) for component_max, else (B', 1, 1)."""
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
                  keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
-                 hungarian_polar_coord: bool = False):
+                 hungarian_polar_coord: bool = False, normalize: bool = False, normalize_method: str = "overall_max"):
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
@@ -895,9 +961,13 @@ class NativeEvalStep:
         self.loss_part = torch.empty(d.B, device=dev, dtype=dt)
         self.loss_out = torch.zeros(1, device=dev, dtype=dt)
         self.loss = self.loss_out[0]
-        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None)
+        self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, normalize=normalize,
+                                        normalize_method=normalize_method)
         self.p4, self.target, self.mask, self.in_scalars, self.assignment, self.status = \
             i.p4, i.target, i.mask, i.in_scalars, i.assignment, i.status
+        self.normalize, self.norm_factor = i.normalize, i.norm_factor
+        self.recon_denorm = torch.empty_like(self.recon) if self.normalize else None
+        self.target_denorm = torch.empty_like(self.target) if self.normalize else None
         P = N.pool_blocks(d.latent_pool)
         self.lat_s = torch.empty(2, d.B, 1, P * d.tau_s, 1, device=dev, dtype=dt) if self.keep_latent else None
         self.lat_v = torch.empty(2, d.B, 1, P * d.tau_v, 4, device=dev, dtype=dt) if self.keep_latent else None
@@ -940,6 +1010,8 @@ class NativeEvalStep:
         if loss_desc is not None:
             args[-3] = C.byref(loss_desc)
         N._check(N.lib().lgn_step_eval_f64(*args, N.stream_ptr()), "lgn_step_eval_f64")
+        if self.normalize:      # p4_recons * norm_factor, p4_target * norm_factor (utils/train.py:294-297): static pointers, capturable
+            _denormalize(self.norm_factor, self.recon, self.recon_denorm, self.target, self.target_denorm)
 
     def _capture(self):
         _warm_up(self._eval)
@@ -983,6 +1055,9 @@ class NativeEvalStep:
         else:
             self._eval()
         out = {"loss": self.loss, "recon": self.recon[:n]}
+        if self.normalize:
+            out["recon_denorm"], out["target_denorm"] = self.recon_denorm[:n], self.target_denorm[:n]
+            out["norm_factors"] = factor_view(self.norm_factor[:n], self.inputs.norm_code)
         if self.keep_latent:
             from .g_lib import GVec
             out["latent"] = GVec({(0, 0): self.lat_s[:, :n], (1, 1): self.lat_v[:, :n]})
@@ -995,18 +1070,26 @@ class ModuleEvalStep:
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
                  keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
-                 hungarian_polar_coord: bool = False):
+                 hungarian_polar_coord: bool = False, normalize: bool = False, normalize_method: str = "overall_max"):
         self.encoder, self.decoder, self.B = encoder, decoder, batch_size
+        self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.get_real_method, self.chamfer_jet_features, self.keep_latent = get_real_method, chamfer_jet_features, keep_latent
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
                                     jet_features=chamfer_jet_features)
 
     @torch.no_grad()
     def run(self, batch: Dict[str, torch.Tensor]):
+        if self.normalize:
+            batch, self.norm_factor = _normalized_batch(batch, self.norm_code, self.encoder.device)
         latent = self.encoder(batch)
         recon = get_real(self.decoder(latent), self.get_real_method)
         loss = self.loss_fn(recon, batch["p4"].to(recon.device))
         out = {"loss": loss, "recon": recon}
+        if self.normalize:
+            recon = recon.contiguous()
+            out["recon_denorm"], out["target_denorm"] = torch.empty_like(recon), torch.empty_like(batch["p4"])
+            _denormalize(self.norm_factor, recon, out["recon_denorm"], batch["p4"], out["target_denorm"])
+            out["norm_factors"] = factor_view(self.norm_factor, self.norm_code)
         if self.keep_latent:
             out["latent"] = latent
         return out

@@ -37,7 +37,7 @@ for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
 names = subprocess.run(["c++filt"], input="\n".join(r[0] for r in rows).encode(), stdout=subprocess.PIPE).stdout.decode().split("\n")
 print(f"{'vgpr':>5} {'agpr':>5} {'sgpr':>5} {'spill':>6} {'scratch':>8} {'lds':>7}  kernel")
 for r, n in zip(rows, names):
-    n = re.sub(r"^void lgn::\(anonymous namespace\)::", "", n)
+    n = re.sub(r"^(?:void )?lgn::\(anonymous namespace\)::", "", n)      # (only templates demangle with their return type)
     n = re.sub(r"\(.*$", "", n)
     if args and not any(a in n for a in args):
         continue
