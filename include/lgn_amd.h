@@ -496,6 +496,64 @@ int lgn_anomaly_scores_f64(const double* recons, const double* target, const dou
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */
 int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row, int* status, void* stream);
 
+/* ---- reconstruction analysis: the numeric half of the reference's plot_p (utils/jet_analysis/utils.py, particle_recon_err.py,
+ * jet_recon_err.py; csrc/analysis.hip).  target, recons [B][N][4] real Cartesian (E, px, py, pz), 1 <= N <= LGN_ANOMALY_NMAX.  One
+ * wavefront per jet; nothing is allocated, nothing waits on the host: capturable into a graph.  B = 0 is no work.  Every output is the
+ * caller's device memory; index 0 of a leading [2] is the target, 1 the reconstruction.
+ *   part_polar    [2][B][N][3] (nullable) get_p_polar_tensor(p, eps = 1e-16): pt = sqrt(px^2 + py^2), eta = asinh(pz / (pt + eps)),
+ *                 phi = atan2(py + eps, px)
+ *   part_polarrel [2][B][N][3] (nullable) get_p_polarrel_tensor: with (Pt, Eta, Phi) the same formulas on the summed jet,
+ *                 (pt / (Pt + eps), Eta - eta, ((Phi - phi + pi) mod 2 pi) - pi), the mod Python's.  Written only with abs_coord:
+ *                 without it the relative-polar frame IS part_polar (plot_particle_recon_err).
+ *   jet_cart      [2][B][4] (m, px, py, pz) of the summed jet (rows in order), m = sqrt|m^2| sign(m^2), m^2 = E^2 - px^2 - py^2 - pz^2
+ *   jet_polar     [2][B][4] (m, pt, eta, phi) with phi = atan2(py, px): get_jet_feature_polar has no eps there
+ *   jet_rel_err   [2][B][4] Cartesian then polar, as plot_jet_recon_err's call computes it: it hands (recons, target) to a lambda
+ *                 written for (target, recons), so the value is (recons - target) / (recons + 1e-16)
+ *   jet_keep      [2][B] uint8, filter_out_zeros' mask per coordinate system: all four target features non-zero
+ *   rel_err       [3][B][N][3] (nullable; needs is_padded and status): Cartesian, polar, relative polar.
+ *                 find_match: col0 = scipy's linear_sum_assignment(cost)[1] of cost[i][j] = |target3[i] - recons3[j]| on (px, py, pz),
+ *                 col1 the same on the relative-polar frame; costs are exact Euclidean distances (a square root of an ordered sum of
+ *                 squares), ties broken as scipy breaks them.
+ *                    Cartesian       (recons3[col0] - target3) / target3: NO eps -- padded rows give +-inf or NaN, and is_padded is
+ *                                    derived from those infinities
+ *                    polar           (polar_r[col0] - polar_t) / (polar_t + 1e-16), on the Cartesian matching
+ *                    relative polar  (polrel_r[col1] - polrel_t) / (polrel_t + 1e-16)
+ *                 without find_match: the identity pairing and get_rel_err's (recons - target) / target, no eps, in all three frames.
+ *   col4row       [2][B][N] int32 (nullable; only with rel_err): col0, col1 (the identity without find_match)
+ *   is_padded     [B][N] uint8: any infinity among the row's three Cartesian relative errors
+ *   status        [B] int32, as lgn_linear_sum_assignment_f64: 1 -- a cost of one of the two assignments is NaN (or -inf);
+ *                 256 -- one is infeasible.  The jet's col4row is then -1, its rel_err NaN and its is_padded 0.
+ * Replaces: get_p_polar_tensor, get_p_polarrel_tensor, get_jet_feature_cartesian / _polar, get_rel_err, get_rel_err_find_match,
+ * filter_out_zeros and the jet relative errors of plot_jet_recon_err. */
+int lgn_recon_analysis_f64(const double* target, const double* recons, int B, int N, int abs_coord, int find_match,
+                           double* part_polar /*nullable*/, double* part_polarrel /*nullable*/, double* jet_cart, double* jet_polar,
+                           double* jet_rel_err, uint8_t* jet_keep, double* rel_err /*nullable*/, int* col4row /*nullable*/,
+                           uint8_t* is_padded, int* status, void* stream);
+
+/* get_rel_err_find_match of particle_recon_err.py on frames the caller computed (each [B][N][3]): the same two assignments and three
+ * gathers as above -- rel_err [3][B][N][3], col4row [2][B][N] (nullable), is_padded [B][N], status [B] -- and nothing else. */
+int lgn_match_rel_err_f64(const double* target3, const double* recons3, const double* target_polar, const double* recons_polar,
+                          const double* target_polarrel, const double* recons_polarrel, int B, int N, double* rel_err,
+                          int* col4row /*nullable*/, uint8_t* is_padded, int* status, void* stream);
+
+/* ---- batched histogram over explicit edges: counts[c][:] = np.histogram(x[keep, c], bins = edges[c][:n_edges[c]])[0] for the
+ * columns c < cols <= ld of the device matrix x [rows][ld] (csrc/analysis.hip).  numpy's semantics exactly: bin i holds
+ * edges[i] <= v < edges[i + 1], the last bin also v == edges[-1]; values outside the range, NaN and +-inf are counted nowhere.
+ * Membership compares with the edge values themselves (bisection), never a scale-and-floor.  Per-workgroup LDS counters, one global
+ * atomic per non-empty bin; the output is cleared by a kernel of the library: capturable, nothing allocated, no host wait.
+ *   edges    [cols][max_edges] device, non-decreasing per column (not checked);  n_edges [cols] HOST ints, read during the call and
+ *            checked before any launch: 2 <= n_edges[c] <= max_edges <= LGN_HIST_MAX_EDGES;  1 <= cols <= LGN_HIST_MAX_COLS
+ *   keep     [rows] uint8, nullable: rows with keep == 0 are left out
+ *   weights  [rows] fp64, nullable.  Without: counts [cols][max_bins] int64 (wcounts NULL), integer atomics -- exact and independent
+ *            of the grid.  With: wcounts [cols][max_bins] fp64 (counts NULL), the sum of the weights per bin in no fixed order:
+ *            within n 2^-52 sum|w| of any other order for a bin of n values.
+ *   bins n_edges[c] - 1 .. max_bins - 1 of a column are written as 0.  rows = 0 clears the output. */
+#define LGN_HIST_MAX_EDGES 1025
+#define LGN_HIST_MAX_COLS 16
+int lgn_histogram_f64(const double* x, long long rows, int ld, int cols, const double* edges, const int* n_edges /*host*/, int max_edges,
+                      const uint8_t* keep /*nullable*/, const double* weights /*nullable*/, long long* counts, double* wcounts,
+                      int max_bins, void* stream);
+
 /* ---- the assignment loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the device
  * code of the whole-step calls' loss stage -- lgn_loss_desc above -- without the output mix): x, y [B][N][4] real 4-vectors ->
  * loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */

@@ -211,6 +211,54 @@ int lgn_linear_sum_assignment_f64(const double* cost, int B, int n, int* col4row
   return linear_sum_assignment(cost, B, n, col4row, status, (hipStream_t)stream);
 }
 
+int lgn_recon_analysis_f64(const double* target, const double* recons, int B, int N, int abs_coord, int find_match, double* part_polar,
+                           double* part_polarrel, double* jet_cart, double* jet_polar, double* jet_rel_err, uint8_t* jet_keep,
+                           double* rel_err, int* col4row, uint8_t* is_padded, int* status, void* stream) {
+  LGN_CHECK_ARG(B >= 0, "recon_analysis: B = %d (need B >= 0)", B);
+  LGN_CHECK_ARG(N >= 1 && N <= LGN_ANOMALY_NMAX, "recon_analysis: N = %d outside 1 .. %d", N, LGN_ANOMALY_NMAX);
+  LGN_CHECK_ARG(target && recons, "recon_analysis: null input pointer (target, recons)");
+  LGN_CHECK_ARG(jet_cart && jet_polar && jet_rel_err && jet_keep,
+                "recon_analysis: null jet output pointer (jet_cart, jet_polar, jet_rel_err, jet_keep)");
+  LGN_CHECK_ARG(!rel_err || status, "recon_analysis: rel_err without status");
+  LGN_CHECK_ARG(!rel_err || is_padded, "recon_analysis: rel_err without is_padded");
+  LGN_CHECK_ARG(rel_err || !col4row, "recon_analysis: col4row without rel_err");
+  if (B == 0) return 0;
+  return recon_analysis(target, recons, B, N, abs_coord != 0, find_match != 0, part_polar, part_polarrel, jet_cart, jet_polar,
+                        jet_rel_err, jet_keep, rel_err, col4row, is_padded, status, (hipStream_t)stream);
+}
+
+int lgn_match_rel_err_f64(const double* target3, const double* recons3, const double* target_polar, const double* recons_polar,
+                          const double* target_polarrel, const double* recons_polarrel, int B, int N, double* rel_err, int* col4row,
+                          uint8_t* is_padded, int* status, void* stream) {
+  LGN_CHECK_ARG(B >= 0, "match_rel_err: B = %d (need B >= 0)", B);
+  LGN_CHECK_ARG(N >= 1 && N <= LGN_ANOMALY_NMAX, "match_rel_err: N = %d outside 1 .. %d", N, LGN_ANOMALY_NMAX);
+  LGN_CHECK_ARG(target3 && recons3 && target_polar && recons_polar && target_polarrel && recons_polarrel,
+                "match_rel_err: null input pointer (six frames)");
+  LGN_CHECK_ARG(rel_err && is_padded && status, "match_rel_err: null output pointer (rel_err, is_padded, status)");
+  if (B == 0) return 0;
+  const double* fr[6] = {target3, recons3, target_polar, recons_polar, target_polarrel, recons_polarrel};
+  return match_rel_err(fr, B, N, rel_err, col4row, is_padded, status, (hipStream_t)stream);
+}
+
+int lgn_histogram_f64(const double* x, long long rows, int ld, int cols, const double* edges, const int* n_edges, int max_edges,
+                      const uint8_t* keep, const double* weights, long long* counts, double* wcounts, int max_bins, void* stream) {
+  LGN_CHECK_ARG(rows >= 0 && rows <= (1LL << 40), "histogram: rows = %lld outside 0 .. 2^40", rows);
+  LGN_CHECK_ARG(cols >= 1 && cols <= LGN_HIST_MAX_COLS, "histogram: cols = %d outside 1 .. %d", cols, LGN_HIST_MAX_COLS);
+  LGN_CHECK_ARG(ld >= cols, "histogram: ld = %d < cols = %d", ld, cols);
+  LGN_CHECK_ARG(n_edges, "histogram: null n_edges");
+  LGN_CHECK_ARG(max_edges >= 2 && max_edges <= LGN_HIST_MAX_EDGES, "histogram: max_edges = %d outside 2 .. %d", max_edges, LGN_HIST_MAX_EDGES);
+  for (int c = 0; c < cols; ++c) {
+    LGN_CHECK_ARG(n_edges[c] >= 2 && n_edges[c] <= max_edges, "histogram: n_edges = %d of column %d outside 2 .. max_edges = %d",
+                  n_edges[c], c, max_edges);
+    LGN_CHECK_ARG(n_edges[c] - 1 <= max_bins, "histogram: column %d has %d bins, max_bins = %d", c, n_edges[c] - 1, max_bins);
+  }
+  LGN_CHECK_ARG(edges, "histogram: null edges");
+  LGN_CHECK_ARG(x || rows == 0, "histogram: null x");
+  LGN_CHECK_ARG(weights ? (wcounts && !counts) : (counts && !wcounts),
+                "histogram: counts (int64) goes with no weights, wcounts (fp64) with weights; exactly one of them");
+  return histogram(x, rows, ld, cols, edges, n_edges, max_edges, keep, weights, counts, wcounts, max_bins, (hipStream_t)stream);
+}
+
 int lgn_hungarian_mse_f64(int B, int N, const double* x, const double* y, int kind, int abs_coord, int polar_coord, double scale,
                           double* loss_part, double* gx, int* assignment, int* status, void* stream) {
   LGN_CHECK_ARG(B >= 1, "hungarian_mse: B = %d (need B >= 1)", B);

@@ -226,6 +226,14 @@ int local_static_pack_batch(const StaticPackJob* jobs, int n, bool unpack, hipSt
 int anomaly_scores(const double* rec, const double* tgt, const double* rec_n, const double* tgt_n, int B, int N, int mask, double* scores,
                    int* col4row, int* status, hipStream_t st);
 int linear_sum_assignment(const double* cost, int B, int n, int* col4row, int* status, hipStream_t st);
+// reconstruction analysis (per-jet frames, jet features, matched relative errors) and the histogram over explicit edges (analysis.hip)
+int recon_analysis(const double* target, const double* recons, int B, int N, int abs_coord, int find_match, double* part_polar,
+                   double* part_polarrel, double* jet_cart, double* jet_polar, double* jet_rel_err, uint8_t* jet_keep, double* rel_err,
+                   int* col4row, uint8_t* is_padded, int* status, hipStream_t st);
+int match_rel_err(const double* const* frames, int B, int N, double* rel_err, int* col4row, uint8_t* is_padded, int* status,
+                  hipStream_t st);
+int histogram(const double* x, long long rows, int ld, int cols, const double* edges, const int* n_edges, int max_edges,
+              const uint8_t* keep, const double* weights, long long* counts, double* wcounts, int max_bins, hipStream_t st);
 // staging of a batch with the per-jet --normalize, and the de-normalisation of reconstruction and target (stage.hip)
 int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, int B, int B_pad, int N, int method, double scale,
                 int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,

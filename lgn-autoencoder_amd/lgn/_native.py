@@ -191,6 +191,12 @@ _SIGNATURES.update({
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
     "lgn_hungarian_mse_f64": [_i, _i, _vp, _vp, _i, _i, _i, _d] + [_vp] * 5,
+    # (target, recons, B, N, abs_coord, find_match, part_polar, part_polarrel, jet_cart, jet_polar, jet_rel_err, jet_keep, rel_err,
+    #  col4row, is_padded, status, stream)
+    "lgn_recon_analysis_f64": [_vp, _vp] + [_i] * 4 + [_vp] * 11,
+    "lgn_match_rel_err_f64": [_vp] * 6 + [_i, _i] + [_vp] * 5,
+    # (x, rows, ld, cols, edges, n_edges [host], max_edges, keep, weights, counts, wcounts, max_bins, stream)
+    "lgn_histogram_f64": [_vp, _ll, _i, _i, _vp, _ip, _i, _vp, _vp, _vp, _vp, _i, _vp],
     # (p4, labels, scalars, B, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars, factor, stream)
     "lgn_stage_batch_f64": [_vp] * 3 + [_i] * 4 + [_d, _i, _i] + [_vp] * 6,
     "lgn_denormalize_f64": [_vp] * 3 + [_i, _i] + [_vp] * 3,
@@ -210,6 +216,7 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_junction_lds_bytes": [_i] * 6,
     "lgn_assign_loss_lds_bytes": [_i, _i],
 }
+HIST_MAX_EDGES, HIST_MAX_COLS = 1025, 16    # LGN_HIST_MAX_EDGES, LGN_HIST_MAX_COLS of include/lgn_amd.h
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
 EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)
 
