@@ -592,6 +592,35 @@ int lgn_stage_batch_f64(const double* p4, const uint8_t* labels /*nullable*/, co
 int lgn_denormalize_f64(const double* x0, const double* x1 /*nullable*/, const double* factor, int B, int N, double* out0,
                         double* out1 /*nullable*/, void* stream);
 
+/* ---- device-resident epochs: an epoch as ceil(count / B) replays of ONE linear graph [gather staging | step | collect] -------------
+ * The dataset stays on the device, the epoch's order is one int32 index tensor, and what tells one step from the next -- the batch
+ * cursor, the loss sum, the step count -- lives in device memory the kernels read and write: no argument changes between replays.
+ *   cursor  [2] long long: [0] batches done in this epoch, [1] the collect kernel's arrival ticket (0 between launches)
+ *   epoch   [2] double:    [0] sum of the steps' losses, one fp64 add per step in step order (the sum a host loop makes of
+ *                          loss.item()), [1] steps counted
+ *   status  [1] int:       LGN_EPOCH_BAD_INDEX once an index outside [0, M) was met (plain store)
+ * lgn_epoch_reset clears all three (one single-thread kernel: capturable, no memset node).
+ *
+ * lgn_stage_gather_f64 is lgn_stage_batch_f64 with the jet of batch row b taken from a resident dataset: jet
+ * index[cursor * B_pad + b] of p4 [M][N][4], labels [M][N] (nullable), scalars [M][N + jet_features][K] (NULL when K = 0).  Row b is a
+ * real jet when cursor * B_pad + b < count, else a padding jet (zeros in every output); an index outside [0, M) forms no address, its
+ * row is a padding jet and status says so.  Everything else -- the four methods, scale, the aliased target, jet node, in_scalars,
+ * factor, alignment -- as lgn_stage_batch_f64, and the outputs are bit for bit what that call writes for p4[index[...]].
+ *
+ * lgn_epoch_collect_f64 runs once behind the step: with n_valid = min(B, count - cursor * B) it copies rows b < n_valid of each of the
+ * n <= LGN_EPOCH_MAX_COLLECT sources src[k] [B][row_doubles[k]] to dst[k] [count][row_doubles[k]] at jet cursor * B + b, adds *loss to
+ * epoch[0], counts the step and -- its last act, one thread -- advances the cursor.  src / dst / row_doubles are HOST arrays read during
+ * the call (n = 0: all three may be NULL).  Only tensors whose batch axis leads can be collected (not the latent). */
+#define LGN_EPOCH_MAX_COLLECT 4
+#define LGN_EPOCH_BAD_INDEX 1
+int lgn_stage_gather_f64(const double* p4, const uint8_t* labels /*nullable*/, const double* scalars /*nullable*/, long long M,
+                         const int* index, long long count, const long long* cursor, int B_pad, int N, int method, double scale,
+                         int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars /*nullable*/,
+                         double* factor, int* status, void* stream);
+int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, long long count, int B, int n,
+                          const double* const* src /*host*/, double* const* dst /*host*/, const int* row_doubles /*host*/, void* stream);
+int lgn_epoch_reset(long long* cursor, double* epoch, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

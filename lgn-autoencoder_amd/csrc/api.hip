@@ -300,4 +300,52 @@ int lgn_denormalize_f64(const double* x0, const double* x1, const double* factor
   return denormalize(x0, x1, factor, B, N, out0, out1, (hipStream_t)stream);
 }
 
+int lgn_stage_gather_f64(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                         const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K, double* p4_in,
+                         double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, void* stream) {
+  LGN_CHECK_ARG(method >= LGN_NORM_NONE && method <= LGN_NORM_JET_E, "stage_gather: unknown method code %d", method);
+  LGN_CHECK_ARG(M >= 1, "stage_gather: M = %lld (need M >= 1)", M);
+  LGN_CHECK_ARG(count >= 1, "stage_gather: count = %lld (need count >= 1)", count);
+  LGN_CHECK_ARG(B_pad >= 1, "stage_gather: B_pad = %d (need B_pad >= 1)", B_pad);
+  LGN_CHECK_ARG(N >= 1, "stage_gather: N = %d (need N >= 1)", N);
+  LGN_CHECK_ARG(K >= 0, "stage_gather: K = %d (need K >= 0)", K);
+  LGN_CHECK_ARG(p4, "stage_gather: null p4");
+  LGN_CHECK_ARG(index && cursor && status, "stage_gather: null epoch pointer (index, cursor, status)");
+  LGN_CHECK_ARG(p4_in && target && mask && factor, "stage_gather: null output pointer (p4_in, target, mask, factor)");
+  LGN_CHECK_ARG(in_scalars || !(jet_features || K > 0), "stage_gather: in_scalars missing (jet_features = %d, K = %d)", jet_features, K);
+  LGN_CHECK_ARG(scalars || K == 0, "stage_gather: null scalars with K = %d", K);
+  LGN_CHECK_ARG(p4_in != target || (scale == 1.0 && !jet_features), "stage_gather: target may be p4_in only with scale 1 and no jet node");
+  LGN_CHECK_ARG(aligned16(p4) && aligned16(p4_in) && aligned16(target) && aligned16(factor),
+                "stage_gather: p4, p4_in, target and factor must be 16-byte aligned");
+  LGN_CHECK_ARG((reinterpret_cast<uintptr_t>(index) & 3) == 0 && (reinterpret_cast<uintptr_t>(cursor) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(status) & 3) == 0, "stage_gather: misaligned index, cursor or status");
+  return stage_gather(p4, labels, scalars, M, index, count, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target, mask,
+                      in_scalars, factor, status, (hipStream_t)stream);
+}
+
+int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
+                          double* const* dst, const int* row_doubles, void* stream) {
+  LGN_CHECK_ARG(count >= 1, "epoch_collect: count = %lld (need count >= 1)", count);
+  LGN_CHECK_ARG(B >= 1, "epoch_collect: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(n >= 0 && n <= LGN_EPOCH_MAX_COLLECT, "epoch_collect: %d tensors to collect (0 .. %d)", n, LGN_EPOCH_MAX_COLLECT);
+  LGN_CHECK_ARG(loss && epoch && cursor, "epoch_collect: null pointer (loss, epoch, cursor)");
+  LGN_CHECK_ARG(((reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(epoch) | reinterpret_cast<uintptr_t>(cursor)) & 7) == 0,
+                "epoch_collect: loss, epoch and cursor must be 8-byte aligned");
+  LGN_CHECK_ARG(n == 0 || (src && dst && row_doubles), "epoch_collect: null src / dst / row_doubles array with n = %d", n);
+  for (int k = 0; k < n; ++k) {
+    LGN_CHECK_ARG(row_doubles[k] >= 1, "epoch_collect: row_doubles = %d of tensor %d (need row_doubles >= 1)", row_doubles[k], k);
+    LGN_CHECK_ARG(src[k] && dst[k], "epoch_collect: null src or dst of tensor %d", k);
+    LGN_CHECK_ARG(((reinterpret_cast<uintptr_t>(src[k]) | reinterpret_cast<uintptr_t>(dst[k])) & 7) == 0,
+                  "epoch_collect: src and dst of tensor %d must be 8-byte aligned", k);
+  }
+  return epoch_collect(loss, epoch, cursor, count, B, n, src, dst, row_doubles, (hipStream_t)stream);
+}
+
+int lgn_epoch_reset(long long* cursor, double* epoch, int* status, void* stream) {
+  LGN_CHECK_ARG(cursor && epoch && status, "epoch_reset: null pointer (cursor, epoch, status)");
+  LGN_CHECK_ARG(((reinterpret_cast<uintptr_t>(cursor) | reinterpret_cast<uintptr_t>(epoch)) & 7) == 0 &&
+                    (reinterpret_cast<uintptr_t>(status) & 3) == 0, "epoch_reset: misaligned cursor, epoch or status");
+  return epoch_reset(cursor, epoch, status, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -239,6 +239,13 @@ int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, 
                 int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,
                 hipStream_t st);
 int denormalize(const double* x0, const double* x1, const double* factor, int B, int N, double* out0, double* out1, hipStream_t st);
+// device-resident epochs (csrc/stage.hip): staging by index at a device cursor, the bookkeeping behind a step, the state's clear
+int stage_gather(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                 const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K, double* p4_in,
+                 double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, hipStream_t st);
+int epoch_collect(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
+                  double* const* dst, const int* row_doubles, hipStream_t st);
+int epoch_reset(long long* cursor, double* epoch, int* status, hipStream_t st);
 int gen_pack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* s, const double* v, double* X, hipStream_t st);
 int gen_unpack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* X, double* s, double* v, hipStream_t st);
 // the same with the packed tensor tile-blocked: XT [tile][C][Q][2][64]  (M nodes; whole tiles are written, padding lanes zero)

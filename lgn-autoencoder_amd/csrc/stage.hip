@@ -11,8 +11,14 @@
 //   pass 3   (jet_features) the jet node, the scalar normsq4(sum over all N + 1 nodes) in column 0 of in_scalars, data['scalars']
 // Jets b >= B (the all-masked padding jets of a short batch) are written as zeros in every output.
 //
+// Device-resident epochs: stage_gather_kernel is the same staging with each row's jet picked by index from a resident dataset at a
+// cursor kept on the device, epoch_collect_kernel the bookkeeping behind the step (loss sum, step count, collected rows, cursor
+// advance), epoch_reset_kernel their state's clear -- [gather | step | collect] is one linear graph, replayed once per batch.
+//
 // Contraction is off: p / f * scale, the products of normsq4 and the sums round one operation at a time, as torch's do.
 #pragma clang fp contract(off)
+
+#include <algorithm>
 
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
@@ -49,10 +55,9 @@ struct StageArgs {
   double* factor;            // [B_pad][4]
 };
 
-__global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const StageArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
-  if (b >= a.B_pad) return;            // whole waves leave; nothing below waits on the workgroup
+// One jet by one wavefront: batch row b of every output from jet `src` of the sources; src < 0 is a padding jet.  The body of both
+// staging kernels -- they differ in where a row's jet comes from, nothing else.
+__device__ __forceinline__ void stage_jet(const StageArgs& a, const long b, const long src_jet, const int lane) {
   const int N = a.N, Nn = N + a.jet, S = a.jet + a.K;
   dbl2* __restrict__ tg = reinterpret_cast<dbl2*>(a.target + (size_t)b * N * 4);
   dbl2* __restrict__ pin = reinterpret_cast<dbl2*>(a.p4_in + (size_t)b * Nn * 4);
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const Sta
   const bool aliased = a.p4_in == a.target;
   const dbl2 zero2 = {0.0, 0.0};
 
-  if (b >= a.B) {                      // padding jet: zeros everywhere
+  if (src_jet < 0) {                   // padding jet: zeros everywhere
     for (int i = lane; i < N; i += 64) { tg[2 * i] = zero2; tg[2 * i + 1] = zero2; }
     if (!aliased)
       for (int i = lane; i < Nn; i += 64) { pin[2 * i] = zero2; pin[2 * i + 1] = zero2; }
@@ -72,7 +77,7 @@ __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const Sta
     return;
   }
 
-  const dbl2* __restrict__ src = reinterpret_cast<const dbl2*>(a.p4 + (size_t)b * N * 4);
+  const dbl2* __restrict__ src = reinterpret_cast<const dbl2*>(a.p4 + (size_t)src_jet * N * 4);
   // ---- pass 1: the factor
   double f[4] = {1.0, 1.0, 1.0, 1.0};
   if (a.method != LGN_NORM_NONE) {
@@ -102,7 +107,7 @@ __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const Sta
   }
 
   // ---- pass 2: target, encoder input, mask; per-lane sums of the encoder input in row order
-  const uint8_t* __restrict__ lab = a.labels ? a.labels + (size_t)b * N : nullptr;
+  const uint8_t* __restrict__ lab = a.labels ? a.labels + (size_t)src_jet * N : nullptr;
   double j[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = lane; i < N; i += 64) {
     const dbl2 lo = src[2 * i], hi = src[2 * i + 1];
@@ -130,12 +135,44 @@ __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const Sta
     for (int i = lane; i < Nn; i += 64) sc[(size_t)i * S] = mass;
   }
   if (a.K > 0) {
-    const double* __restrict__ xs = a.scalars + (size_t)b * Nn * a.K;
+    const double* __restrict__ xs = a.scalars + (size_t)src_jet * Nn * a.K;
     for (int e = lane; e < Nn * a.K; e += 64) {
       const int i = e / a.K, k = e - i * a.K;
       sc[(size_t)i * S + a.jet + k] = xs[e];
     }
   }
+}
+
+__global__ __launch_bounds__(64 * STAGE_WAVES) void stage_batch_kernel(const StageArgs a) {
+  const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
+  if (b >= a.B_pad) return;            // whole waves leave; nothing below waits on the workgroup
+  stage_jet(a, b, b < a.B ? b : -1, threadIdx.x & 63);
+}
+
+// The same staging with the jet of row b taken from a resident dataset: index[cursor * B_pad + b], the cursor read from the device
+// (an epoch replays ONE graph: nothing of a step's position may be a kernel argument).  Rows at or behind `count` are padding jets;
+// so is a row whose index lies outside [0, M) -- no address is formed from it -- and lane 0 then stores LGN_EPOCH_BAD_INDEX.
+struct GatherArgs {
+  const int* index;          // [count]
+  const long long* cursor;   // [0]: batches done in this epoch
+  long long count, M;
+  int* status;
+};
+
+__global__ __launch_bounds__(64 * STAGE_WAVES) void stage_gather_kernel(const StageArgs a, const GatherArgs g) {
+  const int lane = threadIdx.x & 63;
+  const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
+  if (b >= a.B_pad) return;
+  const long long c = g.cursor[0];
+  // (a cursor outside the epoch -- negative, or so large that the product would wrap -- stages padding jets only)
+  const long long pos = (c >= 0 && c <= g.count / a.B_pad) ? c * a.B_pad + b : g.count;
+  long src_jet = -1;
+  if (pos < g.count) {
+    const long long j = g.index[pos];
+    if (j >= 0 && j < g.M) src_jet = (long)j;
+    else if (lane == 0) g.status[0] = LGN_EPOCH_BAD_INDEX;      // (every wave that stores, stores the same word)
+  }
+  stage_jet(a, b, src_jet, lane);
 }
 
 // out[b][i][mu] = x[b][i][mu] * factor[b][mu] for reconstruction and target at once: one thread per row of each tensor
@@ -158,6 +195,61 @@ __global__ __launch_bounds__(BLOCK) void denormalize_kernel(const double* __rest
   }
 }
 
+// The epoch's bookkeeping behind a step, in the step's graph: rows b < n_valid = min(B, count - cursor * B) of up to
+// LGN_EPOCH_MAX_COLLECT static [B][rd] tensors go to [count][rd] epoch buffers at jet cursor * B + b -- rows are contiguous on both
+// sides, so a tensor is ONE run of n_valid * rd doubles, moved as 16-byte vectors where both ends are aligned -- then the workgroup
+// that arrives LAST (a ticket in cursor[1]; every thread of every workgroup has read the cursor by then) adds the step's loss to
+// epoch[0], counts the step in epoch[1], clears the ticket and advances the cursor: one thread, one fp64 add per step, in step order.
+struct CollectArgs {
+  const double* loss;        // the step's loss (device scalar)
+  double* epoch;             // [0] sum of the losses, [1] steps
+  long long* cursor;         // [0] batches done, [1] arrival ticket (0 between launches)
+  long long count;
+  int B, n;
+  const double* src[LGN_EPOCH_MAX_COLLECT];
+  double* dst[LGN_EPOCH_MAX_COLLECT];
+  int rd[LGN_EPOCH_MAX_COLLECT];
+};
+
+__global__ __launch_bounds__(BLOCK) void epoch_collect_kernel(const CollectArgs a) {
+  const long long c = a.cursor[0];
+  long long n_valid = 0;
+  if (c >= 0 && c <= a.count / a.B) n_valid = a.count - c * a.B < a.B ? a.count - c * a.B : a.B;
+  const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nth = (long)gridDim.x * BLOCK;
+  for (int k = 0; k < a.n && n_valid > 0; ++k) {
+    const double* __restrict__ s = a.src[k];
+    double* __restrict__ d = a.dst[k] + c * a.B * a.rd[k];
+    const long total = (long)n_valid * a.rd[k];
+    if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {
+      const dbl2* __restrict__ s2 = reinterpret_cast<const dbl2*>(s);
+      dbl2* __restrict__ d2 = reinterpret_cast<dbl2*>(d);
+      for (long e = tid; e < total / 2; e += nth) d2[e] = s2[e];
+      if ((total & 1) && tid == 0) d[total - 1] = s[total - 1];
+    } else {
+      for (long e = tid; e < total; e += nth) d[e] = s[e];
+    }
+  }
+  __syncthreads();                     // every thread of this workgroup has read the cursor
+  if (threadIdx.x == 0) {
+    __threadfence();
+    const unsigned long long t = atomicAdd(reinterpret_cast<unsigned long long*>(a.cursor + 1), 1ULL);
+    if (t == gridDim.x - 1) {          // the last workgroup to arrive: nobody reads the cursor any more
+      a.cursor[1] = 0;
+      a.epoch[0] += a.loss[0];
+      a.epoch[1] += 1.0;
+      a.cursor[0] = c + 1;
+    }
+  }
+}
+
+__global__ void epoch_reset_kernel(long long* cursor, double* epoch, int* status) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    cursor[0] = 0; cursor[1] = 0;
+    epoch[0] = 0.0; epoch[1] = 0.0;
+    status[0] = 0;
+  }
+}
+
 }  // namespace
 
 int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, int B, int B_pad, int N, int method, double scale,
@@ -172,6 +264,37 @@ int stage_batch(const double* p4, const uint8_t* labels, const double* scalars, 
 int denormalize(const double* x0, const double* x1, const double* factor, int B, int N, double* out0, double* out1, hipStream_t st) {
   const long rows = (long)B * N;
   denormalize_kernel<<<(unsigned)((rows + BLOCK - 1) / BLOCK), BLOCK, 0, st>>>(x0, x1, factor, rows, N, out0, out1);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int stage_gather(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                 const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K, double* p4_in,
+                 double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, hipStream_t st) {
+  const StageArgs a{p4, labels, scalars, B_pad, B_pad, N, method, jet_features ? 1 : 0, K, scale, p4_in, target, mask, in_scalars, factor};
+  const GatherArgs g{index, cursor, count, M, status};
+  stage_gather_kernel<<<cdiv(B_pad, STAGE_WAVES), 64 * STAGE_WAVES, 0, st>>>(a, g);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int epoch_collect(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
+                  double* const* dst, const int* row_doubles, hipStream_t st) {
+  CollectArgs a{loss, epoch, cursor, count, B, n, {}, {}, {}};
+  long most = 0;
+  for (int k = 0; k < n; ++k) {
+    a.src[k] = src[k]; a.dst[k] = dst[k]; a.rd[k] = row_doubles[k];
+    most = std::max(most, (long)B * row_doubles[k]);
+  }
+  // a thread moves about four 16-byte vectors of the largest tensor; a few workgroups saturate what a step's outputs need
+  const long blocks = std::min<long>(std::max<long>((most / 2 + 4 * BLOCK - 1) / (4 * BLOCK), 1), 64);
+  epoch_collect_kernel<<<(unsigned)blocks, BLOCK, 0, st>>>(a);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int epoch_reset(long long* cursor, double* epoch, int* status, hipStream_t st) {
+  epoch_reset_kernel<<<1, 64, 0, st>>>(cursor, epoch, status);
   LGN_CHECK_LAUNCH();
   return 0;
 }

@@ -200,7 +200,14 @@ _SIGNATURES.update({
     # (p4, labels, scalars, B, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars, factor, stream)
     "lgn_stage_batch_f64": [_vp] * 3 + [_i] * 4 + [_d, _i, _i] + [_vp] * 6,
     "lgn_denormalize_f64": [_vp] * 3 + [_i, _i] + [_vp] * 3,
+    # (p4, labels, scalars, M, index, count, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars, factor,
+    #  status, stream)
+    "lgn_stage_gather_f64": [_vp] * 3 + [_ll, _vp, _ll, _vp] + [_i] * 3 + [_d, _i, _i] + [_vp] * 7,
+    # (loss, epoch, cursor, count, B, n, src [host], dst [host], row_doubles [host], stream)
+    "lgn_epoch_collect_f64": [_vp] * 3 + [_ll, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _ip, _vp],
+    "lgn_epoch_reset": [_vp] * 4,
 })
+EPOCH_MAX_COLLECT, EPOCH_BAD_INDEX = 4, 1    # LGN_EPOCH_MAX_COLLECT, LGN_EPOCH_BAD_INDEX of include/lgn_amd.h
 # LGN_NORM_* of include/lgn_amd.h
 NORM_NONE, NORM_COMPONENT_MAX, NORM_OVERALL_MAX, NORM_JET_E = 0, 1, 2, 3
 

@@ -711,6 +711,16 @@ class NativeTrainStep:
         dist.all_reduce(self.flat.grad_buf, op=dist.ReduceOp.SUM, group=self.group)
         self._finalize(do_adam)
 
+    def enqueue(self, do_step: Optional[bool] = None):
+        """The step's native call(s) on the current stream, on the staged buffers, not captured by the step -- for a caller that
+        captures them into a graph of its own (lgn.epoch.EpochRunner); with a collective, the all-reduce between them.
+        do_step: run the optimiser (None: as the step was built)."""
+        do_step = self.optimizer if do_step is None else bool(do_step)
+        if self.collective:
+            self._eager_collective(do_step)
+        else:
+            self._train(do_step)
+
     def _capture(self):
         snap = self.opt_state.snapshot()
         # (with a collective, the communicator / algorithm set-up of this message size happens here, outside the capture)
@@ -1019,6 +1029,22 @@ class NativeEvalStep:
         with _capturing(self._graph):
             self._eval()
 
+    def _follow_params(self) -> bool:
+        """Re-plan if the parameter blocks moved (e.g. a NativeTrainStep re-homed them): new offsets, new graph.  True if they had."""
+        if (self.encoder.flat_params.data_ptr(), self.decoder.flat_params.data_ptr()) == self._ptrs:
+            return False
+        self._plan()
+        if self._ws > self.workspace.numel():
+            self.workspace = torch.empty(self._ws, device=self.workspace.device, dtype=self.workspace.dtype)
+        self._bind()
+        self._graph = None
+        return True
+
+    def enqueue(self):
+        """The step's native call(s) on the current stream, on the staged buffers, not captured by the step -- for a caller that
+        captures them into a graph of its own (lgn.epoch.EpochRunner).  The descriptors are those of a full batch."""
+        self._eval()
+
     def load_batch(self, batch: Dict[str, torch.Tensor]):
         """Stage a batch of B' <= batch_size jets into the static input buffers; rows B' .. batch_size - 1 become all-masked jets."""
         p4 = batch["p4"]
@@ -1035,12 +1061,7 @@ class NativeEvalStep:
         static buffers: the next run overwrites them."""
         if batch is not None:
             self.load_batch(batch)
-        if (self.encoder.flat_params.data_ptr(), self.decoder.flat_params.data_ptr()) != self._ptrs:
-            self._plan()                     # the blocks moved (e.g. a NativeTrainStep re-homed them): new offsets, new graph
-            if self._ws > self.workspace.numel():
-                self.workspace = torch.empty(self._ws, device=self.workspace.device, dtype=self.workspace.dtype)
-            self._bind()
-            self._graph = None
+        self._follow_params()
         n = self.n_real
         if n < self.B and (self.chamfer_jet_features or self.loss_desc is not None):
             # the means (nn.MSELoss of the jet features; mse / hungarian) run over the B' real jets: descriptors of this call's own,
