@@ -491,6 +491,34 @@ int lgn_chamfer_f64(int B, int N, int M, const double* x, const double* y, int j
 int lgn_anomaly_scores_f64(const double* recons, const double* target, const double* recons_n, const double* target_n, int B, int N,
                            int score_mask, double* scores, int* col4row /*nullable*/, int* status, void* stream);
 
+/* ---- ROC curves and AUCs of score columns (the reference's get_ROC_AUC(), utils/jet_analysis/anomaly_detection.py; csrc/roc.hip) ----
+ * For every column k < K of scores (M rows, column k at scores + k, row stride ld >= K: a [B][21] score tensor is read in place):
+ * sklearn.metrics.roc_curve(labels, scores[:, k]) with its defaults (drop_intermediate=True, pos_label inferred: 1), then
+ * sklearn.metrics.auc(fpr, tpr), then the reference's flip: with an AUC < 0.5 the curve and AUC are those of the negated labels --
+ * fpr and tpr exchanged, thresholds unchanged, the AUC summed again from the exchanged curve -- and flipped[k] = 1.
+ * Sorted on the device (bitonic tiles of LGN_ROC_TILE pairs in LDS, then merge passes between two workspace buffers); counts are
+ * int32, each rate is one IEEE division, the AUC is summed in a fixed order (the same input gives the same bits), no floating-point
+ * atomics.  On the caller's stream; nothing is allocated, nothing waits on the host: capturable into a graph.
+ *   labels      [M] fp64: 1 is the positive class; the other class is 0 or -1 (not both)
+ *   fpr, tpr, thresholds [K][M + 1]: the first length[k] entries of row k are the curve; thresholds[k][0] = +inf; a threshold
+ *               that is a zero is +0.0 (sklearn keeps the sign of one of the tied zeros)
+ *   length, flipped, status [K] int32;  auc [K]
+ *   status      LGN_ROC_NONFINITE -- the column holds NaN or +-inf (with LGN_ROC_NAN: a NaN); LGN_ROC_SINGLE_CLASS -- only one class
+ *               among the labels; LGN_ROC_BAD_LABEL -- a label outside {-1, 0, 1}, or both -1 and 0.  Such a column has length 0 and
+ *               auc NaN (its curve rows are unspecified); the other columns are unaffected.
+ *   workspace   8-byte aligned device memory of at least the bytes the workspace query returns (< 0: bad arguments)
+ * Refused before any launch: null pointers, M < 1 or M >= 2^31, K < 1 or K > LGN_ROC_MAX_COLS, ld < K, a short workspace. */
+#define LGN_ROC_TILE 2048
+#define LGN_ROC_MAX_COLS 65535
+#define LGN_ROC_NONFINITE 1
+#define LGN_ROC_SINGLE_CLASS 2
+#define LGN_ROC_BAD_LABEL 4
+#define LGN_ROC_NAN 8
+long long lgn_roc_workspace_bytes(long long M, int K);
+int lgn_roc_auc_f64(const double* scores, long long M, int ld, int K, const double* labels, double* fpr, double* tpr,
+                    double* thresholds, int* length, double* auc, int* flipped, int* status, void* workspace,
+                    long long workspace_bytes, void* stream);
+
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */

@@ -1,7 +1,9 @@
 """
 Per-jet anomaly scores on the GPU: the drop-in of the reference's utils/jet_analysis/anomaly_detection.py ``anomaly_scores()`` /
 ``anomaly_scores_sig_bkg()`` (Chamfer, Hungarian and MSE in five frames, their Lorentz-metric versions and three jet-level scores),
-plus the batched exact assignment solver the Hungarian scores use (``linear_sum_assignment``, scipy's ``col_ind``, ties included).
+plus the batched exact assignment solver the Hungarian scores use (``linear_sum_assignment``, scipy's ``col_ind``, ties included)
+and the drop-in of its ``get_ROC_AUC()``: ROC curves and AUCs of every score kind, sorted on the GPU (``roc_auc_tensor``,
+csrc/roc.hip, C ABI ``lgn_roc_auc_f64``).
 
 One HIP kernel launch per chunk of jets (csrc/anomaly.hip, C ABI ``lgn_anomaly_scores_f64``).  There is no CPU fallback: the scores
 need a GPU.  Deliberate differences from the reference:
@@ -10,8 +12,12 @@ need a GPU.  Deliberate differences from the reference:
   * ``include_emd=True`` raises NotImplementedError (EMD needs the energyflow package and is out of scope).
   * The Hungarian pairing is the reference's own, p[col_ind[r]] against q[r], not the optimal one; kept on purpose.
   * The scores are computed in fp64 whatever the input dtype.
+  * ``get_ROC_AUC`` logs what the reference logs and saves what it saves, but draws nothing; the ROC of labels in {0, 1} flips as
+    that of labels in {-1, 1} does (the reference's negated {0, -1} labels make sklearn raise).
 """
-from typing import Dict, Optional, Tuple
+import logging
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -60,6 +66,8 @@ NMAX = 192                                 # include/lgn_amd.h: LGN_ANOMALY_NMAX
 ALL = (1 << 21) - 1                        # LGN_ANOMALY_ALL
 NO_HUNGARIAN = ALL & ~sum(1 << s for s in HUNGARIAN_INDEX)
 DEFAULT_CHUNK = 65536
+ROC_TILE = N.ROC_TILE                      # LGN_ROC_TILE: rows per sort tile of roc_auc_tensor (its sort changes path at multiples)
+ROC_GROUP_BYTES = 1 << 30                  # get_ROC_AUC: curve buffers + workspace of one group of columns stay below this
 
 
 def _device() -> torch.device:
@@ -189,3 +197,112 @@ def linear_sum_assignment(cost: torch.Tensor) -> torch.Tensor:
         _raise_for_status(status.cpu().numpy())
     col = col.to(torch.int64)
     return col[0] if single else col
+
+
+def roc_auc_tensor(scores: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """ROC curve and AUC of every column of a (M, K) fp64 device tensor against labels (M,) (any real dtype; 1 is the positive
+    class, the other is 0 or -1), with no host sync: chain it after score_tensor().  Per column sklearn's roc_curve(labels, column)
+    with its defaults, sklearn's auc, and the reference's flip (AUC < 0.5: the curve of the negated labels).  A column view of a wider
+    tensor (unit column stride) is read in place.  Returns device tensors: fpr, tpr, thresholds (K, M + 1), of which the first
+    length[k] entries of row k are the curve; length, flipped, status (K,) int32; auc (K,) fp64.  A column with a status bit
+    (_native.ROC_NONFINITE / ROC_SINGLE_CLASS / ROC_BAD_LABEL) has length 0 and auc NaN."""
+    _device()
+    if scores.dim() != 2 or scores.dtype != torch.float64 or not scores.is_cuda:
+        raise ValueError(f"roc_auc_tensor takes a (M, K) fp64 device tensor of scores; got {tuple(scores.shape)} {scores.dtype} on "
+                         f"{scores.device}")
+    M, K = int(scores.shape[0]), int(scores.shape[1])
+    if M < 1 or K < 1:
+        raise ValueError(f"roc_auc_tensor needs at least one row and one column; got {tuple(scores.shape)}")
+    if labels.dim() != 1 or labels.shape[0] != M or labels.is_complex():
+        raise ValueError(f"labels must be a real ({M},) tensor; got {tuple(labels.shape)} {labels.dtype}")
+    if scores.stride(1) != 1 and K > 1 or scores.stride(0) < K and M > 1:
+        scores = scores.contiguous()
+    ld = int(scores.stride(0)) if M > 1 and scores.stride(0) >= K else K
+    dev = scores.device
+    labels = labels.to(device=dev, dtype=torch.float64).contiguous()
+    L = N.lib()
+    nbytes = L.lgn_roc_workspace_bytes(M, K)
+    if nbytes < 0:
+        raise ValueError(N.last_error())
+    curves = torch.empty(3, K, M + 1, device=dev, dtype=torch.float64)
+    ints = torch.empty(3, K, device=dev, dtype=torch.int32)
+    auc = torch.empty(K, device=dev, dtype=torch.float64)
+    work = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    rc = L.lgn_roc_auc_f64(scores.data_ptr(), M, ld, K, N.ptr(labels), curves[0].data_ptr(), curves[1].data_ptr(),
+                           curves[2].data_ptr(), ints[0].data_ptr(), N.ptr(auc), ints[1].data_ptr(), ints[2].data_ptr(),
+                           N.ptr(work), nbytes, N.stream_ptr())
+    N._check(rc, "lgn_roc_auc_f64")
+    return dict(fpr=curves[0], tpr=curves[1], thresholds=curves[2], length=ints[0], auc=auc, flipped=ints[1], status=ints[2])
+
+
+def _raise_for_roc_status(status: np.ndarray):
+    bad = np.flatnonzero(status)
+    if not len(bad):
+        return
+    s = int(np.bitwise_or.reduce(status))
+    if s & N.ROC_BAD_LABEL:
+        raise ValueError("true_labels must hold two classes: 1 and either 0 or -1")
+    k = next((i for i in bad if status[i] & N.ROC_NONFINITE), None)
+    if k is not None:            # sklearn's wording (check_array on y_score); a NaN goes first there too
+        what = "NaN" if status[k] & N.ROC_NAN else "infinity or a value too large for dtype('float64')"
+        raise ValueError(f"Input contains {what}.")
+    raise ValueError("Only one class present in true_labels: the ROC curve is not defined (sklearn's rates are NaN and its auc "
+                     "raises)")
+
+
+def get_ROC_AUC(scores_dict, true_labels, save_path: Union[str, Path] = None, plot_rocs: bool = True,
+                rocs_hlines: List[float] = [1e-1, 1e-2]):
+    """get_ROC_AUC() of utils/jet_analysis/anomaly_detection.py: (roc_curves, aucs) with the keys of scores_dict in its order,
+    roc_curves[kind] = (fpr, tpr, thresholds) as numpy arrays of the true length, aucs[kind] a float.  The values of scores_dict and
+    true_labels may be numpy arrays or CPU or device tensors.  Sorted and summed on the GPU, the columns in groups when they are many
+    and long, with one synchronisation at the end.  Raises ValueError as sklearn words it for NaN or infinite scores, and for labels
+    of one class.  save_path: scores.pt, true_labels.pt, roc_curves.pt and aucs.pt, as the reference saves them.  plot_rocs logs the
+    best AUC and each kind's intercepts at rocs_hlines; nothing is drawn."""
+    dev = _device()
+    keys = list(scores_dict)
+    if not keys:
+        return dict(), dict()
+    cols = [torch.as_tensor(scores_dict[k]).reshape(-1).to(device=dev, dtype=torch.float64) for k in keys]
+    M = int(cols[0].shape[0])
+    if any(int(c.shape[0]) != M for c in cols):
+        raise ValueError("every score kind must have one score per label")
+    labels = torch.as_tensor(true_labels).reshape(-1).to(device=dev)
+    per_col = 3 * 8 * (M + 1) + max(1, N.lib().lgn_roc_workspace_bytes(max(M, 1), 1))
+    group = max(1, min(len(keys), ROC_GROUP_BYTES // per_col))
+    host, small = [], []
+    for k0 in range(0, len(keys), group):
+        out = roc_auc_tensor(torch.stack(cols[k0:k0 + group], dim=1), labels)
+        kg = out["auc"].shape[0]
+        pinned = torch.empty(3, kg, M + 1, dtype=torch.float64).pin_memory()
+        for i, name in enumerate(("fpr", "tpr", "thresholds")):
+            pinned[i].copy_(out[name], non_blocking=True)
+        meta = torch.empty(4, kg, dtype=torch.float64).pin_memory()
+        for i, name in enumerate(("length", "auc", "flipped", "status")):
+            meta[i].copy_(out[name].to(torch.float64), non_blocking=True)
+        host.append(pinned)
+        small.append(meta)
+    torch.cuda.current_stream().synchronize()
+    meta = torch.cat(small, dim=1).numpy()
+    _raise_for_roc_status(meta[3].astype(np.int64))
+    roc_curves, aucs = dict(), dict()
+    for k, kind in enumerate(keys):
+        g, j = divmod(k, group)
+        n = int(meta[0][k])
+        roc_curves[kind] = tuple(host[g][i, j, :n].numpy().copy() for i in range(3))
+        aucs[kind] = float(meta[1][k])
+
+    if save_path is not None:
+        save_path = Path(save_path)
+        save_path.mkdir(exist_ok=True, parents=True)
+        torch.save(scores_dict, save_path / "scores.pt")
+        torch.save(true_labels, save_path / "true_labels.pt")
+        torch.save(roc_curves, save_path / "roc_curves.pt")
+        torch.save(aucs, save_path / "aucs.pt")
+
+    if plot_rocs:
+        auc_sorted = list(sorted(aucs.items(), key=lambda x: x[1], reverse=True))
+        logging.info(f"Best AUC: {auc_sorted[0]}")
+        for kind, _ in auc_sorted:
+            fpr, tpr, _ = roc_curves[kind]
+            logging.info(f"{kind}: {dict((h, tpr[np.searchsorted(fpr, h)]) for h in rocs_hlines)}")
+    return roc_curves, aucs
