@@ -519,6 +519,50 @@ int lgn_roc_auc_f64(const double* scores, long long M, int ld, int K, const doub
                     double* thresholds, int* length, double* auc, int* flipped, int* status, void* workspace,
                     long long workspace_bytes, void* stream);
 
+/* ---- energy mover's distance (csrc/emd.hip, csrc/emd_wave.hpp): the reference's 22nd anomaly score "emd (relative coordinates)",
+ * emd_loss() of utils/jet_analysis/anomaly_detection.py, which calls energyflow.emd.emd(p, q) per jet with its defaults (R = 1, beta = 1,
+ * norm = False, Euclidean ground distance, no periodic phi).  energyflow was not available when this was written: the definition
+ * below, taken from its documentation, is the specification.  For events (pT_i, y_i, phi_i), i < n, and (pT'_j, y'_j, phi'_j), j < m:
+ *      theta_ij = sqrt((y_i - y'_j)^2 + (phi_i - phi'_j)^2) / R
+ *      EMD      = min over f >= 0 of sum f_ij theta_ij + |sum pT - sum pT'|
+ *                 with sum_j f_ij <= pT_i, sum_i f_ij <= pT'_j, sum f_ij = min(sum pT, sum pT')
+ * solved exactly as a balanced transportation problem: one fictitious particle on the lighter side carries the weight difference at
+ * cost 1 to every particle of the other event.  Successive shortest paths, one wavefront per pair of events; the order of the two
+ * arguments does not change the cost.  Nothing is allocated, nothing waits on the host: capturable into a graph.
+ *   lgn_emd_f64: ev0 [B][n][3], ev1 [B][m][3] events of (pT, y, phi); n != m allowed; 1 <= n, m <= LGN_EMD_NMAX; R > 0.
+ *      emd    [B]
+ *      flow   [B][n + 1][m + 1] (nullable): the optimal flow; row n and column m are the fictitious particles (at most one has weight)
+ *      dual0  [B][n + 1], dual1 [B][m + 1] (nullable): potentials with dual0_i + dual1_j <= theta_ij (1 on a fictitious arc), equality
+ *             where flow_ij > 0, so that sum f theta = sum dual0 w + sum dual1 w' certifies the optimum
+ *      status [B] int32: LGN_EMD_INVALID -- NaN or +-inf anywhere, or a negative weight; LGN_EMD_EMPTY -- both events weightless (what
+ *             energyflow returns there is not known); LGN_EMD_ITER -- the cap of 16 (n + m + 2) augmentations was hit;
+ *             LGN_EMD_INFEASIBLE -- more weight was left over than the rounding of the two sums, (n + m) 2^-52 max(sum pT, sum pT'),
+ *             explains.  With a status bit emd (and flow, dual0, dual1) of that pair is NaN; the other pairs are unaffected.
+ *             One event weightless is well defined: the other event's sum pT.
+ *      work   the flow matrices when they do not fit LDS: at least lgn_emd_workspace_bytes(B, max(n, m)) bytes of 8-byte aligned device
+ *             memory (0 bytes: work may be NULL).  lgn_emd_lds_bytes(N): the LDS of one wavefront at N particles per event; the flow
+ *             is in LDS when that is at least 8 (N + 1)^2.
+ *   lgn_emd_relative_f64: recons, target [B][N][4] real Cartesian (E, px, py, pz) jets; each is staged into its relative-polar frame
+ *      (pT / (jet pT + 1e-16), eta - jet eta, wrapped phi - jet phi) exactly as lgn_anomaly_scores_f64 stages it, then solved with
+ *      R = 1: the reference's score.  Zero-padded particles have no weight.
+ *   Refused before any launch (negative return): null pointers, B < 1, n, m or N outside 1 .. LGN_EMD_NMAX, R not a finite positive
+ *   number, a missing, short or misaligned workspace.
+ *   lgn_emd_debug_max_augmentations: DEBUG ONLY, not part of the stable surface (it may change or go without an ABI bump): the
+ *   largest number of augmentations of any pair since the last reset, on the current device only (one counter per device, fed by one
+ *   integer atomic max per pair), read with a blocking copy: it waits on the host and is not capturable.  For tools/emd_bench.py. */
+#define LGN_EMD_NMAX 191
+#define LGN_EMD_INVALID 1
+#define LGN_EMD_EMPTY 2
+#define LGN_EMD_ITER 4
+#define LGN_EMD_INFEASIBLE 8
+long long lgn_emd_workspace_bytes(int B, int N);
+long long lgn_emd_lds_bytes(int N);
+int lgn_emd_f64(const double* ev0, const double* ev1, int B, int n, int m, double R, double* emd, double* flow /*nullable*/,
+                double* dual0 /*nullable*/, double* dual1 /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
+int lgn_emd_relative_f64(const double* recons, const double* target, int B, int N, double* emd, int* status, void* work,
+                         long long work_bytes, void* stream);
+int lgn_emd_debug_max_augmentations(int* out, int reset);
+
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */

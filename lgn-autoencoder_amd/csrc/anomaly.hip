@@ -13,13 +13,14 @@
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
 #include "lsap_wave.hpp"
+#include "polar_dev.hpp"     // polar, wrap_phi: shared with emd.hip
 
 namespace lgn {
 namespace {
 
 constexpr int NMAX = LGN_ANOMALY_NMAX;
 constexpr int NSC = LGN_ANOMALY_NSCORES;
-constexpr double EPS = 1e-16;          // EPS_DEFAULT of the reference
+constexpr double EPS = POLAR_EPS;      // EPS_DEFAULT of the reference
 
 // ---- standalone batched solver: cost[B][n][n] -> col4row[B][n] -----------------------------------------------------------
 struct GlobalCost {
@@ -62,19 +63,6 @@ constexpr int NCOMP = 20;
 __host__ __device__ constexpr int hung_bit(int f) { return f < 5 ? 5 + f : 18; }
 __host__ __device__ constexpr int cham_bit(int f) { return f < 5 ? f : 17; }
 __host__ __device__ constexpr int mse_bit(int f) { return f < 5 ? 10 + f : 19; }
-
-// the reference's torch.remainder(x + pi, 2 pi) - pi (float remainder: the sign follows the divisor)
-__device__ __forceinline__ double wrap_phi(double x) {
-  const double b = 2.0 * M_PI;
-  double m = fmod(x + M_PI, b);
-  if (m != 0.0 && ((m < 0.0) != (b < 0.0))) m += b;
-  return m - M_PI;
-}
-__device__ __forceinline__ void polar(double px, double py, double pz, double& pT, double& eta, double& phi) {
-  pT = sqrt(px * px + py * py);
-  eta = asinh(pz / (pT + EPS));
-  phi = atan2(py + EPS, px + EPS);
-}
 
 template <int K>
 __global__ __launch_bounds__(64 * SC_WAVES) void anomaly_scores_kernel(const double* __restrict__ rec, const double* __restrict__ tgt,

@@ -208,6 +208,11 @@ _SIGNATURES.update({
     "lgn_epoch_reset": [_vp] * 4,
     # (scores, M, ld, K, labels, fpr, tpr, thresholds, length, auc, flipped, status, workspace, workspace_bytes, stream)
     "lgn_roc_auc_f64": [_vp, _ll, _i, _i] + [_vp] * 9 + [_ll, _vp],
+    # (ev0, ev1, B, n, m, R, emd, flow, dual0, dual1, status, work, work_bytes, stream)
+    "lgn_emd_f64": [_vp, _vp, _i, _i, _i, _d] + [_vp] * 6 + [_ll, _vp],
+    # (recons, target, B, N, emd, status, work, work_bytes, stream)
+    "lgn_emd_relative_f64": [_vp, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp],
+    "lgn_emd_debug_max_augmentations": [_ip, _i],
 })
 EPOCH_MAX_COLLECT, EPOCH_BAD_INDEX = 4, 1    # LGN_EPOCH_MAX_COLLECT, LGN_EPOCH_BAD_INDEX of include/lgn_amd.h
 # LGN_NORM_* of include/lgn_amd.h
@@ -225,9 +230,13 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_junction_lds_bytes": [_i] * 6,
     "lgn_assign_loss_lds_bytes": [_i, _i],
     "lgn_roc_workspace_bytes": [_ll, _i],
+    "lgn_emd_workspace_bytes": [_i, _i],
+    "lgn_emd_lds_bytes": [_i],
 }
 ROC_TILE, ROC_MAX_COLS = 2048, 65535        # LGN_ROC_TILE, LGN_ROC_MAX_COLS of include/lgn_amd.h
 ROC_NONFINITE, ROC_SINGLE_CLASS, ROC_BAD_LABEL, ROC_NAN = 1, 2, 4, 8    # LGN_ROC_* status bits
+EMD_NMAX = 191                              # LGN_EMD_NMAX of include/lgn_amd.h
+EMD_INVALID, EMD_EMPTY, EMD_ITER, EMD_INFEASIBLE = 1, 2, 4, 8    # LGN_EMD_* status bits
 HIST_MAX_EDGES, HIST_MAX_COLS = 1025, 16    # LGN_HIST_MAX_EDGES, LGN_HIST_MAX_COLS of include/lgn_amd.h
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
 EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)

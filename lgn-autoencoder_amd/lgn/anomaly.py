@@ -9,7 +9,10 @@ One HIP kernel launch per chunk of jets (csrc/anomaly.hip, C ABI ``lgn_anomaly_s
 need a GPU.  Deliberate differences from the reference:
   * ``batch_size`` is only a chunk size.  The reference's batched paths (batch_size > 0) score the reconstruction against itself
     and return zeros for every Chamfer and Hungarian score; here every batch size returns the unbatched scores.
-  * ``include_emd=True`` raises NotImplementedError (EMD needs the energyflow package and is out of scope).
+  * ``include_emd=True`` raises NotImplementedError, as before the EMD score existed here; ``include_emd="native"`` adds the
+    reference's 22nd score, "emd (relative coordinates)", computed exactly on the GPU (lgn/emd.py, csrc/emd.hip: an optimal-transport
+    solver, one wavefront per jet) from energyflow's documented definition -- the energyflow package is not needed and was not
+    available to compare with.  A jet whose two sides are both weightless raises (what energyflow returns there is not known).
   * The Hungarian pairing is the reference's own, p[col_ind[r]] against q[r], not the optimal one; kept on purpose.
   * The scores are computed in fp64 whatever the input dtype.
   * ``get_ROC_AUC`` logs what the reference logs and saves what it saves, but draws nothing; the ROC of labels in {0, 1} flips as
@@ -23,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import emd as _emd
 
 # the reference's key strings (anomaly_detection.py), in the order anomaly_scores() inserts them
 CHAMFER_PARTICLE_CARTESIAN = "particle, Cartesian, Chamfer distance"
@@ -65,6 +69,8 @@ HUNGARIAN_INDEX = (5, 6, 7, 8, 9, 18)      # score slots of the six assignment v
 NMAX = 192                                 # include/lgn_amd.h: LGN_ANOMALY_NMAX
 ALL = (1 << 21) - 1                        # LGN_ANOMALY_ALL
 NO_HUNGARIAN = ALL & ~sum(1 << s for s in HUNGARIAN_INDEX)
+SCORE_KEYS_EMD = SCORE_KEYS + (EMD_RELATIVE,)     # the 22 keys of include_emd="native", in the reference's order
+EMD_STATUS_SHIFT = 16                      # the EMD score's LGN_EMD_* bits in a combined status
 DEFAULT_CHUNK = 65536
 ROC_TILE = N.ROC_TILE                      # LGN_ROC_TILE: rows per sort tile of roc_auc_tensor (its sort changes path at multiples)
 ROC_GROUP_BYTES = 1 << 30                  # get_ROC_AUC: curve buffers + workspace of one group of columns stay below this
@@ -97,11 +103,13 @@ def _launch(xs, mask: int, scores, status, col4row=None):
 
 
 def score_tensor(recons: torch.Tensor, target: torch.Tensor, recons_normalized: torch.Tensor, target_normalized: torch.Tensor,
-                 hungarian: bool = True, return_status: bool = False, col4row: Optional[torch.Tensor] = None):
+                 hungarian: bool = True, return_status: bool = False, col4row: Optional[torch.Tensor] = None, emd: bool = False):
     """The 21 scores of device tensors as one (B, 21) fp64 device tensor, columns in SCORE_KEYS order, with no host sync (chain it
     after NativeEvalStep.run()).  hungarian=False skips the six assignments (their columns are NaN).  A jet whose Hungarian cost
     holds NaN / -inf gets NaN there and a status bit (return_status=True also returns the (B,) int32 status; see
-    include/lgn_amd.h).  col4row: optional (6, B, N) int32 device tensor that receives the six assignments."""
+    include/lgn_amd.h).  col4row: optional (6, B, N) int32 device tensor that receives the six assignments.  emd=True: (B, 22), the
+    22nd column the EMD score (SCORE_KEYS_EMD order; N <= 191); its LGN_EMD_* status bits are in the status from bit EMD_STATUS_SHIFT
+    up, and such a jet's EMD is NaN."""
     B, n = _check_shapes(recons, target, recons_normalized, target_normalized)
     xs = [N.f64(x.to(torch.float64)) for x in (recons, target, recons_normalized, target_normalized)]
     dev = xs[0].device
@@ -111,6 +119,10 @@ def score_tensor(recons: torch.Tensor, target: torch.Tensor, recons_normalized: 
         raise ValueError(f"col4row must be a (6, {B}, {n}) int32 tensor")
     if B > 0:
         _launch(xs, ALL if hungarian else NO_HUNGARIAN, scores, status, col4row)
+    if emd:
+        e, est = _emd.emd_relative_tensor(xs[0], xs[1], return_status=True)
+        scores = torch.cat([scores, e.unsqueeze(1)], dim=1)
+        status = status | (est << EMD_STATUS_SHIFT)
     return (scores, status) if return_status else scores
 
 
@@ -118,17 +130,22 @@ def _raise_for_status(status: np.ndarray):
     bad = np.flatnonzero(status)
     if len(bad):
         s = int(status[bad[0]])
-        what = "matrix contains invalid numeric entries" if s & 0xFF else "cost matrix is infeasible"
+        if s & 0xFFFF:
+            what = "matrix contains invalid numeric entries" if s & 0xFF else "cost matrix is infeasible"
+        else:
+            what = "EMD score: " + _emd.status_message(s >> EMD_STATUS_SHIFT)
         raise ValueError(f"{what} (jet {int(bad[0])}, {len(bad)} jet(s) in all)")
 
 
 def anomaly_scores(recons: torch.Tensor, target: torch.Tensor, recons_normalized: torch.Tensor, target_normalized: torch.Tensor,
-                   include_emd: bool = False, batch_size: int = -1) -> Dict[str, np.ndarray]:
+                   include_emd: Union[bool, str] = False, batch_size: int = -1) -> Dict[str, np.ndarray]:
     """anomaly_scores() of utils/jet_analysis/anomaly_detection.py: {key: (B,) np.ndarray} for the 21 keys, in the reference's order.
     Inputs may be CPU or device tensors (B, N, 4); CPU inputs travel to the GPU in chunks through pinned buffers.  batch_size > 0
     is the chunk size (default 65,536 jets) and never changes the values.  Raises ValueError, worded as scipy words it, when a
-    Hungarian cost holds NaN or -inf."""
-    if include_emd:
+    Hungarian cost holds NaN or -inf.  include_emd="native": the same 21 keys, then EMD_RELATIVE as the 22nd (N <= 191), computed in
+    the same chunks; raises ValueError when a jet's EMD has a status bit (lgn/emd.py)."""
+    native_emd = isinstance(include_emd, str) and include_emd == "native"
+    if include_emd and not native_emd:
         raise NotImplementedError("include_emd=True: the EMD score needs the energyflow package and is not implemented natively; "
                                   "call anomaly_scores(..., include_emd=False)")
     xs = (recons, target, recons_normalized, target_normalized)
@@ -138,6 +155,10 @@ def anomaly_scores(recons: torch.Tensor, target: torch.Tensor, recons_normalized
     chunk = max(1, min(chunk, B))
     scores = torch.empty(B, 21, device=dev, dtype=torch.float64)
     status = torch.empty(B, device=dev, dtype=torch.int32)
+    if native_emd:
+        if n > _emd.NMAX:
+            raise ValueError(f"the EMD score supports 1 <= N <= {_emd.NMAX} particles per jet; got N = {n}")
+        emd = torch.empty(B, device=dev, dtype=torch.float64)
     on_host = [not x.is_cuda for x in xs]
     pinned = [torch.empty(chunk, n, 4, dtype=torch.float64).pin_memory() if h else None for h in on_host]
     staged = [torch.empty(chunk, n, 4, device=dev, dtype=torch.float64) if h else None for h in on_host]
@@ -157,14 +178,22 @@ def anomaly_scores(recons: torch.Tensor, target: torch.Tensor, recons_normalized
         copied = torch.cuda.Event()
         copied.record()
         _launch(part, ALL, scores[b0:b0 + m], status[b0:b0 + m])
+        if native_emd:
+            e, est = _emd.emd_relative_tensor(part[0], part[1], return_status=True)
+            emd[b0:b0 + m] = e
+            status[b0:b0 + m] |= est << EMD_STATUS_SHIFT
     scores_h = scores.cpu().numpy()
     _raise_for_status(status.cpu().numpy())
-    return {k: np.ascontiguousarray(scores_h[:, i]) for i, k in enumerate(SCORE_KEYS)}
+    out = {k: np.ascontiguousarray(scores_h[:, i]) for i, k in enumerate(SCORE_KEYS)}
+    if native_emd:
+        out[EMD_RELATIVE] = emd.cpu().numpy()
+    return out
 
 
 def anomaly_scores_sig_bkg(sig_recons: torch.Tensor, sig_target: torch.Tensor, sig_recons_normalized: torch.Tensor,
                            sig_target_normalized: torch.Tensor, bkg_recons: torch.Tensor, bkg_target: torch.Tensor,
-                           bkg_recons_normalized: torch.Tensor, bkg_target_normalized: torch.Tensor, include_emd: bool = False,
+                           bkg_recons_normalized: torch.Tensor, bkg_target_normalized: torch.Tensor,
+                           include_emd: Union[bool, str] = False,
                            batch_size: int = -1):
     """anomaly_scores_sig_bkg() of the reference: (scores, true_labels, sig_scores, bkg_scores) with the signal first, labels +1
     for signal and -1 for background."""

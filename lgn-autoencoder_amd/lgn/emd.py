@@ -1,0 +1,121 @@
+"""
+The energy mover's distance on the GPU, exactly: a batched optimal-transport solver (csrc/emd_wave.hpp, one wavefront per pair of
+events, successive shortest paths) and the reference's 22nd anomaly score on top of it (``emd_loss()`` of
+utils/jet_analysis/anomaly_detection.py, which calls ``energyflow.emd.emd`` per jet in a Python loop).
+
+    theta_ij = sqrt((y_i - y'_j)^2 + (phi_i - phi'_j)^2) / R
+    EMD      = min over f >= 0 of sum f_ij theta_ij + |sum pT - sum pT'|
+               with sum_j f_ij <= pT_i, sum_i f_ij <= pT'_j, sum f_ij = min(sum pT, sum pT')
+
+energyflow's defaults otherwise: beta = 1, norm = False, Euclidean ground distance, no periodic phi.  energyflow was not available when
+this was written: the definition above, from its documentation, is the specification (include/lgn_amd.h; tests/_emd_ref.py restates it
+as an LP).  What energyflow returns for two weightless events is not known; here that is a status bit and NaN.
+
+There is no CPU fallback.  The EMD *training* losses (--loss-choice emd / hybrid: jetnet's differentiable QP) are a different
+algorithm and stay refused.
+"""
+from typing import Optional
+
+import torch
+
+from . import _native as N
+
+NMAX = N.EMD_NMAX
+INVALID, EMPTY, ITER, INFEASIBLE = N.EMD_INVALID, N.EMD_EMPTY, N.EMD_ITER, N.EMD_INFEASIBLE
+
+
+def status_message(s: int) -> str:
+    if s & INVALID:
+        return "events hold NaN, infinity or a negative weight"
+    if s & EMPTY:
+        return "both events are weightless"
+    if s & ITER:
+        return "the cap of the solver's augmentations was hit"
+    return "the weights left over exceed the rounding of the two sums"
+
+
+def _workspace(B: int, n: int, dev) -> Optional[torch.Tensor]:
+    nbytes = N.lib().lgn_emd_workspace_bytes(B, n)
+    if nbytes < 0:
+        raise ValueError(N.last_error())
+    return torch.empty(nbytes, device=dev, dtype=torch.uint8) if nbytes else None
+
+
+def flow_in_lds(n: int) -> bool:
+    """Plan-time query: does the flow matrix of events of n particles live in LDS (else in a workspace in device memory)?"""
+    nbytes = N.lib().lgn_emd_lds_bytes(n)
+    if nbytes < 0:
+        raise ValueError(N.last_error())
+    return nbytes >= 8 * (n + 1) * (n + 1)
+
+
+def emd(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_flow: bool = False, return_duals: bool = False,
+        return_status: bool = False):
+    """EMD of events of (pT, y, phi) particles: ev0 (B, n, 3) against ev1 (B, m, 3) device tensors (or one (n, 3) against one (m, 3)),
+    n != m allowed, 1 <= n, m <= 191.  Returns the (B,) fp64 device tensor of distances (a 0-dim tensor for one pair); with
+    return_flow also the optimal flow (B, n + 1, m + 1), with return_duals also the potentials (B, n + 1) and (B, m + 1) -- row n and
+    column m are the fictitious particle that carries the weight difference.  Raises ValueError when a pair has a status bit (NaN,
+    infinity or a negative weight; both events weightless; ...); return_status=True returns the (B,) int32 status last instead (the
+    distance of such a pair is NaN) and does not wait for the device."""
+    single = ev0.dim() == 2
+    a, b = (ev0.unsqueeze(0), ev1.unsqueeze(0)) if single else (ev0, ev1)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"emd takes events (B, n, 3) and (B, m, 3) of (pT, y, phi); got {tuple(ev0.shape)} and {tuple(ev1.shape)}")
+    B, n, m = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
+    if not (1 <= n <= NMAX and 1 <= m <= NMAX):
+        raise ValueError(f"emd supports 1 <= n, m <= {NMAX} particles per event; got n = {n}, m = {m}")
+    if not (R > 0 and R < float("inf")):
+        raise ValueError(f"emd needs a finite R > 0; got {R}")
+    a, b = N.f64(a.to(torch.float64)), N.f64(b.to(torch.float64))
+    dev = a.device
+    out = torch.empty(B, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    flow = torch.empty(B, n + 1, m + 1, device=dev, dtype=torch.float64) if return_flow else None
+    d0 = torch.empty(B, n + 1, device=dev, dtype=torch.float64) if return_duals else None
+    d1 = torch.empty(B, m + 1, device=dev, dtype=torch.float64) if return_duals else None
+    if B > 0:
+        work = _workspace(B, max(n, m), dev)
+        rc = N.lib().lgn_emd_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(flow), N.ptr(d0), N.ptr(d1), N.ptr(status),
+                                 N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_f64")
+    if not return_status:
+        st = status.cpu().numpy()
+        bad = st.nonzero()[0]
+        if len(bad):
+            raise ValueError(f"emd: {status_message(int(st[bad[0]]))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
+    res = [out] + ([flow] if return_flow else []) + ([d0, d1] if return_duals else [])
+    if single:
+        res = [x[0] for x in res]
+    if return_status:
+        res.append(status[0] if single else status)
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def emd_relative_tensor(recons: torch.Tensor, target: torch.Tensor, return_status: bool = False):
+    """The reference's score "emd (relative coordinates)" of (B, N, 4) Cartesian device tensors as a (B,) fp64 device tensor, with no
+    host sync (chain it after NativeEvalStep.run()): each jet is staged into its relative-polar frame (pT / (jet pT + 1e-16), eta - jet
+    eta, wrapped phi - jet phi) exactly as the other 21 scores stage it, then energyflow.emd.emd(target_rel, recons_rel).  A jet with
+    a status bit (see emd()) gets NaN; return_status=True also returns the (B,) int32 status."""
+    if recons.dim() != 3 or recons.shape[-1] != 4 or recons.shape != target.shape:
+        raise ValueError(f"emd_relative_tensor takes two (B, N, 4) Cartesian tensors; got {tuple(recons.shape)} and {tuple(target.shape)}")
+    B, n = int(recons.shape[0]), int(recons.shape[1])
+    if not 1 <= n <= NMAX:
+        raise ValueError(f"the EMD score supports 1 <= N <= {NMAX} particles per jet; got N = {n}")
+    r, t = N.f64(recons.to(torch.float64)), N.f64(target.to(torch.float64))
+    dev = r.device
+    out = torch.empty(B, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    if B > 0:
+        work = _workspace(B, n, dev)
+        rc = N.lib().lgn_emd_relative_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(status), N.ptr(work),
+                                          work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_relative_f64")
+    return (out, status) if return_status else out
+
+
+def max_augmentations(reset: bool = True) -> int:
+    """Debug counter: the largest number of augmentations any pair needed since the last reset (waits for the device)."""
+    import ctypes
+    v = ctypes.c_int(0)
+    N._check(N.lib().lgn_emd_debug_max_augmentations(ctypes.byref(v), int(reset)), "lgn_emd_debug_max_augmentations")
+    return v.value

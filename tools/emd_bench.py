@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""The native EMD score (lgn.emd.emd_relative_tensor, one launch) in jets/s at the shapes of tools/anomaly_bench.py: N = 30 (65,536
+jets, 20 real particles: the flow in LDS) and N = 150 (8,192 jets, 100 real: the flow in a workspace), timed with stream events; also
+the largest number of augmentations any jet needed (the solver's cap is 16 per node).  Each case runs in a child process of its own
+under `timeout -k 10`; the first failure ends the run.  One JSON line per case, printed and appended to profiles/emd_bench.jsonl.
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "lgn-autoencoder_amd"))
+
+CASES = {"n30": (65536, 30, 20), "n150": (8192, 150, 100)}
+OUT = os.path.join(ROOT, "profiles", "emd_bench.jsonl")
+
+
+def one(name, steps, warmup):
+    import torch
+    from lgn import emd as M
+    B, n, real = CASES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    t = torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    t[..., 0] = t[..., 1:].norm(dim=-1) + 0.1
+    t[:, real:] = 0.0
+    r = t + 0.2 * torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    M.max_augmentations(reset=True)
+    for _ in range(warmup):
+        out, st = M.emd_relative_tensor(r, t, return_status=True)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        out, st = M.emd_relative_tensor(r, t, return_status=True)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / steps
+    res = {"case": name, "kind": "emd (relative coordinates)", "B": B, "N": n, "real_particles": real, "flow_in_lds": M.flow_in_lds(n),
+           "ms": ms, "jets_per_s": B / (ms * 1e-3), "max_augmentations": M.max_augmentations(), "aug_cap": 16 * (2 * n + 2),
+           "status_nonzero": int((st != 0).sum().item()), "mean_emd": float(out.mean().item())}
+    line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()})
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "a") as f:
+        f.write(line + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--timeout", type=int, default=180, help="seconds per case")
+    ap.add_argument("--one", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.one:
+        return one(args.one, args.steps, args.warmup)
+    for name in args.cases.split(","):
+        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--one", name,
+               "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        rc = subprocess.run(cmd).returncode
+        if rc != 0:
+            print(json.dumps({"case": name, "error": f"exit status {rc}"}), flush=True)
+            sys.exit(rc)
+
+
+if __name__ == "__main__":
+    main()
