@@ -626,6 +626,91 @@ int lgn_histogram_f64(const double* x, long long rows, int ld, int cols, const d
                       const uint8_t* keep /*nullable*/, const double* weights /*nullable*/, long long* counts, double* wcounts,
                       int max_bins, void* stream);
 
+/* ---- reconstruction statistics: get_stats() and find_fwhm() of utils/jet_analysis/utils.py, the histogram edges plot_p draws over,
+ * and the jet images of utils/jet_analysis/jet_images.py (csrc/stats.hip).  This block only ADDS functions: no struct and no
+ * signature changed, so LGN_AMD_ABI_VERSION stays 19 (the rule above is about changes to what a caller already links against).
+ *
+ * lgn_column_stats_f64: for every column c < cols <= ld of the device matrix x [rows][ld], over the rows the mask keeps -- those
+ * with (mask[r] != 0) == (mask_keep != 0); mask NULL keeps all.  With a_0 <= .. <= a_{n-1} the sorted kept values, stats[c][LGN_STAT_*]:
+ *   quantiles q in {0.1, 0.25, 0.5, 0.75, 0.9} as np.quantile(a, q) (method "linear"): idx = (n - 1) q in fp64, lo = floor(idx),
+ *       g = idx - lo, numpy's _lerp of a[lo], a[min(lo + 1, n - 1)]: a + (b - a) g, or b - (b - a) (1 - g) where g >= 0.5
+ *   MEDIAN as np.median (the middle element or the mean of the two middle ones), FIRST_QUARTILE, THIRD_QUARTILE, Q10, Q90,
+ *   IQR = q.75 - q.25, IDR = q.9 - q.1, MIN, MAX, ABS_MIN = min |a|,
+ *   MAD = scipy.stats.median_abs_deviation(a): the median of |a - median| (selected on the sorted column, no second sort)
+ *   MEAN, STD_DEV (np.std, ddof 0), SKEW = m3 / m2^1.5 and KURTOSIS = m4 / m2^2 - 3 (scipy.stats.skew / kurtosis defaults: biased,
+ *       Fisher) from the two-pass central moments about MEAN, ABS_MEAN = mean |a|
+ *   ABS_MEAN_WITHIN_IQR = mean of |a| over the values with |a| < IQR (this call's own IQR), 1e32 when there is none; _IDR likewise
+ *   FWHM is written as NaN: it is lgn_hist_fwhm_f64's, whose slot it keeps so that the positions are the reference's dict order.
+ * edges[c][:] = np.linspace(median - alpha IQR, median + alpha IQR, num_edges): start + i step with step = (stop - start) /
+ * (num_edges - 1), rounded one operation at a time, the last element stop itself.  kept[c] = n.  status[c]: LGN_STATS_EMPTY (n = 0)
+ * or LGN_STATS_NONFINITE (a kept value is NaN or +-inf): the column's statistics and edges are then NaN, the other columns
+ * unaffected.  A constant column is no error: IQR = 0, m2 = 0, SKEW and KURTOSIS the NaN of 0 / 0.  +-0.0 sort in either order.
+ * Every sum is taken in one fixed order that depends on the multiset of kept values alone: the same bits on every run, for every
+ * grid, row order and column count; no floating-point atomics.  Nothing is allocated, nothing waits on the host: capturable.
+ * Refused before any launch (negative return): null pointers (x may be NULL with rows = 0, edges with num_edges = 0), rows < 0 or
+ * >= 2^31, cols outside 1 .. LGN_STATS_MAX_COLS, ld < cols, num_edges = 1 or > LGN_HIST_MAX_EDGES, alpha not finite, a workspace
+ * shorter than lgn_column_stats_workspace_bytes(rows, cols) or not 8-byte aligned.  rows = 0: every column EMPTY. */
+#define LGN_STATS_TILE 2048
+#define LGN_STATS_MAX_COLS 16
+#define LGN_STATS_EMPTY 1
+#define LGN_STATS_NONFINITE 2
+#define LGN_STAT_MEDIAN 0
+#define LGN_STAT_IQR 1
+#define LGN_STAT_FIRST_QUARTILE 2
+#define LGN_STAT_THIRD_QUARTILE 3
+#define LGN_STAT_IDR 4
+#define LGN_STAT_MAD 5
+#define LGN_STAT_MEAN 6
+#define LGN_STAT_MAX 7
+#define LGN_STAT_MIN 8
+#define LGN_STAT_ABS_MIN 9
+#define LGN_STAT_STD_DEV 10
+#define LGN_STAT_SKEW 11
+#define LGN_STAT_KURTOSIS 12
+#define LGN_STAT_FWHM 13
+#define LGN_STAT_ABS_MEAN 14
+#define LGN_STAT_ABS_MEAN_WITHIN_IQR 15
+#define LGN_STAT_ABS_MEAN_WITHIN_IDR 16
+#define LGN_STAT_Q10 17
+#define LGN_STAT_Q90 18
+#define LGN_STATS_COUNT 19
+long long lgn_column_stats_workspace_bytes(long long rows, int cols);
+int lgn_column_stats_f64(const double* x, long long rows, int ld, int cols, const uint8_t* mask /*nullable*/, int mask_keep,
+                         double alpha, int num_edges, double* stats /* [cols][LGN_STATS_COUNT] */,
+                         double* edges /* [cols][num_edges], nullable with num_edges = 0 */, long long* kept /* [cols] */,
+                         int* status /* [cols] */, void* workspace, long long workspace_bytes, void* stream);
+
+/* find_fwhm (utils.py:352-362) on the output layout of lgn_histogram_f64: i = argmax(counts) (the first maximum), h = counts[i] / 2,
+ * j = argmin |counts - h| (the first minimum), fwhm[c] = 2 |edges[i] - edges[j]|: integer logic and one subtraction, bitwise the
+ * reference's given the same counts and edges.  n_edges [cols] HOST ints as lgn_histogram_f64 takes them; 1 <= cols <=
+ * LGN_HIST_MAX_COLS.  get_stats is then lgn_column_stats_f64 -> lgn_histogram_f64 -> lgn_hist_fwhm_f64 with no host round trip. */
+int lgn_hist_fwhm_f64(const long long* counts, int max_bins, const double* edges, int max_edges, const int* n_edges /*host*/, int cols,
+                      double* fwhm /* [cols] */, void* stream);
+
+/* pixelate (jet_images.py:193-226) of every jet, the first first_n images (get_n_jet_images) and the mean image over all B jets
+ * (get_average_jet_image).  jets [B][N][3] (pt, eta, phi); bins = np.linspace(-maxR, maxR, npix + 1); a particle goes to the pixel
+ * [phi_bin][eta_bin] with bins[i] <= v < bins[i + 1] (np.digitize - 1: a value equal to maxR, outside the range or NaN goes nowhere,
+ * unlike np.histogram), decided by comparing with the edge values themselves; image[phi_bin][eta_bin] += pt in particle order.
+ *   mode 0  jets are relative already (abs_coord = False)
+ *   mode 1  each jet is first taken into its own frame (get_jet_rel + normalize)
+ *   mode 2  into the frame of frame_jets [B][N][3] (the *_same_norm pair: once target with itself, once recons with the target)
+ * The frame is that of the summed massless particles: Px = sum pt cos(phi), Py = sum pt sin(phi), Pz = sum pt sinh(eta) in particle
+ * order, Pt = hypot(Px, Py), Eta = asinh(Pz / Pt), Phi = atan2(Py, Px); then pt / Pt, eta - Eta, ((phi - Phi + pi) mod 2 pi) - pi with
+ * Python's mod.  normalize's escape is kept: when np.isclose(Pt, 0) (|Pt| <= 1e-8) holds for EVERY jet of the call nothing is
+ * normalised (a device-side reduction, no host read).  The reference does this sum with awkward / coffea; the formula written here
+ * is the specification of modes 1 and 2, and no test value of theirs was produced by those packages.
+ * images [min(first_n, B)][npix][npix] (nullable with first_n = 0), average [npix][npix].  One wavefront per jet, image in LDS; the
+ * average is a fixed-order two-stage sum (LGN_JET_IMAGE_PARTS partial images in the workspace, added in order): no floating-point
+ * atomics, the same bits on every run.  Refused: null pointers, B < 1, N outside 1 .. LGN_ANOMALY_NMAX, npix outside
+ * 1 .. LGN_JET_IMAGE_MAX_NPIX, maxR not finite and positive, mode outside 0 .. 2, first_n < 0, a workspace shorter than
+ * lgn_jet_images_workspace_bytes(B, npix) or not 8-byte aligned. */
+#define LGN_JET_IMAGE_MAX_NPIX 64
+#define LGN_JET_IMAGE_PARTS 512
+long long lgn_jet_images_workspace_bytes(int B, int npix);
+int lgn_jet_images_f64(const double* jets, const double* frame_jets /*nullable*/, int B, int N, int mode, int npix, double maxR,
+                       int first_n, double* images /*nullable*/, double* average, void* workspace, long long workspace_bytes,
+                       void* stream);
+
 /* ---- the assignment loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the device
  * code of the whole-step calls' loss stage -- lgn_loss_desc above -- without the output mix): x, y [B][N][4] real 4-vectors ->
  * loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */

@@ -213,6 +213,12 @@ _SIGNATURES.update({
     # (recons, target, B, N, emd, status, work, work_bytes, stream)
     "lgn_emd_relative_f64": [_vp, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp],
     "lgn_emd_debug_max_augmentations": [_ip, _i],
+    # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
+    "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],
+    # (counts, max_bins, edges, max_edges, n_edges [host], cols, fwhm, stream)
+    "lgn_hist_fwhm_f64": [_vp, _i, _vp, _i, _ip, _i, _vp, _vp],
+    # (jets, frame_jets, B, N, mode, npix, maxR, first_n, images, average, workspace, workspace_bytes, stream)
+    "lgn_jet_images_f64": [_vp, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _ll, _vp],
 })
 EPOCH_MAX_COLLECT, EPOCH_BAD_INDEX = 4, 1    # LGN_EPOCH_MAX_COLLECT, LGN_EPOCH_BAD_INDEX of include/lgn_amd.h
 # LGN_NORM_* of include/lgn_amd.h
@@ -232,12 +238,20 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_roc_workspace_bytes": [_ll, _i],
     "lgn_emd_workspace_bytes": [_i, _i],
     "lgn_emd_lds_bytes": [_i],
+    "lgn_column_stats_workspace_bytes": [_ll, _i],
+    "lgn_jet_images_workspace_bytes": [_i, _i],
 }
 ROC_TILE, ROC_MAX_COLS = 2048, 65535        # LGN_ROC_TILE, LGN_ROC_MAX_COLS of include/lgn_amd.h
 ROC_NONFINITE, ROC_SINGLE_CLASS, ROC_BAD_LABEL, ROC_NAN = 1, 2, 4, 8    # LGN_ROC_* status bits
 EMD_NMAX = 191                              # LGN_EMD_NMAX of include/lgn_amd.h
 EMD_INVALID, EMD_EMPTY, EMD_ITER, EMD_INFEASIBLE = 1, 2, 4, 8    # LGN_EMD_* status bits
 HIST_MAX_EDGES, HIST_MAX_COLS = 1025, 16    # LGN_HIST_MAX_EDGES, LGN_HIST_MAX_COLS of include/lgn_amd.h
+# LGN_STATS_*, LGN_STAT_* (the positions in a column's statistics, the reference's dict order) and LGN_JET_IMAGE_* of include/lgn_amd.h
+STATS_TILE, STATS_MAX_COLS, STATS_EMPTY, STATS_NONFINITE = 2048, 16, 1, 2
+STAT_NAMES = ("median", "IQR", "first_quartile", "third_quartile", "IDR", "MAD", "mean", "max", "min", "abs_min", "std_dev", "skew",
+              "kurtosis", "FWHM", "abs_mean", "abs_mean_within_iqr", "abs_mean_within_idr", "q10", "q90")
+STATS_COUNT = len(STAT_NAMES)
+JET_IMAGE_MAX_NPIX, JET_IMAGE_PARTS = 64, 512
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
 EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)
 

@@ -1,8 +1,9 @@
 """
 Reconstruction analysis on the GPU: the numeric half of the reference's ``plot_p`` (utils/jet_analysis/utils.py,
 particle_recon_err.py, jet_recon_err.py) -- particle features in polar and relative-polar coordinates, jet features, the matched
-relative errors of ``get_rel_err_find_match`` (two scipy-exact assignments per jet), the jet relative errors and the histograms the
-plots are drawn from.  The plotting itself (matplotlib, ``get_stats``) stays with the reference.
+relative errors of ``get_rel_err_find_match`` (two scipy-exact assignments per jet), the jet relative errors, the histograms the
+plots are drawn from, ``get_stats`` with the ``err_dict`` JSON the plots dump, the median +- 4 IQR histogram ranges and the jet
+images (csrc/stats.hip).  Only the drawing itself (matplotlib) stays with the reference.
 
 One HIP kernel launch per chunk of jets (csrc/analysis.hip, C ABI ``lgn_recon_analysis_f64``) and one clear + one count launch per
 histogram call (``lgn_histogram_f64``).  There is no CPU fallback.  Deliberate differences from the reference: the
@@ -186,8 +187,8 @@ def particle_histograms(analysis: Dict[str, torch.Tensor], ranges: Dict[str, Seq
                                           (get_p_cartesian / get_p_polar): -> [target counts, recons counts]
       "rel_err_cartesian" / "_polar" / "_polarrel"   the matched relative errors of the non-padded rows
       "padded_cartesian" / "_polar" / "_polarrel"    the reconstructed features of the padded rows
-    Each count entry is a list of three int64 numpy arrays (len(edges) - 1 each).  Choosing the edges from median +- k IQR stays
-    with the caller (it needs a sort).  The keep masks are element-wise torch expressions on the device; the counting is native."""
+    Each count entry is a list of three int64 numpy arrays (len(edges) - 1 each).  recon_stats() chooses the edges from median +- 4 IQR
+    on the device.  The keep masks are element-wise torch expressions on the device; the counting is native."""
     t, r = analysis["target"].reshape(-1, 4), analysis["recons"].reshape(-1, 4)
 
     def count(x, edges, keep):
@@ -288,3 +289,244 @@ def get_rel_err_find_match(p_target_cartesian, p_recons_cartesian, p_target_pola
         raise ValueError(f"{what} (jet {int(bad[0])}, {len(bad)} jet(s) in all)")
     dt = p_target_cartesian.dtype
     return tuple(rel[f].reshape(-1, 3).cpu().to(dt) for f in range(3))
+
+
+# ---- reconstruction statistics: get_stats, the err_dict JSON of plot_p, jet images (csrc/stats.hip) ---------------------------------
+
+STAT_NAMES = N.STAT_NAMES
+REFERENCE_STAT_KEYS = STAT_NAMES[:17]       # the keys of the reference's get_stats dict, in its order
+NUM_BINS = 81                               # utils/jet_analysis/utils.py
+_NONE_IF_NAN = ("mean", "std_dev", "skew", "kurtosis")
+_NONE_IF_EMPTY = ("max", "min", "abs_min")
+
+
+def _need_cuda(*ts):
+    for t in ts:
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise RuntimeError("liblgn_amd.so operates on GPU tensors only (got a CPU tensor); there is no CPU fallback")
+
+
+def _as_mask(mask, rows, dev):
+    if mask is None:
+        return None
+    _need_cuda(mask)
+    mask = (mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)).contiguous()
+    if mask.shape != (rows,):
+        raise ValueError(f"mask must have shape ({rows},); got {tuple(mask.shape)}")
+    return mask
+
+
+def _matrix(x):
+    """(rows, cols) fp64 device view with adjacent columns, and its leading dimension."""
+    _need_cuda(x)
+    if x.dim() == 1:
+        x = x.unsqueeze(-1)
+    if x.dim() != 2:
+        raise ValueError(f"a (rows, cols) matrix is needed; got {tuple(x.shape)}")
+    if x.dtype != torch.float64:
+        x = x.detach().to(torch.float64)
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    if (cols > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < cols):
+        x = x.contiguous()
+    return x, (int(x.stride(0)) if rows > 1 else cols)
+
+
+def column_stats(x: torch.Tensor, mask: Optional[torch.Tensor] = None, mask_keep: bool = True, alpha: float = 4.0,
+                 num_edges: int = 0) -> Dict[str, torch.Tensor]:
+    """lgn_column_stats_f64 (include/lgn_amd.h) on the columns of the device matrix x (rows, cols <= 16), over the rows with
+    bool(mask[r]) == mask_keep: {"stats": (cols, len(STAT_NAMES)) fp64, "edges": (cols, num_edges) fp64 =
+    linspace(median - alpha IQR, median + alpha IQR, num_edges), "kept": (cols,) int64, "status": (cols,) int32}, all on the device;
+    no host sync.  x may be a strided view with adjacent columns, as histogram() takes it."""
+    x, ld = _matrix(x)
+    dev = x.device
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    mask = _as_mask(mask, rows, dev)
+    lib = N.lib()
+    nbytes = lib.lgn_column_stats_workspace_bytes(rows, cols)
+    if nbytes < 0:
+        raise ValueError(N.last_error())
+    out = {"stats": torch.empty(cols, N.STATS_COUNT, device=dev, dtype=torch.float64),
+           "edges": torch.empty(cols, int(num_edges), device=dev, dtype=torch.float64),
+           "kept": torch.empty(cols, device=dev, dtype=torch.int64), "status": torch.empty(cols, device=dev, dtype=torch.int32)}
+    work = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    rc = lib.lgn_column_stats_f64(x.data_ptr() if rows else None, rows, ld, cols, N.ptr(mask), int(bool(mask_keep)), float(alpha),
+                                  int(num_edges), N.ptr(out["stats"]), N.ptr(out["edges"]) if num_edges else None, N.ptr(out["kept"]),
+                                  N.ptr(out["status"]), N.ptr(work), nbytes, N.stream_ptr())
+    if rc < 0:
+        raise ValueError(N.last_error())
+    N._check(rc, "lgn_column_stats_f64")
+    return out
+
+
+def hist_fwhm(counts: torch.Tensor, edges: PackedEdges) -> torch.Tensor:
+    """find_fwhm of the reference on what histogram() returned for these edges: (cols,) fp64 on the device."""
+    _need_cuda(counts)
+    if counts.dtype != torch.int64 or counts.dim() != 2:
+        raise ValueError("hist_fwhm takes the (cols, max_bins) int64 counts of histogram()")
+    cols = int(counts.shape[0])
+    out = torch.empty(cols, device=counts.device, dtype=torch.float64)
+    n_edges = (C.c_int * cols)(*edges.n_edges)
+    rc = N.lib().lgn_hist_fwhm_f64(N.ptr(counts), int(counts.shape[1]), N.ptr(edges.device), int(edges.device.shape[1]), n_edges, cols,
+                                   N.ptr(out), N.stream_ptr())
+    if rc < 0:
+        raise ValueError(N.last_error())
+    N._check(rc, "lgn_hist_fwhm_f64")
+    return out
+
+
+def stats_dict(row, fwhm: float, kept: int) -> dict:
+    """One column's statistics (a sequence of len(STAT_NAMES) numbers) as the reference's get_stats dict of Python floats: its keys in
+    its order, None where it gives None (a NaN mean, std_dev, skew or kurtosis; max, min and abs_min of an empty column)."""
+    d = {}
+    for i, name in enumerate(REFERENCE_STAT_KEYS):
+        v = float(fwhm) if name == "FWHM" else float(row[i])
+        if (name in _NONE_IF_NAN and v != v) or (name in _NONE_IF_EMPTY and kept == 0):
+            v = None
+        d[name] = v
+    return d
+
+
+def get_stats(res: torch.Tensor, bins) -> dict:
+    """get_stats(res, bins) of utils/jet_analysis/utils.py for a 1-d device tensor: column statistics, np.histogram(res, bins) and
+    find_fwhm in three native calls, one host copy at the end.  bins: a 1-d array of edges, on the device or the host."""
+    _need_cuda(res)
+    res = res.reshape(-1)
+    cs = column_stats(res)
+    if isinstance(bins, torch.Tensor) and bins.is_cuda:
+        b = bins.detach().to(torch.float64).reshape(1, -1).contiguous()
+        bins = PackedEdges(b, [b.shape[1]])
+    else:
+        bins = pack_edges(bins, 1)
+    fw = hist_fwhm(histogram(res, bins), bins)
+    flat = torch.cat((cs["stats"].reshape(-1), fw, cs["kept"].to(torch.float64))).cpu().numpy()
+    return stats_dict(flat[:N.STATS_COUNT], flat[N.STATS_COUNT], int(flat[N.STATS_COUNT + 1]))
+
+
+def _linspace(start: torch.Tensor, stop: torch.Tensor, num: int) -> torch.Tensor:
+    """np.linspace(start[c], stop[c], num) per column on the device, rounded as numpy rounds it: arange * step + start, last = stop."""
+    step = (stop - start) / (num - 1)
+    e = torch.arange(num, device=start.device, dtype=torch.float64).unsqueeze(0) * step.unsqueeze(1)
+    e = e + start.unsqueeze(1)
+    e[:, -1] = stop
+    return e
+
+
+def recon_stats(analysis: Dict[str, torch.Tensor], abs_coord: bool = True, custom_ranges=None) -> dict:
+    """The err_dict JSON of plot_particle_recon_err and plot_jet_recon_err from what recon_analysis returned, and the histograms the
+    two draw: {"particle": {frame: {"rel_err": [3 dicts], "pad_recons": [3 dicts or none]}}, "jet": {"cartesian": [<= 4 dicts],
+    "polar": [..]}, "hist": {name: {"counts": (cols, 80) int64, "edges": (cols, 81) fp64}}} with the hist entries device tensors over
+    bins_suitable = linspace(median - 4 IQR, median + 4 IQR, 81).  Every statistic, edge and count is computed on the device; the one
+    synchronisation is the copy of the statistics at the end.
+    custom_ranges: None is custom_particle_recons_ranges=False.  Otherwise the `ranges` argument of plot_particle_recon_err -- per
+    frame (real, padded), each three host arrays of edges -- which the reference then uses both as get_stats' FWHM bins and as the
+    bins it draws: the six particle entries of "hist" are then counted over those edges ("edges": (3, longest) zero padded, and
+    "n_edges": their lengths).  The jet plot's ranges are never custom here (custom_jet_recons_ranges=False).
+    The reference's plot_p also takes a `cutoff`; neither error plot reads it (it only selects the particles of the feature
+    histograms, which particle_histograms() counts), so this function has no such argument."""
+    _need_cuda(analysis["rel_err"])
+    dev = analysis["rel_err"].device
+    pad = analysis["is_padded"].reshape(-1)
+    r = analysis["recons"].reshape(-1, 4)
+    feats = {"cartesian": r[:, 1:], "polar": analysis["part_polar"][1].reshape(-1, 3),
+             "polarrel": (analysis["part_polarrel"] if abs_coord else analysis["part_polar"])[1].reshape(-1, 3)}
+    jobs = []                                   # (group, x, mask, mask_keep, column statistics)
+    for f, frame in enumerate(FRAMES):
+        x = analysis["rel_err"][f].reshape(-1, 3)
+        jobs.append((f"rel_err_{frame}", x, pad, False, column_stats(x, pad, False, 4.0, NUM_BINS)))
+        jobs.append((f"padded_{frame}", feats[frame], pad, True, column_stats(feats[frame], pad, True, 4.0, NUM_BINS)))
+    for s, system in enumerate(("cartesian", "polar")):
+        x, keep = analysis["jet_rel_err"][s], analysis["jet_keep"][s]
+        jobs.append((f"jet_{system}", x, keep, True, column_stats(x, keep, True, 4.0, NUM_BINS)))
+    by_name = {j[0]: j for j in jobs}
+
+    def min_max_bins(name):                     # get_min_max + np.linspace with its default of 50 points
+        st = by_name[name][4]["stats"]
+        med, iqr = st[:, 0], st[:, 1]
+        return _linspace(med - 4.0 * iqr, med + 4.0 * iqr, 50)
+
+    # particle_recon_err.py:355 -- get_bins takes the PADDED Cartesian range from the real Cartesian relative errors
+    # particle_recon_err.py:373 -- and the REAL relative-polar range from the padded relative-polar features
+    fwhm_source = {"rel_err_cartesian": "rel_err_cartesian", "padded_cartesian": "rel_err_cartesian", "rel_err_polar": "rel_err_polar",
+                   "padded_polar": "padded_polar", "rel_err_polarrel": "padded_polarrel", "padded_polarrel": "padded_polarrel"}
+    fw, hist = {}, {}
+    for name, x, mask, keep_flag, cs in jobs:
+        keep = mask if keep_flag else ~mask
+        if name.startswith("jet_"):
+            # jet_recon_err.py:168 -- get_bins indexes the first component's array: component k gets linspace(e, e, NUM_BINS) with e
+            # the k-th kept jet's first relative error
+            order = torch.cumsum(keep.to(torch.int64), 0)
+            idx = torch.searchsorted(order, torch.arange(1, 5, device=dev)).clamp_(max=max(int(x.shape[0]) - 1, 0))
+            e = x[idx, 0] if x.shape[0] else torch.full((4,), float("nan"), device=dev, dtype=torch.float64)
+            bins = _linspace(e, e, NUM_BINS)
+        elif custom_ranges is not None:
+            f = FRAMES.index(name.split("_")[-1])
+            bins = pack_edges([np.asarray(b) for b in custom_ranges[f][int(name.startswith("padded"))]])
+        else:
+            bins = PackedEdges(min_max_bins(fwhm_source[name]), [50] * 3)
+        if not isinstance(bins, PackedEdges):
+            bins = PackedEdges(bins.contiguous(), [bins.shape[1]] * bins.shape[0])
+        counts = histogram(x, bins, keep=keep)
+        fw[name] = hist_fwhm(counts, bins)
+        if custom_ranges is not None and not name.startswith("jet_"):
+            hist[name] = {"counts": counts, "edges": bins.device, "n_edges": bins.n_edges}
+        else:
+            own = PackedEdges(cs["edges"], [NUM_BINS] * int(cs["edges"].shape[0]))
+            hist[name] = {"counts": histogram(x, own, keep=keep), "edges": cs["edges"]}
+
+    flat = torch.cat([torch.cat((cs["stats"].reshape(-1), fw[name], cs["kept"].to(torch.float64))) for name, _, _, _, cs in jobs])
+    flat = flat.cpu().numpy()                   # the one synchronisation
+    dicts, o = {}, 0
+    for name, x, _, _, _ in jobs:
+        cols = int(x.shape[1])
+        st = flat[o:o + cols * N.STATS_COUNT].reshape(cols, N.STATS_COUNT)
+        f = flat[o + cols * N.STATS_COUNT:o + cols * (N.STATS_COUNT + 1)]
+        kept = flat[o + cols * (N.STATS_COUNT + 1):o + cols * (N.STATS_COUNT + 2)]
+        o += cols * (N.STATS_COUNT + 2)
+        dicts[name] = [stats_dict(st[c], f[c], int(kept[c])) for c in range(cols)], int(kept[0])
+    particle = {}
+    for frame in FRAMES:
+        padded, n_pad = dicts[f"padded_{frame}"]
+        particle[frame] = {"rel_err": dicts[f"rel_err_{frame}"][0], "pad_recons": padded if n_pad else []}   # len(p) == 0: continue
+    jet = {system: dicts[f"jet_{system}"][0][:min(4, dicts[f"jet_{system}"][1])] for system in ("cartesian", "polar")}
+    return {"particle": particle, "jet": jet, "hist": hist}
+
+
+def jet_image(jets: torch.Tensor, frame_jets: Optional[torch.Tensor] = None, mode: int = 0, npix: int = 24, maxR: float = 0.5,
+              first_n: int = 0):
+    """lgn_jet_images_f64 (include/lgn_amd.h): jets (B, N, 3) polar (pt, eta, phi) on the device -> (images (min(first_n, B), npix,
+    npix), average (npix, npix)) device tensors.  mode 0: relative already; 1: each jet in its own frame; 2: in frame_jets' frame."""
+    _need_cuda(jets, frame_jets)
+    if jets.dim() != 3 or jets.shape[-1] != 3 or (frame_jets is not None and frame_jets.shape != jets.shape):
+        raise ValueError(f"jet_image takes (B, N, 3) polar jets; got {tuple(jets.shape)}")
+    jets = N.f64(jets.detach().to(torch.float64))
+    frame_jets = None if frame_jets is None else N.f64(frame_jets.detach().to(torch.float64))
+    B, n = int(jets.shape[0]), int(jets.shape[1])
+    lib = N.lib()
+    nbytes = lib.lgn_jet_images_workspace_bytes(B, int(npix))
+    if nbytes < 0:
+        raise ValueError(N.last_error())
+    k = max(0, min(int(first_n), B))
+    images = torch.empty(k, npix, npix, device=jets.device, dtype=torch.float64)
+    average = torch.empty(npix, npix, device=jets.device, dtype=torch.float64)
+    work = torch.empty(nbytes // 8, device=jets.device, dtype=torch.int64)
+    rc = lib.lgn_jet_images_f64(N.ptr(jets), N.ptr(frame_jets), B, n, int(mode), int(npix), float(maxR), int(first_n),
+                                N.ptr(images) if k else None, N.ptr(average), N.ptr(work), nbytes, N.stream_ptr())
+    if rc < 0:
+        raise ValueError(N.last_error())
+    N._check(rc, "lgn_jet_images_f64")
+    return images, average
+
+
+def jet_images(p_target_polar: torch.Tensor, p_recons_polar: torch.Tensor, num_jet_images: int, jet_image_npix: int, abs_coord: bool,
+               same_norm: bool = True, maxR: float = 0.5):
+    """The four arrays plot_jet_image returns (target average, recons average, target images, recons images) as numpy arrays, with
+    its branch: same_norm and abs_coord normalise both sides by the target's frame, else each side by its own (abs_coord) or not at
+    all."""
+    if same_norm and abs_coord:
+        t_pix, t_avg = jet_image(p_target_polar, p_target_polar, 2, jet_image_npix, maxR, num_jet_images)
+        r_pix, r_avg = jet_image(p_recons_polar, p_target_polar, 2, jet_image_npix, maxR, num_jet_images)
+    else:
+        mode = 1 if abs_coord else 0
+        t_pix, t_avg = jet_image(p_target_polar, None, mode, jet_image_npix, maxR, num_jet_images)
+        r_pix, r_avg = jet_image(p_recons_polar, None, mode, jet_image_npix, maxR, num_jet_images)
+    return tuple(a.cpu().numpy() for a in (t_avg, r_avg, t_pix, r_pix))
