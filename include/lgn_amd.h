@@ -711,6 +711,44 @@ int lgn_jet_images_f64(const double* jets, const double* frame_jets /*nullable*/
                        int first_n, double* images /*nullable*/, double* average, void* workspace, long long workspace_bytes,
                        void* stream);
 
+/* ---- the equivariance test (lgn/models/autotest/lgn_tests.py:82-269 with rotate_rep of lgn/g_lib/rotations.py:7-51 and get_node_dev
+ * of autotest/utils.py:22-45; host side lgn/equivariance.py) -------------------------------------------------------------------------
+ * lgn_transform_jets_f64: the T transformed copies of a batch, out[t][b][n][a] = sum_b p4[b][m][b] R[t][b][a] with m = perm[b][n] (n
+ * without perm), each component the four-term sum ((p0 R0a + p1 R1a) + p2 R2a) + p3 R3a of the reference's einsum("...b,ba->...a").
+ *   p4 [B][N][4], R [T][4][4], out [T][B][N][4]; perm [B][N] int32, nullable; scalars [B][N][K] -> scalars_out [T][B][N][K] gathered by
+ *   the same permutation, no matrix (both NULL with K = 0).  Boosts, rotations, and with T = 1, R = identity the permuted batch of
+ *   permutation_invariance_test (then the gathered input, bit for bit).  Refused: null pointers, T outside 1 .. 65535, B or N < 1,
+ *   K < 0, B * N >= 2^31.
+ *
+ * lgn_rep_deviation_f64: every transformation, layer and irrep of one kind in one call.  Part p (one irrep of one GVec, parts <=
+ * LGN_EQUI_MAX_PARTS) is
+ *   a[p] [2][T * B][N][C][d]  features of the transformed input, jet t * B + b (plane 0 real, plane 1 imaginary: the entries of
+ *                             `nodes_all`)
+ *   b[p] [2][B][N][C][d]      features of the untransformed input
+ *   D[p] [T][2][d][d]         planar representation matrix of the irrep per transformation (lorentz_D), d in {1, 3, 4, 9}
+ * with N[p], C[p], d[p]; a, b, D, N, C, d are HOST arrays of `parts` entries read during the call, T and B are common.  Per row of d
+ * complex numbers b' = (b_r D_r + b_i D_i, -b_r D_i + b_i D_r) -- rotate_rep's convention, z times conj(D) -- is formed on the fly (D[t]
+ * in LDS, b' never stored), and over the whole (2, B, N, C, d) block of each (p, t)
+ *   stats[p][t] = { sum(a - b'), sum(b'), max|a - b'|, max|b'|, max|(a - b') / (b' + 1e-16)| }
+ * from which the host forms get_node_dev's metrics: mean |s0 / n / (s1 / n + eps)|, max s4, and the max-norm s2 / (s3 + eps).
+ * perm [B][N] int32 (nullable; then every part has the same N) reads b at particle perm[b][n]: with D the identity the permutation
+ * "equivariance" column.  An entry of perm outside [0, N) forms no address; its rows count as NaN (lgn_transform_jets_f64 writes NaN
+ * rows).  A workgroup reduces LGN_EQUI_TILE rows of one (p, t); its partial row goes to the workspace and a second kernel adds the
+ * partial rows in a fixed order: no floating-point atomics, the same bits on every run.  The maxima keep a NaN as torch.max does, so
+ * a NaN anywhere in a block makes its five numbers NaN.  Nothing is allocated and nothing waits on the host.  Refused: null pointers,
+ * parts outside 1 .. LGN_EQUI_MAX_PARTS, d outside {1, 3, 4, 9}, T outside 1 .. 65535, B, N or C < 1, B * N * C >= 2^31 / 9, a
+ * workspace shorter than lgn_rep_deviation_workspace_bytes says or not 8-byte aligned. */
+#define LGN_EQUI_TILE 256
+#define LGN_EQUI_MAX_PARTS 64
+int lgn_transform_jets_f64(const double* p4, const double* R, const int* perm /*nullable*/, const double* scalars /*nullable*/, int T,
+                           int B, int N, int K, double* out, double* scalars_out /*nullable*/, void* stream);
+long long lgn_rep_deviation_workspace_bytes(int parts, int T, int B, const int* N /*host*/, const int* C /*host*/,
+                                            const int* d /*host*/);
+int lgn_rep_deviation_f64(int parts, int T, int B, const double* const* a /*host*/, const double* const* b /*host*/,
+                          const double* const* D /*host*/, const int* N /*host*/, const int* C /*host*/, const int* d /*host*/,
+                          const int* perm /*nullable*/, double* stats /* [parts][T][5] */, void* workspace, long long workspace_bytes,
+                          void* stream);
+
 /* ---- the assignment loss on its own (module API: lgn/losses.py HungarianMSELoss, the drop-in of the reference's class; the device
  * code of the whole-step calls' loss stage -- lgn_loss_desc above -- without the output mix): x, y [B][N][4] real 4-vectors ->
  * loss_part [B], gx [B][N][4] = d (sum of loss_part) / d x. */

@@ -219,6 +219,10 @@ _SIGNATURES.update({
     "lgn_hist_fwhm_f64": [_vp, _i, _vp, _i, _ip, _i, _vp, _vp],
     # (jets, frame_jets, B, N, mode, npix, maxR, first_n, images, average, workspace, workspace_bytes, stream)
     "lgn_jet_images_f64": [_vp, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _ll, _vp],
+    # (p4, R, perm, scalars, T, B, N, K, out, scalars_out, stream)
+    "lgn_transform_jets_f64": [_vp] * 4 + [_i] * 4 + [_vp] * 3,
+    # (parts, T, B, a [host], b [host], D [host], N [host], C [host], d [host], perm, stats, workspace, workspace_bytes, stream)
+    "lgn_rep_deviation_f64": [_i] * 3 + [C.POINTER(_vp)] * 3 + [_ip] * 3 + [_vp] * 3 + [_ll, _vp],
 })
 EPOCH_MAX_COLLECT, EPOCH_BAD_INDEX = 4, 1    # LGN_EPOCH_MAX_COLLECT, LGN_EPOCH_BAD_INDEX of include/lgn_amd.h
 # LGN_NORM_* of include/lgn_amd.h
@@ -240,6 +244,7 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_emd_lds_bytes": [_i],
     "lgn_column_stats_workspace_bytes": [_ll, _i],
     "lgn_jet_images_workspace_bytes": [_i, _i],
+    "lgn_rep_deviation_workspace_bytes": [_i, _i, _i, _ip, _ip, _ip],
 }
 ROC_TILE, ROC_MAX_COLS = 2048, 65535        # LGN_ROC_TILE, LGN_ROC_MAX_COLS of include/lgn_amd.h
 ROC_NONFINITE, ROC_SINGLE_CLASS, ROC_BAD_LABEL, ROC_NAN = 1, 2, 4, 8    # LGN_ROC_* status bits
@@ -252,6 +257,7 @@ STAT_NAMES = ("median", "IQR", "first_quartile", "third_quartile", "IDR", "MAD",
               "kurtosis", "FWHM", "abs_mean", "abs_mean_within_iqr", "abs_mean_within_idr", "q10", "q90")
 STATS_COUNT = len(STAT_NAMES)
 JET_IMAGE_MAX_NPIX, JET_IMAGE_PARTS = 64, 512
+EQUI_TILE, EQUI_MAX_PARTS = 256, 64         # LGN_EQUI_TILE, LGN_EQUI_MAX_PARTS of include/lgn_amd.h
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
 EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)
 
