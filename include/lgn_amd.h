@@ -317,6 +317,9 @@ typedef struct lgn_loss_desc {
                                     gradients and image staging on the same wave -- the round-5 kernel) instead of the two-role kernel
                                     (eight waves: four carry the chain, four the weight gradients and the staging); below 8 129 rows: one chain
                                     wave per 16-row workgroup instead of a layer split over three; cross-check */
+#define LGN_NET_MLP_FULLTILE 2048 /* LGN_AMD_MLP_FULLTILE=1: the chain CGMLP kernels on 64-row workgroups compute the padded last tile of a hidden
+                                    layer (H = 36: neurons 32 .. 47, four of them real) as a full 16 x 16 x 4 tile, as before the four-neuron
+                                    block instructions (csrc/mlp_chain.hip: Items); cross-check */
 #define LGN_NET_SPLIT_TAIL 128   /* LGN_AMD_SPLIT_TAIL=1: the tail of a step (deferred reductions, radial finalisation, L1 + Adam) as the
                                     three separate launches instead of csrc/step_tail.hip's one (cross-check; bit-identical) */
 

@@ -101,6 +101,8 @@ struct Geo {
   static constexpr int NST = NST_;                          // threads that stage the weight images (256: a 64-row workgroup; 128: the 16-row kernels)
   static constexpr int NT = (H + 15) / 16, HP = 16 * NT;   // hidden tiles
   static constexpr int KSH = H / 4;                         // k-steps over a hidden layer's inputs
+  static constexpr int R = H - 16 * (NT - 1), NB = R / 4;   // real neurons of the last hidden tile, in blocks of four
+  static constexpr bool THIN = R <= 8 && NT >= 2;           // the last tile as NB four-block instructions (see Items)
   static constexpr int KS0 = (D + 3) / 4;                   // k-steps over the MLP's inputs (2C features, zero padded to 4 KS0)
   static constexpr int S = stride2mod4(HP + 1);             // row stride of a weight image; column HP holds the bias
   static constexpr int WSIZE = HP * S;
@@ -202,45 +204,90 @@ __device__ __forceinline__ void stage_prologue(const MlpArgs<double>& a, double*
 }
 
 // ---- one layer of the chain ---------------------------------------------------------------------------
-// hidden layer: hout^T = act(W hin^T + b).  KS = k-steps over the inputs (hin[u][r] <-> k = 16u + 4r + g).  Tile-major: tile t is
-// complete after item (t + 1) KS - 1 and its activation runs two items later, under the next tile's matrix instructions; the
-// bias of tile t + 1 is read while tile t computes.  ext(i) = the step's other work for item i.
-template <class G, int KS, int NTI, bool GEN, int DBG = 0, class ExtF>
+// Item order of a layer's matrix stream over NT tiles of outputs and KS k-steps.  Full tiles: tile-major, i = t KS + ks.
+// TH (G::THIN, H = 36 / 24 / 72: the last tile holds R = 4 or 8 real neurons): the last tile is NB accumulators of
+// v_mfma_f64_4x4x4_4b_f64, four blocks D_b(4x4) += A_b(4x4) B_b(4x4) with (probes/mfma4_probe)
+//   A: lane l holds A_b[i = l&3][k = l>>4], b = (l>>2)&3    B: B_b[k = l>>4][j = l&3]    D: D_b[i = l>>4][j = l&3]
+// i.e. with every block given the same four rows of A: D[neuron g][row c] += sum_k A[neuron c&3][k g'] B[k g'][row c] -- the B
+// operand IS the 16x16x4 one, the result IS register q of the last tile in the chain's layout, a quarter of the pipe time.  Its
+// instructions follow the first tile's, k-step by k-step (a dependent chain of them would wait for its own result; behind a
+// 16x16x4 instruction it does not): items 0 .. KS (1 + NB) - 1 = (tile 0, ks), (block 0, ks), .., then tiles 1 .. NT - 2.
+// tile(i) >= NF names block tile(i) - NF of the last tile.
+template <class G, int KS, bool TH>
+struct Items {
+  static constexpr int NT = G::NT, NB = TH ? G::NB : 0;
+  static constexpr int NF = TH ? NT - 1 : NT;                // full tiles
+  static constexpr int G0 = TH ? KS * (1 + NB) : 0;
+  static constexpr int N = G0 + KS * (TH ? NT - 2 : NT);
+  static_assert(!TH || G::THIN, "a thin last tile");
+  __host__ __device__ static constexpr int tile(int i) {
+    return i >= G0 ? (TH ? 1 : 0) + (i - G0) / KS : i % (1 + NB) == 0 ? 0 : NF + i % (1 + NB) - 1;
+  }
+  __host__ __device__ static constexpr int ks(int i) { return i >= G0 ? (i - G0) % KS : i / (1 + NB); }
+};
+__device__ __forceinline__ double mfma4(double a, double b, double c) { return __builtin_amdgcn_mfma_f64_4x4x4f64(a, b, c, 0, 0, 0); }
+// hidden layer: hout^T = act(W hin^T + b).  KS = k-steps over the inputs (hin[u][r] <-> k = 16u + 4r + g).  Tile t is complete
+// after its last item and its activation runs a few items later, under the next tile's matrix instructions; the
+// bias of tile t + 1 is read while tile t computes.  ext(i) = the step's other work for item i.  TH: registers r >= NB of the last
+// tile are zeros (what the padded neurons of a full tile give under leakyrelu; nothing reads them as operands: the k-steps stop at H).
+template <class G, int KS, int NTI, bool GEN, bool TH, int DBG = 0, class ExtF>
 __device__ __forceinline__ void layer_fwd(const double* Wc, const v4d (&hin)[NTI], v4d (&hout)[G::NT], int c, int g, int act, ExtF ext) {
-  constexpr int S = G::S, NT = G::NT;
+  using It = Items<G, KS, TH>;
+  constexpr int S = G::S, NT = G::NT, NF = It::NF, NB = It::NB;
   const double* wa = Wc + c * S + g;
+  const double* wt = Wc + (16 * NF + (c & 3)) * S + g;       // A fragment of a block: neuron 16 NF + 4q + (c & 3), k = 4 ks + g
   const double* wbias = Wc + g * S + G::HP;
   v4d acc[NT];
 #pragma unroll
   for (int r = 0; r < 4; ++r) acc[0][r] = wbias[4 * r * S];
+#pragma unroll
+  for (int q = 0; q < NB; ++q) acc[NT - 1][q] = wbias[(16 * NF + 4 * q) * S];      // D of block q: neuron 16 NF + 4q + g
   if (DBG) STAMP(30);
-  mfma_stream<KS * NT, LOOKAHEAD>(
-      [&](int i) { return wa[16 * (i / KS) * S + 4 * (i % KS)]; },
+  mfma_stream<It::N, LOOKAHEAD>(
+      [&](int i) {
+        const int t = It::tile(i), ks = It::ks(i);
+        return t < NF ? wa[16 * t * S + 4 * ks] : wt[4 * (t - NF) * S + 4 * ks];
+      },
       [&](int i, double av) {
-        const int t = i / KS, ks = i % KS;
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, hin[ks >> 2][ks & 3], acc[t], 0, 0, 0);
+        const int t = It::tile(i), ks = It::ks(i);
+        if (t < NF) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, hin[ks >> 2][ks & 3], acc[t], 0, 0, 0);
+        else acc[NT - 1][t - NF] = mfma4(av, hin[ks >> 2][ks & 3], acc[NT - 1][t - NF]);
       },
       [&](int i) {
-        const int t = i / KS, ks = i % KS;
-        if (ks == 0 && t + 1 < NT) {
+        const int t = It::tile(i), ks = It::ks(i);
+        if (ks == 0 && t + 1 < NF) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[t + 1 < NT ? t + 1 : 0][r] = wbias[(16 * (t + 1) + 4 * r) * S];
+          for (int r = 0; r < 4; ++r) acc[t + 1 < NF ? t + 1 : 0][r] = wbias[(16 * (t + 1) + 4 * r) * S];
         }
-        constexpr int k1 = KS > 6 ? 5 : KS > 1 ? 1 : 0, k2 = KS > 6 ? 6 : KS > 2 ? 2 : k1;
+        constexpr int k1 = KS > 6 ? 5 : KS > 1 ? 1 : 0, k2 = KS > 6 ? 6 : KS > 2 ? 2 : k1, k3 = k2 + 1 < KS ? k2 + 1 : k2;
 #pragma unroll
         for (int r = 0; r < 4; ++r)                          // tile t - 1 finished a few items ago (its results have left the pipe)
-          if (t > 0 && ks == (r < 2 ? k1 : k2)) {
+          if (t > 0 && t < NF && ks == (r < 2 ? k1 : k2)) {
             double y = act_t<GEN>(acc[t > 0 ? t - 1 : 0][r], act);
             pin(y);
             hout[t > 0 ? t - 1 : 0][r] = y;
+          }
+#pragma unroll
+        for (int q = 0; q < NB; ++q)                         // ... and so did the blocks, which ran beside tile 0
+          if (t == 1 && NF > 1 && ks == k3) {
+            double y = act_t<GEN>(acc[NT - 1][q], act);
+            pin(y);
+            hout[NT - 1][q] = y;
           }
         ext(i);
         if (DBG && (i == 0 || i == 1 || i == 2 || i == 11 || i == 12 || i == 23 || i == 34 || i == 35)) STAMP(31 + i);
       });
   if (DBG) STAMP(28);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) hout[NT - 1][r] = act_t<GEN>(acc[NT - 1][r], act);
-  if (DBG) { double z_ = hout[NT - 1][3]; pin(z_); hout[NT - 1][3] = z_; STAMP(29); }
+  for (int r = 0; r < 4; ++r) hout[NF - 1][r] = act_t<GEN>(acc[NF - 1][r], act);
+  if constexpr (TH) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (r >= NB) hout[NT - 1][r] = 0.0;
+      else if (NF == 1) hout[NT - 1][r] = act_t<GEN>(acc[NT - 1][r], act);
+    }
+  }
+  if (DBG) { double z_ = hout[NF - 1][3]; pin(z_); hout[NF - 1][3] = z_; STAMP(29); }
 }
 // output layer (one tile of 2C <= 16 neurons, no activation)
 template <class G>
@@ -256,29 +303,51 @@ __device__ __forceinline__ v4d layer_out(const double* Wc, const v4d (&hin)[G::N
   return acc;
 }
 // backward through a Linear: gin^T [NTO tiles of inputs] = W^T gpre^T.  KS = k-steps over the layer's OUTPUT neurons
-// (gpre[t][r] <-> o = 16t + 4r + g); A fragment (i = input 16u + c, k = o): the image read transposed.  Tile-major over the
-// input tiles u; fin(u, r) consumes gin[u][r] of a finished tile (activation slope) two items after the tile's last matrix
-// instruction -- except the last tile, which the caller finishes under whatever it issues next.
-template <class G, int KS, int NTO, int NTG, class FinF, class ExtF>
+// (gpre[t][r] <-> o = 16t + 4r + g); A fragment (i = input 16u + c, k = o): the image read transposed.  Item order as in the
+// forward (Items; TH applies where the inputs are a hidden layer's, NTO == NT: the last INPUT tile as blocks, A = rows
+// 16 (NT - 1) + 4q + (c & 3) of W^T).  fin(u, r) consumes gin[u][r] of a finished tile (activation slope) a few items after the
+// tile's last matrix instruction -- except the last full tile (and the blocks, where it is the only full tile), which the caller
+// finishes under whatever it issues next: fin_last.  Of a thin tile fin sees registers r < NB only.
+template <class G, int KS, int NTO, int NTG, bool TH_, class FinF, class ExtF>
 __device__ __forceinline__ void layer_bwd(const double* Wc, const v4d (&gpre)[NTG], v4d (&gin)[NTO], int c, int g, FinF fin, ExtF ext) {
-  constexpr int S = G::S;
+  constexpr bool TH = TH_ && NTO == G::NT;
+  using It = Items<G, KS, TH>;
+  constexpr int S = G::S, NF = TH ? It::NF : NTO, NB = It::NB, N = TH ? It::N : KS * NTO;
   const double* wa = Wc + g * S + c;
+  const double* wt = Wc + g * S + 16 * NF + (c & 3);
 #pragma unroll
   for (int u = 0; u < NTO; ++u) gin[u] = v4d{0, 0, 0, 0};
-  mfma_stream<KS * NTO, LOOKAHEAD>(
-      [&](int i) { return wa[4 * (i % KS) * S + 16 * (i / KS)]; },
+  mfma_stream<N, LOOKAHEAD>(
+      [&](int i) {
+        const int u = It::tile(i), ks = It::ks(i);
+        return u < NF ? wa[4 * ks * S + 16 * u] : wt[4 * ks * S + 4 * (u - NF)];
+      },
       [&](int i, double av) {
-        const int u = i / KS, ks = i % KS;
-        gin[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, gpre[ks >> 2][ks & 3], gin[u], 0, 0, 0);
+        const int u = It::tile(i), ks = It::ks(i);
+        if (u < NF) gin[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, gpre[ks >> 2][ks & 3], gin[u], 0, 0, 0);
+        else gin[NTO - 1][u - NF] = mfma4(av, gpre[ks >> 2][ks & 3], gin[NTO - 1][u - NF]);
       },
       [&](int i) {
-        const int u = i / KS, ks = i % KS;
-        constexpr int k1 = KS > 6 ? 5 : KS > 1 ? 1 : 0, k2 = KS > 6 ? 6 : KS > 2 ? 2 : k1;
+        const int u = It::tile(i), ks = It::ks(i);
+        constexpr int k1 = KS > 6 ? 5 : KS > 1 ? 1 : 0, k2 = KS > 6 ? 6 : KS > 2 ? 2 : k1, k3 = k2 + 1 < KS ? k2 + 1 : k2;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (u > 0 && ks == (r < 2 ? k1 : k2)) fin(u > 0 ? u - 1 : 0, r);
+          if (u > 0 && u < NF && ks == (r < 2 ? k1 : k2)) fin(u > 0 ? u - 1 : 0, r);
+#pragma unroll
+        for (int q = 0; q < NB; ++q)
+          if (TH && u == 1 && NF > 1 && ks == k3) fin(NTO - 1, q);
         ext(i);
       });
+}
+// register r of what layer_bwd left to its caller
+template <class G, int NTO, bool TH_, class FinF>
+__device__ __forceinline__ void fin_last(FinF fin, int r) {
+  constexpr bool TH = TH_ && NTO == G::NT;
+  if (!TH) fin(NTO - 1, r);
+  else {
+    fin(NTO - 2, r);
+    if (NTO == 2 && r < G::NB) fin(NTO - 1, r);
+  }
 }
 
 // Hidden activations kept for the backward (MlpArgs::h_saved): an opaque register image,
@@ -321,7 +390,7 @@ __device__ __forceinline__ void load_x(const MlpArgs<double>& a, int row, int g,
 
 // TWO: eight waves per workgroup -- waves 4 - 7 stage the weight images (global -> registers -> LDS, two steps ahead) and nothing else,
 // waves 0 - 3 carry the chain without the staging pieces in their matrix streams (round 6; see mlp_chain_bwd2_kernel)
-template <int H, int D, bool GEN, bool SAVE, bool TWO = false>
+template <int H, int D, bool GEN, bool SAVE, bool TWO = false, bool TH = false>
 __global__ __launch_bounds__(TWO ? 512 : 256) void mlp_chain_fwd_kernel(MlpArgs<double> a) {
   using G = Geo<H, D>;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -355,9 +424,10 @@ __global__ __launch_bounds__(TWO ? 512 : 256) void mlp_chain_fwd_kernel(MlpArgs<
   // step q: commit the image of layer q + 1 (loaded during step q - 1), request layer q + 2, compute layer q
   // (SAVE: the activations of layer q - 1 are stored under layer q's matrix instructions)
 #define LGN_CHAIN_STEP(Q, HIN, HOUT, KS, NTI)                                                                        \
-  layer_fwd<G, KS, NTI, GEN, (Q == 3)>(Wl + (Q & 1) * G::WSIZE, HIN, HOUT, c, g, a.act, [&](int i) {               \
-    if (!TWO && !LGN_DBG_NOSTAGE) deal<KS * G::NT, stage_pieces<G>()>(i, [&](int j) { stage_piece<G, false, Q>(a, Wl, wrA, wrB, tid, j); });      \
-    if (SAVE && Q > 0) deal<KS * G::NT, 2 * NTI>(i, [&](int j) { save_piece<G>(hs, Q - 1, HIN, j); });              \
+  layer_fwd<G, KS, NTI, GEN, TH, (Q == 3)>(Wl + (Q & 1) * G::WSIZE, HIN, HOUT, c, g, a.act, [&](int i) {           \
+    constexpr int NI = Items<G, KS, TH>::N;                                                                          \
+    if (!TWO && !LGN_DBG_NOSTAGE) deal<NI, stage_pieces<G>()>(i, [&](int j) { stage_piece<G, false, Q>(a, Wl, wrA, wrB, tid, j); });      \
+    if (SAVE && Q > 0) deal<NI, 2 * NTI>(i, [&](int j) { save_piece<G>(hs, Q - 1, HIN, j); });                      \
   });                                                                                                                \
   lds_barrier();                                                                                                     \
   STAMP(2 + Q);
@@ -452,7 +522,7 @@ __device__ __forceinline__ bool dw_layer(const double* Gt, const double* Xt, dou
   return false;
 }
 
-template <int H, int D, bool GEN, bool SAVE>
+template <int H, int D, bool GEN, bool SAVE, bool TH = false>
 __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
   using G = Geo<H, D>;
   constexpr int NT = G::NT, NH = G::NH;
@@ -497,8 +567,8 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
     STAMP(11);
     // ---- recompute the hidden activations: steps q = 0 .. 5, image q in buffer q & 1
 #define LGN_CHAIN_STEP(Q, HIN, KS, NTI)                                                                              \
-  layer_fwd<G, KS, NTI, GEN>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int i) {                          \
-    deal<KS * NT, stage_pieces<G>()>(i, [&](int j) { stage_piece<G, true, Q>(a, Wl, wrA, wrB, tid, j); });          \
+  layer_fwd<G, KS, NTI, GEN, TH>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int i) {                      \
+    deal<Items<G, KS, TH>::N, stage_pieces<G>()>(i, [&](int j) { stage_piece<G, true, Q>(a, Wl, wrA, wrB, tid, j); });  \
   });                                                                                                                \
   lds_barrier();                                                                                                     \
   STAMP(12 + Q);
@@ -512,15 +582,15 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
   }
   // ---- backward sweep: step q = 6 .. 12 handles Linear l = 12 - q (image in buffer q & 1), tiles of parity l & 1.  The g_pre of
   // successive layers alternate between two register arrays: the running stream still reads the old one as its B operands.
-  v4d gpA[NT], gpB[NT], gin[NT];
+  v4d gpA[NT] = {}, gpB[NT] = {}, gin[NT];      // (TH: fin never sees registers r >= NB of the last tile: they stay zero)
   {  // q = 6, l = 6: the output layer
-    constexpr int NI = G::KS0 * NT, NSV = SAVE && NH >= 3 ? saved_pieces<G>() : 0, NPC = 4 + 4 * NT + stage_pieces<G>() + NSV;
+    constexpr int NI = Items<G, G::KS0, TH>::N, NSV = SAVE && NH >= 3 ? saved_pieces<G>() : 0, NPC = 4 + 4 * NT + stage_pieces<G>() + NSV;
     auto fin = [&](int u, int r) {
       double y = gin[u][r] * act_slope_t<GEN>(h[NH - 1][u][r], a.act);
       pin(y);
       gpA[u][r] = y;
     };
-    layer_bwd<G, G::KS0, NT, 1>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
+    layer_bwd<G, G::KS0, NT, 1, TH>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
       deal<NI, NPC>(i, [&](int j) {
         if (j < 4) publish_piece<G, 1>(Gt, gout, wave, c, g, j);
         else if (j < 4 + 4 * NT) publish_piece<G, NT>(Xt, h[NH - 1], wave, c, g, j - 4);
@@ -529,20 +599,20 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
       });
     });
 #pragma unroll
-    for (int r = 0; r < 4; ++r) fin(NT - 1, r);
+    for (int r = 0; r < 4; ++r) fin_last<G, NT, TH>(fin, r);
     lds_barrier();
     STAMP(18);
   }
 #define LGN_CHAIN_BSTEP(L, GP, GN)                                                                                   \
   {                                                                                                                  \
-    constexpr int q_ = 2 * NH - (L), NI = G::KSH * NT, NSV = SAVE && (L) >= 3 ? saved_pieces<G>() : 0,               \
+    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NSV = SAVE && (L) >= 3 ? saved_pieces<G>() : 0,               \
                   NPC = 8 * NT + stage_pieces<G>() + NSV;                                                            \
     auto fin = [&](int u, int r) {                                                                                   \
       double y = gin[u][r] * act_slope_t<GEN>(h[(L) - 1][u][r], a.act);                                              \
       pin(y);                                                                                                        \
       GN[u][r] = y;                                                                                                  \
     };                                                                                                               \
-    layer_bwd<G, G::KSH, NT, NT>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
+    layer_bwd<G, G::KSH, NT, NT, TH>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
       deal<NI, NPC>(i, [&](int j) {                                                                                  \
         if (j < 4 * NT) publish_piece<G, NT>(Gt + ((L) & 1) * G::TSIZE, GP, wave, c, g, j);                          \
         else if (j < 8 * NT) publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], wave, c, g, j - 4 * NT);    \
@@ -551,8 +621,8 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
       });                                                                                                            \
     });                                                                                                              \
     auto tail = [&](int i) {                                                                                         \
-      if (i == 1) { fin(NT - 1, 0); fin(NT - 1, 1); }                                                                \
-      if (i == 2) { fin(NT - 1, 2); fin(NT - 1, 3); }                                                                \
+      if (i == 1) { fin_last<G, NT, TH>(fin, 0); fin_last<G, NT, TH>(fin, 1); }                                                                \
+      if (i == 2) { fin_last<G, NT, TH>(fin, 2); fin_last<G, NT, TH>(fin, 3); }                                                                \
     };                                                                                                               \
     if (!dw_layer<G, (L) + 1>(Gt + (((L) + 1) & 1) * G::TSIZE, Xt + (((L) + 1) & 1) * G::TSIZE, part, wave, c, g, tail)) {   \
       tail(1);                                                                                                       \
@@ -569,7 +639,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
 #undef LGN_CHAIN_BSTEP
   {  // q = 12, l = 0: the first layer; its input tile holds the MLP's input rows (k-steps beyond KS0 never stored or read)
     v4d gx[1];
-    layer_bwd<G, G::KSH, 1, NT>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
+    layer_bwd<G, G::KSH, 1, NT, TH>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
       deal<G::KSH, 4 * NT + 4>(i, [&](int j) {
         if (j < 4 * NT) publish_piece<G, NT>(Gt, gpB, wave, c, g, j);
         else publish_piece<G, 1>(Xt, xb, wave, c, g, j - 4 * NT);
@@ -660,6 +730,66 @@ __device__ __forceinline__ void dw_quarter_sum(const double* qs, double* part, i
   }
 }
 
+// Weight gradient of a HIDDEN Linear L whose last tile holds four neurons (H = 36; two-role kernel with thin tiles): of the 36 x 36
+// matrix only four 16 x 16 tiles are full.  dW wave w takes tile (t, u) = (w >> 1, w & 1) and one 4 x 16 strip as sixteen block
+// instructions over the 64 rows (both LDS tiles are [neuron][64 rows]: either can be the A operand):
+//   waves 0, 1: strip (2, w), rows 32 .. 35:     A = rows 32 + (c & 3) of g_pre^T, B = the fragment of h_in^T -> dW[32 + g][16 w + c]
+//   waves 2, 3: strip (w - 2, 2), columns 32 .. 35, transposed: A = rows 32 + (c & 3) of h_in^T, B = the fragment of g_pre^T
+//                                                                                                -> dW[16 (w - 2) + c][32 + g]
+// and wave 3 the 4 x 4 corner: four block instructions whose blocks are a split over the rows (block b = rows 16 b .. 16 b + 15),
+// added across the blocks in a fixed order.  20 - 21 instruction times per wave where dw_hidden3 has 36, no quarter sums, no LDS for them.
+template <class G, int L, class SideF>
+__device__ __forceinline__ void dw_thin3(const double* Gt, const double* Xt, double* part, int w, int c, int g, SideF side) {
+  static_assert(G::NT == 3 && G::R == 4 && L >= 1 && L < G::NH, "hidden layers of two full tiles and four more neurons");
+  constexpr int SR = G::SR, H = G::H, N = 32, P = 6;
+  const int t = w >> 1, u = w & 1;
+  const bool tr = w >= 2;
+  const double* ga = Gt + (16 * t + c) * SR + g;
+  const double* xb = Xt + (16 * u + c) * SR + g;
+  const double* sa = (tr ? Xt : Gt) + (32 + (c & 3)) * SR + g;
+  const double* sb = (tr ? Gt : Xt) + (16 * u + c) * SR + g;
+  double* pW = part + G::off_w(L);
+  v4d acc = {0, 0, 0, 0};
+  double strip = 0.0, qa[N], qx[N];
+  auto load = [&](int i) {
+    if (i < 16) { qa[i] = ga[4 * i]; qx[i] = xb[4 * i]; }
+    else { qa[i] = sa[4 * (i - 16)]; qx[i] = sb[4 * (i - 16)]; }
+  };
+#pragma unroll
+  for (int i = 0; i < P; ++i) load(i);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if (i + P < N) load(i + P);
+    if (i < 16) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(qa[i], qx[i], acc, 0, 0, 0);
+    else strip = mfma4(qa[i], qx[i], strip);
+    if (i >= 17 && i <= 20) __builtin_nontemporal_store(acc[i - 17], &pW[(16 * t + 4 * (i - 17) + g) * H + 16 * u + c]);
+    side(i);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_nontemporal_store(strip, tr ? &pW[(16 * u + c) * H + 32 + g] : &pW[(32 + g) * H + 16 * u + c]);
+  if (w == 3) {
+    const double* ca = Gt + (32 + (c & 3)) * SR + 16 * (c >> 2) + g;
+    const double* cb = Xt + (32 + (c & 3)) * SR + 16 * (c >> 2) + g;
+    double v = 0.0;
+#pragma unroll
+    for (int sk = 0; sk < 4; ++sk) v = mfma4(ca[4 * sk], cb[4 * sk], v);      // lane: sum over rows 16 (c >> 2) .. + 15 of dW[32 + g][32 + (c & 3)]
+    v += shfl_xor(v, 4);
+    v += shfl_xor(v, 8);
+    if (c < 4) __builtin_nontemporal_store(v, &pW[(32 + g) * H + 32 + c]);
+  } else {
+    // bias gradient: waves 0 and 2 rows 16 t + c from the full tile's A fragments, wave 1 rows 32 + (c & 3) from the strip's -- the
+    // same sixteen values in the same order as dw_hidden3 adds them
+    double d4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int sk = 0; sk < 16; ++sk) d4[sk & 3] += w == 1 ? qa[16 + sk] : qa[sk];
+    double dbs = (d4[0] + d4[1]) + (d4[2] + d4[3]);
+    dbs += shfl_xor(dbs, 16);
+    dbs += shfl_xor(dbs, 32);
+    if (g == 0 && (w != 1 || c < 4)) __builtin_nontemporal_store(dbs, &part[G::off_b(L) + (w == 1 ? 32 : 16 * t) + c]);
+  }
+}
+
 // ---- backward, two roles per workgroup (round 6) ---------------------------------------------------------------------------------
 // The kernel above runs ONE wave per SIMD: whatever a wave waits for -- an LDS fragment, the barrier, the datapath's turn-around
 // after an fp64 vector instruction -- leaves the matrix pipe idle (0.40 busy at cfg2).  Here a workgroup is EIGHT waves over the same
@@ -667,7 +797,7 @@ __device__ __forceinline__ void dw_quarter_sum(const double* qs, double* part, i
 // chain waves did on the side -- the weight gradients dW_l from the published tiles (one step behind the chain, as before) and the
 // staging of the weight images.  Every SIMD then holds two waves with independent instruction streams and the pipe takes whichever is
 // ready.  Same arithmetic, same summation order, same barriers (one per step, over all eight waves); 256 registers per wave.
-template <int H, int D, bool GEN>
+template <int H, int D, bool GEN, bool TH = false>
 __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) {
   using G = Geo<H, D>;
   constexpr int NT = G::NT, NH = G::NH;
@@ -698,18 +828,21 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
     // step q = 2 NH - L: weight gradient of Linear L + 1 from the tiles of parity (L + 1) & 1, staging dealt under its matrix stream
     // (NT = 3: the hidden layers' nine tiles dealt evenly, dw_hidden3; the ninth tile's quarter sums of Linear L + 2 are added up by
     // wave 1 at the head of the step that follows their barrier)
-    constexpr bool EVEN = NT == 3;
-    double* qs = Xt + 2 * G::TSIZE;                          // [2 parities][4 waves][4 registers][64 lanes]
+    // (thin tiles, H = 36: four full tiles, four strips and a corner, dw_thin3 -- no quarter sums)
+    constexpr bool THIN3 = TH && NT == 3 && G::R == 4, EVEN = NT == 3 && !THIN3;
+    double* qs = Xt + 2 * G::TSIZE;                          // [2 parities][4 waves][4 registers][64 lanes] (EVEN only)
 #define LGN_DW_STEP(L)                                                                                               \
   {                                                                                                                  \
     constexpr int q_ = 2 * NH - (L), NS = stage_pieces<G>(), L1 = (L) + 1;                                           \
-    constexpr bool HID = EVEN && L1 >= 1 && L1 < NH;                                                                 \
-    constexpr int NI = HID ? 36 : (L1 == NH || L1 == 0) ? 16 : 16 * NT;                                              \
+    constexpr bool HID = EVEN && L1 >= 1 && L1 < NH, HID3 = THIN3 && L1 >= 1 && L1 < NH;                             \
+    constexpr int NI = HID ? 36 : HID3 ? 32 : (L1 == NH || L1 == 0) ? 16 : 16 * NT;                                  \
     auto side = [&](int i) { deal<NI, NS>(i, [&](int j) { stage_piece<G, true, q_>(a, Wl, wrA, wrB, tid, j); }); };  \
     if constexpr (EVEN && L1 + 1 >= 1 && L1 + 1 < NH) {                                                              \
       if (w4 == 1) dw_quarter_sum<G, (L1 + 1 < NH ? L1 + 1 : 1)>(qs + ((L1 + 1) & 1) * 1024, part, lane, c, g);     \
     }                                                                                                                \
-    if constexpr (HID) {                                                                                             \
+    if constexpr (HID3) {                                                                                            \
+      dw_thin3<G, (HID3 ? L1 : 1)>(Gt + (L1 & 1) * G::TSIZE, Xt + (L1 & 1) * G::TSIZE, part, w4, c, g, side);        \
+    } else if constexpr (HID) {                                                                                      \
       dw_hidden3<G, (HID ? L1 : 1)>(Gt + (L1 & 1) * G::TSIZE, Xt + (L1 & 1) * G::TSIZE, part, qs + (L1 & 1) * 1024, w4, lane, c, g, side); \
     } else if (!dw_layer<G, L1>(Gt + (L1 & 1) * G::TSIZE, Xt + (L1 & 1) * G::TSIZE, part, w4, c, g, side)) {         \
       LGN_STAGE_ALL(q_)                                                                                              \
@@ -743,7 +876,7 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
   lds_barrier();
   STAMP(11);
 #define LGN_CHAIN_STEP(Q, HIN, KS, NTI)                                                                              \
-  layer_fwd<G, KS, NTI, GEN>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int) {});                          \
+  layer_fwd<G, KS, NTI, GEN, TH>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int) {});                          \
   lds_barrier();                                                                                                     \
   STAMP(12 + Q);
   LGN_CHAIN_STEP(0, xb, G::KS0, 1)
@@ -753,41 +886,41 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
   LGN_CHAIN_STEP(4, h[3], G::KSH, NT)
   LGN_CHAIN_STEP(5, h[4], G::KSH, NT)
 #undef LGN_CHAIN_STEP
-  v4d gpA[NT], gpB[NT], gin[NT];
+  v4d gpA[NT] = {}, gpB[NT] = {}, gin[NT];      // (TH: fin never sees registers r >= NB of the last tile: they stay zero)
   {  // q = 6, l = 6: the output layer
-    constexpr int NI = G::KS0 * NT, NPC = 4 + 4 * NT;
+    constexpr int NI = Items<G, G::KS0, TH>::N, NPC = 4 + 4 * NT;
     auto fin = [&](int u, int r) {
       double y = gin[u][r] * act_slope_t<GEN>(h[NH - 1][u][r], a.act);
       pin(y);
       gpA[u][r] = y;
     };
-    layer_bwd<G, G::KS0, NT, 1>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
+    layer_bwd<G, G::KS0, NT, 1, TH>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
       deal<NI, NPC>(i, [&](int j) {
         if (j < 4) publish_piece<G, 1>(Gt, gout, wave, c, g, j);
         else publish_piece<G, NT>(Xt, h[NH - 1], wave, c, g, j - 4);
       });
     });
 #pragma unroll
-    for (int r = 0; r < 4; ++r) fin(NT - 1, r);
+    for (int r = 0; r < 4; ++r) fin_last<G, NT, TH>(fin, r);
     lds_barrier();
     STAMP(18);
   }
 #define LGN_CHAIN_BSTEP(L, GP, GN)                                                                                   \
   {                                                                                                                  \
-    constexpr int q_ = 2 * NH - (L), NI = G::KSH * NT, NPC = 8 * NT;                                                 \
+    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NPC = 8 * NT;                                                 \
     auto fin = [&](int u, int r) {                                                                                   \
       double y = gin[u][r] * act_slope_t<GEN>(h[(L) - 1][u][r], a.act);                                              \
       pin(y);                                                                                                        \
       GN[u][r] = y;                                                                                                  \
     };                                                                                                               \
-    layer_bwd<G, G::KSH, NT, NT>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
+    layer_bwd<G, G::KSH, NT, NT, TH>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
       deal<NI, NPC>(i, [&](int j) {                                                                                  \
         if (j < 4 * NT) publish_piece<G, NT>(Gt + ((L) & 1) * G::TSIZE, GP, wave, c, g, j);                          \
         else publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], wave, c, g, j - 4 * NT);                    \
       });                                                                                                            \
     });                                                                                                              \
     STAMP(56 + (L));                                                                                                 \
-    _Pragma("unroll") for (int r = 0; r < 4; ++r) fin(NT - 1, r);                                                    \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) fin_last<G, NT, TH>(fin, r);                                                    \
     STAMP(50 + (L));                                                                                                 \
     lds_barrier();                                                                                                   \
     STAMP(12 + q_);                                                                                                  \
@@ -800,7 +933,7 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
 #undef LGN_CHAIN_BSTEP
   {  // q = 12, l = 0: the first layer; its input tile holds the MLP's input rows (k-steps beyond KS0 never stored or read)
     v4d gx[1];
-    layer_bwd<G, G::KSH, 1, NT>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
+    layer_bwd<G, G::KSH, 1, NT, TH>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
       deal<G::KSH, 4 * NT + 4>(i, [&](int j) {
         if (j < 4 * NT) publish_piece<G, NT>(Gt, gpB, wave, c, g, j);
         else publish_piece<G, 1>(Xt, xb, wave, c, g, j - 4 * NT);
@@ -854,7 +987,7 @@ __global__ __launch_bounds__(192) void mlp_chain_fwd16_kernel(MlpArgs<double> a)
   v4d h0[G::NT], h1[G::NT];
   double* hs = SAVE ? saved_ptr16<G>(a, lane) : nullptr;
 #define LGN_CHAIN_STEP(Q, HIN, HOUT, KS, NTI)                                                                        \
-  layer_fwd<G, KS, NTI, GEN>(Wl + (Q & 1) * G::WSIZE, HIN, HOUT, c, g, a.act, [&](int i) {                          \
+  layer_fwd<G, KS, NTI, GEN, false>(Wl + (Q & 1) * G::WSIZE, HIN, HOUT, c, g, a.act, [&](int i) {                          \
     if (SAVE && Q > 0) deal<KS * G::NT, 2 * NTI>(i, [&](int j) { save_piece<G>(hs, Q - 1, HIN, j); });              \
   });                                                                                                                \
   lds_barrier();
@@ -990,7 +1123,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd16_kernel(MlpArgs<double> a)
   } else {
     lds_barrier();
 #define LGN_CHAIN_STEP(Q, HIN, KS, NTI)                                                                              \
-  layer_fwd<G, KS, NTI, GEN>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int) {});                          \
+  layer_fwd<G, KS, NTI, GEN, false>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int) {});                          \
   lds_barrier();
     LGN_CHAIN_STEP(0, xb, G::KS0, 1)
     LGN_CHAIN_STEP(1, h[0], G::KSH, NT)
@@ -1008,7 +1141,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd16_kernel(MlpArgs<double> a)
       pin(y);
       gpA[u][r] = y;
     };
-    layer_bwd<G, G::KS0, NT, 1>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
+    layer_bwd<G, G::KS0, NT, 1, false>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
       deal<NI, NPC>(i, [&](int j) {
         if (j < 4) publish_piece<G, 1>(Gt, gout, 0, c, g, j);
         else if (j < 4 + 4 * NT) publish_piece<G, NT>(Xt, h[NH - 1], 0, c, g, j - 4);
@@ -1027,7 +1160,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd16_kernel(MlpArgs<double> a)
       pin(y);                                                                                                        \
       GN[u][r] = y;                                                                                                  \
     };                                                                                                               \
-    layer_bwd<G, G::KSH, NT, NT>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
+    layer_bwd<G, G::KSH, NT, NT, false>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
       deal<NI, NPC>(i, [&](int j) {                                                                                  \
         if (j < 4 * NT) publish_piece<G, NT>(Gt + ((L) & 1) * G::TSIZE, GP, 0, c, g, j);                             \
         else if (j < 8 * NT) publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], 0, c, g, j - 4 * NT);       \
@@ -1045,7 +1178,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd16_kernel(MlpArgs<double> a)
 #undef LGN_CHAIN_BSTEP
   {  // q = 12, l = 0: the first layer
     v4d gx[1];
-    layer_bwd<G, G::KSH, 1, NT>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
+    layer_bwd<G, G::KSH, 1, NT, false>(Wl + 0 * G::WSIZE, gpB, gx, c, g, [&](int, int) {}, [&](int i) {
       deal<G::KSH, 4 * NT + 4>(i, [&](int j) {
         if (j < 4 * NT) publish_piece<G, NT>(Gt, gpB, 0, c, g, j);
         else publish_piece<G, 1>(Xt, xb, 0, c, g, j - 4 * NT);
@@ -1385,20 +1518,20 @@ static int launch16(const MlpArgs<double>& a, bool backward, hipStream_t stream)
 
 // 48 < H <= 96 (C = 5 .. 8): the FORWARD chain only -- its two weight images (up to 150 KB) and ping-ponged activations fit; the
 // backward's tiles and six kept activations do not (LDS 274 KB, > 512 registers), it stays with mlp_mfma_wide.hip
-template <int H, int D>
+template <int H, int D, bool TH>
 static int launch_fwd(const MlpArgs<double>& a, hipStream_t stream) {
   using G = Geo<H, D>;
   static_assert(G::fwd_bytes() <= 160 * 1024, "LDS budget");
   const bool two = !(a.flags & LVL_MLP_BWD1);
-  auto kern = two ? (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true> : mlp_chain_fwd_kernel<H, D, true, false, true>)
-                  : (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false> : mlp_chain_fwd_kernel<H, D, true, false>);
+  auto kern = two ? (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>)
+                  : (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, false, TH> : mlp_chain_fwd_kernel<H, D, true, false, false, TH>);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::fwd_bytes());
   hipLaunchKernelGGL(kern, dim3(cdiv(a.M, 64)), dim3(two ? 512 : 256), G::fwd_bytes(), stream, a);
   LGN_CHECK_LAUNCH();
   return 0;
 }
 
-template <int H, int D>
+template <int H, int D, bool TH>
 static int launch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   using G = Geo<H, D>;
   const int nblk = cdiv(a.M, 64);
@@ -1408,27 +1541,34 @@ static int launch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   LGN_CHECK_ARG(!a.h_saved || a.h_rows >= nblk * 64, "cgmlp: the saved-activation buffer has %d rows per layer, %d rows need %d",
                 a.h_rows, a.M, nblk * 64);
   if (backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {      // (kept activations: the one-role kernel reads them)
-    auto k2 = a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false> : mlp_chain_bwd2_kernel<H, D, true>;
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k2, dim3(nblk), dim3(512), smem, stream, a);
+    auto k2 = a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false, TH> : mlp_chain_bwd2_kernel<H, D, true, TH>;
+    const size_t smem2 = smem - (TH && G::NT == 3 && G::R == 4 ? sizeof(double) * 2 * 1024 : 0);      // (dw_thin3: no quarter sums)
+    if (smem2 > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
+    hipLaunchKernelGGL(k2, dim3(nblk), dim3(512), smem2, stream, a);
     LGN_CHECK_LAUNCH();
     return 0;
   }
   if (!backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {
-    auto k2 = a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true> : mlp_chain_fwd_kernel<H, D, true, false, true>;
+    auto k2 = a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>;
     if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     hipLaunchKernelGGL(k2, dim3(nblk), dim3(512), smem, stream, a);
     LGN_CHECK_LAUNCH();
     return 0;
   }
-  auto kern = a.h_saved ? (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, true> : mlp_chain_fwd_kernel<H, D, false, true>)
-                                      : (backward ? mlp_chain_bwd_kernel<H, D, true, true> : mlp_chain_fwd_kernel<H, D, true, true>))
-                        : (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, false> : mlp_chain_fwd_kernel<H, D, false, false>)
-                                      : (backward ? mlp_chain_bwd_kernel<H, D, true, false> : mlp_chain_fwd_kernel<H, D, true, false>));
+  auto kern = a.h_saved ? (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, true, TH> : mlp_chain_fwd_kernel<H, D, false, true, false, TH>)
+                                      : (backward ? mlp_chain_bwd_kernel<H, D, true, true, TH> : mlp_chain_fwd_kernel<H, D, true, true, false, TH>))
+                        : (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, false, TH> : mlp_chain_fwd_kernel<H, D, false, false, false, TH>)
+                                      : (backward ? mlp_chain_bwd_kernel<H, D, true, false, TH> : mlp_chain_fwd_kernel<H, D, true, false, false, TH>));
   if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), smem, stream, a);
   LGN_CHECK_LAUNCH();
   return 0;
+}
+// the widths whose padded last tile runs as four-neuron blocks (Items) unless LGN_AMD_MLP_FULLTILE asks for the full tile
+template <int H, int D>
+static int launch_thin(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
+  static_assert(Geo<H, D>::THIN, "a last tile of at most eight neurons");
+  return (a.flags & LVL_MLP_FULLTILE) ? launch<H, D, false>(a, backward, stream) : launch<H, D, true>(a, backward, stream);
 }
 
 }  // namespace chain
@@ -1449,15 +1589,15 @@ int mlp_chain_dispatch(const MlpArgs<double>& a, bool backward, hipStream_t stre
     if (a.H == 12 && a.C == 1) return chain::launch16<12, 2>(a, backward, stream);
     return -2;
   }
-  if (a.H == 48 && a.C == 4) return chain::launch<48, 8>(a, backward, stream);
-  if (a.H == 36 && a.C == 3) return chain::launch<36, 6>(a, backward, stream);
-  if (a.H == 24 && a.C == 2) return chain::launch<24, 4>(a, backward, stream);
-  if (a.H == 12 && a.C == 1) return chain::launch<12, 2>(a, backward, stream);
+  if (a.H == 48 && a.C == 4) return chain::launch<48, 8, false>(a, backward, stream);
+  if (a.H == 36 && a.C == 3) return chain::launch_thin<36, 6>(a, backward, stream);
+  if (a.H == 24 && a.C == 2) return chain::launch_thin<24, 4>(a, backward, stream);
+  if (a.H == 12 && a.C == 1) return chain::launch<12, 2, false>(a, backward, stream);
   if (!backward && !a.h_saved) {
-    if (a.H == 60 && a.C == 5) return chain::launch_fwd<60, 10>(a, stream);
-    if (a.H == 72 && a.C == 6) return chain::launch_fwd<72, 12>(a, stream);
-    if (a.H == 84 && a.C == 7) return chain::launch_fwd<84, 14>(a, stream);
-    if (a.H == 96 && a.C == 8) return chain::launch_fwd<96, 16>(a, stream);
+    if (a.H == 60 && a.C == 5) return chain::launch_fwd<60, 10, false>(a, stream);
+    if (a.H == 72 && a.C == 6) return (a.flags & LVL_MLP_FULLTILE) ? chain::launch_fwd<72, 12, false>(a, stream) : chain::launch_fwd<72, 12, true>(a, stream);
+    if (a.H == 84 && a.C == 7) return chain::launch_fwd<84, 14, false>(a, stream);
+    if (a.H == 96 && a.C == 8) return chain::launch_fwd<96, 16, false>(a, stream);
   }
   return -2;
 }
