@@ -320,6 +320,9 @@ typedef struct lgn_loss_desc {
 #define LGN_NET_MLP_FULLTILE 2048 /* LGN_AMD_MLP_FULLTILE=1: the chain CGMLP kernels on 64-row workgroups compute the padded last tile of a hidden
                                     layer (H = 36: neurons 32 .. 47, four of them real) as a full 16 x 16 x 4 tile, as before the four-neuron
                                     block instructions (csrc/mlp_chain.hip: Items); cross-check */
+#define LGN_NET_LIVE_SCALARS 4096 /* LGN_AMD_LIVE_SCALARS=1: the last level of either network, whose scalar output nobody reads and whose scalars carry
+                                    no gradient, runs the level kernels with live scalars -- on the zero block, as before those kernels had a
+                                    form without them; cross-check (bit-identical) */
 #define LGN_NET_SPLIT_TAIL 128   /* LGN_AMD_SPLIT_TAIL=1: the tail of a step (deferred reductions, radial finalisation, L1 + Adam) as the
                                     three separate launches instead of csrc/step_tail.hip's one (cross-check; bit-identical) */
 

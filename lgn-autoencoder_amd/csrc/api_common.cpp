@@ -24,7 +24,8 @@ int level_flags_from_env() {
 }
 static_assert(LVL_DEC_PAIRWISE == LGN_NET_DEC_PAIRWISE && LVL_LEVEL_V2 == LGN_NET_LEVEL_V2 && LVL_MOMENTS_V1 == LGN_NET_MOMENTS_V1 &&
                   LVL_MLP_V1 == LGN_NET_MLP_V1 && LVL_MLP_BWD1 == LGN_NET_MLP_BWD1 && LVL_MLP_FULLTILE == LGN_NET_MLP_FULLTILE &&
-                  LVL_BWD_ORDERED == LGN_NET_BWD_ORDERED && LVL_MOMENTS_SPLIT == LGN_NET_MOMENTS_SPLIT, "LVL_* and LGN_NET_* are the same bits");
+                  LVL_BWD_ORDERED == LGN_NET_BWD_ORDERED && LVL_MOMENTS_SPLIT == LGN_NET_MOMENTS_SPLIT &&
+                  LVL_LIVE_SCALARS == LGN_NET_LIVE_SCALARS, "LVL_* and LGN_NET_* are the same bits");
 }  // namespace lgn
 
 extern "C" {

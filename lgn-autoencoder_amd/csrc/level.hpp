@@ -33,6 +33,7 @@ constexpr int LVL_MOMENTS_V1 = 16;     // table-driven levels: component-chunked
 constexpr int LVL_MLP_BWD1 = 1024;      // CGMLP chain backward: the one-role kernel (four waves: chain + weight gradients + staging) instead of the two-role one
 constexpr int LVL_MLP_FULLTILE = 2048;  // CGMLP chain kernels (64-row workgroups): the padded last hidden tile as a full 16 x 16 tile instead of four-neuron blocks (cross-check)
 constexpr int LVL_MOMENTS_SPLIT = 512; // table-driven encoder levels: the backward's two pair sweeps as two kernels (cross-check of the merged one)
+constexpr int LVL_LIVE_SCALARS = 4096; // last levels whose scalars nobody reads (LevelArgs / LevelBwdArgs::dead_scalars): the kernels with live scalars, on the zero block (cross-check)
 constexpr int LVL_BWD_ORDERED = 64;    // encoder level backward (N <= 40): radial-gradient GEMM per ORDERED pair tile (cross-check of the symmetric sweep)
 int level_flags_from_env();
 
@@ -81,6 +82,9 @@ struct LevelArgs {
   T* loss_gv = nullptr;            // [2][B][N][CO][4] gradient w.r.t. v_out
   T* loss_wpart = nullptr;         // [B][2 CO]
   int flags = 0;                   // LVL_*
+  // Last level of a network whose scalar output nobody reads (step.hip: levels_fwd): the scalar aggregates A3 / A4, the
+  // scalar CatMix rows, s_out and ag0 are neither computed nor stored (both may be null); v_out and ag1 are what they always are.
+  int dead_scalars = 0;
 };
 
 template <typename T>
@@ -108,6 +112,10 @@ struct LevelBwdArgs {
   // arithmetic) rides on this kernel, one partial row [4C] = (dW00 re, im, dW11 re, im) per workgroup like part_mix.
   T* part_in0 = nullptr;
   int flags = 0;             // LVL_*
+  // Last level of a network without an upstream gradient on its scalars (step.hip: levels_bwd; N <= 40 kernel only): every term that
+  // g_s_out == 0 makes an exact zero is left out -- g_s_out and ag0 are not read (may be null), the wm0 half of the part_mix row is
+  // not written.  The N > 40 kernels ignore it: the caller gives them the zero block as g_s_out.
+  int dead_scalars = 0;
 };
 
 // Per-node stride (in scalars) of the node tile kept in LDS: [c][ s_r s_i v_r[4] v_i[4] ] + 2 pad.

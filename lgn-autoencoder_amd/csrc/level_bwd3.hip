@@ -98,7 +98,12 @@ struct Bwd3 {
 // matrix instructions, with the basis rows and transposes that feed it -- on its tiles with I > J, whose share the owner of I adds.
 // 36 instead of 64 radial GEMM tiles per 30-particle jet; waves own the groups in pairs (p, G - 1 - p) so that each gets the same
 // number of them.  Node gradients flow exactly as before (every ordered tile still evaluates R and its edge).
-template <int C, bool DEC, bool SEP, int NWV, bool SYM = false>
+// NOS (LevelBwdArgs::dead_scalars: the last level of a network, whose scalars carry no gradient): g_s_out is identically zero, and so
+// are the gradients of the scalar aggregates (gA3, gA4), the scalar slots of the node / power blocks (a2, a3, a4) and the wm0 gradient.
+// Every term they multiply is left out -- a product with an exact zero added to an accumulator, which changes no bit of it -- and
+// neither g_s_out, ag0 nor the A3 / A4 slots of g_ag are read; the wm0 half of the partial row is not written (its gradient is a
+// row-less segment of the step's tail).  The terms that stay are the same instructions in the same order.
+template <int C, bool DEC, bool SEP, int NWV, bool SYM = false, bool NOS = false>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4 || DEC ? 2 : 1, C <= 4 || DEC ? 2 : 1))) void level_bwd3_kernel(LevelBwdArgs<double> a) {
   static_assert(!SYM || !DEC, "the symmetric sweep is the encoder's");
   using F = Bwd3<C, DEC, NWV>;
@@ -136,10 +141,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     const int eg = tid < N * CO ? tid : 0, ea_ = tid < N * 2 * C ? tid : 0, ew = tid < 2 * CO * K ? tid : 0;
     const size_t ig = (size_t)b * N * CO + eg, ia = (size_t)b * N * 2 * C + ea_;
     double rg[10], ra[10];
-    rg[0] = a.g_s_out[ig];
-    rg[1] = a.g_s_out[plo + ig];
-    ra[0] = a.ag0[ia];
-    ra[1] = a.ag0[pa + ia];
+    if constexpr (!NOS) {
+      rg[0] = a.g_s_out[ig];
+      rg[1] = a.g_s_out[plo + ig];
+      ra[0] = a.ag0[ia];
+      ra[1] = a.ag0[pa + ia];
+    }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       rg[2 + m] = a.g_v_out[ig * 4 + m];
@@ -151,11 +158,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     load_jet_commit<double, C, DEC>(a.s_in, a.v_in, a.p, a.mask, B, N, b, jr, nd, pj, mk);
     if (tid < N * CO) {
 #pragma unroll
-      for (int m = 0; m < 10; ++m) go[tid * 10 + m] = rg[m];
+      for (int m = NOS ? 2 : 0; m < 10; ++m) go[tid * 10 + m] = rg[m];
     }
     if (tid < N * 2 * C) {
 #pragma unroll
-      for (int m = 0; m < 10; ++m) agl[tid * 10 + m] = ra[m];
+      for (int m = NOS ? 2 : 0; m < 10; ++m) agl[tid * 10 + m] = ra[m];
     }
     if (tid < 2 * CO * K) {
       wm[tid] = w0v;
@@ -169,8 +176,10 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     for (int e = tid + BLK; e < N * CO; e += BLK) {
       const size_t idx = (size_t)b * N * CO + e;
       double* g = go + e * 10;
-      g[0] = a.g_s_out[idx];
-      g[1] = a.g_s_out[plo + idx];
+      if constexpr (!NOS) {
+        g[0] = a.g_s_out[idx];
+        g[1] = a.g_s_out[plo + idx];
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         g[2 + m] = a.g_v_out[idx * 4 + m];
@@ -180,8 +189,10 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     for (int e = tid + BLK; e < N * 2 * C; e += BLK) {
       const size_t ea = (size_t)b * N * 2 * C + e;
       double* x = agl + e * 10;
-      x[0] = a.ag0[ea];
-      x[1] = a.ag0[pa + ea];
+      if constexpr (!NOS) {
+        x[0] = a.ag0[ea];
+        x[1] = a.ag0[pa + ea];
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         x[2 + m] = a.ag1[ea * 4 + m];
@@ -204,22 +215,26 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         cx<double> gx0[2] = {{0, 0}, {0, 0}}, gx1[2][4] = {{{0, 0}, {0, 0}, {0, 0}, {0, 0}}, {{0, 0}, {0, 0}, {0, 0}, {0, 0}}};
         for (int o = 0; o < CO; ++o) {
           const double* g = go + (n * CO + o) * 10;
-          const cx<double> gs = {g[0], g[1]};
           cx<double> gv[4];
 #pragma unroll
           for (int m = 0; m < 4; ++m) gv[m] = {g[2 + m], g[6 + m]};
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
-            const cx<double> w0 = {w0r[(0 * CO + o) * K + q * C], w0r[(1 * CO + o) * K + q * C]};
             const cx<double> w1 = {w1r[(0 * CO + o) * K + q * C], w1r[(1 * CO + o) * K + q * C]};
-            cfmac(gx0[q], gs, w0);
+            if constexpr (!NOS) {
+              const cx<double> gs = {g[0], g[1]};
+              const cx<double> w0 = {w0r[(0 * CO + o) * K + q * C], w0r[(1 * CO + o) * K + q * C]};
+              cfmac(gx0[q], gs, w0);
+            }
 #pragma unroll
             for (int m = 0; m < 4; ++m) cfmac(gx1[q][m], gv[m], w1);
           }
         }
         double* gan = ga + n * G::SIZE;
-        gan[G::A3 + 2 * c] = gx0[0].r;  gan[G::A3 + 2 * c + 1] = gx0[0].i;
-        gan[G::A4 + 2 * c] = gx0[1].r;  gan[G::A4 + 2 * c + 1] = gx0[1].i;
+        if constexpr (!NOS) {
+          gan[G::A3 + 2 * c] = gx0[0].r;  gan[G::A3 + 2 * c + 1] = gx0[0].i;
+          gan[G::A4 + 2 * c] = gx0[1].r;  gan[G::A4 + 2 * c + 1] = gx0[1].i;
+        }
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           gan[G::A1 + (c * 4 + m) * 2] = gx1[0][m].r;  gan[G::A1 + (c * 4 + m) * 2 + 1] = gx1[0][m].i;
@@ -231,14 +246,16 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         cx<double> b2[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, b34[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
         for (int o = 0; o < CO; ++o) {
           const double* g = go + (n * CO + o) * 10;
-          const cx<double> gs = {g[0], g[1]};
-          const double* wr0 = w0r + (0 * CO + o) * K;
-          const double* wi0 = w0r + (1 * CO + o) * K;
           const double* wr1 = w1r + (0 * CO + o) * K;
           const double* wi1 = w1r + (1 * CO + o) * K;
-          cfmac(a2, gs, cx<double>{wr0[2 * C], wi0[2 * C]});
-          cfmac(a3, gs, cx<double>{wr0[3 * C], wi0[3 * C]});
-          cfmac(a4, gs, cx<double>{wr0[4 * C], wi0[4 * C]});
+          if constexpr (!NOS) {
+            const cx<double> gs = {g[0], g[1]};
+            const double* wr0 = w0r + (0 * CO + o) * K;
+            const double* wi0 = w0r + (1 * CO + o) * K;
+            cfmac(a2, gs, cx<double>{wr0[2 * C], wi0[2 * C]});
+            cfmac(a3, gs, cx<double>{wr0[3 * C], wi0[3 * C]});
+            cfmac(a4, gs, cx<double>{wr0[4 * C], wi0[4 * C]});
+          }
           const cx<double> w2 = {wr1[2 * C], wi1[2 * C]};
           const cx<double> w34 = {wr1[3 * C] + wr1[4 * C], wi1[3 * C] + wi1[4 * C]};
 #pragma unroll
@@ -255,15 +272,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         for (int m = 0; m < 4; ++m) v[m] = {ni[2 + m], ni[6 + m]};
         metric_perm(v, vt);
         // node block + power blocks: sq(0,0) = [<v,v>, s^2], sq(1,1) = [v s, s v]
-        cx<double> gs = a2;
-        cfmac(gs, cx<double>{2.0 * a4.r, 2.0 * a4.i}, s);
+        cx<double> gs = a2;                                 // (NOS: a2 = a3 = a4 = 0)
+        if constexpr (!NOS) cfmac(gs, cx<double>{2.0 * a4.r, 2.0 * a4.i}, s);
         double* gdn = gd + (n * C + c) * 10;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           cfmac(gs, b34[m], v[m]);
           cx<double> gv = b2[m];
           cfmac(gv, b34[m], s);
-          cfmac(gv, a3, vt[m]);
+          if constexpr (!NOS) cfmac(gv, a3, vt[m]);
           gdn[2 + m] = gv.r;
           gdn[6 + m] = gv.i;
         }
@@ -291,7 +308,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         cx<double> x0, x1[4];
         if (q < 2) {                                  // aggregate blocks, saved by the forward
           const double* x = agl + (n * 2 * C + k) * 10;
-          x0 = {x[0], x[1]};
+          if constexpr (!NOS) x0 = {x[0], x[1]};
 #pragma unroll
           for (int m = 0; m < 4; ++m) x1[m] = {x[2 + m], x[6 + m]};
         } else {
@@ -301,11 +318,13 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
 #pragma unroll
           for (int m = 0; m < 4; ++m) v[m] = {ni[2 + m], ni[6 + m]};
           if (q == 2) {                               // node block
-            x0 = s;
+            if constexpr (!NOS) x0 = s;
 #pragma unroll
             for (int m = 0; m < 4; ++m) x1[m] = v[m];
           } else {                                    // power blocks: (0,0): <v,v> | s^2 ; (1,1): v s | s v
-            if (q == 3) { x0 = bil2(v, v); x0.r *= 0.5; x0.i *= 0.5; } else x0 = cmul(s, s);
+            if constexpr (!NOS) {
+              if (q == 3) { x0 = bil2(v, v); x0.r *= 0.5; x0.i *= 0.5; } else x0 = cmul(s, s);
+            }
 #pragma unroll
             for (int m = 0; m < 4; ++m) x1[m] = cmul(v[m], s);
           }
@@ -314,7 +333,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         for (int o = 0; o < 8; ++o)
           if (o < CO) {
             const double* g = go + (n * CO + o) * 10;
-            cfmac(d0[o], cx<double>{g[0], g[1]}, x0);
+            if constexpr (!NOS) cfmac(d0[o], cx<double>{g[0], g[1]}, x0);
 #pragma unroll
             for (int m = 0; m < 4; ++m) cfmac(d1[o], cx<double>{g[2 + m], g[6 + m]}, x1[m]);
           }
@@ -329,7 +348,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       for (int o = 0; o < 8; ++o)
         if (o < CO) {
           double* r4 = red + ((pi * CO + o) * K + k) * 4;
-          r4[0] = d0[o].r;  r4[1] = d0[o].i;  r4[2] = d1[o].r;  r4[3] = d1[o].i;
+          if constexpr (!NOS) { r4[0] = d0[o].r;  r4[1] = d0[o].i; }
+          r4[2] = d1[o].r;  r4[3] = d1[o].i;
         }
     }
     STAMP(50);
@@ -339,6 +359,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     // (partial row: [x][o][k], x = re / im of the (0,0) weights, re / im of the (1,1) weights)
     for (int ex = tid; ex < 4 * OK; ex += BLK) {
       const int e = ex >> 2, x = ex & 3;
+      if (NOS && x < 2) continue;                     // (the wm0 half: identically zero, nobody reduces it)
       double v = red[ex];
 #pragma unroll
       for (int pp = 1; pp < NPART; ++pp) v += red[pp * OK * 4 + ex];
@@ -403,9 +424,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         }
         const cx<double> vp = bil2(v, pc);
         LGN_PUT(18, vp.r);  LGN_PUT(19, vp.i);
-        const cx<double> g3 = {0.5 * gi[G::A3 + 2 * c], 0.5 * gi[G::A3 + 2 * c + 1]};
-        LGN_PUT(20, gi[G::A4 + 2 * c]);  LGN_PUT(21, gi[G::A4 + 2 * c + 1]);
-        LGN_PUT(22, g3.r);  LGN_PUT(23, g3.i);
+        cx<double> g3 = {0, 0};                             // (NOS: SG4, SG3 and GP3 are zero and nothing below reads them)
+        if constexpr (!NOS) {
+          g3 = {0.5 * gi[G::A3 + 2 * c], 0.5 * gi[G::A3 + 2 * c + 1]};
+          LGN_PUT(20, gi[G::A4 + 2 * c]);  LGN_PUT(21, gi[G::A4 + 2 * c + 1]);
+          LGN_PUT(22, g3.r);  LGN_PUT(23, g3.i);
+        }
         cx<double> gp2 = {0, 0};
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -414,8 +438,10 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
           LGN_PUT(24 + 2 * m, g1.r);  LGN_PUT(25 + 2 * m, g1.i);
           LGN_PUT(32 + 2 * m, g2.r);  LGN_PUT(33 + 2 * m, g2.i);
           cfmac(gp2, g2, pc[m]);
-          const cx<double> gp3 = cmulc(g3, pc[m]);
-          LGN_PUT(42 + 2 * m, gp3.r);  LGN_PUT(43 + 2 * m, gp3.i);
+          if constexpr (!NOS) {
+            const cx<double> gp3 = cmulc(g3, pc[m]);
+            LGN_PUT(42 + 2 * m, gp3.r);  LGN_PUT(43 + 2 * m, gp3.i);
+          }
         }
         LGN_PUT(40, gp2.r);  LGN_PUT(41, gp2.i);
       }
@@ -454,7 +480,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         const cx<double> t = cmulc(cx<double>{q[32 + 2 * m], q[33 + 2 * m]}, pc[m]);
         u.r -= t.r;  u.i -= t.i;
       }
-      cx<double> gs = cmulc(SG4, e0);
+      cx<double> gs = {0, 0};
+      if constexpr (!NOS) gs = cmulc(SG4, e0);
       cfmac(gs, u, R1);
       const size_t ge = ((size_t)b * N + n) * C + c;
       a.g_s_in[ge] = gdn[0] + gs.r;
@@ -462,11 +489,13 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       // Gv[m] = conj(e0) SG1[m] + conj(R1) (GPT3[m] - SG3 conj(pt[m]))
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        cx<double> w = GPT3[m];
-        const cx<double> t = cmulc(SG3, pt[m]);
-        w.r -= t.r;  w.i -= t.i;
         cx<double> gv = cmulc(cx<double>{q[24 + 2 * m], q[25 + 2 * m]}, e0);
-        cfmac(gv, w, R1);
+        if constexpr (!NOS) {
+          cx<double> w = GPT3[m];
+          const cx<double> t = cmulc(SG3, pt[m]);
+          w.r -= t.r;  w.i -= t.i;
+          cfmac(gv, w, R1);
+        }
         a.g_v_in[ge * 4 + m] = gdn[2 + m] + gv.r;
         a.g_v_in[pls * 4 + ge * 4 + m] = gdn[6 + m] + gv.i;
       }
@@ -489,13 +518,17 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
           const cx<double> VSt = {sg * q[2 + 2 * mp], sg * q[3 + 2 * mp]};
           const cx<double> vt = {sg * ni[2 + mp], sg * ni[6 + mp]};
           const cx<double> g2 = {gi[G::A2 + (c * 4 + m) * 2], gi[G::A2 + (c * 4 + m) * 2 + 1]};
-          const cx<double> g3 = {0.5 * gi[G::A3 + 2 * c], 0.5 * gi[G::A3 + 2 * c + 1]};
           cx<double> t = cmulc(g2, S);
-          cfmac(t, g3, VSt);
+          if constexpr (!NOS) {
+            const cx<double> g3 = {0.5 * gi[G::A3 + 2 * c], 0.5 * gi[G::A3 + 2 * c + 1]};
+            cfmac(t, g3, VSt);
+          }
           const cx<double> t2 = cmulc(cx<double>{q[32 + 2 * m], q[33 + 2 * m]}, cx<double>{ni[0], ni[1]});
           t.r -= t2.r;  t.i -= t2.i;
-          const cx<double> t3 = cmulc(SG3, vt);
-          t.r -= t3.r;  t.i -= t3.i;
+          if constexpr (!NOS) {
+            const cx<double> t3 = cmulc(SG3, vt);
+            t.r -= t3.r;  t.i -= t3.i;
+          }
           cfmac(acc, t, R1);
         }
         a.g_p[((size_t)b * N + n) * 4 + m] += acc.r;
@@ -509,7 +542,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       const cx<double> S = {q[0], q[1]};
       double* part = a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, true);
       if (lin == 0) {
-        cx<double> E0 = cmulc(cx<double>{q[20], q[21]}, S);
+        cx<double> E0 = {0, 0};
+        if constexpr (!NOS) E0 = cmulc(cx<double>{q[20], q[21]}, S);
 #pragma unroll
         for (int m = 0; m < 4; ++m) cfmac(E0, cx<double>{q[24 + 2 * m], q[25 + 2 * m]}, cx<double>{q[2 + 2 * m], q[3 + 2 * m]});
         part[tid] = (E0.r + E0.i) + (E0.i - E0.r);          // R0 = b0 (1+i): d b0 = Re G_R0 + Im G_R0, G_R0 = G_e0 (1-i)
@@ -519,11 +553,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         for (int m = 0; m < 4; ++m) VS[m] = {q[2 + 2 * m], q[3 + 2 * m]};
         metric_perm(VS, VSt);
         cx<double> E1 = cmulc(cx<double>{q[40], q[41]}, S);
-        cx<double> neg = cmulc(cx<double>{q[22], q[23]}, cx<double>{q[18], q[19]});
+        cx<double> neg = {0, 0};
+        if constexpr (!NOS) neg = cmulc(cx<double>{q[22], q[23]}, cx<double>{q[18], q[19]});
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
           cfmac(neg, cx<double>{q[32 + 2 * m], q[33 + 2 * m]}, cx<double>{q[10 + 2 * m], q[11 + 2 * m]});
-          cfmac(E1, cx<double>{q[42 + 2 * m], q[43 + 2 * m]}, VSt[m]);
+          if constexpr (!NOS) cfmac(E1, cx<double>{q[42 + 2 * m], q[43 + 2 * m]}, VSt[m]);
         }
         part[tid] = (E1.r - neg.r) + (E1.i - neg.i);
       }
@@ -707,16 +742,22 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         if (ok && ch < C) {
           const cx<double> R0 = {R[g][0], R[g][1]}, R1 = {R[g][2], R[g][3]};
           const cx<double> e0 = {R0.r - R0.i, R0.r + R0.i};
-          const cx<double> gA3 = {0.5 * gi[G::A3 + 2 * ch], 0.5 * gi[G::A3 + 2 * ch + 1]};
-          const cx<double> gA4 = {gi[G::A4 + 2 * ch], gi[G::A4 + 2 * ch + 1]};
+          cx<double> gA3 = {0, 0}, gA4 = {0, 0};           // (NOS: zero, and every term they multiply is left out below)
+          if constexpr (!NOS) {
+            gA3 = {0.5 * gi[G::A3 + 2 * ch], 0.5 * gi[G::A3 + 2 * ch + 1]};
+            gA4 = {gi[G::A4 + 2 * ch], gi[G::A4 + 2 * ch + 1]};
+          }
           cx<double> gA1[4], gA2[4];
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             gA1[m] = {gi[G::A1 + (ch * 4 + m) * 2], gi[G::A1 + (ch * 4 + m) * 2 + 1]};
             gA2[m] = {gi[G::A2 + (ch * 4 + m) * 2], gi[G::A2 + (ch * 4 + m) * 2 + 1]};
           }
-          cfmac(Gs[g], gA4, e0);
-          cx<double> ge0 = cmulc(gA4, sj[g]);
+          cx<double> ge0 = {0, 0};
+          if constexpr (!NOS) {
+            cfmac(Gs[g], gA4, e0);
+            ge0 = cmulc(gA4, sj[g]);
+          }
           cx<double> gR1;
           if (!DEC) {
             // The edge e1[m] = R1 q[m] enters only through P2 = sum_m gA2[m] conj(q[m]), V = <v_j, q> and Z = gA3 conj(R1);
@@ -726,25 +767,29 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
             P2.r = __builtin_fma(gA2[0].r, qd0, __builtin_fma(gA2[2].r, qd3, __builtin_fma(qa, dg.r, -qb * sg.i)));
             P2.i = __builtin_fma(gA2[0].i, qd0, __builtin_fma(gA2[2].i, qd3, __builtin_fma(qa, dg.i, qb * sg.r)));
             cfmac(Gs[g], P2, R1);                              // sum_m gA2[m] conj(e1[m]) = conj(R1) P2
-            const cx<double> Z = cmulc(gA3, R1);              // gA3 conj(e1t[m]) = Z conj(qt[m])
 #pragma unroll
             for (int m = 0; m < 4; ++m) cfmac(Gv[g][m], gA1[m], e0);
-            Gv[g][0].r = __builtin_fma(Z.r, qd0, Gv[g][0].r);   Gv[g][0].i = __builtin_fma(Z.i, qd0, Gv[g][0].i);
-            Gv[g][2].r = __builtin_fma(-Z.r, qd3, Gv[g][2].r);  Gv[g][2].i = __builtin_fma(-Z.i, qd3, Gv[g][2].i);
-            const double aZr = qa * Z.r, aZi = qa * Z.i;
-            const double bZr = qb * Z.r, bZi = qb * Z.i;
-            Gv[g][1].r -= aZr + bZi;  Gv[g][1].i += bZr - aZi;   // Z (-a + ib)
-            Gv[g][3].r += aZr - bZi;  Gv[g][3].i += aZi + bZr;   // Z ( a + ib)
+            if constexpr (!NOS) {
+              const cx<double> Z = cmulc(gA3, R1);              // gA3 conj(e1t[m]) = Z conj(qt[m])
+              Gv[g][0].r = __builtin_fma(Z.r, qd0, Gv[g][0].r);   Gv[g][0].i = __builtin_fma(Z.i, qd0, Gv[g][0].i);
+              Gv[g][2].r = __builtin_fma(-Z.r, qd3, Gv[g][2].r);  Gv[g][2].i = __builtin_fma(-Z.i, qd3, Gv[g][2].i);
+              const double aZr = qa * Z.r, aZi = qa * Z.i;
+              const double bZr = qb * Z.r, bZi = qb * Z.i;
+              Gv[g][1].r -= aZr + bZi;  Gv[g][1].i += bZr - aZi;   // Z (-a + ib)
+              Gv[g][3].r += aZr - bZi;  Gv[g][3].i += aZi + bZr;   // Z ( a + ib)
+            }
             gR1 = {0, 0};
             if (kind != 0) {                                   // (b) gradient w.r.t. the radial values of this pair
 #pragma unroll
               for (int m = 0; m < 4; ++m) cfmac(ge0, gA1[m], vj[g][m]);
-              // V = <v_j, q> = v0 d0 - v2 d3 + a (v3 - v1) - ib (v1 + v3)
-              cx<double> V;
-              V.r = __builtin_fma(vj[g][0].r, qd0, __builtin_fma(-vj[g][2].r, qd3, __builtin_fma(qa, dvj[g].r, qb * svj[g].i)));
-              V.i = __builtin_fma(vj[g][0].i, qd0, __builtin_fma(-vj[g][2].i, qd3, __builtin_fma(qa, dvj[g].i, -qb * svj[g].r)));
               gR1 = cmulc(P2, sj[g]);                          // sum_m ge1[m] conj(q[m]) = conj(s_j) P2 + gA3 conj(V)
-              cfmac(gR1, gA3, V);
+              if constexpr (!NOS) {
+                // V = <v_j, q> = v0 d0 - v2 d3 + a (v3 - v1) - ib (v1 + v3)
+                cx<double> V;
+                V.r = __builtin_fma(vj[g][0].r, qd0, __builtin_fma(-vj[g][2].r, qd3, __builtin_fma(qa, dvj[g].r, qb * svj[g].i)));
+                V.i = __builtin_fma(vj[g][0].i, qd0, __builtin_fma(-vj[g][2].i, qd3, __builtin_fma(qa, dvj[g].i, -qb * svj[g].r)));
+                cfmac(gR1, gA3, V);
+              }
             }
             if constexpr (SYM) {
               if (kind == 2) {
@@ -756,9 +801,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
                 cx<double> vi[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) vi[m] = {ni[2 + m], ni[6 + m]};
-                const cx<double> hA3 = {0.5 * gj[G::A3 + 2 * ch], 0.5 * gj[G::A3 + 2 * ch + 1]};
-                const cx<double> hA4 = {gj[G::A4 + 2 * ch], gj[G::A4 + 2 * ch + 1]};
-                cx<double> he0 = cmulc(hA4, si);
+                cx<double> he0 = {0, 0};
+                if constexpr (!NOS) {
+                  const cx<double> hA4 = {gj[G::A4 + 2 * ch], gj[G::A4 + 2 * ch + 1]};
+                  he0 = cmulc(hA4, si);
+                }
                 cx<double> hA2[4];
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
@@ -770,12 +817,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
                 cx<double> Q2;                                 // sum_m hA2[m] conj(q[m]) (the reverse edge's is its negative)
                 Q2.r = __builtin_fma(hA2[0].r, qd0, __builtin_fma(hA2[2].r, qd3, __builtin_fma(qa, hd.r, -qb * hs.i)));
                 Q2.i = __builtin_fma(hA2[0].i, qd0, __builtin_fma(hA2[2].i, qd3, __builtin_fma(qa, hd.i, qb * hs.r)));
-                const cx<double> dvi = {vi[3].r - vi[1].r, vi[3].i - vi[1].i}, svi = {vi[1].r + vi[3].r, vi[1].i + vi[3].i};
-                cx<double> W;                                  // <v_i, q>
-                W.r = __builtin_fma(vi[0].r, qd0, __builtin_fma(-vi[2].r, qd3, __builtin_fma(qa, dvi.r, qb * svi.i)));
-                W.i = __builtin_fma(vi[0].i, qd0, __builtin_fma(-vi[2].i, qd3, __builtin_fma(qa, dvi.i, -qb * svi.r)));
                 cx<double> hR1 = cmulc(Q2, si);
-                cfmac(hR1, hA3, W);
+                if constexpr (!NOS) {
+                  const cx<double> hA3 = {0.5 * gj[G::A3 + 2 * ch], 0.5 * gj[G::A3 + 2 * ch + 1]};
+                  const cx<double> dvi = {vi[3].r - vi[1].r, vi[3].i - vi[1].i}, svi = {vi[1].r + vi[3].r, vi[1].i + vi[3].i};
+                  cx<double> W;                                  // <v_i, q>
+                  W.r = __builtin_fma(vi[0].r, qd0, __builtin_fma(-vi[2].r, qd3, __builtin_fma(qa, dvi.r, qb * svi.i)));
+                  W.i = __builtin_fma(vi[0].i, qd0, __builtin_fma(-vi[2].i, qd3, __builtin_fma(qa, dvi.i, -qb * svi.r)));
+                  cfmac(hR1, hA3, W);
+                }
                 ge0.r += he0.r;  ge0.i += he0.i;
                 gR1.r -= hR1.r;  gR1.i -= hR1.i;
               }
@@ -790,12 +840,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
             for (int m = 0; m < 4; ++m) {
               // (a) gradient w.r.t. the source node j
               cfmac(Gv[g][m], gA1[m], e0);
-              cfmac(Gv[g][m], gA3, e1t[m]);
+              if constexpr (!NOS) cfmac(Gv[g][m], gA3, e1t[m]);
               cfmac(Gs[g], gA2[m], e1[m]);
               // (b) gradient w.r.t. the edge of this pair
               cfmac(ge0, gA1[m], vj[g][m]);
               cx<double> ge1 = cmulc(gA2[m], sj[g]);
-              cfmac(ge1, gA3, vtj[g][m]);
+              if constexpr (!NOS) cfmac(ge1, gA3, vtj[g][m]);
               cfmac(gR1, ge1, q[m]);
               cfmac(Gq[m], ge1, R1);
             }
@@ -869,10 +919,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       const int ch = 4 * g + cg;
       const double sr = rs > 1 ? Gs[g].r : quad_sum(Gs[g].r), si = rs > 1 ? Gs[g].i : quad_sum(Gs[g].i);
       const bool wr = jok && ti == 0 && ch < C;
+      // (with the input stage's backward riding below, the node gradient ends here: nothing after this kernel reads g_s_in / g_v_in)
+      const bool st = wr && (DEC || !a.part_in0);
       const size_t e = ((size_t)b * N + jj) * C + (ch < C ? ch : 0);
       const double* gdn = gd + (jj * C + (ch < C ? ch : 0)) * 10;
       const double gsr = gdn[0] + sr, gsi = gdn[1] + si;
-      if (wr) {
+      if (st) {
         a.g_s_in[e] = gsr;
         a.g_s_in[pls + e] = gsi;
       }
@@ -881,7 +933,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       for (int m = 0; m < 4; ++m) {
         const double vr = rs > 1 ? Gv[g][m].r : quad_sum(Gv[g][m].r), vi = rs > 1 ? Gv[g][m].i : quad_sum(Gv[g][m].i);
         gvn[m] = {gdn[2 + m] + vr, gdn[6 + m] + vi};
-        if (wr) {
+        if (st) {
           a.g_v_in[e * 4 + m] = gvn[m].r;
           a.g_v_in[pls * 4 + e * 4 + m] = gvn[m].i;
         }
@@ -943,12 +995,13 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
               for (int m = 0; m < 4; ++m) v[m] = {nj[2 + m], nj[6 + m]};
               metric_perm(v, vt);
               const cx<double> R1 = {bias[g][2], bias[g][3]};
-              const cx<double> gA3 = {0.5 * gi[G::A3 + 2 * ch], 0.5 * gi[G::A3 + 2 * ch + 1]};
+              cx<double> gA3 = {0, 0};
+              if constexpr (!NOS) gA3 = {0.5 * gi[G::A3 + 2 * ch], 0.5 * gi[G::A3 + 2 * ch + 1]};
 #pragma unroll
               for (int m = 0; m < 4; ++m) {
                 const cx<double> gA2 = {gi[G::A2 + (ch * 4 + m) * 2], gi[G::A2 + (ch * 4 + m) * 2 + 1]};
                 cx<double> ge1 = cmulc(gA2, s);
-                cfmac(ge1, gA3, vt[m]);
+                if constexpr (!NOS) cfmac(ge1, gA3, vt[m]);
                 cfmac(Gq[m], ge1, R1);
               }
             }
@@ -1067,15 +1120,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
 
 bool level_bwd3_fits(int N) { return N <= 40; }
 
-template <int C, bool DEC, bool SEP, int NWV>
+template <int C, bool DEC, bool SEP, int NWV, bool NOS>
 static int launch_bwd3_w(const LevelBwdArgs<double>& a, int split, hipStream_t stream) {
   size_t smem = Bwd3<C, DEC, NWV>::smem(a.N, a.CO);
   LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd: N=%d C=%d needs %zu B of LDS", a.N, a.C, smem);
   LGN_CHECK_ARG(a.CO <= 8, "level_bwd: C_out=%d unsupported (1..8)", a.CO);
-  auto kern = level_bwd3_kernel<C, DEC, SEP, NWV>;
+  auto kern = level_bwd3_kernel<C, DEC, SEP, NWV, false, NOS>;
   if constexpr (!DEC && C <= 4) {       // whole jets per workgroup: the sweep that uses R(i, j) = R(j, i) (LVL_BWD_ORDERED: the plain one;
                                         // C > 4: two lane groups of channels, the second pass would double the spills)
-    if (split == 1 && !(a.flags & LVL_BWD_ORDERED)) kern = level_bwd3_kernel<C, DEC, SEP, NWV, true>;
+    if (split == 1 && !(a.flags & LVL_BWD_ORDERED)) kern = level_bwd3_kernel<C, DEC, SEP, NWV, true, NOS>;
   }
   if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   hipLaunchKernelGGL(kern, dim3(a.B, split), dim3(64 * NWV), smem, stream, a);
@@ -1085,7 +1138,8 @@ static int launch_bwd3_w(const LevelBwdArgs<double>& a, int split, hipStream_t s
 template <int C, bool DEC, bool SEP>
 static int launch_bwd3(const LevelBwdArgs<double>& a, hipStream_t stream) {
   // small batches: several workgroups per jet (level.hpp: level_jet_split); the separable decoder form has no sweep to split
-  return launch_bwd3_w<C, DEC, SEP, 4>(a, SEP ? 1 : level_jet_split(a.B, a.N), stream);
+  const int split = SEP ? 1 : level_jet_split(a.B, a.N);
+  return a.dead_scalars ? launch_bwd3_w<C, DEC, SEP, 4, true>(a, split, stream) : launch_bwd3_w<C, DEC, SEP, 4, false>(a, split, stream);
 }
 
 // whole level backward in one launch; one CatMix partial row and one radial partial row per jet

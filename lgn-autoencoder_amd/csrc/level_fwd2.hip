@@ -70,7 +70,10 @@ struct Fwd2 {
 // O(N C) instead of O(N^2 C) work per jet, same values up to summation order.  SEP = false keeps the pair sweep.
 // TRAIN = false (evaluation step, level_fwd_eval): the aggregate is not stored (nothing runs a backward) and the riding loss tail
 // is its forward-only form; the sweep, its summation order, CatMix and the riding input stage are the same code.
-template <int C, bool DEC, bool SEP, bool TRAIN>
+// NOS (LevelArgs::dead_scalars: a last level whose scalar output nobody reads): the scalar aggregates A3 / A4 and the values only they
+// need are not accumulated, the scalar CatMix rows are not run (wave 0 takes a share of the vector items), s_out and ag0 are not
+// stored; every vector value is computed by the same instructions in the same order.
+template <int C, bool DEC, bool SEP, bool TRAIN, bool NOS>
 __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double> a, int chunk) {
   using F = Fwd2<C, DEC>;
   constexpr int NG = F::NG;
@@ -230,8 +233,10 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
           const cx<double> sp = cmul(sn, pc[m]);
           LGN_PUT(10 + 2 * m, sp.r);  LGN_PUT(11 + 2 * m, sp.i);
         }
-        const cx<double> vp = bil2(v, pc);
-        LGN_PUT(18, vp.r);  LGN_PUT(19, vp.i);
+        if constexpr (!NOS) {
+          const cx<double> vp = bil2(v, pc);
+          LGN_PUT(18, vp.r);  LGN_PUT(19, vp.i);
+        }
       }
       wave_sum_store<12>(a0, sums + c * 20, lane);
       wave_sum_store<8>(a1, sums + c * 20 + 12, lane);
@@ -252,7 +257,9 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
     constexpr int K = 5 * C;
     const int nr = c1 - c0;
     const size_t plo = (size_t)B * N * CO;
-    if (wave == 0) {
+    // (NOS: no scalar rows -- the vector items go round all the waves)
+    const int vfirst = NOS ? tid : lane + 64 * (wave - 1), vstep = NOS ? nthr : 64 * (nw - 1);
+    if (!NOS && wave == 0) {
       for (int rl = lane; rl < nr; rl += 64) {
         const int r = c0 + rl;
         const double* st = agl + rl * F::AGS;
@@ -285,7 +292,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
         }
       }
     } else {
-      for (int it = lane + 64 * (wave - 1); it < nr * 4; it += 64 * (nw - 1)) {
+      for (int it = vfirst; it < nr * 4; it += vstep) {
         const int rl = it >> 2, m = it & 3, r = c0 + rl;
         const double* st = agl + rl * F::AGS;
         const double* ni = nd + r * F::NS;
@@ -330,12 +337,14 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
         pc[m] = {pn[m], pn[4 + m]};
       }
       double* st = agl + rl * F::AGS;
-      const cx<double> a4 = cmul(S, e0);
-      cx<double> t = bil2(VS, pc);
-      t.r -= sm[18];  t.i -= sm[19];
-      cx<double> a3 = cmul(R1, t);
-      st[F::A3 + 2 * c] = 0.5 * a3.r;  st[F::A3 + 2 * c + 1] = 0.5 * a3.i;
-      st[F::A4 + 2 * c] = a4.r;        st[F::A4 + 2 * c + 1] = a4.i;
+      if constexpr (!NOS) {
+        const cx<double> a4 = cmul(S, e0);
+        cx<double> t = bil2(VS, pc);
+        t.r -= sm[18];  t.i -= sm[19];
+        cx<double> a3 = cmul(R1, t);
+        st[F::A3 + 2 * c] = 0.5 * a3.r;  st[F::A3 + 2 * c + 1] = 0.5 * a3.i;
+        st[F::A4 + 2 * c] = a4.r;        st[F::A4 + 2 * c + 1] = a4.i;
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         const cx<double> a1 = cmul(VS[m], e0);
@@ -435,7 +444,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
               vj[m] = {nj[ch * 10 + 2 + m], nj[ch * 10 + 6 + m]};
               cfma(A1[g][m], vj[m], e0);
             }
-            cfma(A4[g], sj, e0);
+            if constexpr (!NOS) cfma(A4[g], sj, e0);
             if (!DEC) {
               // e1[m] = R1 q[m] with real momenta q = [d0, a - ib, d3, -a - ib]:
               //   A2[m] += (s_j R1) q[m],   A3 += R1 <v_j, q>,  <v_j, q> = v0 d0 - v2 d3 + a (v3 - v1) - ib (v1 + v3)
@@ -446,11 +455,13 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
               const double aTr = qa * Tm.r, aTi = qa * Tm.i, bTr = qb * Tm.r, bTi = qb * Tm.i;
               A2[g][1].r += aTr + bTi;  A2[g][1].i += aTi - bTr;       // T ( a - ib)
               A2[g][3].r += bTi - aTr;  A2[g][3].i -= aTi + bTr;       // T (-a - ib)
-              const cx<double> dv = {vj[3].r - vj[1].r, vj[3].i - vj[1].i}, sv = {vj[1].r + vj[3].r, vj[1].i + vj[3].i};
-              cx<double> V;
-              V.r = __builtin_fma(vj[0].r, qd0, __builtin_fma(-vj[2].r, qd3, __builtin_fma(qa, dv.r, qb * sv.i)));
-              V.i = __builtin_fma(vj[0].i, qd0, __builtin_fma(-vj[2].i, qd3, __builtin_fma(qa, dv.i, -qb * sv.r)));
-              cfma(A3[g], R1, V);
+              if constexpr (!NOS) {
+                const cx<double> dv = {vj[3].r - vj[1].r, vj[3].i - vj[1].i}, sv = {vj[1].r + vj[3].r, vj[1].i + vj[3].i};
+                cx<double> V;
+                V.r = __builtin_fma(vj[0].r, qd0, __builtin_fma(-vj[2].r, qd3, __builtin_fma(qa, dv.r, qb * sv.i)));
+                V.i = __builtin_fma(vj[0].i, qd0, __builtin_fma(-vj[2].i, qd3, __builtin_fma(qa, dv.i, -qb * sv.r)));
+                cfma(A3[g], R1, V);
+              }
             } else {
               cx<double> e1[4];
 #pragma unroll
@@ -458,9 +469,11 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
                 e1[m] = cmul(R1, T.q[m]);
                 cfma(A2[g][m], sj, e1[m]);
               }
-              const cx<double> t = bil2(vj, e1);
-              A3[g].r += t.r;
-              A3[g].i += t.i;
+              if constexpr (!NOS) {
+                const cx<double> t = bil2(vj, e1);
+                A3[g].r += t.r;
+                A3[g].i += t.i;
+              }
             }
           }
         }
@@ -486,8 +499,10 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
     // ---- combine the 4 neighbour slots of a tile (quad lanes), stage + store the aggregate -----------------
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-      A3[g].r = quad_sum(A3[g].r) * 0.5;  A3[g].i = quad_sum(A3[g].i) * 0.5;
-      A4[g].r = quad_sum(A4[g].r);        A4[g].i = quad_sum(A4[g].i);
+      if constexpr (!NOS) {
+        A3[g].r = quad_sum(A3[g].r) * 0.5;  A3[g].i = quad_sum(A3[g].i) * 0.5;
+        A4[g].r = quad_sum(A4[g].r);        A4[g].i = quad_sum(A4[g].i);
+      }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         A1[g][m].r = quad_sum(A1[g][m].r);  A1[g][m].i = quad_sum(A1[g][m].i);
@@ -500,8 +515,10 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
       for (int g = 0; g < NG; ++g) {
         const int ch = 4 * g + cg;
         if (ch < C) {
-          st[F::A3 + 2 * ch] = A3[g].r;  st[F::A3 + 2 * ch + 1] = A3[g].i;
-          st[F::A4 + 2 * ch] = A4[g].r;  st[F::A4 + 2 * ch + 1] = A4[g].i;
+          if constexpr (!NOS) {
+            st[F::A3 + 2 * ch] = A3[g].r;  st[F::A3 + 2 * ch + 1] = A3[g].i;
+            st[F::A4 + 2 * ch] = A4[g].r;  st[F::A4 + 2 * ch + 1] = A4[g].i;
+          }
 #pragma unroll
           for (int m = 0; m < 4; ++m) {
             st[F::A1 + (ch * 4 + m) * 2] = A1[g][m].r;  st[F::A1 + (ch * 4 + m) * 2 + 1] = A1[g][m].i;
@@ -522,6 +539,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
     __syncthreads();
     const int tot = 4 * ngr * F::AGS;
     for (int e = tid; e < tot; e += nthr) {
+      if (NOS && e % F::AGS < F::A1) continue;              // (the A3 / A4 slots hold nothing)
       double v = agl[e];
       for (int pp = 1; pp < rs; ++pp) v += agl[pp * tot + e];
       agl[e] = v;
@@ -534,12 +552,14 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   // ---- aggregate -> global (saved for the backward): ag0 [2][B][N][2C], ag1 [2][B][N][2C][4] -----------------------
   if constexpr (TRAIN) {
     const size_t pl0 = (size_t)B * N * 2 * C;
-    for (int e = tid; e < (c1 - c0) * 2 * C; e += nthr) {        // e = n * 2C + (blk * C + ch), blk 0: A3, 1: A4
-      const int n = e / (2 * C), r = e - n * 2 * C, blk = r / C, ch = r - blk * C;
-      const double* st = agl + n * F::AGS + (blk ? F::A4 : F::A3) + 2 * ch;
-      const size_t ge = ((size_t)b * N + c0) * 2 * C + e;
-      a.ag0[ge] = st[0];
-      a.ag0[pl0 + ge] = st[1];
+    if constexpr (!NOS) {
+      for (int e = tid; e < (c1 - c0) * 2 * C; e += nthr) {        // e = n * 2C + (blk * C + ch), blk 0: A3, 1: A4
+        const int n = e / (2 * C), r = e - n * 2 * C, blk = r / C, ch = r - blk * C;
+        const double* st = agl + n * F::AGS + (blk ? F::A4 : F::A3) + 2 * ch;
+        const size_t ge = ((size_t)b * N + c0) * 2 * C + e;
+        a.ag0[ge] = st[0];
+        a.ag0[pl0 + ge] = st[1];
+      }
     }
     for (int e = tid; e < (c1 - c0) * 2 * C * 4; e += nthr) {    // e = (n * 2C + blk * C + ch) * 4 + m, blk 0: A1, 1: A2
       const int n = e / (8 * C), r = e - n * 8 * C, blk = r / (4 * C), cm = r - blk * 4 * C;
@@ -565,7 +585,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   }
 }
 
-template <int C, bool DEC, bool SEP, bool TRAIN>
+template <int C, bool DEC, bool SEP, bool TRAIN, bool NOS>
 static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
   using F = Fwd2<C, DEC>;
   // aggregate rows kept in LDS: the whole jet if that still leaves room for two workgroups per CU (or nothing does),
@@ -589,7 +609,7 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
     if (smem < dec_out_loss_bytes(a.N, a.CO)) smem = dec_out_loss_bytes(a.N, a.CO);
   }
   LGN_CHECK_ARG(smem <= 160 * 1024, "level_fwd: N=%d C=%d needs %zu B of LDS (> 160 KiB)", a.N, a.C, smem);
-  auto kern = level_fwd2_kernel<C, DEC, SEP, TRAIN>;
+  auto kern = level_fwd2_kernel<C, DEC, SEP, TRAIN, NOS>;
   if (smem > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
@@ -605,7 +625,7 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
 
 bool level_fwd_carries_loss(int N, int flags) { return N <= 40 && !(flags & LVL_DEC_PAIRWISE); }
 
-template <bool TRAIN>
+template <bool TRAIN, bool NOS>
 static int level_fwd_run(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
   LGN_CHECK_ARG(a.B > 0 && a.N > 0, "level_fwd: empty batch (B=%d N=%d)", a.B, a.N);
   LGN_CHECK_ARG(!a.in_w0 || (!decoder && a.in_w1 && a.in_s && a.in_v), "level_fwd: the input stage rides on encoder levels only");
@@ -613,8 +633,8 @@ static int level_fwd_run(const LevelArgs<double>& a, int decoder, hipStream_t st
   const bool pairwise = (a.flags & LVL_DEC_PAIRWISE) != 0;   // the decoder on the O(N^2) pair sweep (cross-check of the separable form)
 #define LGN_CASE(CC)                                                                                         \
   case CC:                                                                                                   \
-    if (!decoder) return launch_level_fwd2<CC, false, false, TRAIN>(a, stream);                              \
-    return pairwise ? launch_level_fwd2<CC, true, false, TRAIN>(a, stream) : launch_level_fwd2<CC, true, true, TRAIN>(a, stream);
+    if (!decoder) return launch_level_fwd2<CC, false, false, TRAIN, NOS>(a, stream);                         \
+    return pairwise ? launch_level_fwd2<CC, true, false, TRAIN, NOS>(a, stream) : launch_level_fwd2<CC, true, true, TRAIN, NOS>(a, stream);
   switch (a.C) {
 #ifdef LGN_DEV_ONLY_C4      // development builds: one channel count (compile time)
     LGN_CASE(4)
@@ -630,10 +650,12 @@ static int level_fwd_run(const LevelArgs<double>& a, int decoder, hipStream_t st
 
 template <>
 int level_fwd_dispatch<double>(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
-  return level_fwd_run<true>(a, decoder, stream);
+  return a.dead_scalars ? level_fwd_run<true, true>(a, decoder, stream) : level_fwd_run<true, false>(a, decoder, stream);
 }
 
 // evaluation step: ag0 / ag1 are not read (may be null); a riding loss tail writes get_real(recon) [B][N][4] and loss_part only
-int level_fwd_eval(const LevelArgs<double>& a, int decoder, hipStream_t stream) { return level_fwd_run<false>(a, decoder, stream); }
+int level_fwd_eval(const LevelArgs<double>& a, int decoder, hipStream_t stream) {
+  return a.dead_scalars ? level_fwd_run<false, true>(a, decoder, stream) : level_fwd_run<false, false>(a, decoder, stream);
+}
 
 }  // namespace lgn

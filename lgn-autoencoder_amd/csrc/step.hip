@@ -298,7 +298,8 @@ MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const dou
 // last_scalars = false: the caller consumes no output of the last level's CGMLP (the last level's scalars n.s[L]), which is then
 // not launched and leaves n.s[L] unwritten -- a step that returns no latent scalars, for either network (the decoder's output
 // and loss read only its last level's vectors; the latent vectors only the encoder's, and the latent scalars, which then mean
-// nothing, carry no gradient: LatentStage).
+// nothing, carry no gradient: LatentStage).  The last level's kernel then runs without live scalars (LevelArgs::dead_scalars: no
+// scalar aggregates, no scalar CatMix rows, n.smix / n.ag0 of that level unwritten); LVL_LIVE_SCALARS keeps the full kernel (cross-check).
 int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, const int64_t* off, NetBuf& n, const double* pos,
                const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr, bool eval = false,
                bool last_scalars = true) {
@@ -319,8 +320,10 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       a.loss_part = loss->loss_part; a.loss_gv = loss->g_v; a.loss_wpart = loss->wpart;
     }
     a.flags = d.flags;
+    const bool no_mlp = l + 1 == d.n_levels && (!last_scalars || (eval && dec));
+    a.dead_scalars = no_mlp && !(d.flags & LVL_LIVE_SCALARS);
     LGN_TRY(eval ? level_fwd_eval(a, dec, st) : level_fwd_dispatch<double>(a, dec, st));
-    if (l + 1 == d.n_levels && (!last_scalars || (eval && dec))) break;
+    if (no_mlp) break;
     MlpArgs<double> m = level_mlp_args(d, dec, l, P, off);
     m.s_in = n.smix[l]; m.s_out = n.s[l + 1];
     m.h_saved = n.hsave[l]; m.h_rows = mlp_saved_rows(m.M);
@@ -366,6 +369,11 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
                            p(S.rad(dec, l, 0)), p(S.rad(dec, l, 1)), p(S.rad(dec, l, 2)), p(S.rad(dec, l, 3)), p(S.rad(dec, l, 4)),
                            p(S.rad(dec, l, 5)), p(S.rad(dec, l, 6)), p(S.mix(dec, l, 0)), p(S.mix(dec, l, 1)), n.ag0[l], n.ag1[l],
                            g_smix, w.gv[cur], w.g_ag, w.gs[nxt], w.gv[nxt], dec ? w.g_p : nullptr, part_mix, part_rad};
+    // No gradient on this level's scalars (the first level this loop runs): the one-kernel backward leaves out every term it zeroes
+    // (LevelBwdArgs::dead_scalars).  The N > 40 kernels (level_bwd.hip, level_bwd2.hip) have no such form and keep reading the zero
+    // block; what they write into the wm0 half of their partial rows is not reduced either (the forward has not stored ag0).
+    const bool dead_s = !has_s_grad && !(d.flags & LVL_LIVE_SCALARS);
+    a.dead_scalars = dead_s;
     const bool carry_in0 = !dec && l == 0 && in0_done && level_bwd_carries_input(d.N, d.flags);
     const RowLayout rin = enc_input_rows(1, C);
     if (carry_in0) { DQ_TAKE(a.part_in0, (size_t)rm * rin.width); }
@@ -376,7 +384,9 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       *in0_done = true;
     }
     // deferred reductions: CatMix weights (partial row = [wm0 | wm1]) + radial sums
-    dq.add(part_mix, rm, nmix, 0, nmix / 2, g(S.mix(dec, l, 0)));
+    // (dead scalars: the wm0 gradient is exactly zero -- a row-less segment, like every parameter nothing produces a gradient for)
+    if (dead_s) dq.add(nullptr, 0, 0, 0, nmix / 2, g(S.mix(dec, l, 0)));
+    else dq.add(part_mix, rm, nmix, 0, nmix / 2, g(S.mix(dec, l, 0)));
     dq.add(part_mix, rm, nmix, nmix / 2, nmix / 2, g(S.mix(dec, l, 1)));
     if (dec) {   // only the Linear biases receive gradient (all edges are "masked")
       dq.add(part_rad, rr, nrad, 0, C, g(S.rad(dec, l, 4)));
