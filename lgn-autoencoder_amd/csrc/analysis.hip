@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
 #include "lsap_wave.hpp"
+#include "polar_dev.hpp"     // p_polar_tensor, wrap_phi
 
 namespace lgn {
 namespace {
@@ -33,19 +34,6 @@ constexpr int NFR = 10;                // staged rows per side
 __host__ __device__ constexpr size_t ra_wave_doubles(int N) { return (size_t)(2 * NFR + 1) * N + 8; }   // frames, row duals, jet sums
 inline size_t ra_lds_bytes(int N) { return RA_WAVES * (ra_wave_doubles(N) * sizeof(double) + (size_t)2 * N * sizeof(int)); }
 
-// Python's (x + pi) % (2 pi) - pi: the remainder takes the sign of the divisor
-__device__ __forceinline__ double wrap_phi(double x) {
-  const double b = 2.0 * M_PI;
-  double m = fmod(x + M_PI, b);
-  if (m != 0.0 && m < 0.0) m += b;
-  return m - M_PI;
-}
-// get_p_polar_tensor(p, eps = 1e-16): the eps goes on py only
-__device__ __forceinline__ void polar(double px, double py, double pz, double& pt, double& eta, double& phi) {
-  pt = sqrt(px * px + py * py);
-  eta = asinh(pz / (pt + EPS));
-  phi = atan2(py + EPS, px);
-}
 __device__ __forceinline__ bool is_inf(double x) { return fabs(x) == INFINITY; }
 
 template <int K>
@@ -202,10 +190,10 @@ __global__ __launch_bounds__(64 * RA_WAVES) void recon_analysis_kernel(const RaA
   for (int side = 0; side < 2; ++side) {
     double* f = F + side * NFR * N;
     double Pt, Eta, Phi;
-    polar(jet[4 * side + 1], jet[4 * side + 2], jet[4 * side + 3], Pt, Eta, Phi);
+    p_polar_tensor(jet[4 * side + 1], jet[4 * side + 2], jet[4 * side + 3], Pt, Eta, Phi);
     for (int r = lane; r < N; r += 64) {
       double pt, eta, phi;
-      polar(f[N + r], f[2 * N + r], f[3 * N + r], pt, eta, phi);
+      p_polar_tensor(f[N + r], f[2 * N + r], f[3 * N + r], pt, eta, phi);
       f[4 * N + r] = pt, f[5 * N + r] = eta, f[6 * N + r] = phi;
       const size_t o = ((side * B + b) * N + r) * 3;
       if (a.part_polar) a.part_polar[o] = pt, a.part_polar[o + 1] = eta, a.part_polar[o + 2] = phi;

@@ -13,7 +13,7 @@
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
 #include "lsap_wave.hpp"
-#include "polar_dev.hpp"     // polar, wrap_phi: shared with emd.hip
+#include "polar_dev.hpp"     // p4_polar, wrap_phi: shared with emd.hip
 
 namespace lgn {
 namespace {
@@ -98,17 +98,17 @@ __global__ __launch_bounds__(64 * SC_WAVES) void anomaly_scores_kernel(const dou
     double* f = F + side * NCOMP * N + r;
     const double E = x[0], px = x[1], py = x[2], pz = x[3];
     double pT, eta, phi;
-    polar(px, py, pz, pT, eta, phi);
+    p4_polar(px, py, pz, pT, eta, phi);
     f[0] = E, f[N] = px, f[2 * N] = py, f[3 * N] = pz;
     f[4 * N] = E, f[5 * N] = pT, f[6 * N] = eta, f[7 * N] = phi;
     const double En = xn[0], pxn = xn[1], pyn = xn[2], pzn = xn[3];
     double pTn, etan, phin;
-    polar(pxn, pyn, pzn, pTn, etan, phin);
+    p4_polar(pxn, pyn, pzn, pTn, etan, phin);
     f[8 * N] = En, f[9 * N] = pxn, f[10 * N] = pyn, f[11 * N] = pzn;
     f[12 * N] = En, f[13 * N] = pTn, f[14 * N] = etan, f[15 * N] = phin;
     const double* J = jet + 4 * side;
     double jpT, jeta, jphi;
-    polar(J[1], J[2], J[3], jpT, jeta, jphi);
+    p4_polar(J[1], J[2], J[3], jpT, jeta, jphi);
     f[16 * N] = pT / (jpT + EPS);
     f[17 * N] = eta - jeta;
     f[18 * N] = wrap_phi(phi - jphi);

@@ -19,6 +19,7 @@
 #include "net_dev.hpp"
 #include "net.hpp"
 #include "lsap_wave.hpp"
+#include "polar_dev.hpp"     // p_polar_loss
 
 namespace lgn {
 namespace {
@@ -35,11 +36,9 @@ __host__ __device__ inline int frame_of(int kind, int abs_coord, int polar_coord
 __host__ __device__ inline size_t core_doubles(int N) { return (size_t)18 * N + 4 + ((size_t)N + 1) / 2; }
 
 struct Polar { double pt, eta, phi; };
-__device__ __forceinline__ Polar polar_of(double px, double py, double pz) {      // get_p_polar
+__device__ __forceinline__ Polar polar_of(double px, double py, double pz) {
   Polar r;
-  r.pt = sqrt((px * px + py * py) + EPS);
-  r.eta = asinh(pz / (r.pt + EPS));
-  r.phi = atan2(py + EPS, px + EPS);
+  p_polar_loss(px, py, pz, r.pt, r.eta, r.phi);
   return r;
 }
 

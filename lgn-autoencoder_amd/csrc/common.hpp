@@ -73,6 +73,23 @@ __device__ __forceinline__ T shfl_xor(T v, int m) {
   return __shfl_xor(v, m, 64);
 }
 
+// max that keeps a NaN on either side, as torch.amax and torch.max do (device fmax returns the other operand): once m is NaN no
+// comparison is true and it stays; a NaN v replaces m
+__device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
+__device__ __forceinline__ double wave_nan_max(double v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v = nan_max(v, shfl_xor(v, m));
+  return v;
+}
+
+// One wavefront's LDS writes become visible to its own lanes: the waves of a workgroup that work on their own do not need the
+// workgroup's barrier.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // Sum over the JS consecutive lanes that share a row (JS power of two <= 64).
 template <int JS, typename T>
 __device__ __forceinline__ T group_sum(T v) {

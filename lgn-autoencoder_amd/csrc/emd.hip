@@ -105,14 +105,14 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
       }
       wave_sync();
       double jpT0, jeta0, jphi0, jpT1, jeta1, jphi1;
-      polar(jet[1], jet[2], jet[3], jpT0, jeta0, jphi0);
-      polar(jet[5], jet[6], jet[7], jpT1, jeta1, jphi1);
+      p4_polar(jet[1], jet[2], jet[3], jpT0, jeta0, jphi0);
+      p4_polar(jet[5], jet[6], jet[7], jpT1, jeta1, jphi1);
       for (int i = lane; i < rows; i += 64) {
         double w = 0.0, y = 0.0, ph = 0.0;
         if (i < n) {
           const double* x = a0 + base + 4 * i;
           double pT, eta, phi;
-          polar(x[1], x[2], x[3], pT, eta, phi);
+          p4_polar(x[1], x[2], x[3], pT, eta, phi);
           w = pT / (jpT0 + POLAR_EPS);
           y = eta - jeta0;
           ph = wrap_phi(phi - jphi0);
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
         if (j < m) {
           const double* x = a1 + base + 4 * j;
           double pT, eta, phi;
-          polar(x[1], x[2], x[3], pT, eta, phi);
+          p4_polar(x[1], x[2], x[3], pT, eta, phi);
           w = pT / (jpT1 + POLAR_EPS);
           y = eta - jeta1;
           ph = wrap_phi(phi - jphi1);

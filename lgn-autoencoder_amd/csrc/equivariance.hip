@@ -37,9 +37,6 @@ struct EquiParts {           // by value in the kernel arguments (2.6 KB): nothi
   int tile0[LGN_EQUI_MAX_PARTS + 1];      // first tile of each part in the flattened grid; tile0[parts] = all tiles
 };
 
-// max that keeps a NaN: once m is NaN no comparison is true and it stays; a NaN x replaces m
-__device__ __forceinline__ double nan_max(double m, double x) { return (x > m || x != x) ? x : m; }
-
 __global__ void __launch_bounds__(EQ_BLOCK) transform_jets_kernel(const double* __restrict__ p4, const double* __restrict__ R,
                                                                   const int* __restrict__ perm, const double* __restrict__ scalars,
                                                                   int B, int N, int K, double* __restrict__ out,

@@ -49,11 +49,6 @@ __device__ __forceinline__ double fast_rcp(double u) {
   e = __builtin_fma(-u, r, 1.0);
   return __builtin_fma(r, e, r);
 }
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // per-lane constants of the radial network in MFMA fragment form (see level_fwd2.hip)
 template <int C, bool DEC>

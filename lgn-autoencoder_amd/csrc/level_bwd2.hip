@@ -44,11 +44,6 @@ __device__ __forceinline__ double fast_rcp(double u) {
 template <int C> struct GA2 {
   static constexpr int A3 = 0, A4 = 2 * C, A1 = 4 * C, A2 = 12 * C, SIZE = 20 * C;
 };
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 LGN_STAMP_DECL
 }  // namespace
 LGN_STAMP_READER(lgn_debug_stamps_bwd2)

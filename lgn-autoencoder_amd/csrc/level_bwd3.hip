@@ -42,11 +42,6 @@ __device__ __forceinline__ double fast_rcp(double u) {
   e = __builtin_fma(-u, r, 1.0);
   return __builtin_fma(r, e, r);
 }
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 template <int C> struct GA3 {
   // (+ 2: rows of 20 C doubles put every second node of C = 4 on the same LDS banks -- the pair sweep reads four nodes' rows at once)
   static constexpr int A3 = 0, A4 = 2 * C, A1 = 4 * C, A2 = 12 * C, SIZE = 20 * C + 2;

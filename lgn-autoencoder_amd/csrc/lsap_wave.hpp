@@ -27,11 +27,6 @@ namespace lgn {
 constexpr int LSAP_NMAX = 192;         // three columns per lane (LGN_ANOMALY_NMAX of include/lgn_amd.h)
 constexpr int LSAP_INFEASIBLE = 2;
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 __device__ __forceinline__ double wave_min(double x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {

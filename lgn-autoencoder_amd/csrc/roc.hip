@@ -16,16 +16,14 @@
 #pragma clang fp contract(off)
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
+#include "sort_dev.hpp"
 
 namespace lgn {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int RT = LGN_ROC_TILE;        // pairs per sort tile, per merge chunk and per scan block
 constexpr int RB = 256;                 // threads per workgroup
 constexpr int RI = RT / RB;             // consecutive items of a thread
-constexpr u64 SIGN = 0x8000000000000000ull;
-constexpr u64 EXPO = 0x7FF0000000000000ull;
 static_assert(RT == RB * RI && (RT & (RT - 1)) == 0, "the tile is a power of two and a multiple of the workgroup");
 
 // label classes met (one word for the call: the labels are the same for every column)
@@ -47,16 +45,12 @@ struct RocCtx {
   double* auc;
 };
 
-__device__ __forceinline__ u64 key_of(double x) {
+// unsigned order of the keys = descending order of the doubles
+__device__ __forceinline__ u64 roc_key(double x) {
   if (x == 0.0) x = 0.0;                                   // -0.0 ties with +0.0
-  const u64 u = (u64)__double_as_longlong(x);
-  const u64 a = (u & SIGN) ? ~u : (u | SIGN);              // ascending order of the doubles
-  return ~a;
+  return ~key_of(x);
 }
-__device__ __forceinline__ double value_of(u64 key) {
-  const u64 a = ~key;
-  return __longlong_as_double((long long)((a & SIGN) ? (a ^ SIGN) : ~a));
-}
+__device__ __forceinline__ double roc_value(u64 key) { return value_of(~key); }
 
 // ---- 1. keys, status, tile sort --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(RB) void roc_init(int* status, int* labstat, int K) {
@@ -74,8 +68,7 @@ __global__ __launch_bounds__(RB) void roc_tile_sort(const double* __restrict__ s
   const int tid = threadIdx.x, k = blockIdx.y;
   const long long base = (long long)blockIdx.x * RT;
   const int n = (int)(M - base < RT ? M - base : RT);       // 1 .. RT rows of this tile
-  int p2 = 2;
-  while (p2 < n) p2 <<= 1;                                  // the sort runs on the next power of two, padded with the largest key
+  const int p2 = bitonic_size(n);
   if (tid == 0) { s_lab = 0; s_bad = 0; }
   __syncthreads();
   int lab = 0, bad = 0;
@@ -86,9 +79,9 @@ __global__ __launch_bounds__(RB) void roc_tile_sort(const double* __restrict__ s
       const double x = scores[(base + j) * ld + k];
       const double l = labels[base + j];
       const u64 u = (u64)__double_as_longlong(x);
-      if ((u & EXPO) == EXPO) bad |= LGN_ROC_NONFINITE | ((u & ~(SIGN | EXPO)) ? LGN_ROC_NAN : 0);
+      if (nonfinite_bits(u)) bad |= LGN_ROC_NONFINITE | ((u & ~(F64_SIGN | F64_EXPO)) ? LGN_ROC_NAN : 0);
       lab |= l == 1.0 ? LAB_POS : l == 0.0 ? LAB_ZERO : l == -1.0 ? LAB_NEG : LAB_OTHER;
-      key = key_of(x);
+      key = roc_key(x);
       b = l == 1.0;
     }
     sk[j] = key;
@@ -96,21 +89,7 @@ __global__ __launch_bounds__(RB) void roc_tile_sort(const double* __restrict__ s
   }
   if (bad) atomicOr(&s_bad, bad);
   if (k == 0) atomicOr(&s_lab, lab);
-  for (int size = 2; size <= p2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (p2 >> 1); t += RB) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool up = (lo & size) == 0;
-        const u64 a = sk[lo], c = sk[hi];
-        if ((a > c) == up) {
-          sk[lo] = c; sk[hi] = a;
-          const uint8_t ba = sb[lo]; sb[lo] = sb[hi]; sb[hi] = ba;
-        }
-      }
-    }
-  }
-  __syncthreads();
+  bitonic_sort_lds<RB>(sk, sb, p2);
   const long long col = (long long)k * M + base;
   for (int j = tid; j < n; j += RB) {
     keys[col + j] = sk[j];
@@ -123,85 +102,12 @@ __global__ __launch_bounds__(RB) void roc_tile_sort(const double* __restrict__ s
 }
 
 // ---- 2. one merge pass: runs of W sorted rows -> runs of 2 W -------------------------------------------------------------------
-// rows of a taken before equal rows of b, everywhere: the splits of neighbouring chunks and threads then agree
-template <typename I>
-__device__ __forceinline__ I merge_path(const u64* a, I na, const u64* b, I nb, I diag) {
-  I lo = diag > nb ? diag - nb : 0, hi = diag < na ? diag : na;
-  while (lo < hi) {
-    const I mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= b[diag - 1 - mid]) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(RB) void roc_merge_pass(const u64* __restrict__ kin, const uint8_t* __restrict__ bin,
                                                      u64* __restrict__ kout, uint8_t* __restrict__ bout, long long M, long long W) {
-  __shared__ u64 sk[RT], ok[RT];
-  __shared__ uint8_t sb[RT], ob[RT];
-  __shared__ long long s_split[2];
-  const int tid = threadIdx.x;
-  const long long col = (long long)blockIdx.y * M;
-  const long long o0 = (long long)blockIdx.x * RT, o1 = o0 + RT < M ? o0 + RT : M;
-  const long long pair0 = o0 / (2 * W) * (2 * W);           // W is a multiple of the chunk: a chunk lies inside one pair of runs
-  const long long a_end = pair0 + W < M ? pair0 + W : M, b_end = pair0 + 2 * W < M ? pair0 + 2 * W : M;
-  const long long na = a_end - pair0, nbb = b_end - a_end;  // an unpaired run has nbb = 0 and is copied
-  const u64* A = kin + col + pair0;
-  const u64* B = kin + col + a_end;
-  if (tid < 2) s_split[tid] = merge_path<long long>(A, na, B, nbb, (tid ? o1 : o0) - pair0);
-  __syncthreads();
-  const long long a0 = s_split[0], a1 = s_split[1], b0 = (o0 - pair0) - a0, b1 = (o1 - pair0) - a1;
-  const int ca = (int)(a1 - a0), cb = (int)(b1 - b0), n = ca + cb;       // ca + cb = o1 - o0 <= RT
-  for (int j = tid; j < n; j += RB) {
-    const long long src = j < ca ? pair0 + a0 + j : a_end + b0 + (j - ca);
-    sk[j] = kin[col + src];
-    sb[j] = bin[col + src];
-  }
-  __syncthreads();
-  const int d = tid * RI < n ? tid * RI : n;
-  int i = merge_path<int>(sk, ca, sk + ca, cb, d), j = d - i;
-#pragma unroll
-  for (int e = 0; e < RI; ++e) {
-    if (d + e < n) {
-      const bool take_a = j >= cb || (i < ca && sk[i] <= sk[ca + j]);
-      const int s = take_a ? i : ca + j;
-      ok[d + e] = sk[s];
-      ob[d + e] = sb[s];
-      i += take_a;
-      j += !take_a;
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < n; q += RB) {
-    kout[col + o0 + q] = ok[q];
-    bout[col + o0 + q] = ob[q];
-  }
+  merge_chunk<RT, RB>(kin, bin, kout, bout, (long long)blockIdx.y * M, M, W);
 }
 
 // ---- 3. batched exclusive int32 scan: block sums, scan of the block sums, apply ----------------------------------------------
-// exclusive prefix of v over the workgroup's threads, and the workgroup's sum
-__device__ __forceinline__ int block_excl_scan(int v, int& total) {
-  __shared__ int ws[RB / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();                       // the previous call's readers are done with ws
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int q = 0; q < RB / 64; ++q) {
-    if (q < w) off += ws[q];
-    tot += ws[q];
-  }
-  total = tot;
-  return off + inc - v;
-}
-
 // the value scanned at position i < M of column k.  0: the label bit; 1: row i ends a tie group; 2: point i of the tie-group
 // sequence is kept by roc_curve's drop_intermediate (first, last, or a nonzero second difference of fps or tps)
 template <int STAGE>
@@ -230,7 +136,7 @@ __global__ __launch_bounds__(RB) void roc_block_sums(RocCtx c) {
   for (int e = 0; e < RI; ++e)
     if (i0 + e < c.M) s += roc_flag<STAGE>(c, k, i0 + e);
   int total;
-  block_excl_scan(s, total);
+  block_excl_scan<RB>(s, total);
   if (threadIdx.x == 0) c.sums[(long long)k * c.nb + blockIdx.x] = total;
 }
 
@@ -243,7 +149,7 @@ __global__ __launch_bounds__(RB) void roc_scan_sums(RocCtx c) {
     const int q = base + threadIdx.x;
     const int v = q < c.nb ? s[q] : 0;
     int total;
-    const int ex = block_excl_scan(v, total);
+    const int ex = block_excl_scan<RB>(v, total);
     if (q < c.nb) s[q] = carry + ex;
     carry += total;
   }
@@ -261,7 +167,7 @@ __global__ __launch_bounds__(RB) void roc_apply(RocCtx c) {
     s += f[e];
   }
   int total;
-  int ex = c.sums[(long long)k * c.nb + blockIdx.x] + block_excl_scan(s, total);
+  int ex = c.sums[(long long)k * c.nb + blockIdx.x] + block_excl_scan<RB>(s, total);
   const long long out = (long long)k * (c.M + 1);
   if (STAGE == 2 && blockIdx.x == 0 && threadIdx.x == 0) {   // roc_curve's extra first point
     c.fpr[out] = 0.0;
@@ -284,7 +190,7 @@ __global__ __launch_bounds__(RB) void roc_apply(RocCtx c) {
         const long long fps = r + 1 - tps, neg = c.M - pos;
         c.fpr[out + 1 + ex] = (double)fps / (double)neg;
         c.tpr[out + 1 + ex] = (double)tps / (double)pos;
-        c.thr[out + 1 + ex] = value_of(c.keys[col + r]);
+        c.thr[out + 1 + ex] = roc_value(c.keys[col + r]);
       }
       ex += 1;
     }
@@ -292,15 +198,6 @@ __global__ __launch_bounds__(RB) void roc_apply(RocCtx c) {
 }
 
 // ---- 4. AUC in a fixed order, flip --------------------------------------------------------------------------------------------
-__device__ __forceinline__ double block_sum_fixed(double v, double* ws) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
 __global__ __launch_bounds__(RB) void roc_auc_partial(RocCtx c) {
   __shared__ double ws[RB / 64];
   const int k = blockIdx.y;
@@ -319,8 +216,8 @@ __global__ __launch_bounds__(RB) void roc_auc_partial(RocCtx c) {
       y0 = y1;
     }
   }
-  a = block_sum_fixed(a, ws);
-  b = block_sum_fixed(b, ws);
+  a = block_sum_fixed<RB>(a, ws);
+  b = block_sum_fixed<RB>(b, ws);
   if (threadIdx.x == 0) {
     double* p = c.part + ((long long)k * c.nb + blockIdx.x) * 2;
     p[0] = a;
@@ -337,8 +234,8 @@ __global__ __launch_bounds__(RB) void roc_auc_final(RocCtx c) {
     a += p[2 * q];
     b += p[2 * q + 1];
   }
-  a = block_sum_fixed(a, ws);
-  b = block_sum_fixed(b, ws);
+  a = block_sum_fixed<RB>(a, ws);
+  b = block_sum_fixed<RB>(b, ws);
   if (threadIdx.x == 0) {
     const int lab = *c.labstat;
     int st = c.status[k];
@@ -348,7 +245,7 @@ __global__ __launch_bounds__(RB) void roc_auc_final(RocCtx c) {
     c.status[k] = st;
     c.length[k] = st ? 0 : c.totals[k * 4 + 2] + 1;
     c.flipped[k] = flip;
-    c.auc[k] = st ? __longlong_as_double(0x7FF8000000000000ll) : flip ? b : a;
+    c.auc[k] = st ? qnan() : flip ? b : a;
   }
 }
 
@@ -365,7 +262,6 @@ __global__ __launch_bounds__(RB) void roc_swap(RocCtx c) {
 }
 
 // ---- workspace -----------------------------------------------------------------------------------------------------------------
-inline long long up256(long long b) { return (b + 255) / 256 * 256; }
 struct RocLayout {
   long long key_a, key_b, bit_a, bit_b, sums, totals, part, labstat, total;
   int nb;

@@ -33,15 +33,6 @@ constexpr int STAGE_WAVES = 4;
 
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 
-// max that keeps a NaN on either side (torch.amax); device fmax returns the other operand
-__device__ __forceinline__ double nan_max(double m, double v) { return (v > m || v != v) ? v : m; }
-
-__device__ __forceinline__ double wave_nan_max(double v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v = nan_max(v, shfl_xor(v, m));
-  return v;
-}
-
 struct StageArgs {
   const double* p4;          // [B][N][4]
   const uint8_t* labels;     // [B][N] or null

@@ -8,7 +8,7 @@
 //   1. compaction   the mask is one per row, so one count | scan | scatter serves every column; the scatter writes order-preserving
 //                   64-bit keys of the kept doubles and the column's NONFINITE bit (an integer atomic).
 //   2. sort         a bitonic sort of LGN_STATS_TILE keys in LDS, then ceil(log2(rows / tile)) merge passes between two buffers, a
-//                   workgroup per output tile located by a merge-path search: the scheme of roc.hip, keys only.
+//                   workgroup per output tile located by a merge-path search: sort_dev.hpp, shared with roc.hip, keys only.
 //   3. selection    one thread per column: quantiles, median, min, max, abs_min by index; the MAD as a k-th-of-two-sorted-runs
 //                   selection (left of the median the deviations fall, right of it they rise, rounding is monotone); the runs
 //                   |a| < IQR and |a| < IDR by bisection; the edges.
@@ -24,28 +24,18 @@
 
 #include "common.hpp"
 #include "../../include/lgn_amd.h"
+#include "polar_dev.hpp"     // wrap_phi
+#include "sort_dev.hpp"
 
 namespace lgn {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int ST = LGN_STATS_TILE;      // keys per sort tile, merge chunk and moment partial
 constexpr int SB = 256;                 // threads per workgroup
 constexpr int SI = ST / SB;             // consecutive items of a thread
-constexpr u64 SIGN = 0x8000000000000000ull;
-constexpr u64 EXPO = 0x7FF0000000000000ull;
 constexpr int NSTAT = LGN_STATS_COUNT;
 static_assert(ST == SB * SI && (ST & (ST - 1)) == 0, "the tile is a power of two and a multiple of the workgroup");
 static_assert(LGN_STATS_MAX_COLS <= SB, "the init kernel clears one status word per thread");
-
-__device__ __forceinline__ u64 key_of(double x) {            // unsigned order of the keys = ascending order of the doubles
-  const u64 u = (u64)__double_as_longlong(x);
-  return (u & SIGN) ? ~u : (u | SIGN);
-}
-__device__ __forceinline__ double value_of(u64 a) {
-  return __longlong_as_double((long long)((a & SIGN) ? (a ^ SIGN) : ~a));
-}
-__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7FF8000000000000ll); }
 
 struct StatsCtx {
   const double* x;
@@ -64,38 +54,6 @@ struct StatsCtx {
   int* status;
 };
 
-// exclusive prefix of v over the workgroup's threads, and the workgroup's sum
-__device__ __forceinline__ int block_excl_scan(int v, int& total) {
-  __shared__ int ws[SB / 64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  __syncthreads();                       // the previous call's readers are done with ws
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int q = 0; q < SB / 64; ++q) {
-    if (q < w) off += ws[q];
-    tot += ws[q];
-  }
-  total = tot;
-  return off + inc - v;
-}
-
-__device__ __forceinline__ double block_sum_fixed(double v, double* ws) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((ws[0] + ws[1]) + ws[2]) + ws[3];
-}
-
 __device__ __forceinline__ bool row_kept(const StatsCtx& c, long long r) {
   return !c.mask || (c.mask[r] != 0) == (c.mask_keep != 0);
 }
@@ -108,7 +66,7 @@ __global__ __launch_bounds__(SB) void stats_count(StatsCtx c) {
   for (int e = 0; e < SI; ++e)
     if (r0 + e < c.rows) s += row_kept(c, r0 + e);
   int total;
-  block_excl_scan(s, total);
+  block_excl_scan<SB>(s, total);
   if (threadIdx.x == 0) c.blk[blockIdx.x] = total;
   if (blockIdx.x == 0 && threadIdx.x < c.cols) c.status[threadIdx.x] = 0;
 }
@@ -119,7 +77,7 @@ __global__ __launch_bounds__(SB) void stats_scan(StatsCtx c) {
     const int q = base + threadIdx.x;
     const int v = q < c.nb ? c.blk[q] : 0;
     int total;
-    const int ex = block_excl_scan(v, total);
+    const int ex = block_excl_scan<SB>(v, total);
     if (q < c.nb) c.blk[q] = (int)(carry + ex);        // < rows < 2^31
     carry += total;
   }
@@ -138,13 +96,13 @@ __global__ __launch_bounds__(SB) void stats_scatter(StatsCtx c) {
     s += f[e];
   }
   int total;
-  long long o = (long long)k * c.rows + c.blk[blockIdx.x] + block_excl_scan(s, total);     // the scan's barriers order s_bad = 0
+  long long o = (long long)k * c.rows + c.blk[blockIdx.x] + block_excl_scan<SB>(s, total);     // the scan's barriers order s_bad = 0
   int bad = 0;
 #pragma unroll
   for (int e = 0; e < SI; ++e) {
     if (!f[e]) continue;
     const double v = c.x[(r0 + e) * c.ld + k];
-    if (((u64)__double_as_longlong(v) & EXPO) == EXPO) bad = 1;
+    if (nonfinite_bits((u64)__double_as_longlong(v))) bad = 1;
     c.key_a[o++] = key_of(v);              // o - k rows < n <= rows
   }
   if (bad) atomicOr(&s_bad, LGN_STATS_NONFINITE);
@@ -159,70 +117,19 @@ __global__ __launch_bounds__(SB) void stats_tile_sort(StatsCtx c) {
   const long long M = *c.count, base = (long long)blockIdx.x * ST;
   if (base >= M) return;
   const int n = (int)(M - base < ST ? M - base : ST);
-  int p2 = 2;
-  while (p2 < n) p2 <<= 1;                                  // the sort runs on the next power of two, padded with the largest key
+  const int p2 = bitonic_size(n);
   u64* col = c.key_a + (long long)blockIdx.y * c.rows + base;
   for (int j = tid; j < p2; j += SB) sk[j] = j < n ? col[j] : ~0ull;
-  for (int size = 2; size <= p2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = tid; t < (p2 >> 1); t += SB) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool up = (lo & size) == 0;
-        const u64 a = sk[lo], b = sk[hi];
-        if ((a > b) == up) { sk[lo] = b; sk[hi] = a; }
-      }
-    }
-  }
-  __syncthreads();
+  bitonic_sort_lds<SB>(sk, (NoPayload*)nullptr, p2);
   for (int j = tid; j < n; j += SB) col[j] = sk[j];
-}
-
-template <typename I>
-__device__ __forceinline__ I merge_path(const u64* a, I na, const u64* b, I nb, I diag) {
-  I lo = diag > nb ? diag - nb : 0, hi = diag < na ? diag : na;
-  while (lo < hi) {
-    const I mid = lo + ((hi - lo) >> 1);
-    if (a[mid] <= b[diag - 1 - mid]) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // runs of W sorted keys -> runs of 2 W; an unpaired run (and a whole column shorter than W) is copied
 __global__ __launch_bounds__(SB) void stats_merge_pass(const u64* __restrict__ kin, u64* __restrict__ kout, long long rows,
                                                        const long long* __restrict__ count, long long W) {
-  __shared__ u64 sk[ST], ok[ST];
-  __shared__ long long s_split[2];
-  const int tid = threadIdx.x;
   const long long M = *count;
-  const long long o0 = (long long)blockIdx.x * ST;
-  if (o0 >= M) return;
-  const long long col = (long long)blockIdx.y * rows, o1 = o0 + ST < M ? o0 + ST : M;
-  const long long pair0 = o0 / (2 * W) * (2 * W);           // W is a multiple of the chunk: a chunk lies inside one pair of runs
-  const long long a_end = pair0 + W < M ? pair0 + W : M, b_end = pair0 + 2 * W < M ? pair0 + 2 * W : M;
-  const long long na = a_end - pair0, nbb = b_end - a_end;
-  const u64* A = kin + col + pair0;
-  const u64* B = kin + col + a_end;
-  if (tid < 2) s_split[tid] = merge_path<long long>(A, na, B, nbb, (tid ? o1 : o0) - pair0);
-  __syncthreads();
-  const long long a0 = s_split[0], a1 = s_split[1], b0 = (o0 - pair0) - a0, b1 = (o1 - pair0) - a1;
-  const int ca = (int)(a1 - a0), cb = (int)(b1 - b0), n = ca + cb;       // ca + cb = o1 - o0 <= ST
-  for (int j = tid; j < n; j += SB) sk[j] = kin[col + (j < ca ? pair0 + a0 + j : a_end + b0 + (j - ca))];
-  __syncthreads();
-  const int d = tid * SI < n ? tid * SI : n;
-  int i = merge_path<int>(sk, ca, sk + ca, cb, d), j = d - i;
-#pragma unroll
-  for (int e = 0; e < SI; ++e) {
-    if (d + e < n) {
-      const bool take_a = j >= cb || (i < ca && sk[i] <= sk[ca + j]);
-      ok[d + e] = sk[take_a ? i : ca + j];
-      i += take_a;
-      j += !take_a;
-    }
-  }
-  __syncthreads();
-  for (int q = tid; q < n; q += SB) kout[col + o0 + q] = ok[q];
+  if ((long long)blockIdx.x * ST >= M) return;
+  merge_chunk<ST, SB>(kin, (const NoPayload*)nullptr, kout, (NoPayload*)nullptr, (long long)blockIdx.y * rows, M, W);
 }
 
 // ---- 3. selection ----------------------------------------------------------------------------------------------------------------
@@ -351,7 +258,7 @@ __global__ __launch_bounds__(SB) void stats_partial(StatsCtx c) {
   double* p = c.part + ((long long)k * c.nb + blockIdx.x) * 4;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const double t = block_sum_fixed(s[q], ws);
+    const double t = block_sum_fixed<SB>(s[q], ws);
     if (threadIdx.x == 0) p[q] = t;
   }
 }
@@ -370,7 +277,7 @@ __global__ __launch_bounds__(SB) void stats_final(StatsCtx c) {
     for (int j = 0; j < 4; ++j) s[j] += p[4 * q + j];
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) s[j] = block_sum_fixed(s[j], ws);
+  for (int j = 0; j < 4; ++j) s[j] = block_sum_fixed<SB>(s[j], ws);
   if (threadIdx.x) return;
   double* out = c.stats + (long long)k * NSTAT;
   const double dn = (double)n;
@@ -388,7 +295,6 @@ __global__ __launch_bounds__(SB) void stats_final(StatsCtx c) {
   }
 }
 
-inline long long up256(long long b) { return (b + 255) / 256 * 256; }
 struct StatsLayout {
   long long key_a, key_b, blk, count, part, runs, total;
   int nb;
@@ -450,19 +356,6 @@ __global__ __launch_bounds__(64) void hist_fwhm_kernel(const long long* __restri
 // ---- jet images ----------------------------------------------------------------------------------------------------------------
 constexpr int JW = 2;                          // waves per workgroup: each holds an image and a running sum of npix^2 doubles
 constexpr int JP = LGN_JET_IMAGE_PARTS;
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// numpy's (x + pi) % (2 pi) - pi: the remainder takes the sign of the divisor
-__device__ __forceinline__ double wrap_phi(double x) {
-  const double b = 2.0 * M_PI;
-  double m = fmod(x + M_PI, b);
-  if (m != 0.0 && m < 0.0) m += b;
-  return m - M_PI;
-}
 
 __host__ __device__ constexpr size_t ji_wave_bytes(int N, int npix) {
   return (size_t)(2 * npix * npix + N) * sizeof(double) + (size_t)N * sizeof(int);
