@@ -98,6 +98,37 @@ __device__ __forceinline__ T group_sum(T v) {
   return v;
 }
 
+// Operand and accumulator registers of v_mfma_f64_16x16x4_f64 (a lane holds four of the 16 x 16 results).
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+// Exchange inside a quad of lanes on the DPP path: quad_perm [1,0,3,2] = 0xB1 (lane ^ 1), [2,3,0,1] = 0x4E (lane ^ 2).
+__device__ __forceinline__ double dppq(double v, int xor2) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  if (xor2) {
+    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
+  } else {
+    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
+  }
+  return __hiloint2double(hi, lo);
+}
+// Sum over the 4 lanes of a quad (the 4 partner slots of a pair tile): (v + v^1) + (that of lane ^ 2).
+__device__ __forceinline__ double quad_sum(double v) {
+  v += dppq(v, 0);
+  v += dppq(v, 1);
+  return v;
+}
+
+// 1/u for u >= 1: hardware reciprocal seed + two Newton steps (the reference divides; relative difference <= 1 ulp)
+__device__ __forceinline__ double fast_rcp(double u) {
+  double r = __builtin_amdgcn_rcp(u);
+  double e = __builtin_fma(-u, r, 1.0);
+  r = __builtin_fma(r, e, r);
+  e = __builtin_fma(-u, r, 1.0);
+  return __builtin_fma(r, e, r);
+}
+
 // Phase stamps (debug builds only: `make stamps` -> liblgn_amd_stamps.so, read by tools/kbench.py with KB_STAMPS=1).
 // Thread 0 of workgroup 0 records s_memtime at each STAMP(i); compiled out of the shipped library.
 // Slots 64 .. 127 hold the constant-rate counter (wall_clock64 = s_memrealtime) at the same points: the ratio of the two differences
@@ -126,10 +157,6 @@ __device__ __forceinline__ T group_sum(T v) {
 #define LGN_STAMP_READER(name)
 #endif
 
-template <typename T>
-__device__ __forceinline__ T leaky(T x) {
-  return fmax(x, T(0.01) * x);         // == x > 0 ? x : 0.01 x; nn.LeakyReLU default slope (generic_levels.py:121-122)
-}
 // The CGMLP's activation (get_activation_fn, lgn/nn/generic_levels.py:119-135; ids = LGN_ACT_* of include/lgn_amd.h).  The choice is
 // wave uniform; id 0 (LeakyReLU, the reference default) takes the first branch.
 __device__ __forceinline__ double act_apply(double x, int act) {

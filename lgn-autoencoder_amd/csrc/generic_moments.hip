@@ -16,112 +16,31 @@
 // accumulators stay in registers (the radial part is recomputed per chunk).
 #include <stdlib.h>
 
-#include "level_dev.hpp"
+#include "pair_dev.hpp"
 #include "ops.hpp"
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 namespace {
 constexpr int QC = 5;      // components per sweep
 
-__device__ __forceinline__ double dppq(double v, int xor2) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  if (xor2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  }
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v) {
-  v += dppq(v, 0);
-  v += dppq(v, 1);
-  return v;
-}
-__device__ __forceinline__ double fast_rcp(double u) {
-  double r = __builtin_amdgcn_rcp(u);
-  double e = __builtin_fma(-u, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-u, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
-
-// per-lane constants of the radial network in MFMA fragment form (see level_fwd2.hip)
-template <int C, bool DEC>
-struct RadConst {
-  static constexpr int NG = (C + 3) / 4;
-  double ak[5], bk[5], ck2[5], wf[NG][5], bias[NG][4];
-  __device__ __forceinline__ void load(const GenArgs& a, int lane) {
-    const int cg = lane >> 4;
-    if (!DEC) {
-#pragma unroll
-      for (int s = 0; s < 5; ++s) {
-        const int k = 4 * s + cg;
-        ak[s] = a.ra[k];
-        bk[s] = a.rb[k];
-        const double c = a.rc[k];
-        ck2[s] = c * c;
-      }
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int rr = lane & 15, q = rr >> 2, ch = 4 * g + (rr & 3);
-        const double* w = (q >> 1) ? a.w1 : a.w0;
-#pragma unroll
-        for (int s = 0; s < 5; ++s) wf[g][s] = ch < C ? w[(2 * ch + (q & 1)) * NB + 4 * s + cg] : 0.0;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int ch = 4 * g + cg;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const double* bb = (q >> 1) ? a.b1 : a.b0;
-        bias[g][q] = ch < C ? (DEC ? bb[ch] : bb[2 * ch + (q & 1)]) : 0.0;
-      }
-    }
-  }
-};
-
 // geometry + radial values of the ordered pair (i, j) held by this lane; returns R[g] = (R0r, R0i, R1r, R1i)
+// (the select form of the radial network: pair_dev.hpp)
 template <int C, bool DEC>
-__device__ __forceinline__ void pair_radial(const RadConst<C, DEC>& rc, const double* pi, const double* pjj, bool ok, bool mi,
-                                            bool mj, cx<double> (&q)[4], v4d (&R)[RadConst<C, DEC>::NG], double& an, bool& on) {
-  constexpr int NG = RadConst<C, DEC>::NG;
+__device__ __forceinline__ void pair_radial(const RadLane<C, DEC>& rc, const double* pi, const double* pjj, bool ok, bool mi,
+                                            bool mj, cx<double> (&q)[4], v4d (&R)[RadLane<C, DEC>::NG], double& an, bool& on) {
   if (DEC) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) q[m] = {pi[m] - pjj[m], pi[4 + m] - pjj[4 + m]};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) R[g] = v4d{rc.bias[g][0], rc.bias[g][1], rc.bias[g][2], rc.bias[g][3]};
+    radial_bias(rc.bias, R);
     an = 0.0;
     on = false;
   } else {
-    const double d0 = pi[0] - pjj[0], d1 = pi[1] - pjj[1], d2 = pi[2] - pjj[2], d3 = pi[3] - pjj[3];
-    const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
-    const double nsq = (2.0 * q0 - (((q0 + q1) + q2) + q3)) + 1e-16;
-    an = fabs(nsq);
-    on = ok && mi && mj && (nsq != 0.0);
-    const double h = rsqrt2<double>();
-    q[0] = {d0, 0.0};
-    q[1] = {d1 * h, -d2 * h};
-    q[2] = {d3, 0.0};
-    q[3] = {-d1 * h, -d2 * h};
-    double beta[5];
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-      const double u = (1.0 + rc.ck2[s] * an) + 1e-16;
-      const double bv = __builtin_fma(rc.bk[s], fast_rcp(u), rc.ak[s]);
-      beta[s] = on ? bv : 0.0;
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      R[g] = v4d{rc.bias[g][0], rc.bias[g][1], rc.bias[g][2], rc.bias[g][3]};
-#pragma unroll
-      for (int s = 0; s < 5; ++s) R[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(rc.wf[g][s], beta[s], R[g], 0, 0, 0);
-    }
+    const EncPair ep = enc_pair(pi, pjj, ok, mi, mj);
+    an = ep.an;
+    on = ep.on;
+    ep.canonical(q);
+    radial_select(rc, rc.wf, rc.bias, an, on, R);
   }
 }
 
@@ -171,8 +90,8 @@ __global__ __launch_bounds__(BLOCK) void moments_fwd_kernel(GenArgs a) {
   const size_t xplane = (size_t)B * N * C * Q;
   if (XL) load_packed(a.X, B, N, C, Q, b, xs);
   load_pos<DEC>(a, b, pj, mk);
-  RadConst<C, DEC> rc;
-  rc.load(a, lane);
+  RadLane<C, DEC> rc;
+  rc.load(a.ra, a.rb, a.rc, a.w0, a.b0, a.w1, a.b1, lane);
   __syncthreads();
 
   const int pr = lane & 15, cg = lane >> 4, ti = pr >> 2, tj = pr & 3;
@@ -258,8 +177,8 @@ __global__ __launch_bounds__(BLOCK) void moments_bwd_nodes_kernel(GenArgs a) {
   double* pj = reinterpret_cast<double*>(smem_raw);           // N * PS
   uint8_t* mk = reinterpret_cast<uint8_t*>(pj + N * PS);
   load_pos<DEC>(a, b, pj, mk);
-  RadConst<C, DEC> rc;
-  rc.load(a, lane);
+  RadLane<C, DEC> rc;
+  rc.load(a.ra, a.rb, a.rc, a.w0, a.b0, a.w1, a.b1, lane);
   __syncthreads();
 
   const int pr = lane & 15, cg = lane >> 4, tj = pr >> 2, ti = pr & 3;
@@ -364,24 +283,23 @@ template <int C, bool DEC, bool XL>
 __global__ __launch_bounds__(BLOCK) void moments_bwd_rad_kernel(GenArgs a) {
   constexpr int NG = (C + 3) / 4;
   constexpr int PS = DEC ? 8 : 4;
-  constexpr int TS = 18;
   const int N = a.N, B = a.B, Q = a.Q;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   double* xs = reinterpret_cast<double*>(smem_raw);           // N * C * Q * 2 (XL; else read from global memory, see moments_fwd_kernel)
   double* pj = xs + (XL ? (size_t)N * C * Q * 2 : 0);         // N * PS
   const size_t xplane = (size_t)B * N * C * Q;
-  double* tr = pj + N * PS;                                   // 4 waves * (NG + 3) * 16 * TS   (also the final reduction buffer)
-  constexpr int TRSZ = 4 * (NG + 3) * 16 * TS > 4 * 64 * NG * 12 ? 4 * (NG + 3) * 16 * TS : 4 * 64 * NG * 12;
+  double* tr = pj + N * PS;                                   // 4 waves' transpose tiles (also the final reduction buffer)
+  constexpr int TRSZ = 4 * pair_scratch(NG);
   uint8_t* mk = reinterpret_cast<uint8_t*>(tr + TRSZ);
   if (XL) load_packed(a.X, B, N, C, Q, b, xs);
   load_pos<DEC>(a, b, pj, mk);
-  RadConst<C, DEC> rc;
-  rc.load(a, lane);
+  RadLane<C, DEC> rc;
+  rc.load(a.ra, a.rb, a.rc, a.w0, a.b0, a.w1, a.b1, lane);
   __syncthreads();
 
   const int pr = lane & 15, cg = lane >> 4, ti = pr >> 2, tj = pr & 3;
-  double* trw = tr + wave * (NG + 3) * 16 * TS;
+  double* trw = tr + wave * pair_tiles(NG);
   v4d T[NG][3];
 #pragma unroll
   for (int g = 0; g < NG; ++g)
@@ -410,22 +328,11 @@ __global__ __launch_bounds__(BLOCK) void moments_bwd_rad_kernel(GenArgs a) {
       double an;
       bool on;
       pair_radial<C, DEC>(rc, pi, pj + jj * PS, ok, mi, DEC ? false : (mk[jj] != 0), q, R, an, on);
-      double* xb = trw + NG * 16 * TS;
       if (!DEC) {
+        double rho[5];
 #pragma unroll
-        for (int s = 0; s < 5; ++s) {
-          const double rho = on ? fast_rcp((1.0 + rc.ck2[s] * an) + 1e-16) : 0.0;
-          const double x2 = an * rho * rho;
-          if (s < 4) {
-            xb[pr * TS + 4 * s + cg] = rho;
-            xb[16 * TS + pr * TS + 4 * s + cg] = x2;
-          } else {
-            xb[32 * TS + pr * TS + cg] = rho;
-            xb[32 * TS + pr * TS + 4 + cg] = x2;
-          }
-        }
-        xb[32 * TS + pr * TS + 8 + 2 * cg] = cg == 0 ? (on ? 1.0 : 0.0) : 0.0;
-        xb[32 * TS + pr * TS + 9 + 2 * cg] = cg == 0 ? (ok ? 1.0 : 0.0) : 0.0;
+        for (int s = 0; s < 5; ++s) rho[s] = rho_select(rc.ck2[s], an, on);
+        rad_b_rows(trw + NG * 16 * PAIR_TS, pr, cg, rho, an, on, ok);
       }
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -455,30 +362,10 @@ __global__ __launch_bounds__(BLOCK) void moments_bwd_rad_kernel(GenArgs a) {
           dB0[g] += G0r + G0i;          // R0 = b0 (1+i): d b0 = Re G_R0 + Im G_R0
           dB1[g] += G1r + G1i;
         } else {
-          double* ta = trw + g * 16 * TS;
-          ta[pr * TS + cg] = G0r;
-          ta[pr * TS + 4 + cg] = G0i;
-          ta[pr * TS + 8 + cg] = G1r;
-          ta[pr * TS + 12 + cg] = G1i;
+          rad_a_rows(trw + g * 16 * PAIR_TS, pr, cg, G0r, G0i, G1r, G1i);
         }
       }
-      if (!DEC) {
-        wave_sync();
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int prow = 4 * s + cg;
-          double bv[3];
-#pragma unroll
-          for (int t = 0; t < 3; ++t) bv[t] = xb[t * 16 * TS + prow * TS + pr];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) {
-            const double av = trw[g * 16 * TS + prow * TS + pr];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) T[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], T[g][t], 0, 0, 0);
-          }
-        }
-        wave_sync();
-      }
+      if (!DEC) rad_gemm_step(trw, pr, cg, T);
     }
     if (DEC) {
       const size_t plp = (size_t)B * N * 4;
@@ -498,62 +385,13 @@ __global__ __launch_bounds__(BLOCK) void moments_bwd_rad_kernel(GenArgs a) {
   __syncthreads();
   double* part = a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, DEC);
   if (DEC) {
-    // sum over pair slots (lane & 15) and waves; lane>>4 = channel in group
-    double* red = tr;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      double x0 = dB0[g], x1 = dB1[g];
-      for (int m = 1; m < 16; m <<= 1) { x0 += shfl_xor(x0, m); x1 += shfl_xor(x1, m); }
-      if (pr == 0) {
-        red[(wave * NG + g) * 8 + cg] = x0;
-        red[(wave * NG + g) * 8 + 4 + cg] = x1;
-      }
-    }
+    dec_bias_store(tr, wave, pr, cg, dB0, dB1);
     __syncthreads();
-    if (tid < 2 * C) {
-      const int lin = tid / C, ch = tid - lin * C, g = ch >> 2, c4 = ch & 3;
-      double s = 0;
-      for (int w = 0; w < 4; ++w) s += red[(w * NG + g) * 8 + lin * 4 + c4];
-      part[tid] = s;
-    }
+    dec_bias_sum<C, 4>(tr, part, tid);
   } else {
-    double* red = tr;
-    {
-      double* mine = red + (size_t)(wave * 64 + lane) * NG * 12;
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) mine[(g * 3 + t) * 4 + q] = T[g][t][q];
-    }
+    rad_rows_store(tr, wave, lane, T);
     __syncthreads();
-    if (wave == 0) {
-      constexpr int R = 4 * C;
-      const int col = lane & 15;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int ch = 4 * g + cg;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int e = (g * 3 + t) * 4 + q;
-            const double v = (red[(size_t)(0 * 64 + lane) * NG * 12 + e] + red[(size_t)(1 * 64 + lane) * NG * 12 + e]) +
-                             (red[(size_t)(2 * 64 + lane) * NG * 12 + e] + red[(size_t)(3 * 64 + lane) * NG * 12 + e]);
-            if (ch >= C) continue;
-            const int r = (q >> 1) * 2 * C + 2 * ch + (q & 1);
-            if (t == 0) part[r * NB + col] = v;
-            else if (t == 1) part[R * NB + r * NB + col] = v;
-            else {
-              if (col < 4) part[r * NB + 16 + col] = v;
-              else if (col < 8) part[R * NB + r * NB + 16 + (col - 4)] = v;
-              else if (col == 8) part[2 * R * NB + r] = v;
-              else if (col == 9) part[2 * R * NB + R + r] = v;
-            }
-          }
-      }
-    }
+    if (wave == 0) rad_rows_sum<C, 4, WaveSum::Pairwise>(tr, part, lane);
   }
 }
 
@@ -588,7 +426,7 @@ static int launch_moments(const GenArgs& a, int which, hipStream_t st) {
     if ((rc = set_smem(k, pos, "moments_bwd_nodes"))) return rc;
     hipLaunchKernelGGL(k, dim3(a.B), dim3(BLOCK), pos, st, a);
   } else {
-    constexpr int TRSZ = 4 * (NG + 3) * 16 * 18 > 4 * 64 * NG * 12 ? 4 * (NG + 3) * 16 * 18 : 4 * 64 * NG * 12;
+    constexpr int TRSZ = 4 * pair_scratch(NG);
     const bool xl = xs + pos + sizeof(double) * TRSZ <= 160 * 1024;
     auto k = xl ? moments_bwd_rad_kernel<C, DEC, true> : moments_bwd_rad_kernel<C, DEC, false>;
     const size_t smem = (xl ? xs : 0) + pos + sizeof(double) * TRSZ;

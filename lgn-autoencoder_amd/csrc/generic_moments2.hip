@@ -16,7 +16,7 @@
 //            (the [4C x pairs] . [pairs x 42] matrix-core GEMM of v1, now without the q loop); decoder: bias sums and d p.
 #include <stdlib.h>
 
-#include "level_dev.hpp"
+#include "pair_dev.hpp"
 #include "ops.hpp"
 
 namespace lgn {
@@ -24,13 +24,6 @@ namespace m2 {
 
 constexpr int MAXN = 32;      // lane >> 1 indexes the row: 32 rows per sweep
 
-__device__ __forceinline__ double fast_rcp(double u) {
-  double r = __builtin_amdgcn_rcp(u);
-  double e = __builtin_fma(-u, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-u, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
 // add the value held by the neighbouring lane (lane ^ 1)
 __device__ __forceinline__ double pair_sum(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);
@@ -896,8 +889,6 @@ __global__ __launch_bounds__(BLOCK) void moments_dec_sep_bwd_kernel(GenArgs a) {
 // moments_bwd_rad_kernel (generic_moments.hip) on the matrix cores, without the q loop.
 //   T1[r][k] = sum_p G[p][r] on rho_k    T2[r][k] = sum_p G[p][r] on n^2 rho_k^2    S[r] = sum_p G on    dB[r] = sum_p G
 // ---------------------------------------------------------------------------------------------------------
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 template <int C>
 __global__ __launch_bounds__(BLOCK) void moments_rad_reduce2_kernel(GenArgs a, const double* Gbuf) {
   constexpr int NG = (C + 3) / 4;
@@ -997,14 +988,12 @@ __global__ __launch_bounds__(BLOCK) void moments_rad_reduce2_kernel(GenArgs a, c
     fetch(ci[PF - 1], cj[PF - 1], cok[PF - 1], cav[PF - 1]);
     const double* pi = pj + i * 4;
     const double* pq = pj + j * 4;
-    const double d0 = pi[0] - pq[0], d1 = pi[1] - pq[1], d2 = pi[2] - pq[2], d3 = pi[3] - pq[3];
-    const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
-    const double nsq = (2.0 * q0 - (((q0 + q1) + q2) + q3)) + 1e-16;
-    const double an = fabs(nsq);
-    const bool on = ok && mk[i] != 0 && mk[j] != 0 && nsq != 0.0;
-    // B fragments: three column blocks of 16
-    const double rho0 = on ? fast_rcp((1.0 + ck2[0] * an) + 1e-16) : 0.0;
-    const double rho2 = on ? fast_rcp((1.0 + ck2[1] * an) + 1e-16) : 0.0;
+    const EncPair ep = enc_pair(pi, pq, ok, mk[i] != 0, mk[j] != 0);
+    const double an = ep.an;
+    const bool on = ep.on;
+    // B fragments: three column blocks of 16 (the select form of rho, pair_dev.hpp; here a lane holds COLUMNS, not a pair's row)
+    const double rho0 = rho_select(ck2[0], an, on);
+    const double rho2 = rho_select(ck2[1], an, on);
     double bv[3];
     bv[0] = rho0;
     bv[1] = an * rho0 * rho0;
@@ -1015,43 +1004,9 @@ __global__ __launch_bounds__(BLOCK) void moments_rad_reduce2_kernel(GenArgs a, c
       for (int t = 0; t < 3; ++t) T[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[g], bv[t], T[g][t], 0, 0, 0);
   }
   // D fragment: lane holds rows (lane >> 4) + 4 * reg = channel cc = lane >> 4 of group g, quantity reg; column lane & 15
-  {
-    double* mine = red + (size_t)(wave * 64 + lane) * NG * 12;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) mine[(g * 3 + t) * 4 + q] = T[g][t][q];
-  }
+  rad_rows_store(red, wave, lane, T);
   __syncthreads();
-  double* part = a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false);
-  if (wave == 0) {
-    constexpr int R = 4 * C;
-    const int cg = lane >> 4;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int ch = 4 * g + cg;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int e = (g * 3 + t) * 4 + q;
-          const double v = (red[(size_t)(0 * 64 + lane) * NG * 12 + e] + red[(size_t)(1 * 64 + lane) * NG * 12 + e]) +
-                           (red[(size_t)(2 * 64 + lane) * NG * 12 + e] + red[(size_t)(3 * 64 + lane) * NG * 12 + e]);
-          if (ch >= C) continue;
-          const int r = (q >> 1) * 2 * C + 2 * ch + (q & 1);
-          if (t == 0) part[r * NB + col] = v;
-          else if (t == 1) part[R * NB + r * NB + col] = v;
-          else {
-            if (col < 4) part[r * NB + 16 + col] = v;
-            else if (col < 8) part[R * NB + r * NB + 16 + (col - 4)] = v;
-            else if (col == 8) part[2 * R * NB + r] = v;
-            else if (col == 9) part[2 * R * NB + R + r] = v;
-          }
-        }
-    }
-  }
+  if (wave == 0) rad_rows_sum<C, 4, WaveSum::Pairwise>(red, a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false), lane);
 }
 
 template <typename K>

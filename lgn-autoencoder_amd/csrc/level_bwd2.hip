@@ -10,40 +10,12 @@
 //                      are one GEMM  [r x pairs] x [pairs x 42 columns]  executed with v_mfma_f64_16x16x4_f64; the
 //                      two operands are produced pair-per-lane and turned into A/B fragments by a 16x16 transpose
 //                      through a wave-private LDS tile (4 writes + 4 reads per lane for A, 12 + 12 for B).
-#include "level_dev.hpp"
+#include "pair_dev.hpp"
 #include "ops.hpp"
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 namespace {
-__device__ __forceinline__ double dppq(double v, int xor2) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  if (xor2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  }
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v) {
-  v += dppq(v, 0);
-  v += dppq(v, 1);
-  return v;
-}
-__device__ __forceinline__ double fast_rcp(double u) {
-  double r = __builtin_amdgcn_rcp(u);
-  double e = __builtin_fma(-u, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-u, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
-template <int C> struct GA2 {
-  static constexpr int A3 = 0, A4 = 2 * C, A1 = 4 * C, A2 = 12 * C, SIZE = 20 * C;
-};
 LGN_STAMP_DECL
 }  // namespace
 LGN_STAMP_READER(lgn_debug_stamps_bwd2)
@@ -51,11 +23,14 @@ LGN_STAMP_READER(lgn_debug_stamps_bwd2)
 // =========================================================================================================
 // j-centric pass
 // =========================================================================================================
+// (This kernel spells out what pair_dev.hpp holds as enc_pair, radial_select and edge_P2: its C >= 5 instantiations sit at the
+// 168-register bound of a 768-thread workgroup and spill already; every restatement through the shared pieces moved their spill
+// counts, some up.  A change to those pieces is made here too.)
 template <int C, bool DEC>
 __global__ __launch_bounds__(3 * BLOCK) void level_bwd_nodes2_kernel(LevelBwdArgs<double> a) {
   constexpr int NG = (C + 3) / 4;
   constexpr int PS = DEC ? 8 : 4;
-  using G = GA2<C>;
+  using G = GARow<C>;
   const int N = a.N, B = a.B;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthr = blockDim.x, nw = nthr >> 6;            // 4 or 8 waves: 8 when the batch alone cannot fill the SIMDs
@@ -202,7 +177,7 @@ __global__ __launch_bounds__(3 * BLOCK) void level_bwd_nodes2_kernel(LevelBwdArg
             cfmac(Gs[g], gA4, e0);
             if (!DEC) {
               // the edge e1[m] = R1 q[m] enters through P2 = sum_m gA2[m] conj(q[m]) and Z = gA3 conj(R1) only; with real
-              // momenta q = [d0, a - ib, d3, -a - ib] (level_bwd3.hip)
+              // momenta q = [d0, a - ib, d3, -a - ib] (pair_dev.hpp: edge_P2)
               const cx<double> dg = {gA2[1].r - gA2[3].r, gA2[1].i - gA2[3].i}, sg = {gA2[1].r + gA2[3].r, gA2[1].i + gA2[3].i};
               cx<double> P2;
               P2.r = __builtin_fma(gA2[0].r, qd0, __builtin_fma(gA2[2].r, qd3, __builtin_fma(qa, dg.r, -qb * sg.i)));
@@ -280,8 +255,7 @@ template <int C>
 __global__ __launch_bounds__(2 * BLOCK) void level_bwd_rad2_kernel(LevelBwdArgs<double> a) {
   constexpr int NG = (C + 3) / 4;
   constexpr int NS = node_stride(C);
-  using G = GA2<C>;
-  constexpr int TS = 18;                                   // padded row stride of the 16 x 16 transpose tiles (scalars)
+  using G = GARow<C>;
   const int N = a.N, B = a.B;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nw = blockDim.x >> 6;                            // 4 or 8 waves
@@ -289,22 +263,18 @@ __global__ __launch_bounds__(2 * BLOCK) void level_bwd_rad2_kernel(LevelBwdArgs<
   extern __shared__ __align__(16) unsigned char smem_raw[];
   double* nd = reinterpret_cast<double*>(smem_raw);          // N * NS     source node features
   double* pj = nd + ((N * NS + 1) & ~1);                     // N * 4
-  double* tr = pj + N * 4;                                   // 4 waves * (NG + 3) tiles * 16 * TS
-  double* red = tr;                                          // 4 waves * 64 lanes * NG * 12, aliases the transpose tiles (used after the sweep)
-  uint8_t* mk = reinterpret_cast<uint8_t*>(tr + nw * ((NG + 3) * 16 * TS > 64 * NG * 12 ? (NG + 3) * 16 * TS : 64 * NG * 12));
+  double* tr = pj + N * 4;                                   // nw * pair_scratch(NG): each wave's transpose tiles ...
+  double* red = tr;                                          // ... and, after the sweep, its accumulator rows
+  uint8_t* mk = reinterpret_cast<uint8_t*>(tr + nw * pair_scratch(NG));
 
   load_jet<double, C, false>(a.s_in, a.v_in, a.p, a.mask, B, N, b, nd, pj, mk);
   const int pr = lane & 15, cg = lane >> 4;
   const int ti = pr >> 2, tj = pr & 3;
-  double ck2[5];
-#pragma unroll
-  for (int s = 0; s < 5; ++s) {
-    const double c = a.rc[4 * s + cg];
-    ck2[s] = c * c;
-  }
+  RadLane<C, false> rl;                                      // (only c^2 of the bells is read: this pass needs rho, not R)
+  rl.load_bells(a.ra, a.rb, a.rc, lane);
   __syncthreads();
 
-  double* trw = tr + wave * (NG + 3) * 16 * TS;              // this wave's transpose tiles: NG x G, 3 x X
+  double* trw = tr + wave * pair_tiles(NG);                  // this wave's transpose tiles: NG x G, 3 x X
   v4d T[NG][3];
 #pragma unroll
   for (int g = 0; g < NG; ++g)
@@ -316,11 +286,10 @@ __global__ __launch_bounds__(2 * BLOCK) void level_bwd_rad2_kernel(LevelBwdArgs<
     const int i = rg * 4 + ti;
     const bool iok = i < N;
     const int ii = iok ? i : N - 1;
-    const double pi0 = pj[ii * 4], pi1 = pj[ii * 4 + 1], pi2 = pj[ii * 4 + 2], pi3 = pj[ii * 4 + 3];
+    const double pi[4] = {pj[ii * 4], pj[ii * 4 + 1], pj[ii * 4 + 2], pj[ii * 4 + 3]};
     const bool mi = mk[ii] != 0;
     // gradient of the aggregate of this lane's receiver i and channel(s): registers for the whole sweep
-    cx<double> rA1[NG][4], rA2[NG][4], rA3[NG], rA4[NG];
-    cx<double> dA2[NG], sA2[NG];                             // gA2[1] - gA2[3], gA2[1] + gA2[3]
+    AggGrad u[NG];
     {
       const double* gi = a.g_ag + ((size_t)b * N + ii) * G::SIZE;
 #pragma unroll
@@ -328,51 +297,26 @@ __global__ __launch_bounds__(2 * BLOCK) void level_bwd_rad2_kernel(LevelBwdArgs<
         const int ch = 4 * g + cg;
         const bool live = iok && ch < C;
         const int cs = ch < C ? ch : 0;
-        rA3[g] = live ? cx<double>{0.5 * gi[G::A3 + 2 * cs], 0.5 * gi[G::A3 + 2 * cs + 1]} : cx<double>{0, 0};
-        rA4[g] = live ? cx<double>{gi[G::A4 + 2 * cs], gi[G::A4 + 2 * cs + 1]} : cx<double>{0, 0};
+        u[g].gA3 = live ? cx<double>{0.5 * gi[G::A3 + 2 * cs], 0.5 * gi[G::A3 + 2 * cs + 1]} : cx<double>{0, 0};
+        u[g].gA4 = live ? cx<double>{gi[G::A4 + 2 * cs], gi[G::A4 + 2 * cs + 1]} : cx<double>{0, 0};
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
-          rA1[g][m] = live ? cx<double>{gi[G::A1 + (cs * 4 + m) * 2], gi[G::A1 + (cs * 4 + m) * 2 + 1]} : cx<double>{0, 0};
-          rA2[g][m] = live ? cx<double>{gi[G::A2 + (cs * 4 + m) * 2], gi[G::A2 + (cs * 4 + m) * 2 + 1]} : cx<double>{0, 0};
+          u[g].gA1[m] = live ? cx<double>{gi[G::A1 + (cs * 4 + m) * 2], gi[G::A1 + (cs * 4 + m) * 2 + 1]} : cx<double>{0, 0};
+          u[g].gA2[m] = live ? cx<double>{gi[G::A2 + (cs * 4 + m) * 2], gi[G::A2 + (cs * 4 + m) * 2 + 1]} : cx<double>{0, 0};
         }
-        dA2[g] = {rA2[g][1].r - rA2[g][3].r, rA2[g][1].i - rA2[g][3].i};
-        sA2[g] = {rA2[g][1].r + rA2[g][3].r, rA2[g][1].i + rA2[g][3].i};
       }
     }
     for (int j0 = 0; j0 < N; j0 += 4) {
       const int j = j0 + tj;
       const bool ok = iok && j < N;
       const int jj = j < N ? j : N - 1;
-      const double* pjj = pj + jj * 4;
-      const double d0 = pi0 - pjj[0], d1 = pi1 - pjj[1], d2 = pi2 - pjj[2], d3 = pi3 - pjj[3];
-      const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
-      const double nsq = (2.0 * q0 - (((q0 + q1) + q2) + q3)) + 1e-16;
-      const double an = fabs(nsq);
-      const bool on = ok && mi && (mk[jj] != 0) && (nsq != 0.0);
-      const double h = rsqrt2<double>();
-      cx<double> q[4];
-      q[0] = {d0, 0.0};
-      q[1] = {d1 * h, -d2 * h};
-      q[2] = {d3, 0.0};
-      q[3] = {-d1 * h, -d2 * h};
+      const EncPair ep = enc_pair(pi, pj + jj * 4, ok, mi, mk[jj] != 0);
 
       // ---- B operand source: this lane's pair (row pr), columns k = 4s + cg ----------------------------
-      double* xb = trw + NG * 16 * TS;                         // three 16 x 16 tiles [pair][col]
+      double rho[5];
 #pragma unroll
-      for (int s = 0; s < 5; ++s) {
-        const double rho = on ? fast_rcp((1.0 + ck2[s] * an) + 1e-16) : 0.0;
-        const double x2 = an * rho * rho;
-        if (s < 4) {
-          xb[pr * TS + 4 * s + cg] = rho;                      // tile 0: X1[k], k = 4s + cg < 16
-          xb[16 * TS + pr * TS + 4 * s + cg] = x2;             // tile 1: X2[k]
-        } else {
-          xb[32 * TS + pr * TS + cg] = rho;                    // tile 2: cols 0..3 X1[16 + cg]
-          xb[32 * TS + pr * TS + 4 + cg] = x2;                 //         cols 4..7 X2[16 + cg]
-        }
-      }
-      // cols 8 (on), 9 (one), 10..15 zero: each of the 4 channel lanes of a pair fills two of them
-      xb[32 * TS + pr * TS + 8 + 2 * cg] = cg == 0 ? (on ? 1.0 : 0.0) : 0.0;
-      xb[32 * TS + pr * TS + 9 + 2 * cg] = cg == 0 ? (ok ? 1.0 : 0.0) : 0.0;
+      for (int s = 0; s < 5; ++s) rho[s] = rho_select(rl.ck2[s], ep.an, ep.on);
+      rad_b_rows(trw + NG * 16 * PAIR_TS, pr, cg, rho, ep.an, ep.on, ok);
 
       // ---- A operand source: dL/d rad of this lane's pair and channel -------------------------------------
       const double* njp = nd + jj * NS;
@@ -381,94 +325,25 @@ __global__ __launch_bounds__(2 * BLOCK) void level_bwd_rad2_kernel(LevelBwdArgs<
         const int ch = 4 * g + cg;
         double G0r = 0, G0i = 0, G1r = 0, G1i = 0;
         if (ok && ch < C) {
-          const cx<double> s = {njp[ch * 10], njp[ch * 10 + 1]};
-          cx<double> v[4];
-#pragma unroll
-          for (int m = 0; m < 4; ++m) v[m] = {njp[ch * 10 + 2 + m], njp[ch * 10 + 6 + m]};
-          cx<double> ge0 = cmulc(rA4[g], s);
-#pragma unroll
-          for (int m = 0; m < 4; ++m) cfmac(ge0, rA1[g][m], v[m]);
-          // G_R1 = sum_m ge1[m] conj(q[m]) = conj(s_j) P2 + gA3 conj(V), P2 = sum_m gA2[m] conj(q[m]), V = <v_j, q>, with the
-          // real-momentum structure q = [d0, a - ib, d3, -a - ib] (level_bwd3.hip)
-          const double qa = d1 * h, qb = d2 * h;
-          cx<double> P2, V;
-          P2.r = __builtin_fma(rA2[g][0].r, d0, __builtin_fma(rA2[g][2].r, d3, __builtin_fma(qa, dA2[g].r, -qb * sA2[g].i)));
-          P2.i = __builtin_fma(rA2[g][0].i, d0, __builtin_fma(rA2[g][2].i, d3, __builtin_fma(qa, dA2[g].i, qb * sA2[g].r)));
-          const cx<double> dv = {v[3].r - v[1].r, v[3].i - v[1].i}, sv = {v[1].r + v[3].r, v[1].i + v[3].i};
-          V.r = __builtin_fma(v[0].r, d0, __builtin_fma(-v[2].r, d3, __builtin_fma(qa, dv.r, qb * sv.i)));
-          V.i = __builtin_fma(v[0].i, d0, __builtin_fma(-v[2].i, d3, __builtin_fma(qa, dv.i, -qb * sv.r)));
-          cx<double> gR1 = cmulc(P2, s);
-          cfmac(gR1, rA3[g], V);
+          SrcFeat xj;
+          xj.load(njp + ch * 10);
+          cx<double> ge0, gR1;
+          enc_edge_rad(u[g], ep, xj, ge0, gR1);
           G0r = ge0.r + ge0.i;  G0i = ge0.i - ge0.r;          // e0 = R0 (1+i)  ->  G_R0 = G_e0 (1-i)
           G1r = gR1.r;  G1i = gR1.i;
         }
-        double* ta = trw + g * 16 * TS;                       // [pair][r' = cg + 4q]
-        ta[pr * TS + cg] = G0r;
-        ta[pr * TS + 4 + cg] = G0i;
-        ta[pr * TS + 8 + cg] = G1r;
-        ta[pr * TS + 12 + cg] = G1i;
+        rad_a_rows(trw + g * 16 * PAIR_TS, pr, cg, G0r, G0i, G1r, G1i);
       }
-      wave_sync();
-      // ---- T[r'][col] += sum_pairs G[pair][r'] X[pair][col] : A[i = r' = lane&15][k = pair], B[k = pair][j = col] ----
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int prow = 4 * s + cg;                          // pair index held by this lane for k-step s
-        double bv[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bv[t] = xb[t * 16 * TS + prow * TS + pr];
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          const double av = trw[g * 16 * TS + prow * TS + pr];
-#pragma unroll
-          for (int t = 0; t < 3; ++t) T[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], T[g][t], 0, 0, 0);
-        }
-      }
-      wave_sync();
+      rad_gemm_step(trw, pr, cg, T);
     }
   }
 
   // ---- cross-wave reduction; D layout: lane holds T[r' = (lane>>4) + 4q][col = lane & 15] -----------------
   __syncthreads();                                           // every wave is done with its transpose tiles (aliased by red)
-  {
-    double* mine = red + (size_t)(wave * 64 + lane) * NG * 12;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) mine[(g * 3 + t) * 4 + q] = T[g][t][q];
-  }
+  rad_rows_store(red, wave, lane, T);
   __syncthreads();
-  if (wave == 0) {
-    constexpr int R = 4 * C;
-    double* part = a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false);
-    const int col = lane & 15;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int ch = 4 * g + cg;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int e = (g * 3 + t) * 4 + q;
-          double v = (red[(size_t)(0 * 64 + lane) * NG * 12 + e] + red[(size_t)(1 * 64 + lane) * NG * 12 + e]) +
-                     (red[(size_t)(2 * 64 + lane) * NG * 12 + e] + red[(size_t)(3 * 64 + lane) * NG * 12 + e]);
-          if (nw == 8)
-            v += (red[(size_t)(4 * 64 + lane) * NG * 12 + e] + red[(size_t)(5 * 64 + lane) * NG * 12 + e]) +
-                 (red[(size_t)(6 * 64 + lane) * NG * 12 + e] + red[(size_t)(7 * 64 + lane) * NG * 12 + e]);
-          if (ch >= C) continue;
-          const int r = (q >> 1) * 2 * C + 2 * ch + (q & 1);       // row of the partial layout: lin*2C + 2c + z
-          if (t == 0) part[r * NB + col] = v;                      // T1[r][k = col]
-          else if (t == 1) part[R * NB + r * NB + col] = v;        // T2[r][k = col]
-          else {
-            if (col < 4) part[r * NB + 16 + col] = v;
-            else if (col < 8) part[R * NB + r * NB + 16 + (col - 4)] = v;
-            else if (col == 8) part[2 * R * NB + r] = v;           // S
-            else if (col == 9) part[2 * R * NB + R + r] = v;       // dB
-          }
-        }
-    }
-  }
+  if (wave == 0)
+    rad_rows_sum<C, 0, WaveSum::Pairwise>(red, a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false), lane, 0, nw);
 }
 
 // =========================================================================================================
@@ -487,9 +362,9 @@ template <int C, int NWV, bool SYM>
 __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) void level_bwd_sweep_enc_kernel(LevelBwdArgs<double> a, int ichunk) {
   constexpr bool sym = SYM;
   constexpr int NG = (C + 3) / 4;
-  using G = GA2<C>;
-  constexpr int TS = 18, BLK = 64 * NWV;
-  constexpr int TRW = (NG + 3) * 16 * TS > 64 * NG * 12 ? (NG + 3) * 16 * TS : 64 * NG * 12;   // per wave: transpose tiles, later the reduction rows
+  using G = GARow<C>;
+  constexpr int BLK = 64 * NWV;
+  constexpr int TRW = pair_scratch(NG);                      // per wave: transpose tiles, later the reduction rows
   const int N = a.N, B = a.B;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -508,35 +383,18 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
   }
   const int pr = lane & 15, cg = lane >> 4;
   const int tj = pr >> 2, ti = pr & 3;                      // which of the wave's 4 source particles j / slot in the i tile
-  double ak[5], bk[5], ck2[5], wf[NG][5], bias[NG][4];
+  RadLane<C, false> rl;
+  rl.load(a.ra, a.rb, a.rc, a.w0, a.b0, a.w1, a.b1, lane);
   // sym: the 15 bell constants of the lane's five basis functions live in LDS (one row per lane group, read per tile) -- with them
   // in registers the second pass of the tiles below the diagonal spills into the hot loop
   __shared__ double rkt[4][16];
-  const double* rkl = rkt[cg];
+  const BellRow rkl = {rkt[cg]};
+  if (sym && pr == 0) {
 #pragma unroll
-  for (int s = 0; s < 5; ++s) {
-    const int k = 4 * s + cg;
-    ak[s] = a.ra[k];
-    bk[s] = a.rb[k];
-    const double c = a.rc[k];
-    ck2[s] = c * c;
-    if (sym && pr == 0) {
-      rkt[cg][s] = ak[s];
-      rkt[cg][5 + s] = bk[s];
-      rkt[cg][10 + s] = ck2[s];
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int rr = lane & 15, q = rr >> 2, ch = 4 * g + (rr & 3);
-    const double* w = (q >> 1) ? a.w1 : a.w0;
-#pragma unroll
-    for (int s = 0; s < 5; ++s) wf[g][s] = ch < C ? w[(2 * ch + (q & 1)) * NB + 4 * s + cg] : 0.0;
-    const int chl = 4 * g + cg;
-#pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2) {
-      const double* bb = (q2 >> 1) ? a.b1 : a.b0;
-      bias[g][q2] = chl < C ? bb[2 * chl + (q2 & 1)] : 0.0;
+    for (int s = 0; s < 5; ++s) {
+      rkt[cg][s] = rl.ak[s];
+      rkt[cg][5 + s] = rl.bk[s];
+      rkt[cg][10 + s] = rl.ck2[s];
     }
   }
 
@@ -549,7 +407,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
   const size_t pls = (size_t)B * N * C;
   const int ngroups = (N + 3) >> 2;
   // Which source groups this wave owns.  sym (R(i, j) = R(j, i): the radial-parameter GEMM runs once per UNORDERED tile, as in
-  // level_bwd3.hip): a group's cost grows with its index -- tiles with receiver group I < J carry both directions' radial
+  // level_bwd3_kernel): a group's cost grows with its index -- tiles with receiver group I < J carry both directions' radial
   // gradient, tiles with I > J none -- so the groups are dealt by longest-processing-time-first on that cost model (every wave runs
   // the same few hundred scalar steps); else round robin.
   unsigned long long mine = 0;
@@ -611,7 +469,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
       for (int m = 0; m < 4; ++m) pme[m] = pj[jj * 4 + m];
       const bool mj = mk[jj] != 0;
       cx<double> Gs[NG], Gv[NG][4];
-      cx<double> sj[NG], vj[NG][4], dvj[NG], svj[NG];       // own (source) node features; v_j[3] - v_j[1], v_j[1] + v_j[3]
+      SrcFeat xj[NG];                                        // own (source) node features
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
         Gs[g] = {0, 0};
@@ -619,11 +477,10 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
         for (int m = 0; m < 4; ++m) Gv[g][m] = {0, 0};
         const int ch = 4 * g + cg;
         const size_t e = ((size_t)b * N + jj) * C + (ch < C ? ch : 0);
-        sj[g] = {a.s_in[e], a.s_in[pls + e]};
+        xj[g].s = {a.s_in[e], a.s_in[pls + e]};
 #pragma unroll
-        for (int m = 0; m < 4; ++m) vj[g][m] = {a.v_in[e * 4 + m], a.v_in[pls * 4 + e * 4 + m]};
-        dvj[g] = {vj[g][3].r - vj[g][1].r, vj[g][3].i - vj[g][1].i};
-        svj[g] = {vj[g][1].r + vj[g][3].r, vj[g][1].i + vj[g][3].i};
+        for (int m = 0; m < 4; ++m) xj[g].v[m] = {a.v_in[e * 4 + m], a.v_in[pls * 4 + e * 4 + m]};
+        xj[g].diffs();
       }
 
       if (rg == 0) STAMP(ilo ? 13 : 4);
@@ -636,47 +493,12 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
         const int ii = i < ihi ? i : ihi - 1;
         const double* pii = pj + ii * 4;
         v4d R[NG];
+        const EncPair ep = enc_pair(pii, pme, ok, mj, mk[ii] != 0);
+        const double qd0 = ep.qd0, qd3 = ep.qd3, qa = ep.qa, qb = ep.qb;   // q = [d0, a - ib, d3, -a - ib] (real momenta)
         double rho[5];
-        const double d0 = pii[0] - pme[0], d1 = pii[1] - pme[1], d2 = pii[2] - pme[2], d3 = pii[3] - pme[3];
-        const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
-        const double nsq = (2.0 * q0 - (((q0 + q1) + q2) + q3)) + 1e-16;
-        const double an = fabs(nsq);
-        const bool on = ok && mj && (mk[ii] != 0) && (nsq != 0.0);
-        const double h = rsqrt2<double>();
-        const double qd0 = d0, qd3 = d3, qa = d1 * h, qb = d2 * h;   // q = [d0, a - ib, d3, -a - ib] (real momenta)
-        double beta[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 5; ++s) rho[s] = 0.0;
-        if (on) {                                            // (EXEC-masked block: no per-value selects)
-#pragma unroll
-          for (int s = 0; s < 5; ++s) beta[s] = 1.0 + (sym ? rkl[10 + s] : ck2[s]) * an;      // (+ 1e-16: absorbed, the sum is >= 1)
-          rcp5(beta, rho);
-#pragma unroll
-          for (int s = 0; s < 5; ++s) beta[s] = __builtin_fma(sym ? rkl[5 + s] : bk[s], rho[s], sym ? rkl[s] : ak[s]);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          R[g] = v4d{bias[g][0], bias[g][1], bias[g][2], bias[g][3]};
-#pragma unroll
-          for (int s = 0; s < 5; ++s) R[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[g][s], beta[s], R[g], 0, 0, 0);
-        }
-        // B-operand source of the radial GEMM: this lane's pair (row pr), columns k = 4s + cg
-        double* xb = trw + NG * 16 * TS;
-        if (kind != 0) {
-#pragma unroll
-          for (int s = 0; s < 5; ++s) {
-            const double x2 = an * rho[s] * rho[s];
-            if (s < 4) {
-              xb[pr * TS + 4 * s + cg] = rho[s];
-              xb[16 * TS + pr * TS + 4 * s + cg] = x2;
-            } else {
-              xb[32 * TS + pr * TS + cg] = rho[s];
-              xb[32 * TS + pr * TS + 4 + cg] = x2;
-            }
-          }
-          xb[32 * TS + pr * TS + 8 + 2 * cg] = cg == 0 ? (on ? 1.0 : 0.0) : 0.0;
-          xb[32 * TS + pr * TS + 9 + 2 * cg] = cg == 0 ? (ok ? 1.0 : 0.0) : 0.0;
-        }
+        if constexpr (sym) radial_masked(rkl, rl.wf, rl.bias, ep.an, ep.on, R, rho);
+        else radial_masked(rl, rl.wf, rl.bias, ep.an, ep.on, R, rho);
+        if (kind != 0) rad_b_rows(trw + NG * 16 * PAIR_TS, pr, cg, rho, ep.an, ep.on, ok);
 
         const double* gi = ga + (size_t)(ii - ilo) * G::SIZE;
 #pragma unroll
@@ -695,9 +517,9 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
               gA2[m] = {gi[G::A2 + (ch * 4 + m) * 2], gi[G::A2 + (ch * 4 + m) * 2 + 1]};
             }
             cfmac(Gs[g], gA4, e0);
-            cx<double> ge0 = cmulc(gA4, sj[g]);
+            cx<double> ge0 = cmulc(gA4, xj[g].s);
             // the edge e1[m] = R1 q[m] enters through P2 = sum_m gA2[m] conj(q[m]), V = <v_j, q> and Z = gA3 conj(R1) only
-            // (level_bwd3.hip, phase 2)
+            // (level_bwd3.hip, phase 2: the same statements; pair_dev.hpp says why they are not one function)
             const cx<double> dg = {gA2[1].r - gA2[3].r, gA2[1].i - gA2[3].i}, sg = {gA2[1].r + gA2[3].r, gA2[1].i + gA2[3].i};
             cx<double> P2;
             P2.r = __builtin_fma(gA2[0].r, qd0, __builtin_fma(gA2[2].r, qd3, __builtin_fma(qa, dg.r, -qb * sg.i)));
@@ -714,15 +536,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
             cx<double> gR1 = {0, 0};
             if (kind != 0) {                                   // gradient w.r.t. the radial values of this pair
 #pragma unroll
-              for (int m = 0; m < 4; ++m) cfmac(ge0, gA1[m], vj[g][m]);
+              for (int m = 0; m < 4; ++m) cfmac(ge0, gA1[m], xj[g].v[m]);
               cx<double> V;
-              V.r = __builtin_fma(vj[g][0].r, qd0, __builtin_fma(-vj[g][2].r, qd3, __builtin_fma(qa, dvj[g].r, qb * svj[g].i)));
-              V.i = __builtin_fma(vj[g][0].i, qd0, __builtin_fma(-vj[g][2].i, qd3, __builtin_fma(qa, dvj[g].i, -qb * svj[g].r)));
-              gR1 = cmulc(P2, sj[g]);
+              V.r = __builtin_fma(xj[g].v[0].r, qd0, __builtin_fma(-xj[g].v[2].r, qd3, __builtin_fma(qa, xj[g].dv.r, qb * xj[g].sv.i)));
+              V.i = __builtin_fma(xj[g].v[0].i, qd0, __builtin_fma(-xj[g].v[2].i, qd3, __builtin_fma(qa, xj[g].dv.i, -qb * xj[g].sv.r)));
+              gR1 = cmulc(P2, xj[g].s);
               cfmac(gR1, gA3, V);
             }
             if (kind == 2) {
-              // the reverse edge (receiver j, source i, momentum difference -q): level_bwd3.hip, SYM
+              // the reverse edge (receiver j, source i, momentum difference -q): level_bwd3.hip, SYM (the same statements)
               const double* gj = gajw + tj * G::SIZE;
               const double* ni = xn + ((size_t)(ii - ilo) * C + ch) * 10;
               const cx<double> si = {ni[0], ni[1]};
@@ -755,31 +577,9 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
             G0r = ge0.r + ge0.i;  G0i = ge0.i - ge0.r;        // e0 = R0 (1+i)  ->  G_R0 = G_e0 (1-i)
             G1r = gR1.r;  G1i = gR1.i;
           }
-          if (kind != 0) {
-            double* ta = trw + g * 16 * TS;                   // [pair][r' = cg + 4q]
-            ta[pr * TS + cg] = G0r;
-            ta[pr * TS + 4 + cg] = G0i;
-            ta[pr * TS + 8 + cg] = G1r;
-            ta[pr * TS + 12 + cg] = G1i;
-          }
+          if (kind != 0) rad_a_rows(trw + g * 16 * PAIR_TS, pr, cg, G0r, G0i, G1r, G1i);
         }
-        if (kind != 0) {
-          wave_sync();
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            const int prow = 4 * s + cg;
-            double bv[3];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) bv[t] = xb[t * 16 * TS + prow * TS + pr];
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-              const double av = trw[g * 16 * TS + prow * TS + pr];
-#pragma unroll
-              for (int t = 0; t < 3; ++t) T[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], T[g][t], 0, 0, 0);
-            }
-          }
-          wave_sync();
-        }
+        if (kind != 0) rad_gemm_step(trw, pr, cg, T);
       }
 
       if (rg == 0) STAMP(ilo ? 14 : 5);
@@ -827,50 +627,17 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(2))) v
   STAMP(20);
   __syncthreads();                                           // every wave is done with its transpose tiles (aliased by the rows below)
   STAMP(21);
-  {
-    double* mine = tr + (size_t)(wave * 64 + lane) * NG * 12;
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) mine[(g * 3 + t) * 4 + q] = T[g][t][q];
-  }
+  rad_rows_store(tr, wave, lane, T);
   __syncthreads();
-  if (wave == 0) {
-    constexpr int R = 4 * C;
-    double* part = a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false);
-    const int col = lane & 15;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int ch = 4 * g + cg;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int e = (g * 3 + t) * 4 + q;
-          double v = 0.0;
-          for (int w = 0; w < NWV; ++w) v += tr[(size_t)(w * 64 + lane) * NG * 12 + e];
-          if (ch >= C) continue;
-          const int r = (q >> 1) * 2 * C + 2 * ch + (q & 1);       // row of the partial layout: lin*2C + 2c + z
-          if (t == 0) part[r * NB + col] = v;
-          else if (t == 1) part[R * NB + r * NB + col] = v;
-          else {
-            if (col < 4) part[r * NB + 16 + col] = v;
-            else if (col < 8) part[R * NB + r * NB + 16 + (col - 4)] = v;
-            else if (col == 8) part[2 * R * NB + r] = v;
-            else if (col == 9) part[2 * R * NB + R + r] = v;
-          }
-        }
-    }
-  }
+  if (wave == 0)
+    rad_rows_sum<C, NWV, WaveSum::Sequential>(tr, a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false), lane);
 }
 
 template <int C, int NWV>
 static int launch_sweep_enc_w(const LevelBwdArgs<double>& a, hipStream_t stream) {
   constexpr int NG = (C + 3) / 4;
-  constexpr size_t TRW = (NG + 3) * 16 * 18 > 64 * NG * 12 ? (NG + 3) * 16 * 18 : 64 * NG * 12;
-  // sym (level_bwd3.hip: R(i, j) = R(j, i), the radial-parameter GEMM once per unordered tile): the chunk also holds the receivers'
+  constexpr size_t TRW = pair_scratch(NG);
+  // sym (level_bwd3.hip, SYM: R(i, j) = R(j, i), the radial-parameter GEMM once per unordered tile): the chunk also holds the receivers'
   // node features, every wave the g_ag rows of its own four particles
   // (C <= 4: with two lane groups of channels the second pass does not fit the register file beside the first)
   const bool sym = !(a.flags & LVL_BWD_ORDERED) && C <= 4 && (a.N + 3) / 4 <= 64;     // (group ownership is a 64-bit mask)
@@ -931,7 +698,7 @@ static int launch_rad2(const LevelBwdArgs<double>& a, hipStream_t stream) {
   constexpr int NG = (C + 3) / 4;
   auto bytes = [&](int nw) {
     return sizeof(double) * ((((size_t)a.N * node_stride(C) + 1) & ~size_t(1)) + (size_t)a.N * 4 +
-                             (size_t)nw * ((NG + 3) * 16 * 18 > 64 * NG * 12 ? (NG + 3) * 16 * 18 : 64 * NG * 12)) + a.N + 16;
+                             (size_t)nw * pair_scratch(NG)) + a.N + 16;
   };
   int f = sweep_wave_factor(a.B, a.N);
   if (f == 2 && bytes(8) > 160 * 1024) f = 1;

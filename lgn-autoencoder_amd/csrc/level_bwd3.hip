@@ -10,43 +10,13 @@
 //            matrix cores.  Per pair: (a) g_node_j += g_ag_i (x) conj(edge_ij); (b) encoder: dL/d rad of the pair ->
 //            16x16 LDS transposes -> T1|T2|S|dB GEMM on the matrix cores; decoder: bias sums and d p_j
 //   phase 3  decoder only: i-centric sweep for d p_i
-#include "level_dev.hpp"
+#include "pair_dev.hpp"
 #include "ops.hpp"
 #include "wave_sum.hpp"
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 namespace {
-__device__ __forceinline__ double dppq(double v, int xor2) {
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  if (xor2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  }
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v) {
-  v += dppq(v, 0);
-  v += dppq(v, 1);
-  return v;
-}
-__device__ __forceinline__ double fast_rcp(double u) {
-  double r = __builtin_amdgcn_rcp(u);
-  double e = __builtin_fma(-u, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-u, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
-template <int C> struct GA3 {
-  // (+ 2: rows of 20 C doubles put every second node of C = 4 on the same LDS banks -- the pair sweep reads four nodes' rows at once)
-  static constexpr int A3 = 0, A4 = 2 * C, A1 = 4 * C, A2 = 12 * C, SIZE = 20 * C + 2;
-};
-constexpr int TS = 18;
 LGN_STAMP_DECL
 }  // namespace
 LGN_STAMP_READER(lgn_debug_stamps_bwd3)
@@ -59,7 +29,7 @@ struct Bwd3 {
   static constexpr int NG = (C + 3) / 4;
   static constexpr int NS = node_stride(C);
   static constexpr int PS = DEC ? 8 : 4;
-  static constexpr int TRSZ = DEC ? NWV * 64 : (NWV * (NG + 3) * 16 * TS > NWV * 64 * NG * 12 ? NWV * (NG + 3) * 16 * TS : NWV * 64 * NG * 12);
+  static constexpr int TRSZ = DEC ? NWV * 64 : NWV * pair_scratch(NG);
   // phase-1 scratch (upstream gradient tile + CatMix weights) and phase-2 scratch (transpose tiles) share one region
   // phase 1: upstream gradient tile | CatMix weights | aggregate saved by the forward; then (aliased, after a barrier)
   // the per-part partial sums of the CatMix weight gradient
@@ -103,7 +73,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
   static_assert(!SYM || !DEC, "the symmetric sweep is the encoder's");
   using F = Bwd3<C, DEC, NWV>;
   constexpr int BLK = F::BLK;
-  using G = GA3<C>;
+  using G = GARow<C, 2>;                                   // (padded rows: the sweep reads four nodes' rows at once)
   constexpr int NG = F::NG, NS = F::NS, PS = F::PS, K = 5 * C;
   const int N = a.N, B = a.B, CO = a.CO;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -566,39 +536,14 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
   // ---------------- per-lane constants of the pair sweep --------------------------------------------------------
   const int pr = lane & 15, cg = lane >> 4;
   const int tj = pr >> 2, ti = pr & 3;                  // which of the wave's 4 source particles j / slot in the i tile
-  double ak[5], bk[5], ck2[5], wf[NG][5], bias[NG][4];
-  if (!DEC) {
-#pragma unroll
-    for (int s = 0; s < 5; ++s) {
-      const int k = 4 * s + cg;
-      ak[s] = a.ra[k];
-      bk[s] = a.rb[k];
-      const double c = a.rc[k];
-      ck2[s] = c * c;
-    }
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const int rr = lane & 15, q = rr >> 2, ch = 4 * g + (rr & 3);
-      const double* w = (q >> 1) ? a.w1 : a.w0;
-#pragma unroll
-      for (int s = 0; s < 5; ++s) wf[g][s] = ch < C ? w[(2 * ch + (q & 1)) * NB + 4 * s + cg] : 0.0;
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int ch = 4 * g + cg;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double* bb = (q >> 1) ? a.b1 : a.b0;
-      bias[g][q] = ch < C ? (DEC ? bb[ch] : bb[2 * ch + (q & 1)]) : 0.0;
-    }
-  }
+  RadLane<C, DEC> rl;
+  rl.load(a.ra, a.rb, a.rc, a.w0, a.b0, a.w1, a.b1, lane);
   STAMP(4);
   __syncthreads();                                      // g_ag / gd of the whole jet are in LDS; phase-1 scratch is dead
   STAMP(5);
 
   // ---------------- phase 2: one sweep over the ordered pairs (i, j), j-centric ------------------------------------
-  double* trw = tr + wave * (NG + 3) * 16 * TS;         // encoder: transpose tiles of this wave
+  double* trw = tr + wave * pair_tiles(NG);             // encoder: transpose tiles of this wave
   v4d T[NG][3];
   double dB0[NG], dB1[NG];
 #pragma unroll
@@ -644,8 +589,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     for (int m = 0; m < PS; ++m) pme[m] = pj[jj * PS + m];
     const bool mj = DEC ? false : (mk[jj] != 0);
     cx<double> Gs[NG], Gv[NG][4], Gq[4];
-    cx<double> sj[NG], vj[NG][4], vtj[NG][4];            // own (source) node features
-    cx<double> dvj[NG], svj[NG];                         // v_j[3] - v_j[1], v_j[1] + v_j[3]
+    SrcFeat xj[NG];                                      // own (source) node features
+    cx<double> vtj[NG][4];
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       Gs[g] = {0, 0};
@@ -653,12 +598,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       for (int m = 0; m < 4; ++m) Gv[g][m] = {0, 0};
       const int ch = 4 * g + cg, cs = ch < C ? ch : 0;
       const double* nj = nd + jj * NS + cs * 10;
-      sj[g] = {nj[0], nj[1]};
-#pragma unroll
-      for (int m = 0; m < 4; ++m) vj[g][m] = {nj[2 + m], nj[6 + m]};
-      metric_perm(vj[g], vtj[g]);
-      dvj[g] = {vj[g][3].r - vj[g][1].r, vj[g][3].i - vj[g][1].i};
-      svj[g] = {vj[g][1].r + vj[g][3].r, vj[g][1].i + vj[g][3].i};
+      xj[g].load(nj);
+      metric_perm(xj[g].v, vtj[g]);
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) Gq[m] = {0, 0};
@@ -674,59 +615,17 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       const double* pii = pj + ii * PS;
       cx<double> q[4];
       v4d R[NG];
-      double rho[5], an = 0.0;
       double qd0 = 0.0, qd3 = 0.0, qa = 0.0, qb = 0.0;   // encoder: q = [d0, a - ib, d3, -a - ib] (real momenta)
-      bool on = false;
       if (DEC) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) q[m] = {pii[m] - pme[m], pii[4 + m] - pme[4 + m]};
-#pragma unroll
-        for (int g = 0; g < NG; ++g) R[g] = v4d{bias[g][0], bias[g][1], bias[g][2], bias[g][3]};
+        radial_bias(rl.bias, R);
       } else {
-        const double d0 = pii[0] - pme[0], d1 = pii[1] - pme[1], d2 = pii[2] - pme[2], d3 = pii[3] - pme[3];
-        const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
-        const double nsq = (2.0 * q0 - (((q0 + q1) + q2) + q3)) + 1e-16;
-        an = fabs(nsq);
-        on = ok && mj && (mk[ii] != 0) && (nsq != 0.0);
-        const double h = rsqrt2<double>();
-        q[0] = {d0, 0.0};
-        q[1] = {d1 * h, -d2 * h};
-        q[2] = {d3, 0.0};
-        q[3] = {-d1 * h, -d2 * h};
-        qd0 = d0;  qd3 = d3;  qa = d1 * h;  qb = d2 * h;
-        double beta[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 5; ++s) rho[s] = 0.0;
-        if (on) {                                            // (EXEC-masked block: no per-value selects)
-#pragma unroll
-          for (int s = 0; s < 5; ++s) beta[s] = 1.0 + ck2[s] * an;      // (+ 1e-16 of position_levels.py:146: absorbed, the sum is >= 1)
-          rcp5(beta, rho);
-#pragma unroll
-          for (int s = 0; s < 5; ++s) beta[s] = __builtin_fma(bk[s], rho[s], ak[s]);
-        }
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-          R[g] = v4d{bias[g][0], bias[g][1], bias[g][2], bias[g][3]};
-#pragma unroll
-          for (int s = 0; s < 5; ++s) R[g] = __builtin_amdgcn_mfma_f64_16x16x4f64(wf[g][s], beta[s], R[g], 0, 0, 0);
-        }
-        // B-operand source of the radial GEMM: this lane's pair (row pr), columns k = 4s + cg
-        if (kind != 0) {
-          double* xb = trw + NG * 16 * TS;
-#pragma unroll
-          for (int s = 0; s < 5; ++s) {
-            const double x2 = an * rho[s] * rho[s];
-            if (s < 4) {
-              xb[pr * TS + 4 * s + cg] = rho[s];
-              xb[16 * TS + pr * TS + 4 * s + cg] = x2;
-            } else {
-              xb[32 * TS + pr * TS + cg] = rho[s];
-              xb[32 * TS + pr * TS + 4 + cg] = x2;
-            }
-          }
-          xb[32 * TS + pr * TS + 8 + 2 * cg] = cg == 0 ? (on ? 1.0 : 0.0) : 0.0;
-          xb[32 * TS + pr * TS + 9 + 2 * cg] = cg == 0 ? (ok ? 1.0 : 0.0) : 0.0;
-        }
+        const EncPair ep = enc_pair(pii, pme, ok, mj, mk[ii] != 0);
+        qd0 = ep.qd0;  qd3 = ep.qd3;  qa = ep.qa;  qb = ep.qb;
+        double rho[5];
+        radial_masked(rl, rl.wf, rl.bias, ep.an, ep.on, R, rho);
+        if (kind != 0) rad_b_rows(trw + NG * 16 * PAIR_TS, pr, cg, rho, ep.an, ep.on, ok);
       }
       if (rg == glo && i0 < 32) STAMP(17 + (i0 >> 2) * 4);
       const double* gi = ga + ii * G::SIZE;
@@ -751,7 +650,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
           cx<double> ge0 = {0, 0};
           if constexpr (!NOS) {
             cfmac(Gs[g], gA4, e0);
-            ge0 = cmulc(gA4, sj[g]);
+            ge0 = cmulc(gA4, xj[g].s);
           }
           cx<double> gR1;
           if (!DEC) {
@@ -776,13 +675,13 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
             gR1 = {0, 0};
             if (kind != 0) {                                   // (b) gradient w.r.t. the radial values of this pair
 #pragma unroll
-              for (int m = 0; m < 4; ++m) cfmac(ge0, gA1[m], vj[g][m]);
-              gR1 = cmulc(P2, sj[g]);                          // sum_m ge1[m] conj(q[m]) = conj(s_j) P2 + gA3 conj(V)
+              for (int m = 0; m < 4; ++m) cfmac(ge0, gA1[m], xj[g].v[m]);
+              gR1 = cmulc(P2, xj[g].s);                          // sum_m ge1[m] conj(q[m]) = conj(s_j) P2 + gA3 conj(V)
               if constexpr (!NOS) {
                 // V = <v_j, q> = v0 d0 - v2 d3 + a (v3 - v1) - ib (v1 + v3)
                 cx<double> V;
-                V.r = __builtin_fma(vj[g][0].r, qd0, __builtin_fma(-vj[g][2].r, qd3, __builtin_fma(qa, dvj[g].r, qb * svj[g].i)));
-                V.i = __builtin_fma(vj[g][0].i, qd0, __builtin_fma(-vj[g][2].i, qd3, __builtin_fma(qa, dvj[g].i, -qb * svj[g].r)));
+                V.r = __builtin_fma(xj[g].v[0].r, qd0, __builtin_fma(-xj[g].v[2].r, qd3, __builtin_fma(qa, xj[g].dv.r, qb * xj[g].sv.i)));
+                V.i = __builtin_fma(xj[g].v[0].i, qd0, __builtin_fma(-xj[g].v[2].i, qd3, __builtin_fma(qa, xj[g].dv.i, -qb * xj[g].sv.r)));
                 cfmac(gR1, gA3, V);
               }
             }
@@ -838,8 +737,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
               if constexpr (!NOS) cfmac(Gv[g][m], gA3, e1t[m]);
               cfmac(Gs[g], gA2[m], e1[m]);
               // (b) gradient w.r.t. the edge of this pair
-              cfmac(ge0, gA1[m], vj[g][m]);
-              cx<double> ge1 = cmulc(gA2[m], sj[g]);
+              cfmac(ge0, gA1[m], xj[g].v[m]);
+              cx<double> ge1 = cmulc(gA2[m], xj[g].s);
               if constexpr (!NOS) cfmac(ge1, gA3, vtj[g][m]);
               cfmac(gR1, ge1, q[m]);
               cfmac(Gq[m], ge1, R1);
@@ -852,32 +751,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
           dB0[g] += G0r + G0i;                              // R0 = b0 (1+i): d b0 = Re G_R0 + Im G_R0
           dB1[g] += G1r + G1i;
         } else if (kind != 0) {
-          double* ta = trw + g * 16 * TS;                   // [pair][r' = cg + 4q]
-          ta[pr * TS + cg] = G0r;
-          ta[pr * TS + 4 + cg] = G0i;
-          ta[pr * TS + 8 + cg] = G1r;
-          ta[pr * TS + 12 + cg] = G1i;
+          rad_a_rows(trw + g * 16 * PAIR_TS, pr, cg, G0r, G0i, G1r, G1i);
         }
       }
       if (rg == glo && i0 < 32) STAMP(18 + (i0 >> 2) * 4);
-      if (!DEC && kind != 0) {
-        wave_sync();
-        const double* xb = trw + NG * 16 * TS;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int prow = 4 * s + cg;
-          double bv[3];
-#pragma unroll
-          for (int t = 0; t < 3; ++t) bv[t] = xb[t * 16 * TS + prow * TS + pr];
-#pragma unroll
-          for (int g = 0; g < NG; ++g) {
-            const double av = trw[g * 16 * TS + prow * TS + pr];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) T[g][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv[t], T[g][t], 0, 0, 0);
-          }
-        }
-        wave_sync();
-      }
+      if (!DEC && kind != 0) rad_gemm_step(trw, pr, cg, T);
     }
 
     if (rg == glo) STAMP(6);
@@ -899,7 +777,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       __syncthreads();                                       // (rs > 1 is workgroup-uniform and every wave runs this iteration)
       if (rpart != 0) break;
       for (int pp = 1; pp < rs; ++pp) {
-        const double* oth = trw + pp * (NG + 3) * 16 * TS + lane;
+        const double* oth = trw + pp * pair_tiles(NG) + lane;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
           Gs[g].r += oth[(g * 10 + 0) * 64];  Gs[g].i += oth[(g * 10 + 1) * 64];
@@ -989,7 +867,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
 #pragma unroll
               for (int m = 0; m < 4; ++m) v[m] = {nj[2 + m], nj[6 + m]};
               metric_perm(v, vt);
-              const cx<double> R1 = {bias[g][2], bias[g][3]};
+              const cx<double> R1 = {rl.bias[g][2], rl.bias[g][3]};
               cx<double> gA3 = {0, 0};
               if constexpr (!NOS) gA3 = {0.5 * gi[G::A3 + 2 * ch], 0.5 * gi[G::A3 + 2 * ch + 1]};
 #pragma unroll
@@ -1047,68 +925,15 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
   }
   double* part = a.part_rad + prow * rad_partial_size(C, DEC);
   if (DEC) {
-    double* red = tr;
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      double x0 = dB0[g], x1 = dB1[g];
-      for (int m = 1; m < 16; m <<= 1) { x0 += shfl_xor(x0, m); x1 += shfl_xor(x1, m); }
-      if (pr == 0) {
-        red[(wave * NG + g) * 8 + cg] = x0;
-        red[(wave * NG + g) * 8 + 4 + cg] = x1;
-      }
-    }
+    dec_bias_store(tr, wave, pr, cg, dB0, dB1);
     __syncthreads();
-    if (tid < 2 * C) {
-      const int lin = tid / C, ch = tid - lin * C, g = ch >> 2, c4 = ch & 3;
-      double s = 0;
-      for (int w = 0; w < NWV; ++w) s += red[(w * NG + g) * 8 + lin * 4 + c4];
-      part[tid] = s;
-    }
+    dec_bias_sum<C, NWV>(tr, part, tid);
   } else {
-    double* red = tr;
-    {
-      double* mine = red + (size_t)(wave * 64 + lane) * NG * 12;
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) mine[(g * 3 + t) * 4 + q] = T[g][t][q];
-    }
+    rad_rows_store(tr, wave, lane, T);
     __syncthreads();
-    // the 12 NG sums of a lane position are dealt to the first four waves by q (every wave reads LDS only: one wave doing all of them
-    // was 4 000 cycles of the kernel's tail with the other waves idle)
+    // (every wave reads LDS only: the 12 NG sums of a lane position are dealt to the first four waves by q)
     const int wq = __builtin_amdgcn_readfirstlane(wave);
-    if (wq < 4) {
-      constexpr int R = 4 * C;
-      const int col = lane & 15;
-#pragma unroll
-      for (int g = 0; g < NG; ++g) {
-        const int ch = 4 * g + cg;
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            if (q != wq) continue;
-            const int e = (g * 3 + t) * 4 + q;
-            double v = (red[(size_t)(0 * 64 + lane) * NG * 12 + e] + red[(size_t)(1 * 64 + lane) * NG * 12 + e]) +
-                       (red[(size_t)(2 * 64 + lane) * NG * 12 + e] + red[(size_t)(3 * 64 + lane) * NG * 12 + e]);
-            if (NWV == 8)
-              v += (red[(size_t)(4 * 64 + lane) * NG * 12 + e] + red[(size_t)(5 * 64 + lane) * NG * 12 + e]) +
-                   (red[(size_t)(6 * 64 + lane) * NG * 12 + e] + red[(size_t)(7 * 64 + lane) * NG * 12 + e]);
-            if (ch >= C) continue;
-            const int r = (q >> 1) * 2 * C + 2 * ch + (q & 1);
-            if (t == 0) part[r * NB + col] = v;
-            else if (t == 1) part[R * NB + r * NB + col] = v;
-            else {
-              if (col < 4) part[r * NB + 16 + col] = v;
-              else if (col < 8) part[R * NB + r * NB + 16 + (col - 4)] = v;
-              else if (col == 8) part[2 * R * NB + r] = v;
-              else if (col == 9) part[2 * R * NB + R + r] = v;
-            }
-          }
-      }
-    }
+    if (wq < 4) rad_rows_sum<C, NWV, WaveSum::Pairwise, true>(tr, part, lane, wq);
   }
   STAMP(10);
 }

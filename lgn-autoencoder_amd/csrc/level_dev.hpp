@@ -110,37 +110,6 @@ __device__ __forceinline__ void load_jet(const T* __restrict__ s_in, const T* __
   load_jet_commit<T, C, DEC>(s_in, v_in, p, mask, B, N, b, r, nd, pj, mk);
 }
 
-// Radial parameters -> LDS.  encoder: a,b,c, Wt[k][R] (transposed so that the R outputs of one basis
-// function are contiguous), bias[R] with R index = lin*2C + (2c+z).  decoder: bias[R] only, where both
-// planes of channel c carry the same real bias (position_levels.py:184-188 with an all-zero mask).
-template <typename T, int C, bool DEC>
-__device__ __forceinline__ void load_radial(const T* ra, const T* rb, const T* rc, const T* w0, const T* b0,
-                                            const T* w1, const T* b1, T* rp) {
-  using L = Carve<C, DEC>;
-  const int tid = threadIdx.x;
-  if (DEC) {
-    for (int e = tid; e < L::R; e += BLOCK) {
-      int lin = e / (2 * C), c = (e - lin * 2 * C) >> 1;
-      rp[L::RBIAS + e] = lin ? b1[c] : b0[c];
-    }
-  } else {
-    for (int e = tid; e < NB; e += BLOCK) {
-      rp[L::RA + e] = ra[e];
-      rp[L::RB + e] = rb[e];
-      rp[L::RC + e] = rc[e];
-    }
-    for (int e = tid; e < NB * L::R; e += BLOCK) {
-      int k = e / L::R, r = e - k * L::R;
-      int lin = r / (2 * C), f = r - lin * 2 * C;
-      rp[L::RW + e] = (lin ? w1 : w0)[f * NB + k];
-    }
-    for (int e = tid; e < L::R; e += BLOCK) {
-      int lin = e / (2 * C), f = e - lin * 2 * C;
-      rp[L::RBIAS + e] = (lin ? b1 : b0)[f];
-    }
-  }
-}
-
 // Geometry of one ordered pair (i, j): q = canonical(p_i - p_j); encoder also the signed norm + mask.
 template <typename T, bool DEC>
 struct PairGeom {
@@ -169,32 +138,6 @@ __device__ __forceinline__ PairGeom<T, DEC> pair_geom(const T* pi, const T* pjj,
     g.q[3] = {-d1 * h, -d2 * h};
   }
   return g;
-}
-
-// Radial network of one pair: rad[lin*2C + 2c + z].  Masked pairs keep the Linear bias
-// (position_levels.py:144-149: the mask zeroes the basis, not the output).
-template <typename T, int C, bool DEC>
-__device__ __forceinline__ void radial_eval(const T* rp, T nrm, bool on, T (&rad)[4 * C]) {
-  using L = Carve<C, DEC>;
-#pragma unroll
-  for (int r = 0; r < L::R; ++r) rad[r] = rp[L::RBIAS + r];
-  if (!DEC) {
-    if (on) {
-      for (int k = 0; k < NB; ++k) {
-        T t = rp[L::RC + k] * nrm;
-        T u = (T(1) + t * t) + T(1e-16);
-        T beta = rp[L::RB + k] * (T(1) / u) + rp[L::RA + k];
-        const T* w = rp + L::RW + k * L::R;
-#pragma unroll
-        for (int r = 0; r < L::R; ++r) rad[r] += w[r] * beta;
-      }
-    }
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ cx<T> ld_cx(const T* base, int off_r, int off_i) {
-  return {base[off_r], base[off_i]};
 }
 
 // <a, b> * 2 = a0 b0 + a1 b3 - a2 b2 + a3 b1  (the 1/2 of the CG coefficient is applied by the caller)

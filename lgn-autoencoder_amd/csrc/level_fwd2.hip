@@ -23,36 +23,8 @@
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 LGN_STAMP_DECL
 LGN_STAMP_READER(lgn_debug_stamps_fwd2)
-
-__device__ __forceinline__ double dpp_quad(double v, int ctrl_is_xor2) {
-  // quad_perm [1,0,3,2] = 0xB1 (xor 1), [2,3,0,1] = 0x4E (xor 2)
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  if (ctrl_is_xor2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  }
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double quad_sum(double v) {
-  v += dpp_quad(v, 0);
-  v += dpp_quad(v, 1);
-  return v;
-}
-
-// 1/u for u >= 1: hardware reciprocal seed + two Newton steps (the reference divides; relative difference <= 1 ulp)
-__device__ __forceinline__ double fast_rcp(double u) {
-  double r = __builtin_amdgcn_rcp(u);
-  double e = __builtin_fma(-u, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-u, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
 
 template <int C, bool DEC>
 struct Fwd2 {
@@ -393,6 +365,8 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
       int jj;
       bool ok;
     };
+    // (prep() spells out enc_pair and radial_masked of pair_dev.hpp, the form level_bwd3 and level_bwd_sweep_enc call: restated through
+    // them, the C = 8 dead-scalar instantiation of this kernel gained spills.  A change to those two pieces is made here too.)
     auto prep = [&](int j0, Tile& T) {
       const int j = j0 + tj;
       T.ok = iok && j < N;

@@ -28,7 +28,6 @@
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 namespace { LGN_STAMP_DECL }
 #ifdef LGN_STAMPS
 #define DSTAMP(i) do { if (threadIdx.x == 256 && blockIdx.x == 0) g_stamps[i] = clock64(); } while (0)

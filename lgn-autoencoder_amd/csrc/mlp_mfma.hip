@@ -27,7 +27,6 @@
 
 namespace lgn {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 namespace { LGN_STAMP_DECL }
 LGN_STAMP_READER(lgn_debug_stamps_mlp)
 

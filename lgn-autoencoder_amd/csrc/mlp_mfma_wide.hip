@@ -14,8 +14,6 @@
 namespace lgn {
 namespace wide {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 __host__ __device__ constexpr int pad4(int x) { return (x + 3) & ~3; }
 __host__ __device__ constexpr int lds_stride(int x) { return x + ((6 - (x & 3)) & 3); }   // == 2 (mod 4): conflict-free b64 reads
 
