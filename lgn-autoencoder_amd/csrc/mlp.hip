@@ -10,12 +10,6 @@
 
 namespace lgn {
 
-static size_t mlp_param_count(int C, int H, int nlin) {
-  const int D = 2 * C;
-  if (nlin == 1) return (size_t)D * D + D;
-  return ((size_t)H * D + H) + (size_t)(nlin - 2) * ((size_t)H * H + H) + ((size_t)D * H + D);
-}
-
 template <typename T>
 int mlp_dispatch(const MlpArgs<T>& a, bool backward, hipStream_t stream) {
   LGN_CHECK_ARG(a.M > 0 && a.C > 0, "cgmlp: empty input (M=%d C=%d)", a.M, a.C);
@@ -23,7 +17,7 @@ int mlp_dispatch(const MlpArgs<T>& a, bool backward, hipStream_t stream) {
   LGN_CHECK_ARG(a.C <= 8, "cgmlp: %d channels unsupported (1..8)", a.C);
   LGN_CHECK_ARG(a.act >= 0 && a.act < LGN_ACT_COUNT, "cgmlp: unknown activation id %d (LGN_ACT_*)", a.act);
   LGN_CHECK_ARG(a.H >= 2 * a.C && a.H <= 96, "cgmlp: hidden width %d unsupported (2C..96)", a.H);
-  if (backward) LGN_CHECK_ARG((size_t)a.psize == mlp_param_count(a.C, a.H, a.nlin), "cgmlp: psize mismatch");
+  if (backward) LGN_CHECK_ARG(a.psize == mlp_param_count(a.C, a.H, a.nlin), "cgmlp: psize mismatch");
   int rc = mlp_chain_dispatch(a, backward, stream);
   if (rc == -2) rc = mlp_mfma_dispatch(a, backward, stream);
   if (rc == -2) rc = mlp_mfma_wide_dispatch(a, backward, stream);

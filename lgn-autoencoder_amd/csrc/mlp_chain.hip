@@ -116,7 +116,7 @@ struct Geo {
   static constexpr int hout(int l) { return l == NH ? D : H; }
   static constexpr int hin(int l) { return l == 0 ? D : H; }
   static constexpr int off_b(int l) { return off_w(l) + hout(l) * hin(l); }
-  static constexpr int psize() { return off_b(NH) + D; }
+  static constexpr int psize() { return mlp_param_count(D / 2, H, NH + 1); }
 };
 
 // ---- weight images ---------------------------------------------------------------------------------

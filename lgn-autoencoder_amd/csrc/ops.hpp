@@ -115,6 +115,10 @@ __host__ __device__ inline size_t mlp_out_index(const MlpArgs<T>& a, int z, int 
   if (a.tbQ > 0) return ((size_t)((row >> 6) * a.C + ch) * a.tbQ) * 128 + z * 64 + (row & 63);
   return ((size_t)z * a.M * a.C + (size_t)row * a.C + ch) * a.ld;
 }
+// parameters of a CGMLP = doubles of a partial row of its gradients, concat_l (W_l, b_l): Linear(2C -> H), nlin - 2 x Linear(H -> H), Linear(H -> 2C)
+constexpr int mlp_param_count(int C, int H, int nlin) {
+  return nlin == 1 ? 2 * C * 2 * C + 2 * C : (H * 2 * C + H) + (nlin - 2) * (H * H + H) + (2 * C * H + 2 * C);
+}
 template <typename T> int mlp_dispatch(const MlpArgs<T>&, bool backward, hipStream_t);
 // standalone Clebsch-Gordan product (cg_product.hip)
 int cg_product_fwd(int R, int N, int C, int D1, int D2, int DO, int mode, int nnz, const int* row_ptr, const int* col, const double* coef,

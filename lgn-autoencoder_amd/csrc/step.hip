@@ -117,11 +117,6 @@ int end_step(Deferred& dq, const RadFinJob& fin, double* grads, long long n_para
 
 inline int in_K(const lgn_net_desc& d) { return d.n_in_scalars > 1 ? d.n_in_scalars : 1; }      // encoder input scalars per node
 
-int mlp_psize(int C, int H, int nlin) {
-  const int D = 2 * C;
-  return nlin == 1 ? D * D + D : (H * D + H) + (nlin - 2) * (H * H + H) + (D * H + D);
-}
-
 // decoder node count of a whole step: its own (jet_features gives the encoder one node more than the decoder reconstructs), or N
 inline int dec_nodes(const lgn_net_desc& d) { return d.dec_N > 0 ? d.dec_N : d.N; }
 // the step takes the two-kernel junction and the riding input stage only when both networks work on the same nodes and the mass is
@@ -189,7 +184,7 @@ size_t net_parts(const lgn_net_desc& d, bool dec, int N) {
   for (int l = 0; l < d.n_levels; ++l) {
     const int H = d.mlp_hidden_mul * 2 * ch[l + 1];
     sum += r16((size_t)rm * 4 * ch[l + 1] * 5 * ch[l]) + r16((size_t)rr * rad_partial_size(ch[l], dec)) +
-           r16((size_t)mlp_partial_rows(d.B * (dec ? dec_nodes(d) : N), H) * mlp_psize(ch[l + 1], H, d.mlp_nlin));
+           r16((size_t)mlp_partial_rows(d.B * (dec ? dec_nodes(d) : N), H) * mlp_param_count(ch[l + 1], H, d.mlp_nlin));
   }
   // the encoder's input-stage rows: one per jet, or one per workgroup of the first level's backward when they ride on it
   return sum + end_parts(d, dec, N, rm > d.B ? rm : d.B);
@@ -352,7 +347,7 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       m.s_in = n.smix[l]; m.g_out = w.gs[cur]; m.g_in = w.gsmix;
       m.h_saved = n.hsave[l];
       m.h_rows = mlp_saved_rows(BN);
-      m.psize = mlp_psize(CO, m.H, m.nlin);
+      m.psize = mlp_param_count(CO, m.H, m.nlin);
       DQ_TAKE(m.part, (size_t)mlp_partial_rows(BN, m.H) * m.psize);
       LGN_TRY(mlp_dispatch<double>(m, true, st));
       // the MLP's parameters are contiguous in the flat buffer in (W_0, b_0, W_1, ...) order (checked at plan time)
@@ -603,7 +598,7 @@ size_t gen_net_parts(const lgn_net_desc& d, bool dec) {
     const size_t lrows = tb ? (sep ? (size_t)local_sep_part_rows(d.B) : tiles) * local_static_packed_doubles(g.tab[l]->static_kind, g.ch[l], g.ch[l + 1])
                             : (size_t)local_partial_rows((int)BN) * 2 * g.tab[l]->n_w;
     sum += r16(lrows) + r16((size_t)d.B * rad_partial_size(g.ch[l], dec)) +
-           r16((size_t)mlp_partial_rows((int)BN, H) * mlp_psize(g.ch[l + 1], H, d.mlp_nlin));
+           r16((size_t)mlp_partial_rows((int)BN, H) * mlp_param_count(g.ch[l + 1], H, d.mlp_nlin));
   }
   return sum + end_parts(d, dec, d.N, d.B);
 }
@@ -727,7 +722,7 @@ int gen_levels_bwd(const lgn_net_desc& d, bool dec, const double* P, double* G, 
       m.s_in = a.smix[l];
       if (tb) { m.g_out = sc.gX[cur] + (size_t)g.qs[l + 1] * 128; m.g_in = sc.gX[cur] + (size_t)g.qs[l + 1] * 128; m.tbQ = g.Q[l + 1]; }
       else { m.g_out = sc.gX[cur] + g.qs[l + 1]; m.g_in = sc.gX[cur] + g.qs[l + 1]; m.ld = g.Q[l + 1]; }
-      m.psize = mlp_psize(CO, m.H, m.nlin);
+      m.psize = mlp_param_count(CO, m.H, m.nlin);
       DQ_TAKE(m.part, (size_t)mlp_partial_rows(BN, m.H) * m.psize);
       LGN_TRY(mlp_dispatch<double>(m, true, st));
       dq.add(m.part, mlp_partial_rows(BN, m.H), m.psize, 0, m.psize, G + off[S.mlp(dec, l, 0)]);

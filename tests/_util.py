@@ -1,5 +1,6 @@
 """Helpers shared by the tests: golden-fixture loading, tolerance helpers."""
 import ast
+import hashlib
 import json
 import os
 
@@ -30,6 +31,12 @@ def params_from(npz, prefix):
 
 def meta(npz):
     return json.loads(str(npz["meta"]))
+
+
+def sha(bufs):
+    """{name: sha256 of the tensor's bytes} of device buffers, after the device has finished: the bit-for-bit pins"""
+    torch.cuda.synchronize()
+    return {k: hashlib.sha256(np.ascontiguousarray(v.detach().cpu().numpy()).tobytes()).hexdigest() for k, v in bufs.items()}
 
 
 def relerr(a, b):

@@ -7,7 +7,6 @@ generators with fixed seeds.  Shapes (C, CO, N, B) are the smallest that reach e
 jets per workgroup with a padded third group (symmetric backward: tiles above, on and below the diagonal); 2 jets of 9 =
 level_jet_split with the rs = 2 and rs = 4 receiver split; N = 41 = level_bwd_mix + level_bwd_sweep_enc with four waves; N = 150,
 one jet = eight waves and several receiver chunks; N = 33 at maxdim 3 = the moments kernels of generic_moments.hip by size."""
-import hashlib
 import json
 import os
 
@@ -51,12 +50,6 @@ Q3 = 4 + 3 + 3 + 9 + 1          # packed components of a maxdim = 3 node: (1,1),
 CH = ((3, 3, 4, 4), (4, 4, 3, 3))   # channels of the training step, as tests/test_gpu_step_plumbing_bits.py
 
 
-def _sha(bufs):
-    import numpy as np
-    torch.cuda.synchronize()
-    return {k: hashlib.sha256(np.ascontiguousarray(v.detach().cpu().numpy()).tobytes()).hexdigest() for k, v in bufs.items()}
-
-
 def _radial(decoder, C, g):
     """the seven radial parameters of one level, O(1) so that every gradient path carries digits; on the device"""
     from oracle import lgn_oracle as O
@@ -92,7 +85,7 @@ def level_bits(decoder, C, CO, N, B):
     bufs.update({f"g_rad{k}": t for k, t in enumerate(rg)})
     if decoder:
         bufs["g_p"] = g_p
-    return _sha(bufs)
+    return U.sha(bufs)
 
 
 def moments_bits(decoder, C, N, B):
@@ -110,7 +103,7 @@ def moments_bits(decoder, C, N, B):
     bufs.update({f"g_rad{k}": t for k, t in enumerate(rg)})
     if decoder:
         bufs["g_p"] = g_p
-    return _sha(bufs)
+    return U.sha(bufs)
 
 
 def step_bits(N, B):
@@ -124,8 +117,8 @@ def step_bits(N, B):
     st = NativeTrainStep(enc, dec, batch_size=B, lr=1e-3, l1_lambda=1e-6, use_graph=True)
     losses = torch.stack([st.step(batch)[0].clone() for _ in range(2)])
     torch.cuda.synchronize()
-    return _sha({"losses": losses, "loss_out": st.loss_out, "grad": st.flat.grad, "adam_m": st.adam_m, "adam_v": st.adam_v,
-                 "weights": st.flat.flat, "step": st.step_dev, "recon": st.recon, "loss_part": st.loss_part})
+    return U.sha({"losses": losses, "loss_out": st.loss_out, "grad": st.flat.grad, "adam_m": st.adam_m, "adam_v": st.adam_v,
+                  "weights": st.flat.flat, "step": st.step_dev, "recon": st.recon, "loss_part": st.loss_part})
 
 
 def case_bits(case):
