@@ -212,6 +212,7 @@ class CGModule(nn.Module):
                 with torch.no_grad():
                     v.copy_(state_dict[k])
             del state_dict[k]
+        self._zero_padding()
         seen = {k[len(prefix):] for k in mine}
         missing_keys.extend(prefix + n for n in views if n not in seen)
 
@@ -233,7 +234,16 @@ class CGModule(nn.Module):
             for k, v in views.items():
                 if k in state_dict:
                     v.copy_(state_dict[k])
+        self._zero_padding()
         return _IncompatibleKeys(missing, unexpected)
+
+    def _zero_padding(self):
+        """A checkpoint holds the reference-shaped tensors only: after loading one, the padding columns of the wider stored
+        blocks are zero whatever the block held before (what _flatten_parameters promises the kernels)."""
+        with torch.no_grad():
+            for t, shape in zip(self._p_stores, self._p_shapes):
+                if tuple(t.shape) != tuple(shape):
+                    t[..., shape[-1]:].zero_()
 
     def zero_grad(self, set_to_none: bool = True):
         """nn.Module.zero_grad walks the whole module tree (~100 sub-modules, 0.1 ms of host time per call); every parameter

@@ -173,11 +173,12 @@ def test_native_step_maxdim3_fused_decoder_matches_the_two_kernel_form(B, N, che
             monkeypatch.delenv("LGN_AMD_DEC_UNFUSED")
         st.step(batch)
         loss, recon = st.step(batch)          # (the replay)
-        runs.append((loss.clone(), recon.clone(), st.flat.grad.clone()))
+        runs.append((loss.clone(), recon.clone(), st.flat.grad.clone(), [(k, g.clone()) for k, g in U.named_grads(enc, dec)]))
     U.assert_close(runs[0][0], runs[1][0], 1e-13, "loss")
     U.assert_close(runs[0][1], runs[1][1], 1e-12, "recon")
     # gradients: every named tensor against its own scale (the two forms add the same terms in a different order)
     U.assert_close(runs[0][2], runs[1][2], 1e-11, "flat gradient")
+    U.assert_named_grads_close(runs[0][3], dict(runs[1][3]), 1e-11, "per tensor")
     assert torch.isfinite(runs[0][2]).all()
 
 
@@ -217,6 +218,7 @@ def test_native_step_full_size_properties(name, B, N, maxdim, che, chd):
     U.assert_close(la, lb, 1e-12, "loss")
     U.assert_close(ra, rb, 1e-12, "recon")
     U.assert_close(a.flat.grad, b.flat.grad, 1e-9, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), dict(U.named_grads(enc2, dec2)), 1e-9, "per tensor")
     assert torch.isfinite(a.flat.grad).all()
 
 
@@ -244,6 +246,7 @@ def test_native_step_batch_regimes(B, monkeypatch):
     U.assert_close(la, lb, 1e-12, "loss")
     U.assert_close(ra, rb, 1e-12, "recon")
     U.assert_close(a.flat.grad, b.flat.grad, 1e-9, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), dict(U.named_grads(enc2, dec2)), 1e-9, "per tensor")
     # every size runs chain CGMLP kernels (16-row workgroups below 8 129 rows, since round 6): against the 12-wave kernels
     enc3, dec3 = G._models(N, che, chd, dev, seed=5)
     monkeypatch.setenv("LGN_AMD_MLP_V1", "1")
@@ -299,6 +302,7 @@ def test_native_step_mlp_widths(width, maxdim, B):
     U.assert_close(la, lb, 1e-12, "loss")
     U.assert_close(ra, rb, 1e-12, "recon")
     U.assert_close(a.flat.grad, b.flat.grad, 1e-9, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), dict(U.named_grads(enc2, dec2)), 1e-9, "per tensor")
     assert torch.isfinite(a.flat.grad).all()
 
 
@@ -728,6 +732,7 @@ def test_native_step_maxdim3_other_shapes_match_per_op_path(N, chans):
     U.assert_close(la, lb, 1e-11, "loss")
     U.assert_close(ra, rb, 1e-11, "recon")
     U.assert_close(a.flat.grad, b.flat.grad, 1e-9, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), dict(U.named_grads(enc2, dec2)), 1e-9, "per tensor")
 
 
 @pytest.mark.parametrize("maxdim,ch_enc,ch_dec,N,B", [(3, (2, 4, 7, 8), (8, 6, 5, 3), 13, 5), (3, (4, 4, 6, 6), (6, 6, 4, 4), 30, 3),
@@ -756,12 +761,14 @@ def test_poisoned_buffers_padding_lanes_never_reach_a_result(maxdim, ch_enc, ch_
     assert torch.isfinite(a.flat.grad).all() and torch.isfinite(ra).all() and torch.isfinite(la)
     U.assert_close(la, lb, 1e-11, "native step: loss")
     U.assert_close(a.flat.grad, ref.flat.grad, 1e-9, "native step: flat gradient")
+    U.assert_named_grads_close(U.named_grads(*nets[0]), dict(U.named_grads(*nets[2])), 1e-9, "native step: per tensor")
     monkeypatch.setenv("LGN_AMD_POISON", "1")
     m = TrainStep(*nets[1], optimizer=False)          # whole-network native calls under autograd
     lm, rm = m.forward_backward(batch)
     assert torch.isfinite(m.flat.grad).all() and torch.isfinite(rm).all()
     U.assert_close(lm, lb, 1e-11, "module path: loss")
     U.assert_close(m.flat.grad, ref.flat.grad, 1e-9, "module path: flat gradient")
+    U.assert_named_grads_close(U.named_grads(*nets[1]), dict(U.named_grads(*nets[2])), 1e-9, "module path: per tensor")
 
 
 def test_deepcopy_of_a_network_that_has_run():

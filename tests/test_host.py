@@ -338,6 +338,10 @@ def test_fewer_radial_bells_are_stored_padded_and_seen_unpadded():
     enc2.load_state_dict(sd)
     for (k, v), (_, w) in zip(enc2.state_dict().items(), sd.items()):
         assert torch.equal(v, w), k
+    padded = [(t, s) for t, s in zip(enc2._p_stores, enc2._p_shapes) if tuple(t.shape) != tuple(s)]
+    assert len(padded) == 2 * 5, "a, b, c and the two Linear weights of both levels are stored wider than the reference's shape"
+    for stored, shape in padded:
+        assert float(stored[..., shape[-1]:].abs().max()) == 0, "load_state_dict must leave the padding columns at zero"
     assert enc2.flat_params.data_ptr() != enc.flat_params.data_ptr()
     # gradients: named_grads are the narrow views of the flat gradient
     enc.flat_params.grad = torch.arange(enc.flat_params.numel(), dtype=torch.float64)
