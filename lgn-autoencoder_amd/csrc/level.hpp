@@ -34,6 +34,7 @@ constexpr int LVL_MLP_BWD1 = 1024;      // CGMLP chain backward: the one-role ke
 constexpr int LVL_MLP_FULLTILE = 2048;  // CGMLP chain kernels (64-row workgroups): the padded last hidden tile as a full 16 x 16 tile instead of four-neuron blocks (cross-check)
 constexpr int LVL_MOMENTS_SPLIT = 512; // table-driven encoder levels: the backward's two pair sweeps as two kernels (cross-check of the merged one)
 constexpr int LVL_LIVE_SCALARS = 4096; // last levels whose scalars nobody reads (LevelArgs / LevelBwdArgs::dead_scalars): the kernels with live scalars, on the zero block (cross-check)
+constexpr int LVL_DEC_STORE_AG = 16384; // separable decoder levels of the sequencers (N <= 40): store and re-read the aggregate instead of rebuilding it from the jet sums (LevelArgs::sep_sums; cross-check)
 constexpr int LVL_BWD_ORDERED = 64;    // encoder level backward (N <= 40): radial-gradient GEMM per ORDERED pair tile (cross-check of the symmetric sweep)
 int level_flags_from_env();
 
@@ -85,7 +86,13 @@ struct LevelArgs {
   // Last level of a network whose scalar output nobody reads (step.hip: levels_fwd): the scalar aggregates A3 / A4, the
   // scalar CatMix rows, s_out and ag0 are neither computed nor stored (both may be null); v_out and ag1 are what they always are.
   int dead_scalars = 0;
+  // Separable decoder level of a sequencer (step.hip; N <= 40, training): [B][20 C + 8] -- the jet-level sums S | VS | SP | VP of every
+  // channel, then the eight means the momenta were centred on.  When set, the forward stores this block INSTEAD of ag0 / ag1 (neither
+  // is written): every row of the aggregate is a function of it and the node's centred momentum (level_dev.hpp: dec_sep_row), which the
+  // backward evaluates again.  Null in the per-operator calls and in every other form of the level.
+  T* sep_sums = nullptr;
 };
+constexpr int sep_sums_doubles(int C) { return 20 * C + 8; }
 
 template <typename T>
 struct LevelBwdArgs {
@@ -116,6 +123,9 @@ struct LevelBwdArgs {
   // g_s_out == 0 makes an exact zero is left out -- g_s_out and ag0 are not read (may be null), the wm0 half of the part_mix row is
   // not written.  The N > 40 kernels ignore it: the caller gives them the zero block as g_s_out.
   int dead_scalars = 0;
+  // Separable decoder level whose forward stored LevelArgs::sep_sums instead of the aggregate: ag0 / ag1 are not read, the rows are
+  // rebuilt in LDS from this block.
+  const T* sep_sums = nullptr;
 };
 
 // Per-node stride (in scalars) of the node tile kept in LDS: [c][ s_r s_i v_r[4] v_i[4] ] + 2 pad.

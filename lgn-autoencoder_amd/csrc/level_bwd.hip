@@ -429,6 +429,9 @@ static bool use_v3(int N, int flags) { return !(flags & LVL_LEVEL_V2) && level_b
 
 // does the level backward for N-particle jets run as the one kernel that can carry the input stage's backward (LevelBwdArgs::part_in0)?
 bool level_bwd_carries_input(int N, int flags) { return use_v3(N, flags); }
+// does a decoder level of N-particle jets, run by a sequencer, leave its jet sums instead of the aggregate (LevelArgs::sep_sums)?  The
+// separable forward and the one-kernel separable backward of a training step; LVL_DEC_STORE_AG keeps the stored aggregate
+bool level_dec_rebuilds(int N, int flags) { return use_v3(N, flags) && !(flags & (LVL_DEC_PAIRWISE | LVL_DEC_STORE_AG)); }
 
 // number of partial rows the backward launch writes (host side must size the workspace with these)
 void level_bwd_partial_rows(int B, int N, int decoder, int flags, int* rows_mix, int* rows_rad) {
@@ -453,6 +456,7 @@ static int launch_level_bwd(const LevelBwdArgs<T>& a, hipStream_t stream) {
   const int N = a.N, CO = a.CO, tiles = cdiv(N, 32);
   int rc;
   if (use_v3(N, a.flags)) return level_bwd3_dispatch(a, DEC, stream);
+  LGN_CHECK_ARG(!a.sep_sums, "level_bwd: N=%d: this form of the backward reads the stored aggregate", N);
   {  // 1. CatMix / power
     auto kern = level_bwd_mix_kernel<T, C>;
     size_t smem = sizeof(T) * (4 * CO * 5 * C + 32 * (5 * C * 10) + 32 * CO * 10);

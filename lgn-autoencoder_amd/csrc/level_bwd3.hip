@@ -95,6 +95,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
   double* sm = tr + F::scratch(N, CO);                         // decoder: 50 C jet-level sums
   uint8_t* mk = reinterpret_cast<uint8_t*>(sm + F::SEPSZ);
 
+  // Separable decoder level whose forward left its jet sums instead of the aggregate (LevelBwdArgs::sep_sums): ag0 / ag1 are not
+  // read; the forward's 20 C sums and eight means arrive with the staging round trip (in `sm`, which nothing uses before the
+  // separable block below), and the rows of `agl` are filled from them by the forward's own row function before phase 1.
+  bool rebuild = false;
+  if constexpr (DEC && SEP) rebuild = a.sep_sums != nullptr;      // (workgroup-uniform)
   // ---------------- staging ----------------------------------------------------------------------------
   STAMP(0);
   // Every thread's first item of every array is requested before anything is written to LDS (see load_jet_issue): the jet, the
@@ -105,19 +110,29 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     load_jet_issue<double, C, DEC>(a.s_in, a.v_in, a.p, a.mask, B, N, b, jr);
     const int eg = tid < N * CO ? tid : 0, ea_ = tid < N * 2 * C ? tid : 0, ew = tid < 2 * CO * K ? tid : 0;
     const size_t ig = (size_t)b * N * CO + eg, ia = (size_t)b * N * 2 * C + ea_;
-    double rg[10], ra[10];
+    double rg[10], ra[10], fs = 0.0;
     if constexpr (!NOS) {
       rg[0] = a.g_s_out[ig];
       rg[1] = a.g_s_out[plo + ig];
-      ra[0] = a.ag0[ia];
-      ra[1] = a.ag0[pa + ia];
     }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       rg[2 + m] = a.g_v_out[ig * 4 + m];
       rg[6 + m] = a.g_v_out[plo * 4 + ig * 4 + m];
-      ra[2 + m] = a.ag1[ia * 4 + m];
-      ra[6 + m] = a.ag1[(pa + ia) * 4 + m];
+    }
+    if (!rebuild) {
+      if constexpr (!NOS) {
+        ra[0] = a.ag0[ia];
+        ra[1] = a.ag0[pa + ia];
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        ra[2 + m] = a.ag1[ia * 4 + m];
+        ra[6 + m] = a.ag1[(pa + ia) * 4 + m];
+      }
+    } else if constexpr (DEC && SEP) {
+      static_assert(sep_sums_doubles(C) <= BLK && sep_sums_doubles(C) <= F::SEPSZ, "the forward's sums are one item per thread, kept in sm");
+      fs = a.sep_sums[(size_t)b * sep_sums_doubles(C) + (tid < sep_sums_doubles(C) ? tid : 0)];
     }
     const double w0v = a.wm0[ew], w1v = a.wm1[ew];
     load_jet_commit<double, C, DEC>(a.s_in, a.v_in, a.p, a.mask, B, N, b, jr, nd, pj, mk);
@@ -125,10 +140,11 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
 #pragma unroll
       for (int m = NOS ? 2 : 0; m < 10; ++m) go[tid * 10 + m] = rg[m];
     }
-    if (tid < N * 2 * C) {
+    if (!rebuild && tid < N * 2 * C) {
 #pragma unroll
       for (int m = NOS ? 2 : 0; m < 10; ++m) agl[tid * 10 + m] = ra[m];
     }
+    if (rebuild && tid < sep_sums_doubles(C)) sm[tid] = fs;
     if (tid < 2 * CO * K) {
       wm[tid] = w0v;
       wm[2 * CO * K + tid] = w1v;
@@ -151,7 +167,7 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
         g[6 + m] = a.g_v_out[plo * 4 + idx * 4 + m];
       }
     }
-    for (int e = tid + BLK; e < N * 2 * C; e += BLK) {
+    for (int e = tid + BLK; !rebuild && e < N * 2 * C; e += BLK) {
       const size_t ea = (size_t)b * N * 2 * C + e;
       double* x = agl + e * 10;
       if constexpr (!NOS) {
@@ -166,6 +182,29 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     }
   }
   __syncthreads();
+  if constexpr (DEC && SEP) {
+    if (rebuild) {
+      // centre the momenta on the forward's means (the values the block below would compute again), then the rows as the forward did
+      for (int e = tid; e < N * 8; e += BLK) pj[e] -= sm[20 * C + (e & 7)];
+      __syncthreads();
+      for (int e = tid; e < N * C; e += BLK) {
+        const int n = e / C, c = e - n * C;
+        const SepRow row = dec_sep_row<NOS>(sm + c * 20, pj + n * 8, a.b0[c], a.b1[c]);
+        double* x0 = agl + (n * 2 * C + c) * 10;             // cat slot q = 0: A3 | A1
+        double* x1 = agl + (n * 2 * C + C + c) * 10;         //          q = 1: A4 | A2
+        if constexpr (!NOS) {
+          x0[0] = row.a3h.r;  x0[1] = row.a3h.i;
+          x1[0] = row.a4.r;   x1[1] = row.a4.i;
+        }
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          x0[2 + m] = row.a1[m].r;  x0[6 + m] = row.a1[m].i;
+          x1[2 + m] = row.a2[m].r;  x1[6 + m] = row.a2[m].i;
+        }
+      }
+      __syncthreads();
+    }
+  }
   STAMP(1);
 
   // ---------------- phase 1a: per (node, channel) CatMix^H, power backward ---------------------------------
@@ -336,19 +375,21 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
     STAMP(3);
     __syncthreads();                                    // g_ag / gd are complete; the phase-1 scratch is dead
     STAMP(4);
-    // centre the momenta on the jet mean (only differences enter; see level_fwd2.hip)
-    if (tid < 64) {                                       // lane = (node part, component): 8 x 8, parts meet by shuffles
-      const int k = tid & 7, part = tid >> 3;
-      double mean = 0.0;
-      for (int n = part; n < N; n += 8) mean += pj[n * 8 + k];
-      mean += shfl_xor(mean, 8);
-      mean += shfl_xor(mean, 16);
-      mean += shfl_xor(mean, 32);
-      if (part == 0) sm[k] = mean / N;
+    // centre the momenta on the jet mean (only differences enter; see level_fwd2.hip) -- unless they were, to rebuild the aggregate
+    if (!rebuild) {
+      if (tid < 64) {                                       // lane = (node part, component): 8 x 8, parts meet by shuffles
+        const int k = tid & 7, part = tid >> 3;
+        double mean = 0.0;
+        for (int n = part; n < N; n += 8) mean += pj[n * 8 + k];
+        mean += shfl_xor(mean, 8);
+        mean += shfl_xor(mean, 16);
+        mean += shfl_xor(mean, 32);
+        if (part == 0) sm[k] = mean / N;
+      }
+      __syncthreads();
+      for (int e = tid; e < N * 8; e += BLK) pj[e] -= sm[e & 7];
+      __syncthreads();
     }
-    __syncthreads();
-    for (int e = tid; e < N * 8; e += BLK) pj[e] -= sm[e & 7];
-    __syncthreads();
     // ---- jet-level sums: wave = channel, lane = node; the 50 per-node terms stay in registers and are summed over the lanes
     //      by transposing butterflies (wave_sum.hpp) -- no LDS round trip, no barrier per round (round 2: three rounds of 20
     //      reals per (node, channel) through LDS, each a barrier, a 30-deep serial sum by 80 threads and another barrier)
@@ -945,6 +986,7 @@ static int launch_bwd3_w(const LevelBwdArgs<double>& a, int split, hipStream_t s
   size_t smem = Bwd3<C, DEC, NWV>::smem(a.N, a.CO);
   LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd: N=%d C=%d needs %zu B of LDS", a.N, a.C, smem);
   LGN_CHECK_ARG(a.CO <= 8, "level_bwd: C_out=%d unsupported (1..8)", a.CO);
+  LGN_CHECK_ARG(!a.sep_sums || (DEC && SEP), "level_bwd: only the separable decoder backward rebuilds the aggregate from jet sums");
   auto kern = level_bwd3_kernel<C, DEC, SEP, NWV, false, NOS>;
   if constexpr (!DEC && C <= 4) {       // whole jets per workgroup: the sweep that uses R(i, j) = R(j, i) (LVL_BWD_ORDERED: the plain one;
                                         // C > 4: two lane groups of channels, the second pass would double the spills)

@@ -152,6 +152,60 @@ __device__ __forceinline__ cx<T> bil2(const cx<T> (&a)[4], const cx<T> (&b)[4]) 
   return r;
 }
 
+// One row of the separable decoder aggregate (level_fwd2.hip: SEP), one channel of one node:
+//   A4 = S e0            A1[m] = VS[m] e0            e0 = R0 (1 + i), R0 = b0 (1 + i)
+//   A3 = R1 (<VS, p> - VP) / 2        A2[m] = R1 (p[m] S - SP[m])        R1 = b1 (1 + i)
+// from the channel's jet sums sm = S | VS[4] | SP[4] | VP and the node's centred momentum pn = re[4] | im[4].  The forward computes the
+// row and the backward computes it AGAIN instead of reading it back (LevelArgs::sep_sums), so the two must agree bit for bit, and the
+// forward's s_out / v_out are pinned: every multiply-add is spelled out, as in tail_dev.hpp, in the form the forward compiled to when
+// the products were written with * and + (which of a complex product's two terms went into the fused multiply-add differed from
+// product to product: the imaginary parts below are not all the same shape on purpose).  NOS: no A3 / A4 (a3h, a4 unset).
+struct SepRow {
+  cx<double> a3h, a4, a1[4], a2[4];       // a3h = A3 with the CG coefficient 1/2 applied
+};
+template <bool NOS>
+__device__ __forceinline__ SepRow dec_sep_row(const double* sm, const double* pn, double b0, double b1) {
+#pragma clang fp contract(off)
+  const cx<double> e0 = {b0 - b0, b0 + b0};
+  const cx<double> S = {sm[0], sm[1]};
+  cx<double> VS[4], pc[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    VS[m] = {sm[2 + 2 * m], sm[3 + 2 * m]};
+    pc[m] = {pn[m], pn[4 + m]};
+  }
+  SepRow o;
+  if constexpr (!NOS) {
+    o.a4.r = __builtin_fma(S.r, e0.r, -(S.i * e0.i));
+    o.a4.i = __builtin_fma(S.r, e0.i, S.i * e0.r);
+    cx<double> t, u;                                            // t = 2 <VS, p> (bil2), then - VP
+    t.r = __builtin_fma(VS[0].r, pc[0].r, -(VS[0].i * pc[0].i));
+    t.i = __builtin_fma(VS[0].i, pc[0].r, VS[0].r * pc[0].i);
+    cfma(t, VS[1], pc[3]);
+    u.r = __builtin_fma(VS[2].r, pc[2].r, -(VS[2].i * pc[2].i));
+    u.i = __builtin_fma(VS[2].i, pc[2].r, VS[2].r * pc[2].i);
+    t.r -= u.r;  t.i -= u.i;
+    cfma(t, VS[3], pc[1]);
+    t.r -= sm[18];  t.i -= sm[19];
+    const double w = b1 * t.i;
+    o.a3h.r = 0.5 * __builtin_fma(b1, t.r, -w);
+    o.a3h.i = 0.5 * __builtin_fma(b1, t.r, w);
+  }
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    o.a1[m].r = __builtin_fma(VS[m].r, e0.r, -(VS[m].i * e0.i));
+    o.a1[m].i = __builtin_fma(VS[m].r, e0.i, VS[m].i * e0.r);
+    cx<double> u;
+    u.r = __builtin_fma(pc[m].r, S.r, -(pc[m].i * S.i));
+    u.i = __builtin_fma(pc[m].r, S.i, pc[m].i * S.r);
+    u.r -= sm[10 + 2 * m];  u.i -= sm[11 + 2 * m];
+    const double w = b1 * u.i;
+    o.a2[m].r = __builtin_fma(b1, u.r, -w);
+    o.a2[m].i = __builtin_fma(b1, u.r, w);
+  }
+  return o;
+}
+
 // metric-permuted copy: tilde(x)[m] such that <a, b> = 1/2 sum_m a[m] * tilde(b)[m]
 template <typename T>
 __device__ __forceinline__ void metric_perm(const cx<T> (&x)[4], cx<T> (&y)[4]) {

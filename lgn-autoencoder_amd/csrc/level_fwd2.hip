@@ -170,7 +170,13 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
       mean += shfl_xor(mean, 8);
       mean += shfl_xor(mean, 16);
       mean += shfl_xor(mean, 32);
-      if (part == 0) sums[k] = mean / N;
+      if (part == 0) {
+        const double mu = mean / N;
+        sums[k] = mu;
+        if constexpr (TRAIN) {
+          if (a.sep_sums) a.sep_sums[(size_t)b * sep_sums_doubles(C) + 20 * C + k] = mu;
+        }
+      }
     }
     __syncthreads();
     for (int e = tid; e < N * 8; e += nthr) pj[e] -= sums[e & 7];
@@ -215,6 +221,10 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
     }
 #undef LGN_PUT
     __syncthreads();
+    if constexpr (TRAIN) {       // the backward rebuilds the aggregate rows from these sums and the means (LevelArgs::sep_sums)
+      if (a.sep_sums)
+        for (int e = tid; e < 20 * C; e += nthr) a.sep_sums[(size_t)b * sep_sums_doubles(C) + e] = sums[e];
+    }
   }
 
   // this workgroup's share of the jet's rows (level.hpp: level_jet_split; the whole jet unless the batch is small), processed
@@ -297,34 +307,16 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   if constexpr (DEC && SEP) {
     for (int e = tid; e < (c1 - c0) * C; e += nthr) {
       const int rl = e / C, c = e - rl * C, n = c0 + rl;
-      const double* sm = sums + c * 20;
-      const double* pn = pj + n * 8;
-      const cx<double> R0 = {a.b0[c], a.b0[c]}, R1 = {a.b1[c], a.b1[c]};
-      const cx<double> e0 = {R0.r - R0.i, R0.r + R0.i};
-      const cx<double> S = {sm[0], sm[1]};
-      cx<double> VS[4], pc[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        VS[m] = {sm[2 + 2 * m], sm[3 + 2 * m]};
-        pc[m] = {pn[m], pn[4 + m]};
-      }
+      const SepRow row = dec_sep_row<NOS>(sums + c * 20, pj + n * 8, a.b0[c], a.b1[c]);
       double* st = agl + rl * F::AGS;
       if constexpr (!NOS) {
-        const cx<double> a4 = cmul(S, e0);
-        cx<double> t = bil2(VS, pc);
-        t.r -= sm[18];  t.i -= sm[19];
-        cx<double> a3 = cmul(R1, t);
-        st[F::A3 + 2 * c] = 0.5 * a3.r;  st[F::A3 + 2 * c + 1] = 0.5 * a3.i;
-        st[F::A4 + 2 * c] = a4.r;        st[F::A4 + 2 * c + 1] = a4.i;
+        st[F::A3 + 2 * c] = row.a3h.r;  st[F::A3 + 2 * c + 1] = row.a3h.i;
+        st[F::A4 + 2 * c] = row.a4.r;   st[F::A4 + 2 * c + 1] = row.a4.i;
       }
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        const cx<double> a1 = cmul(VS[m], e0);
-        cx<double> u = cmul(pc[m], S);
-        u.r -= sm[10 + 2 * m];  u.i -= sm[11 + 2 * m];
-        const cx<double> a2 = cmul(R1, u);
-        st[F::A1 + (c * 4 + m) * 2] = a1.r;  st[F::A1 + (c * 4 + m) * 2 + 1] = a1.i;
-        st[F::A2 + (c * 4 + m) * 2] = a2.r;  st[F::A2 + (c * 4 + m) * 2 + 1] = a2.i;
+        st[F::A1 + (c * 4 + m) * 2] = row.a1[m].r;  st[F::A1 + (c * 4 + m) * 2 + 1] = row.a1[m].i;
+        st[F::A2 + (c * 4 + m) * 2] = row.a2[m].r;  st[F::A2 + (c * 4 + m) * 2 + 1] = row.a2[m].i;
       }
     }
   } else {
@@ -524,7 +516,8 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
   STAMP(20);
 
   // ---- aggregate -> global (saved for the backward): ag0 [2][B][N][2C], ag1 [2][B][N][2C][4] -----------------------
-  if constexpr (TRAIN) {
+  // (a separable decoder level that left its jet sums in sep_sums stores no aggregate: the backward rebuilds the rows)
+  if (TRAIN && !(DEC && SEP && a.sep_sums)) {
     const size_t pl0 = (size_t)B * N * 2 * C;
     if constexpr (!NOS) {
       for (int e = tid; e < (c1 - c0) * 2 * C; e += nthr) {        // e = n * 2C + (blk * C + ch), blk 0: A3, 1: A4
@@ -582,6 +575,8 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
                   "level_fwd: the loss rides on the separable decoder forward of jets of <= 40 particles only");
     if (smem < dec_out_loss_bytes(a.N, a.CO)) smem = dec_out_loss_bytes(a.N, a.CO);
   }
+  LGN_CHECK_ARG(!a.sep_sums || (DEC && SEP && TRAIN && a.N <= 40),
+                "level_fwd: only the separable decoder forward of a training step (N <= 40) leaves jet sums instead of the aggregate");
   LGN_CHECK_ARG(smem <= 160 * 1024, "level_fwd: N=%d C=%d needs %zu B of LDS (> 160 KiB)", a.N, a.C, smem);
   auto kern = level_fwd2_kernel<C, DEC, SEP, TRAIN, NOS>;
   if (smem > 64 * 1024) {

@@ -58,6 +58,7 @@ struct StepTailArgs {
 int step_tail(const std::vector<RedSeg<double>>& segs, const RadFinJob& fin, const StepTailArgs& ta, hipStream_t st);
 void level_bwd_partial_rows(int B, int N, int decoder, int flags, int* rows_mix, int* rows_rad);
 bool level_bwd_carries_input(int N, int flags);   // the encoder's first level may take LevelBwdArgs::part_in0 (one-kernel backward, N <= 40)
+bool level_dec_rebuilds(int N, int flags);        // a sequencer's decoder level keeps its jet sums, not the aggregate (LevelArgs::sep_sums)
 bool level_fwd_carries_loss(int N, int flags);    // the decoder's last level may take LevelArgs::loss_* (separable one-workgroup-per-jet forward)
 // does the level's CGMLP ride on the level kernel (LevelArgs::mlp / LevelBwdArgs::mlp)?  The forward and the backward decide
 // independently (the forward always leaves the scalars before AND after the MLP)

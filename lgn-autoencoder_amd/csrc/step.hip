@@ -31,6 +31,7 @@ struct Bump {                       // workspace carving (also used for the size
 struct NetBuf {                     // per-network activations kept for the backward pass
   double *s[5], *v[5], *smix[4], *ag0[4], *ag1[4];
   double* hsave[4];                 // hidden activations of the level's CGMLP, kept for its backward (null: recomputed)
+  double* sep[4];                   // decoder: jet sums of a separable level, kept instead of ag0 / ag1 (LevelArgs::sep_sums)
 };
 
 struct Work {
@@ -208,6 +209,7 @@ Work carve(const lgn_net_desc& d, double* base) {
       n.smix[l] = b.take(2 * BN * ch[l + 1]);
       n.ag0[l] = b.take(4 * BN * ch[l]);
       n.ag1[l] = b.take(16 * BN * ch[l]);
+      n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
       // the last level's scalars never reach the loss: its CGMLP has no backward
       // (a CGMLP that rides on the level kernels recomputes: nothing kept)
       const size_t hs = l + 1 < L && BN <= mlp_save_max_rows()
@@ -315,6 +317,7 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       a.loss_part = loss->loss_part; a.loss_gv = loss->g_v; a.loss_wpart = loss->wpart;
     }
     a.flags = d.flags;
+    if (dec && !eval && level_dec_rebuilds(d.N, d.flags)) a.sep_sums = n.sep[l];     // (levels_bwd makes the same choice)
     const bool no_mlp = l + 1 == d.n_levels && (!last_scalars || (eval && dec));
     a.dead_scalars = no_mlp && !(d.flags & LVL_LIVE_SCALARS);
     LGN_TRY(eval ? level_fwd_eval(a, dec, st) : level_fwd_dispatch<double>(a, dec, st));
@@ -373,6 +376,7 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
     const RowLayout rin = enc_input_rows(1, C);
     if (carry_in0) { DQ_TAKE(a.part_in0, (size_t)rm * rin.width); }
     a.flags = d.flags;
+    if (dec && level_dec_rebuilds(d.N, d.flags)) a.sep_sums = n.sep[l];
     LGN_TRY(level_bwd_dispatch<double>(a, dec, st));
     if (carry_in0) {
       rin.add(dq, a.part_in0, rm, G, off);
@@ -1022,6 +1026,7 @@ NetAct carve_act(const lgn_net_desc& d, bool dec, double* base) {
     a.n.smix[l] = b.take(2 * BN * ch[l + 1]);
     a.n.ag0[l] = b.take(4 * BN * ch[l]);
     a.n.ag1[l] = b.take(16 * BN * ch[l]);
+    a.n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
     // (the caller's upstream gradient may reach every level)
     const size_t hs = BN <= mlp_save_max_rows()
                           ? mlp_saved_doubles((int)BN, d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) : 0;
