@@ -5,10 +5,13 @@
 // on the caller's stream, no host synchronisation, every buffer caller-owned and static -> the call can be
 // captured into a HIP graph (the Python harness does so) and replayed.  Parameter gradients are written
 // straight into the caller's flat gradient buffer at the same offsets as the parameters.
+//
+// The file, top to bottom: shared plumbing -- one maxdim-2 network (levels_fwd / levels_bwd, encoder_fwd / encoder_bwd, decoder_fwd /
+// decoder_bwd) -- one table-driven network (the gen_* counterparts) -- the per-network carves -- the training steps -- the evaluation
+// step; then the C calls in the same order.  Each workspace layout is one carve, each end-stage sequence one function.
 #include <stdlib.h>
 
 #include <algorithm>
-#include <mutex>
 #include <vector>
 
 #include "net.hpp"
@@ -17,46 +20,32 @@
 namespace lgn {
 namespace {
 
+// ---------------------------------------------------------------------------------------------------------
+// shared plumbing
+// ---------------------------------------------------------------------------------------------------------
+inline size_t r16(size_t n) { return (n + 15) & ~size_t(15); }     // 128-byte granules: what a take of n doubles occupies
+
 struct Bump {                       // workspace carving (also used for the size query with base == nullptr)
   double* base;
   size_t off = 0;
+  double* here() const { return base ? base + off : nullptr; }       // where the next take starts
   double* take(size_t n) {
-    n = (n + 15) & ~size_t(15);     // 128-byte granules
-    double* p = base ? base + off : nullptr;
-    off += n;
+    double* p = here();
+    off += r16(n);
     return p;
   }
-};
-
-struct NetBuf {                     // per-network activations kept for the backward pass
-  double *s[5], *v[5], *smix[4], *ag0[4], *ag1[4];
-  double* hsave[4];                 // hidden activations of the level's CGMLP, kept for its backward (null: recomputed)
-  double* sep[4];                   // decoder: jet sums of a separable level, kept instead of ag0 / ag1 (LevelArgs::sep_sums)
-};
-
-struct Work {
-  NetBuf enc, dec;
-  double *lat_s, *lat_v, *pdec, *g_lat_s, *g_lat_v, *g_p;
-  double *gs[2], *gv[2], *gsmix, *g_ag, *zeros_s;
-  double *parts;               // bump region: every producer of partial rows gets its own slice (reduced at the end)
-  size_t parts_size;
-  double* tot[2][4];           // reduced radial sums per (network, level)
-  int* idx;
-  size_t total;
-  double* tail_cnt;            // 4 counters of the fused reduction (step_tail.hip, reduce_only), inside the zero block
-  double* zero0() const { return tail_cnt < zeros_s ? tail_cnt : zeros_s; }     // start of the zero block
-  size_t zero_doubles;         // zeros_s | g_p | g_lat_s | tail_cnt are contiguous: one memset
 };
 
 // deferred reductions: producers register their column ranges, one or two launches at the end reduce everything
 struct Deferred {
   std::vector<RedSeg<double>> segs;
   double* parts;
-  size_t off = 0, cap = 0;
+  size_t off = 0, cap;
+  Deferred(double* rows, size_t doubles) : parts(rows), cap(doubles) {}       // opened on a carve's partial-row region
   // nullptr when the slice does not fit: callers test it (DQ_TAKE) BEFORE enqueuing the kernel that would write there --
   // the capacity mirrors the take sequence (net_parts / gen_net_parts), a disagreement must not reach the device
   double* take(size_t n) {
-    n = (n + 15) & ~size_t(15);
+    n = r16(n);
     if (off + n > cap) return nullptr;
     double* p = parts + off;
     off += n;
@@ -75,6 +64,17 @@ struct Deferred {
     return 0;
   }
 };
+
+#define DQ_NEW(var, n) double* var = nullptr; DQ_TAKE(var, n)
+#define DQ_TAKE(lhs, n)                                                                                           \
+  lhs = dq.take(n);                                                                                             \
+  LGN_CHECK_ARG((lhs) != nullptr, "partial-row workspace overflow: %zu + %zu doubles > capacity %zu (carve / take mismatch)", \
+                dq.off, (size_t)(n), dq.cap)
+#define LGN_TRY(expr)            \
+  do {                           \
+    int rc_ = (expr);            \
+    if (rc_ != 0) return rc_;    \
+  } while (0)
 
 // The end of a backward whose gradients go on to somebody else (the all-reduce of a data-parallel step, autograd under the module
 // API): every deferred reduction and the radial finalisation as ONE launch (step_tail.hip, reduce_only) -- `counters`: 4 words of the
@@ -125,12 +125,12 @@ inline int dec_nodes(const lgn_net_desc& d) { return d.dec_N > 0 ? d.dec_N : d.N
 inline bool step_is_split(const lgn_net_desc& d) { return dec_nodes(d) != d.N || d.n_in_scalars > 1; }
 // latent vectors per jet the decoder's input stage reads: its own tau_v_in, or the encoder's pooled ones
 inline int dec_tin(const lgn_net_desc& d) { return d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v; }
-// a whole step's decoder consumes the encoder's pooled latent vectors
-int check_latent_match(const lgn_net_desc& d) {
-  const int Tin = pool_blocks(d.latent_pool) * d.tau_v;
-  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step: the decoder must consume the encoder's %d pooled latent vectors", Tin);
-  return 0;
-}
+
+// buffer sizes every carve states through these: the encoder's pooled latent scalars [2][B][P Ts] and vectors [2][B][P Tv][4], and
+// the pooling indices of its latent stage (ints, two to a double)
+inline size_t lat_s_doubles(const lgn_net_desc& d) { return (size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s; }
+inline size_t lat_v_doubles(const lgn_net_desc& d) { return (size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_v * 4; }
+inline size_t pool_idx_doubles(const lgn_net_desc& d) { return ((size_t)d.B * 2 * (d.tau_s + d.tau_v) * 2 + 1) / 2 + 8; }
 
 struct Slots {                      // canonical parameter slot order shared with lgn/step.py
   int L, nlin;
@@ -167,7 +167,6 @@ RowLayout dec_output_rows(const lgn_net_desc& d, int CL) {
   return {2 * CL, 1, {0}, {2 * CL}, {Slots{d.n_levels, d.mlp_nlin}.out0(true) + 1}};
 }
 
-inline size_t r16(size_t n) { return (n + 15) & ~size_t(15); }     // a Deferred::take of n doubles
 // partial rows of a network's two end stages on N nodes; in_rows: rows of the encoder's input stage
 size_t end_parts(const lgn_net_desc& d, bool dec, int N, int in_rows) {
   const int* ch = dec ? d.dec_channels : d.enc_channels;
@@ -175,6 +174,166 @@ size_t end_parts(const lgn_net_desc& d, bool dec, int N, int in_rows) {
   if (dec) return r16((size_t)d.B * dec_output_rows(d, ch[L]).width) + r16((size_t)d.B * dec_input_rows(ch[0], N, dec_tin(d)).width);
   return r16((size_t)d.B * enc_latent_rows(d, N, ch[L]).width) + r16((size_t)in_rows * enc_input_rows(in_K(d), ch[0]).width);
 }
+
+// Zero-fill of up to three ranges in ONE launch of our own.  NOT hipMemsetAsync: under stream capture (ROCm 7.2, torch 2.10) the
+// memset node of a replayed graph fills its range with a stale 16-byte pattern -- two pointer-like words, i.e. denormals ~7e-310 --
+// from the second replay on (tools/graph_memset_check.py).  As gradients of dead parameters and "zero" upstream gradients that
+// went unnoticed numerically; as counters it does not.
+struct ZeroJob { double* p[3]; size_t n[3]; };
+__global__ __launch_bounds__(BLOCK) void zero_ranges_kernel(ZeroJob job) {
+  const size_t stride = (size_t)gridDim.x * BLOCK;
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < job.n[q]; i += stride) job.p[q][i] = 0.0;
+}
+int zero_ranges(double* a, size_t na, double* b, size_t nb, double* c, size_t nc, hipStream_t st) {
+  const ZeroJob job{{a, b, c}, {a ? na : 0, b ? nb : 0, c ? nc : 0}};
+  const size_t most = std::max(job.n[0], std::max(job.n[1], job.n[2]));
+  if (!most) return 0;
+  const int blocks = (int)std::min<size_t>((most + BLOCK - 1) / BLOCK, 1024);
+  hipLaunchKernelGGL(zero_ranges_kernel, dim3(blocks), dim3(BLOCK), 0, st, job);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+// grads [n] and the zero block [nz]: one range when the caller laid them out back to back (lgn/ops.py does)
+int zero_grads_and_block(double* grads, size_t n, double* zeros, size_t nz, hipStream_t st) {
+  if (zeros >= grads + n && zeros <= grads + n + 16) return zero_ranges(grads, (size_t)((zeros + nz) - grads), nullptr, 0, nullptr, 0, st);
+  return zero_ranges(grads, n, zeros, nz, nullptr, 0, st);
+}
+
+int check_desc(const lgn_net_desc* d) {
+  LGN_CHECK_ARG(d, "step: null descriptor");
+  LGN_CHECK_ARG(d->B > 0 && d->N > 0, "step: empty batch (B=%d N=%d)", d->B, d->N);
+  LGN_CHECK_ARG(d->n_levels >= 1 && d->n_levels <= 4, "step: n_levels=%d unsupported (1..4)", d->n_levels);
+  LGN_CHECK_ARG(d->mlp_nlin >= 4 && d->mlp_nlin <= 7, "step: mlp_depth must be 3 .. 6 (4 .. 7 Linear layers), got %d layers", d->mlp_nlin);
+  LGN_CHECK_ARG(d->tau_s >= 1 && d->tau_v >= 1 && d->tau_v_in >= 0, "step: latent multiplicities must be positive");
+  LGN_CHECK_ARG(d->n_in_scalars >= 0 && d->n_in_scalars <= 8, "step: n_in_scalars=%d unsupported (0..8)", d->n_in_scalars);
+  LGN_CHECK_ARG(pool_valid(d->latent_pool), "step: latent_pool=%d is not an LGN_POOL(...) code", d->latent_pool);
+  for (int l = 0; l <= d->n_levels; ++l)
+    LGN_CHECK_ARG(d->enc_channels[l] >= 1 && d->enc_channels[l] <= 8 && d->dec_channels[l] >= 1 && d->dec_channels[l] <= 8,
+                  "step: channel counts must be in 1..8");
+  LGN_CHECK_ARG(d->get_real >= LGN_REAL_SUM && d->get_real <= LGN_REAL_NORM, "step: get_real=%d is not an LGN_REAL_* code", d->get_real);
+  LGN_CHECK_ARG(d->jet_loss_scale >= 0.0, "step: jet_loss_scale=%g must be >= 0", d->jet_loss_scale);
+  LGN_CHECK_ARG(d->dec_N >= 0, "step: dec_N=%d must be >= 0", d->dec_N);
+  if (d->dec_N > 0) {        // the whole step's decoder end stages are one workgroup per jet of dec_N particles
+    const size_t need = decoder_end_lds_bytes(d->dec_N, d->dec_channels[0], dec_tin(*d), d->dec_channels[d->n_levels]);
+    LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: dec_N=%d: the decoder end stages need %zu B of LDS (> %d)", d->dec_N, need, LGN_LDS_LIMIT);
+  }
+  return 0;
+}
+
+// a whole step's decoder consumes the encoder's pooled latent vectors
+int check_latent_match(const lgn_net_desc& d) {
+  const int Tin = pool_blocks(d.latent_pool) * d.tau_v;
+  LGN_CHECK_ARG(d.tau_v_in == 0 || d.tau_v_in == Tin, "step: the decoder must consume the encoder's %d pooled latent vectors", Tin);
+  return 0;
+}
+
+int check_mlp_contiguous(const lgn_net_desc& d, bool dec, const int64_t* off) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
+  for (int l = 0; l < d.n_levels; ++l) {
+    const int D = 2 * ch[l + 1], H = d.mlp_hidden_mul * D;
+    int64_t expect = off[S.mlp(dec, l, 0)];
+    for (int q = 0; q < d.mlp_nlin; ++q) {
+      const int hin = q == 0 ? D : H, hout = q == d.mlp_nlin - 1 ? D : H;
+      LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q)] == expect, "MLP weights are not contiguous in the flat parameter buffer");
+      expect += (int64_t)hin * hout;
+      LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q + 1)] == expect, "MLP biases are not contiguous in the flat parameter buffer");
+      expect += hout;
+    }
+  }
+  return 0;
+}
+
+// the arguments of level l's CGMLP every caller shares: shape (M = B N), activation, weights and biases
+MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const double* P, const int64_t* off) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int CO = (dec ? d.dec_channels : d.enc_channels)[l + 1];
+  MlpArgs<double> m{};
+  m.M = d.B * d.N; m.C = CO; m.H = d.mlp_hidden_mul * 2 * CO; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
+  for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = P + off[S.mlp(dec, l, 2 * q)]; m.b[q] = P + off[S.mlp(dec, l, 2 * q + 1)]; }
+  return m;
+}
+
+// decoder-side operands of junction_bwd (whole step): the decoder's input stage backward and the encoder's latent stage backward of
+// a jet are then ONE launch, made by the encoder's backward
+struct JunctionBwd {
+  int C0, Tin;
+  const double *lat_v, *wg1, *w1, *pdec, *g_p, *g_s0, *g_v0;
+  double* part_dec;
+};
+
+// The loss argument of the whole-step calls: nullptr for Chamfer, else the assignment loss the step's last stage
+// runs (net.hpp: AssignLoss).  Every refusal is made here, before anything is enqueued.
+int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, AssignLoss& al, const AssignLoss** out) {
+  *out = nullptr;
+  if (!loss || loss->kind == LGN_LOSS_CHAMFER) return 0;
+  if (int rc = check_desc(d)) return rc;
+  al = AssignLoss{loss->kind, loss->abs_coord, loss->polar_coord, loss->scale, assignment, status};
+  const int Nd = dec_nodes(*d), CL = d->dec_channels[d->n_levels];
+  if (int rc = check_assign_loss(al, Nd)) return rc;
+  LGN_CHECK_ARG(d->jet_loss_scale == 0.0, "step: jet_loss_scale=%g with loss kind %d: the jet-feature term is a Chamfer option "
+                "(--chamfer-jet-features)", d->jet_loss_scale, loss->kind);
+  const size_t need = assign_loss_lds_bytes(Nd, CL);
+  LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the assignment-loss stage at N=%d needs %zu B of LDS (> %d)", Nd, need, LGN_LDS_LIMIT);
+  *out = &al;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// one maxdim-2 network: level stack, encoder, decoder (shared by the per-network calls, the training step and the evaluation step)
+// ---------------------------------------------------------------------------------------------------------
+struct NetBuf {                     // per-network activations kept for the backward pass
+  double *s[5], *v[5], *smix[4], *ag0[4], *ag1[4];
+  double* hsave[4];                 // hidden activations of the level's CGMLP, kept for its backward (null: recomputed)
+  double* sep[4];                   // decoder: jet sums of a separable level, kept instead of ag0 / ag1 (LevelArgs::sep_sums)
+};
+// The activations a network keeps on BN = B N nodes.  last_mlp_bwd: does the last level's CGMLP have a backward?  The step never runs
+// it (the last level's scalars never reach the loss), so nothing is kept for it there; a per-network caller's
+// upstream gradient may reach every level.  (A CGMLP that rides on the level kernels recomputes: nothing kept.)
+void carve_net(Bump& b, const lgn_net_desc& d, bool dec, size_t BN, bool last_mlp_bwd, NetBuf& n) {
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
+  const int L = d.n_levels;
+  for (int l = 0; l <= L; ++l) {
+    n.s[l] = b.take(2 * BN * ch[l]);
+    n.v[l] = b.take(8 * BN * ch[l]);
+  }
+  for (int l = 0; l < L; ++l) {
+    n.smix[l] = b.take(2 * BN * ch[l + 1]);
+    n.ag0[l] = b.take(4 * BN * ch[l]);
+    n.ag1[l] = b.take(16 * BN * ch[l]);
+    n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
+    const size_t hs = (last_mlp_bwd || l + 1 < L) && BN <= mlp_save_max_rows()
+                          ? mlp_saved_doubles((int)BN, d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) : 0;
+    n.hsave[l] = hs ? b.take(hs) : nullptr;
+  }
+}
+
+// What a backward through level stacks works in -- levels_bwd reads and writes nothing else.  The step has one for both networks.
+struct BwdScratch {
+  double *gs[2], *gv[2];       // gradient w.r.t. a level's features, two buffers used in turn
+  double *gsmix, *g_ag;
+  // the zero block: zeros_s (the scalar gradient nobody produced), g_p (decoder: d p, accumulated), g_lat_s (the latent scalars'
+  // gradient nobody produced), tail_cnt (4 counters of the fused reduction: step_tail.hip, reduce_only) -- contiguous, one clear;
+  // first in the per-network scratch (tail_cnt leading), behind the gradient buffers in the step (tail_cnt closing): carve_scratch / carve
+  double *zeros_s, *g_p, *g_lat_s, *tail_cnt;
+  size_t zero_doubles;
+  double* zero0() const { return tail_cnt < zeros_s ? tail_cnt : zeros_s; }     // start of the zero block
+  double* tot[4];              // encoder: reduced radial sums per level
+  double* parts;               // bump region: every producer of partial rows gets its own slice (reduced at the end)
+  size_t parts_size;
+};
+void carve_level_grads(Bump& b, size_t BN, int cmax, BwdScratch& k) {
+  for (int q = 0; q < 2; ++q) {
+    k.gs[q] = b.take(2 * BN * cmax);
+    k.gv[q] = b.take(8 * BN * cmax);
+  }
+  k.gsmix = b.take(2 * BN * cmax);
+  k.g_ag = b.take(20 * BN * cmax);
+}
+inline size_t tot_doubles(int C, bool dec) { return rad_partial_size(C, dec) + 16; }
+
 // partial-row capacity of one maxdim-2 network on N nodes: its level stack (levels_bwd) and its end stages.  (The decoder's CGMLP rows
 // are counted on dec_nodes(d) even for a per-network call, where the descriptor's dec_N is 0 -- as the layout has always been sized.)
 size_t net_parts(const lgn_net_desc& d, bool dec, int N) {
@@ -190,76 +349,6 @@ size_t net_parts(const lgn_net_desc& d, bool dec, int N) {
   // the encoder's input-stage rows: one per jet, or one per workgroup of the first level's backward when they ride on it
   return sum + end_parts(d, dec, N, rm > d.B ? rm : d.B);
 }
-
-Work carve(const lgn_net_desc& d, double* base) {
-  Work w{};
-  Bump b{base};
-  const int Nd = dec_nodes(d), Nmax = d.N > Nd ? d.N : Nd;
-  const size_t BNe = (size_t)d.B * d.N, BNd = (size_t)d.B * Nd, BN = (size_t)d.B * Nmax;
-  const int L = d.n_levels;
-  int cmax = 0;
-  for (int l = 0; l <= L; ++l) cmax = cmax > d.enc_channels[l] ? cmax : d.enc_channels[l], cmax = cmax > d.dec_channels[l] ? cmax : d.dec_channels[l];
-  auto net = [&](NetBuf& n, const int* ch, bool dec) {
-    const size_t BN = dec ? BNd : BNe;
-    for (int l = 0; l <= L; ++l) {
-      n.s[l] = b.take(2 * BN * ch[l]);
-      n.v[l] = b.take(8 * BN * ch[l]);
-    }
-    for (int l = 0; l < L; ++l) {
-      n.smix[l] = b.take(2 * BN * ch[l + 1]);
-      n.ag0[l] = b.take(4 * BN * ch[l]);
-      n.ag1[l] = b.take(16 * BN * ch[l]);
-      n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
-      // the last level's scalars never reach the loss: its CGMLP has no backward
-      // (a CGMLP that rides on the level kernels recomputes: nothing kept)
-      const size_t hs = l + 1 < L && BN <= mlp_save_max_rows()
-                            ? mlp_saved_doubles((int)BN, d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) : 0;
-      n.hsave[l] = hs ? b.take(hs) : nullptr;
-    }
-  };
-  net(w.enc, d.enc_channels, false);
-  net(w.dec, d.dec_channels, true);
-  const int Ts = d.tau_s, Tv = d.tau_v, PB = pool_blocks(d.latent_pool);
-  w.lat_s = b.take((size_t)2 * d.B * PB * Ts);
-  w.lat_v = b.take((size_t)2 * d.B * PB * Tv * 4);
-  w.g_lat_v = b.take((size_t)2 * d.B * PB * Tv * 4);
-  w.pdec = b.take(8 * BN);
-  for (int q = 0; q < 2; ++q) {
-    w.gs[q] = b.take(2 * BN * cmax);
-    w.gv[q] = b.take(8 * BN * cmax);
-  }
-  w.gsmix = b.take(2 * BN * cmax);
-  w.g_ag = b.take(20 * BN * cmax);
-  {  // contiguous zero-initialised region
-    const size_t z0 = b.off;
-    w.zeros_s = b.take(2 * BN * cmax);
-    w.g_p = b.take(8 * BN);
-    w.g_lat_s = b.take((size_t)2 * d.B * PB * d.tau_s);
-    w.tail_cnt = b.take(8);
-    w.zero_doubles = b.off - z0;
-  }
-  w.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (Ts + Tv) * 2 + 1) / 2 + 8));
-  for (int dec = 0; dec < 2; ++dec)
-    for (int l = 0; l < L; ++l) w.tot[dec][l] = b.take(rad_partial_size((dec ? d.dec_channels : d.enc_channels)[l], dec != 0) + 16);
-  // partial rows: every producer keeps its own slice until the deferred reduction at the end of the step
-  const size_t psum = net_parts(d, false, d.N) + net_parts(d, true, Nd);
-  w.parts = b.take(psum);
-  w.parts_size = psum;
-  w.total = b.off;
-  return w;
-}
-
-#define HIPOK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { set_error("%s: %s", #e, hipGetErrorString(e_)); return (int)e_; } } while (0)
-#define DQ_NEW(var, n) double* var = nullptr; DQ_TAKE(var, n)
-#define DQ_TAKE(lhs, n)                                                                                           \
-  lhs = dq.take(n);                                                                                             \
-  LGN_CHECK_ARG((lhs) != nullptr, "partial-row workspace overflow: %zu + %zu doubles > capacity %zu (carve / take mismatch)", \
-                dq.off, (size_t)(n), dq.cap)
-#define LGN_TRY(expr)            \
-  do {                           \
-    int rc_ = (expr);            \
-    if (rc_ != 0) return rc_;    \
-  } while (0)
 
 // The encoder's input stage (input_func_node on mass and canonical momenta) rides on the first level's kernel, which then
 // is the first kernel of the call and also clears z1 / z2 (LevelArgs::in_w0).
@@ -279,16 +368,6 @@ struct LossStage {
   double *recon, *loss_part, *g_v, *wpart;
 };
 
-// the arguments of level l's CGMLP every caller shares: shape (M = B N), activation, weights and biases
-MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const double* P, const int64_t* off) {
-  const Slots S{d.n_levels, d.mlp_nlin};
-  const int CO = (dec ? d.dec_channels : d.enc_channels)[l + 1];
-  MlpArgs<double> m{};
-  m.M = d.B * d.N; m.C = CO; m.H = d.mlp_hidden_mul * 2 * CO; m.nlin = d.mlp_nlin; m.act = d.activation; m.flags = d.flags;
-  for (int q = 0; q < d.mlp_nlin; ++q) { m.w[q] = P + off[S.mlp(dec, l, 2 * q)]; m.b[q] = P + off[S.mlp(dec, l, 2 * q + 1)]; }
-  return m;
-}
-
 // forward of one network's level stack; returns via buffers
 // eval (evaluation step): the level kernels without the aggregate stores (level_fwd_eval; n.ag0 / ag1 unused), a riding loss
 // tail in its forward-only form, and no CGMLP after the decoder's last level (its scalars never reach the output)
@@ -297,10 +376,10 @@ MlpArgs<double> level_mlp_args(const lgn_net_desc& d, bool dec, int l, const dou
 // and loss read only its last level's vectors; the latent vectors only the encoder's, and the latent scalars, which then mean
 // nothing, carry no gradient: LatentStage).  The last level's kernel then runs without live scalars (LevelArgs::dead_scalars: no
 // scalar aggregates, no scalar CatMix rows, n.smix / n.ag0 of that level unwritten); LVL_LIVE_SCALARS keeps the full kernel (cross-check).
-int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, const int64_t* off, NetBuf& n, const double* pos,
-               const uint8_t* mask, hipStream_t st, const InputStage* in0 = nullptr, const LossStage* loss = nullptr, bool eval = false,
-               bool last_scalars = true) {
+int levels_fwd(const lgn_net_desc& d, bool dec, const double* P, const int64_t* off, NetBuf& n, const double* pos, const uint8_t* mask,
+               hipStream_t st, const InputStage* in0, const LossStage* loss, bool eval, bool last_scalars) {
   const Slots S{d.n_levels, d.mlp_nlin};
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
   for (int l = 0; l < d.n_levels; ++l) {
     auto p = [&](int slot) { return P + off[slot]; };
     LevelArgs<double> a{d.B, d.N, ch[l], ch[l + 1], n.s[l], n.v[l], pos, mask,
@@ -335,10 +414,11 @@ int levels_fwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
 // scalars never reach the loss).  On exit gs[cur]/gv[cur] hold the gradient w.r.t. level 0.
 // in0_done (encoder only, optional): the input stage's backward (mass only) may ride on the first level's.  When that level's
 // backward is the one-kernel form, it does (LevelBwdArgs::part_in0) and *in0_done is set; otherwise the caller launches enc_input_bwd.
-int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, double* G, const int64_t* off, const NetBuf& n,
-               const double* pos, const uint8_t* mask, Work& w, Deferred& dq, RadFinJob& fin, int& cur, bool has_s_grad,
-               hipStream_t st, bool* in0_done = nullptr) {
+int levels_bwd(const lgn_net_desc& d, bool dec, const double* P, double* G, const int64_t* off, const NetBuf& n, const double* pos,
+               const uint8_t* mask, BwdScratch& w, Deferred& dq, RadFinJob& fin, int& cur, bool has_s_grad, hipStream_t st,
+               bool* in0_done = nullptr) {
   const Slots S{d.n_levels, d.mlp_nlin};
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
   const int BN = d.B * d.N;
   for (int l = d.n_levels - 1; l >= 0; --l) {
     auto p = [&](int slot) { return P + off[slot]; };
@@ -391,7 +471,7 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
       dq.add(part_rad, rr, nrad, 0, C, g(S.rad(dec, l, 4)));
       dq.add(part_rad, rr, nrad, C, C, g(S.rad(dec, l, 6)));
     } else {
-      double* tot = w.tot[0][l];
+      double* tot = w.tot[l];
       dq.add(part_rad, rr, nrad, 0, nrad, tot);
       fin.it[fin.n++] = RadFinJob::Item{tot, C, p(S.rad(dec, l, 0)), p(S.rad(dec, l, 1)), p(S.rad(dec, l, 2)), p(S.rad(dec, l, 3)),
                                         p(S.rad(dec, l, 5)), g(S.rad(dec, l, 0)), g(S.rad(dec, l, 1)), g(S.rad(dec, l, 2)),
@@ -403,105 +483,93 @@ int levels_bwd(const lgn_net_desc& d, bool dec, const int* ch, const double* P, 
   return 0;
 }
 
-int check_desc(const lgn_net_desc* d) {
-  LGN_CHECK_ARG(d, "step: null descriptor");
-  LGN_CHECK_ARG(d->B > 0 && d->N > 0, "step: empty batch (B=%d N=%d)", d->B, d->N);
-  LGN_CHECK_ARG(d->n_levels >= 1 && d->n_levels <= 4, "step: n_levels=%d unsupported (1..4)", d->n_levels);
-  LGN_CHECK_ARG(d->mlp_nlin >= 4 && d->mlp_nlin <= 7, "step: mlp_depth must be 3 .. 6 (4 .. 7 Linear layers), got %d layers", d->mlp_nlin);
-  LGN_CHECK_ARG(d->tau_s >= 1 && d->tau_v >= 1 && d->tau_v_in >= 0, "step: latent multiplicities must be positive");
-  LGN_CHECK_ARG(d->n_in_scalars >= 0 && d->n_in_scalars <= 8, "step: n_in_scalars=%d unsupported (0..8)", d->n_in_scalars);
-  LGN_CHECK_ARG(pool_valid(d->latent_pool), "step: latent_pool=%d is not an LGN_POOL(...) code", d->latent_pool);
-  for (int l = 0; l <= d->n_levels; ++l)
-    LGN_CHECK_ARG(d->enc_channels[l] >= 1 && d->enc_channels[l] <= 8 && d->dec_channels[l] >= 1 && d->dec_channels[l] <= 8,
-                  "step: channel counts must be in 1..8");
-  LGN_CHECK_ARG(d->get_real >= LGN_REAL_SUM && d->get_real <= LGN_REAL_NORM, "step: get_real=%d is not an LGN_REAL_* code", d->get_real);
-  LGN_CHECK_ARG(d->jet_loss_scale >= 0.0, "step: jet_loss_scale=%g must be >= 0", d->jet_loss_scale);
-  LGN_CHECK_ARG(d->dec_N >= 0, "step: dec_N=%d must be >= 0", d->dec_N);
-  if (d->dec_N > 0) {        // the whole step's decoder end stages are one workgroup per jet of dec_N particles
-    const size_t need = decoder_end_lds_bytes(d->dec_N, d->dec_channels[0], dec_tin(*d), d->dec_channels[d->n_levels]);
-    LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: dec_N=%d: the decoder end stages need %zu B of LDS (> %d)", d->dec_N, need, LGN_LDS_LIMIT);
-  }
-  return 0;
-}
-
-// The loss argument of the whole-step calls: nullptr for Chamfer, else the assignment loss the step's last stage
-// runs (net.hpp: AssignLoss).  Every refusal is made here, before anything is enqueued.
-int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, AssignLoss& al, const AssignLoss** out) {
-  *out = nullptr;
-  if (!loss || loss->kind == LGN_LOSS_CHAMFER) return 0;
-  if (int rc = check_desc(d)) return rc;
-  al = AssignLoss{loss->kind, loss->abs_coord, loss->polar_coord, loss->scale, assignment, status};
-  const int Nd = dec_nodes(*d), CL = d->dec_channels[d->n_levels];
-  if (int rc = check_assign_loss(al, Nd)) return rc;
-  LGN_CHECK_ARG(d->jet_loss_scale == 0.0, "step: jet_loss_scale=%g with loss kind %d: the jet-feature term is a Chamfer option "
-                "(--chamfer-jet-features)", d->jet_loss_scale, loss->kind);
-  const size_t need = assign_loss_lds_bytes(Nd, CL);
-  LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the assignment-loss stage at N=%d needs %zu B of LDS (> %d)", Nd, need, LGN_LDS_LIMIT);
-  *out = &al;
-  return 0;
-}
-
-}  // namespace
-
-}  // namespace lgn
-
-
-namespace lgn {
-namespace {
-// Zero-fill of up to three ranges in ONE launch of our own.  NOT hipMemsetAsync: under stream capture (ROCm 7.2, torch 2.10) the
-// memset node of a replayed graph fills its range with a stale 16-byte pattern -- two pointer-like words, i.e. denormals ~7e-310 --
-// from the second replay on (tools/graph_memset_check.py).  As gradients of dead parameters and "zero" upstream gradients that
-// went unnoticed numerically; as counters it does not.
-struct ZeroJob { double* p[3]; size_t n[3]; };
-__global__ __launch_bounds__(BLOCK) void zero_ranges_kernel(ZeroJob job) {
-  const size_t stride = (size_t)gridDim.x * BLOCK;
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < job.n[q]; i += stride) job.p[q][i] = 0.0;
-}
-int zero_ranges(double* a, size_t na, double* b, size_t nb, double* c, size_t nc, hipStream_t st) {
-  const ZeroJob job{{a, b, c}, {a ? na : 0, b ? nb : 0, c ? nc : 0}};
-  const size_t most = std::max(job.n[0], std::max(job.n[1], job.n[2]));
-  if (!most) return 0;
-  const int blocks = (int)std::min<size_t>((most + BLOCK - 1) / BLOCK, 1024);
-  hipLaunchKernelGGL(zero_ranges_kernel, dim3(blocks), dim3(BLOCK), 0, st, job);
-  LGN_CHECK_LAUNCH();
-  return 0;
-}
-// grads [n] and the zero block [nz]: one range when the caller laid them out back to back (lgn/ops.py does)
-int zero_grads_and_block(double* grads, size_t n, double* zeros, size_t nz, hipStream_t st) {
-  if (zeros >= grads + n && zeros <= grads + n + 16) return zero_ranges(grads, (size_t)((zeros + nz) - grads), nullptr, 0, nullptr, 0, st);
-  return zero_ranges(grads, n, zeros, nz, nullptr, 0, st);
-}
-
-int check_mlp_contiguous(const lgn_net_desc& d, bool dec, const int64_t* off) {
+// ---- one maxdim-2 network, forward / backward, in the shape of gen_encoder_fwd ... gen_decoder_bwd below --------------
+// ride: the input stage rides on the first level's kernel, which then also makes ride's two clears (the mass as the only input scalar);
+//   nullptr: enc_input_fwd as a launch of its own on the K scalars xs
+// with_latent = false (fused whole step): the latent stage runs in the junction kernel together with the decoder's input stage
+// last_scalars = false: nobody reads the latent scalars -- no last CGMLP, the latent stage takes the last level's scalars as zero
+int encoder_fwd(const lgn_net_desc& d, const double* P, const int64_t* off, const double* p4, const uint8_t* mask, const double* xs,
+                NetBuf& n, double* lat_s, double* lat_v, int* idx, hipStream_t st, const InputStage* ride, bool with_latent = true,
+                bool eval = false, bool last_scalars = true) {
   const Slots S{d.n_levels, d.mlp_nlin};
-  const int* ch = dec ? d.dec_channels : d.enc_channels;
-  for (int l = 0; l < d.n_levels; ++l) {
-    const int D = 2 * ch[l + 1], H = d.mlp_hidden_mul * D;
-    int64_t expect = off[S.mlp(dec, l, 0)];
-    for (int q = 0; q < d.mlp_nlin; ++q) {
-      const int hin = q == 0 ? D : H, hout = q == d.mlp_nlin - 1 ? D : H;
-      LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q)] == expect, "MLP weights are not contiguous in the flat parameter buffer");
-      expect += (int64_t)hin * hout;
-      LGN_CHECK_ARG(off[S.mlp(dec, l, 2 * q + 1)] == expect, "MLP biases are not contiguous in the flat parameter buffer");
-      expect += hout;
-    }
+  const int L = d.n_levels;
+  const int* ce = d.enc_channels;
+  if (!ride) LGN_TRY(enc_input_fwd(d.B, d.N, ce[0], in_K(d), p4, xs, P + off[0], P + off[1], n.s[0], n.v[0], st));
+  LGN_TRY(levels_fwd(d, false, P, off, n, p4, mask, st, ride, nullptr, eval, last_scalars));
+  if (with_latent)
+    LGN_TRY(enc_latent_fwd(d.B, d.N, ce[L], d.tau_s, d.tau_v, d.latent_pool, last_scalars ? n.s[L] : nullptr, n.v[L], P + off[S.out0(false)],
+                           P + off[S.out0(false) + 1], lat_s, lat_v, idx, st));
+  return 0;
+}
+
+// The caller has zero-filled G and k's zero block; dq / fin are the caller's and are run by the caller.  The latent stage's backward
+// writes k.gs[cur] / k.gv[cur].  g_lat_s = nullptr: no gradient on the latent scalars (the zero block's g_lat_s stands in), and then
+// none on the last level's scalars and its CGMLP.  last_scalars: as in encoder_fwd.
+// ride_in0: the input stage's backward rides on the first level's where that is the one-kernel form (levels_bwd); else, and where it
+//   is not, enc_input_bwd is a launch of its own.
+// jb (fused whole step): the decoder's input stage backward and this latent stage backward of a jet in one launch
+int encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int64_t* off, const double* p4, const uint8_t* mask,
+                const double* xs, const NetBuf& n, const int* idx, const double* g_lat_s, const double* g_lat_v, BwdScratch& k, int cur,
+                Deferred& dq, RadFinJob& fin, hipStream_t st, bool ride_in0, bool last_scalars = true, const JunctionBwd* jb = nullptr) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int L = d.n_levels, B = d.B, N = d.N, K = in_K(d);
+  const int* ce = d.enc_channels;
+  {
+    const RowLayout rl = enc_latent_rows(d, N, ce[L]);
+    const double *sL = last_scalars ? n.s[L] : nullptr, *wl0 = P + off[S.out0(false)], *wl1 = P + off[S.out0(false) + 1];
+    DQ_NEW(parte, (size_t)B * rl.width);
+    if (jb)
+      LGN_TRY(junction_bwd(B, N, jb->C0, jb->Tin, jb->lat_v, jb->wg1, jb->w1, jb->pdec, jb->g_p, jb->g_s0, jb->g_v0, const_cast<double*>(g_lat_v),
+                           jb->part_dec, ce[L], d.tau_s, d.tau_v, d.latent_pool, sL, n.v[L], wl0, wl1, g_lat_s ? g_lat_s : k.g_lat_s, idx,
+                           k.gs[cur], k.gv[cur], parte, st));
+    else
+      LGN_TRY(enc_latent_bwd(B, N, ce[L], d.tau_s, d.tau_v, d.latent_pool, sL, n.v[L], wl0, wl1, g_lat_s ? g_lat_s : k.g_lat_s, g_lat_v, idx,
+                             k.gs[cur], k.gv[cur], parte, st));
+    rl.add(dq, parte, B, G, off);
+  }
+  bool in0_done = false;
+  LGN_TRY(levels_bwd(d, false, P, G, off, n, p4, mask, k, dq, fin, cur, /*has_s_grad=*/g_lat_s != nullptr, st, ride_in0 ? &in0_done : nullptr));
+  if (!in0_done) {      // (several input scalars, a split step, or the three-kernel level backward: N > 40, LGN_AMD_LEVEL_V2)
+    const RowLayout ri = enc_input_rows(K, ce[0]);
+    DQ_NEW(part, (size_t)B * ri.width);
+    LGN_TRY(enc_input_bwd(B, N, ce[0], K, p4, xs, k.gs[cur], k.gv[cur], part, st));
+    ri.add(dq, part, B, G, off);
   }
   return 0;
 }
 
-}  // namespace
-}  // namespace lgn
+// forward up to the last level's features (the caller applies dec_output_fwd, or a loss kernel where the loss does not ride)
+// with_input = false (fused whole step): the junction kernel has run the input stage
+// loss: output + loss ride on the last level's kernel;  eval, last_scalars: as in levels_fwd
+int decoder_fwd(const lgn_net_desc& d, const double* P, const int64_t* off, const double* lat_v, NetBuf& n, double* pdec, hipStream_t st,
+                bool with_input = true, const LossStage* loss = nullptr, bool eval = false, bool last_scalars = true) {
+  if (with_input)
+    LGN_TRY(dec_input_fwd(d.B, d.N, d.dec_channels[0], dec_tin(d), lat_v, P + off[1], P + off[2], P + off[3], pdec, n.s[0], n.v[0], st));
+  return levels_fwd(d, true, P, off, n, pdec, nullptr, st, nullptr, loss, eval, last_scalars);
+}
+
+// k.gv[cur] holds the gradient w.r.t. the last level's vectors (from dec_output_bwd or a loss kernel); on exit `cur` is the buffer
+// pair with the gradient w.r.t. the level-0 features.  dq / fin are the caller's and are run by the caller.
+// part_in (fused whole step): the input stage's backward is the caller's (junction kernel) -- its partial rows are allocated and their
+// reductions registered here, *part_in tells the caller where they go
+int decoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int64_t* off, const double* lat_v, const NetBuf& n,
+                const double* pdec, double* g_lat_v, BwdScratch& k, int& cur, Deferred& dq, RadFinJob& fin, hipStream_t st,
+                double** part_in = nullptr) {
+  const int B = d.B, N = d.N, C0 = d.dec_channels[0], Tin = dec_tin(d);
+  LGN_TRY(levels_bwd(d, true, P, G, off, n, pdec, nullptr, k, dq, fin, cur, /*has_s_grad=*/false, st));
+  const RowLayout ri = dec_input_rows(C0, N, Tin);
+  DQ_NEW(part, (size_t)B * ri.width);
+  if (part_in) *part_in = part;
+  else LGN_TRY(dec_input_bwd(B, N, C0, Tin, lat_v, P + off[1], P + off[3], pdec, k.g_p, k.gs[cur], k.gv[cur], g_lat_v, part, st));
+  ri.add(dq, part, B, G, off);
+  return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------------
-// table-driven networks (maxdim = 3): same structure as above on packed features X_l [2][B][N][C_l][Q_l]
+// one table-driven network (maxdim = 3): same structure as above on packed features X_l [2][B][N][C_l][Q_l]
 //   level forward : moments (generic_moments.hip) -> sparse CG + CatMix (generic_local.hip) -> CGMLP in place on the
 //                   scalar column; backward in reverse.  Reference: LGNCG.forward lgn/models/lgn_cg.py:164-172.
 // ---------------------------------------------------------------------------------------------------------
-namespace lgn {
-namespace {
-
 inline bool is_generic(const lgn_net_desc& d, bool dec) { return (dec ? d.dec_tables[0] : d.enc_tables[0]) != nullptr; }
 
 struct GenGeom {                   // per-network view of the descriptor
@@ -574,7 +642,7 @@ GenAct carve_gen_act(const lgn_net_desc& d, bool dec, double* base) {
   a.sL = b.take(2 * BN * g.ch[L]);
   a.vL = b.take(8 * BN * g.ch[L]);
   if (dec) a.pdec = b.take(8 * BN);
-  else a.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (d.tau_s + d.tau_v) * 2 + 1) / 2 + 8));
+  else a.idx = reinterpret_cast<int*>(b.take(pool_idx_doubles(d)));
   a.total = b.off;
   return a;
 }
@@ -622,7 +690,7 @@ GenScratch carve_gen_scratch(const lgn_net_desc& d, bool dec, double* base) {
     const size_t z0 = b.off;
     s.zero0 = b.take(2 * BN * cmax);
     s.g_p = b.take(dec ? 8 * BN : 0);
-    s.g_lat_s = b.take(dec ? 0 : (size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s);
+    s.g_lat_s = b.take(dec ? 0 : lat_s_doubles(d));
     s.zero_doubles = b.off - z0;
   }
   s.gs = b.take(2 * BN * cmax);
@@ -637,7 +705,7 @@ GenScratch carve_gen_scratch(const lgn_net_desc& d, bool dec, double* base) {
     s.gpb[l] = sep ? b.take((size_t)g.ch[l] * BN * 8) : nullptr;
   }
   s.gbuf = (!dec && d.N <= 32) ? b.take(moments2_gbuf_doubles(d.B, d.N, (int)cmax)) : nullptr;
-  for (int l = 0; l < L; ++l) s.tot[l] = b.take(rad_partial_size(g.ch[l], dec) + 16);
+  for (int l = 0; l < L; ++l) s.tot[l] = b.take(tot_doubles(g.ch[l], dec));
   const size_t psum = gen_net_parts(d, dec);
   s.parts = b.take(psum);
   s.parts_size = psum;
@@ -800,12 +868,6 @@ int net_unpack(const lgn_net_desc& d, bool dec, int l, const double* X, double* 
   return gen_unpack((size_t)d.B * d.N * g.ch[l], g.Q[l], g.qs[l], g.qv[l], X, s, v, st);
 }
 
-// decoder-side operands of junction_bwd (whole step)
-struct JunctionBwd {
-  int C0, Tin;
-  const double *lat_v, *wg1, *w1, *pdec, *g_p, *g_s0, *g_v0;
-  double* part_dec;
-};
 
 // ---- one table-driven network, forward / backward (shared by the per-network API and the whole step) ----------------
 // with_latent = false (whole step): the latent stage runs in the junction kernel together with the decoder's input stage
@@ -832,9 +894,7 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
   const Slots S{d.n_levels, d.mlp_nlin};
   const GenGeom g = geom(d, false);
   const int L = d.n_levels, B = d.B, N = d.N, Ts = d.tau_s, Tv = d.tau_v;
-  Deferred dq;
-  dq.parts = sc.parts;
-  dq.cap = sc.parts_size;
+  Deferred dq(sc.parts, sc.parts_size);
   RadFinJob fin{};
   int cur = 0;
   {
@@ -861,7 +921,6 @@ int gen_encoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
     LGN_TRY(enc_input_bwd(B, N, C0, in_K(d), p4, xs, sc.gs, sc.gv, part, st));
     ri.add(dq, part, B, G, off);
   }
-  LGN_CHECK_ARG(dq.off <= dq.cap, "encoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
   if (hand_dq) {
     LGN_CHECK_ARG(post.empty() && hand_fin && hand_fin->n + fin.n <= (int)(sizeof(fin.it) / sizeof(fin.it[0])), "encoder_bwd: hand-over");
     hand_dq->segs.insert(hand_dq->segs.end(), dq.segs.begin(), dq.segs.end());
@@ -914,6 +973,122 @@ int gen_decoder_bwd(const lgn_net_desc& d, const double* P, double* G, const int
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// one network at a time (module API: LGNEncoder.forward / LGNDecoder.forward and their autograd backward): the two buffers of a
+// maxdim-2 network (the table-driven ones are carve_gen_act / carve_gen_scratch above)
+// ---------------------------------------------------------------------------------------------------------
+struct NetAct {                     // written by *_fwd, read by *_bwd
+  NetBuf n;
+  double* pdec;                     // decoder: complex canonical positions [2][B][N][4]
+  int* idx;                         // encoder: pooling indices
+  size_t total;
+};
+NetAct carve_act(const lgn_net_desc& d, bool dec, double* base) {
+  NetAct a{};
+  Bump b{base};
+  const size_t BN = (size_t)d.B * d.N;
+  carve_net(b, d, dec, BN, /*last_mlp_bwd=*/true, a.n);
+  if (dec) a.pdec = b.take(8 * BN);
+  else a.idx = reinterpret_cast<int*>(b.take(pool_idx_doubles(d)));
+  a.total = b.off;
+  return a;
+}
+
+struct NetScratch : BwdScratch {    // backward only
+  size_t total;
+};
+NetScratch carve_scratch(const lgn_net_desc& d, bool dec, double* base) {
+  NetScratch s{};
+  Bump b{base};
+  const size_t BN = (size_t)d.B * d.N;
+  const int L = d.n_levels;
+  const int* ch = dec ? d.dec_channels : d.enc_channels;
+  const int cmax = *std::max_element(ch, ch + L + 1);
+  {  // zero-initialised block FIRST: a caller that places `grads` right in front of the scratch gets one memset for both
+    const size_t z0 = b.off;
+    s.tail_cnt = b.take(8);
+    s.zeros_s = b.take(2 * BN * cmax);
+    s.g_p = b.take(dec ? 8 * BN : 0);
+    s.g_lat_s = b.take(dec ? 0 : lat_s_doubles(d));
+    s.zero_doubles = b.off - z0;
+  }
+  carve_level_grads(b, BN, cmax, s);
+  for (int l = 0; l < L; ++l) s.tot[l] = b.take(tot_doubles(ch[l], dec));      // (the decoder's: nothing reads them)
+  s.parts_size = net_parts(d, dec, d.N);
+  s.parts = b.take(s.parts_size);
+  s.total = b.off;
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// training steps
+// ---------------------------------------------------------------------------------------------------------
+struct StepNets {                   // what the forward of a whole maxdim-2 step runs on, training and evaluation alike
+  NetBuf enc, dec;
+  double *lat_s, *lat_v, *pdec;
+  int* idx;
+};
+struct Work : StepNets {
+  double* g_lat_v;
+  BwdScratch k;                     // one for both networks
+  size_t total;
+};
+Work carve(const lgn_net_desc& d, double* base) {
+  Work w{};
+  Bump b{base};
+  const int Nd = dec_nodes(d), Nmax = d.N > Nd ? d.N : Nd;
+  const size_t BN = (size_t)d.B * Nmax;
+  const int L = d.n_levels;
+  const int cmax = std::max(*std::max_element(d.enc_channels, d.enc_channels + L + 1), *std::max_element(d.dec_channels, d.dec_channels + L + 1));
+  carve_net(b, d, false, (size_t)d.B * d.N, /*last_mlp_bwd=*/false, w.enc);
+  carve_net(b, d, true, (size_t)d.B * Nd, /*last_mlp_bwd=*/false, w.dec);
+  w.lat_s = b.take(lat_s_doubles(d));
+  w.lat_v = b.take(lat_v_doubles(d));
+  w.g_lat_v = b.take(lat_v_doubles(d));
+  w.pdec = b.take(8 * BN);
+  BwdScratch& k = w.k;
+  carve_level_grads(b, BN, cmax, k);
+  {  // contiguous zero-initialised region
+    const size_t z0 = b.off;
+    k.zeros_s = b.take(2 * BN * cmax);
+    k.g_p = b.take(8 * BN);
+    k.g_lat_s = b.take(lat_s_doubles(d));
+    k.tail_cnt = b.take(8);
+    k.zero_doubles = b.off - z0;
+  }
+  w.idx = reinterpret_cast<int*>(b.take(pool_idx_doubles(d)));
+  for (int l = 0; l < L; ++l) k.tot[l] = b.take(tot_doubles(d.enc_channels[l], false));
+  for (int l = 0; l < L; ++l) b.take(tot_doubles(d.dec_channels[l], true));      // (nothing reads these: kept so that no buffer moves)
+  // partial rows: every producer keeps its own slice until the deferred reduction at the end of the step
+  k.parts_size = net_parts(d, false, d.N) + net_parts(d, true, Nd);
+  k.parts = b.take(k.parts_size);
+  w.total = b.off;
+  return w;
+}
+
+// Forward of a whole maxdim-2 step up to the decoder's last level, training and evaluation alike.  Two forms of the same level stacks:
+//   fused: both networks on the same N nodes, the mass the only input scalar -- the encoder's input stage (and ride's clears) rides on
+//          its first level's kernel, the latent stage and the decoder's input stage are one junction kernel;
+//   split (step_is_split: jet_features gives the encoder N + 1 nodes, lgn/models/lgn_encoder.py:372-411; data['scalars'] more input
+//          scalars): the four end stages are launches of their own, each on its network's node count, and nothing rides on the encoder.
+// dd: the decoder's view of the descriptor (N = dec_nodes).  keep_s: the latent scalars are returned -- otherwise nobody reads them
+// (the decoder never does): the encoder's last CGMLP does not run and the latent stage takes its scalars as zero
+// (LatentStage).  The decoder's last CGMLP never runs.
+int autoencoder_fwd(const lgn_net_desc& d, const lgn_net_desc& dd, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                    const double* p4, const uint8_t* mask, const double* in_scalars, StepNets& w, const InputStage& ride,
+                    const LossStage* loss, bool eval, bool keep_s, hipStream_t st) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  const int L = d.n_levels;
+  const bool split = step_is_split(d);
+  LGN_TRY(encoder_fwd(d, params, enc_off, p4, mask, in_scalars, w.enc, w.lat_s, w.lat_v, w.idx, st, split ? nullptr : &ride,
+                      /*with_latent=*/split, eval, keep_s));
+  if (!split)
+    LGN_TRY(junction_fwd(d.B, d.N, d.enc_channels[L], d.tau_s, d.tau_v, d.latent_pool, keep_s ? w.enc.s[L] : nullptr, w.enc.v[L],
+                         params + enc_off[S.out0(false)], params + enc_off[S.out0(false) + 1], w.lat_s, w.lat_v, w.idx, d.dec_channels[0],
+                         params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
+  return decoder_fwd(dd, params, dec_off, w.lat_v, w.dec, w.pdec, st, /*with_input=*/split, loss, eval, /*last_scalars=*/false);
+}
+
 // ---- whole training step on table-driven networks -------------------------------------------------------------------
 struct GenStep {
   GenAct ea, da;
@@ -923,18 +1098,28 @@ struct GenStep {
 };
 GenStep carve_gen_step(const lgn_net_desc& d, double* base) {
   GenStep g{};
-  auto at = [&](size_t off) { return base ? base + off : nullptr; };
-  size_t off = 0;
-  g.ea = carve_gen_act(d, false, at(off)); off += (g.ea.total + 15) & ~size_t(15);
-  g.da = carve_gen_act(d, true, at(off)); off += (g.da.total + 15) & ~size_t(15);
-  g.es = carve_gen_scratch(d, false, at(off)); off += (g.es.total + 15) & ~size_t(15);
-  g.ds = carve_gen_scratch(d, true, at(off)); off += (g.ds.total + 15) & ~size_t(15);
-  const int Tin = dec_tin(d);
-  g.lat_s = at(off); off += ((size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s + 15) & ~size_t(15);
-  g.lat_v = at(off); off += ((size_t)2 * d.B * Tin * 4 + 15) & ~size_t(15);
-  g.g_lat_v = at(off); off += ((size_t)2 * d.B * Tin * 4 + 15) & ~size_t(15);
-  g.total = off;
+  Bump b{base};
+  g.ea = carve_gen_act(d, false, b.here()); b.take(g.ea.total);
+  g.da = carve_gen_act(d, true, b.here()); b.take(g.da.total);
+  g.es = carve_gen_scratch(d, false, b.here()); b.take(g.es.total);
+  g.ds = carve_gen_scratch(d, true, b.here()); b.take(g.ds.total);
+  g.lat_s = b.take(lat_s_doubles(d));
+  g.lat_v = b.take(lat_v_doubles(d));        // (= the dec_tin(d) vectors the decoder reads: check_latent_match)
+  g.g_lat_v = b.take(lat_v_doubles(d));
+  g.total = b.off;
   return g;
+}
+
+// forward of a whole table-driven step up to the decoder's unpacked last-level features, training and evaluation alike: the encoder's
+// latent stage + the decoder's input stage of a jet are ONE launch (the junction kernel of the maxdim-2 step)
+int gen_autoencoder_fwd(const lgn_net_desc& d, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
+                        const uint8_t* mask, GenAct& ea, GenAct& da, double* lat_s, double* lat_v, hipStream_t st) {
+  const Slots S{d.n_levels, d.mlp_nlin};
+  LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, ea, lat_s, lat_v, st, nullptr, /*with_latent=*/false));
+  LGN_TRY(junction_fwd(d.B, d.N, d.enc_channels[d.n_levels], d.tau_s, d.tau_v, d.latent_pool, ea.sL, ea.vL, params + enc_off[S.out0(false)],
+                       params + enc_off[S.out0(false) + 1], lat_s, lat_v, ea.idx, d.dec_channels[0], params + dec_off[1], params + dec_off[2],
+                       params + dec_off[3], da.pdec, da.s0, da.v0, st));
+  return gen_decoder_fwd(d, params, dec_off, lat_v, da, st, /*with_input=*/false);
 }
 
 int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
@@ -952,16 +1137,8 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   const Slots S{d.n_levels, d.mlp_nlin};
   const int L = d.n_levels, B = d.B, N = d.N, CL = d.dec_channels[L];
   LGN_TRY(zero_ranges(grads, (size_t)n_params, g.es.zero0, g.es.zero_doubles, g.ds.zero0, g.ds.zero_doubles, st));
-  // encoder latent stage + decoder input stage of a jet: ONE launch (the junction kernels of the maxdim-2 step), forward and backward
-  const int Tin = dec_tin(d), CLe = d.enc_channels[d.n_levels], C0d = d.dec_channels[0];
-  LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, g.ea, g.lat_s, g.lat_v, st, nullptr, /*with_latent=*/false));
-  LGN_TRY(junction_fwd(B, N, CLe, d.tau_s, d.tau_v, d.latent_pool, g.ea.sL, g.ea.vL, params + enc_off[S.out0(false)],
-                       params + enc_off[S.out0(false) + 1], g.lat_s, g.lat_v, g.ea.idx, C0d, params + dec_off[1], params + dec_off[2],
-                       params + dec_off[3], g.da.pdec, g.da.s0, g.da.v0, st));
-  LGN_TRY(gen_decoder_fwd(d, params, dec_off, g.lat_v, g.da, st, /*with_input=*/false));
-  Deferred dq;
-  dq.parts = g.ds.parts;
-  dq.cap = g.ds.parts_size;
+  LGN_TRY(gen_autoencoder_fwd(d, params, enc_off, dec_off, p4, mask, g.ea, g.da, g.lat_s, g.lat_v, st));
+  Deferred dq(g.ds.parts, g.ds.parts_size);
   RadFinJob fin{};
   {
     const RowLayout ro = dec_output_rows(d, CL);
@@ -977,7 +1154,7 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   std::vector<UnpackJob> post;
   double* part_in = nullptr;
   LGN_TRY(gen_decoder_bwd(d, params, grads, dec_off, g.lat_v, g.da, g.g_lat_v, g.ds, dq, fin, post, st, &part_in));
-  LGN_CHECK_ARG(dq.off <= dq.cap, "step: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
+  const int Tin = dec_tin(d), C0d = d.dec_channels[0];
   const JunctionBwd jb{C0d, Tin, g.lat_v, params + dec_off[1], params + dec_off[3], g.da.pdec, g.ds.g_p, g.ds.gs, g.ds.gv, part_in};
   // Round 6: the static levels leave their CatMix partial rows in PARAMETER layout (nothing to unpack after the reduction), so the
   // two networks' reductions wait for ONE launch at the end of the step -- with `tail` (single process) the fused tail of the
@@ -998,306 +1175,14 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   return end_step(dq, fin, grads, n_params, /*counters=*/nullptr, d.flags, tail, st);
 }
 
-}  // namespace
-}  // namespace lgn
-
-// ---------------------------------------------------------------------------------------------------------
-// one network at a time (module API: LGNEncoder.forward / LGNDecoder.forward and their autograd backward)
-// ---------------------------------------------------------------------------------------------------------
-namespace lgn {
-namespace {
-
-struct NetAct {                     // written by *_fwd, read by *_bwd
-  NetBuf n;
-  double* pdec;                     // decoder: complex canonical positions [2][B][N][4]
-  int* idx;                         // encoder: pooling indices
-  size_t total;
-};
-NetAct carve_act(const lgn_net_desc& d, bool dec, double* base) {
-  NetAct a{};
-  Bump b{base};
-  const size_t BN = (size_t)d.B * d.N;
-  const int* ch = dec ? d.dec_channels : d.enc_channels;
-  for (int l = 0; l <= d.n_levels; ++l) {
-    a.n.s[l] = b.take(2 * BN * ch[l]);
-    a.n.v[l] = b.take(8 * BN * ch[l]);
-  }
-  for (int l = 0; l < d.n_levels; ++l) {
-    a.n.smix[l] = b.take(2 * BN * ch[l + 1]);
-    a.n.ag0[l] = b.take(4 * BN * ch[l]);
-    a.n.ag1[l] = b.take(16 * BN * ch[l]);
-    a.n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
-    // (the caller's upstream gradient may reach every level)
-    const size_t hs = BN <= mlp_save_max_rows()
-                          ? mlp_saved_doubles((int)BN, d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) : 0;
-    a.n.hsave[l] = hs ? b.take(hs) : nullptr;
-  }
-  if (dec) a.pdec = b.take(8 * BN);
-  else a.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (d.tau_s + d.tau_v) * 2 + 1) / 2 + 8));
-  a.total = b.off;
-  return a;
-}
-
-struct NetScratch {                 // backward only
-  Work w;                           // gs, gv, gsmix, g_ag, zeros_s, g_p, g_lat_s (zero block), tot, parts
-  size_t total;
-};
-NetScratch carve_scratch(const lgn_net_desc& d, bool dec, double* base) {
-  NetScratch s{};
-  Work& w = s.w;
-  Bump b{base};
-  const size_t BN = (size_t)d.B * d.N;
-  const int L = d.n_levels;
-  const int* ch = dec ? d.dec_channels : d.enc_channels;
-  int cmax = 0;
-  for (int l = 0; l <= L; ++l) cmax = cmax > ch[l] ? cmax : ch[l];
-  {  // zero-initialised block FIRST: a caller that places `grads` right in front of the scratch gets one memset for both
-    const size_t z0 = b.off;
-    w.tail_cnt = b.take(8);
-    w.zeros_s = b.take(2 * BN * cmax);
-    w.g_p = b.take(dec ? 8 * BN : 0);
-    w.g_lat_s = b.take(dec ? 0 : (size_t)2 * d.B * pool_blocks(d.latent_pool) * d.tau_s);
-    w.zero_doubles = b.off - z0;
-  }
-  for (int q = 0; q < 2; ++q) {
-    w.gs[q] = b.take(2 * BN * cmax);
-    w.gv[q] = b.take(8 * BN * cmax);
-  }
-  w.gsmix = b.take(2 * BN * cmax);
-  w.g_ag = b.take(20 * BN * cmax);
-  for (int l = 0; l < L; ++l) w.tot[dec ? 1 : 0][l] = b.take(rad_partial_size(ch[l], dec) + 16);
-  const size_t psum = net_parts(d, dec, d.N);
-  w.parts = b.take(psum);
-  w.parts_size = psum;
-  s.total = b.off;
-  return s;
-}
-
-}  // namespace
-}  // namespace lgn
-
-using namespace lgn;
-
-extern "C" {
-
-long long lgn_net_workspace_doubles(const lgn_net_desc* d, int decoder, int which) {
-  if (check_desc(d)) return -1;
-  if (is_generic(*d, decoder != 0)) {
-    if (check_generic(*d, decoder != 0)) return -1;
-    return which == 0 ? (long long)carve_gen_act(*d, decoder != 0, nullptr).total : (long long)carve_gen_scratch(*d, decoder != 0, nullptr).total;
-  }
-  return which == 0 ? (long long)carve_act(*d, decoder != 0, nullptr).total : (long long)carve_scratch(*d, decoder != 0, nullptr).total;
-}
-
-int lgn_encoder_fwd_f64(const lgn_net_desc* d, const double* params, const int64_t* off, const double* p4, const uint8_t* mask,
-                        const double* in_scalars, double* act, long long act_doubles, double* lat_s, double* lat_v, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  LGN_CHECK_ARG(params && off && p4 && mask && act && lat_s && lat_v, "encoder_fwd: null pointer");
-  LGN_CHECK_ARG(d->n_in_scalars <= 1 || in_scalars, "encoder_fwd: %d input scalars per node, but in_scalars is NULL", d->n_in_scalars);
-  if (is_generic(*d, false)) {
-    if (int rc = check_generic(*d, false)) return rc;
-    GenAct ga = carve_gen_act(*d, false, act);
-    LGN_CHECK_ARG((long long)ga.total <= act_doubles, "encoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, ga.total);
-    return gen_encoder_fwd(*d, params, off, p4, mask, ga, lat_s, lat_v, (hipStream_t)stream, in_scalars);
-  }
-  NetAct a = carve_act(*d, false, act);
-  LGN_CHECK_ARG((long long)a.total <= act_doubles, "encoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, a.total);
-  hipStream_t st = (hipStream_t)stream;
-  const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels;
-  const int* ce = d->enc_channels;
-  if (in_K(*d) > 1) {        // several input scalars: the input stage is its own launch
-    LGN_TRY(enc_input_fwd(d->B, d->N, ce[0], in_K(*d), p4, in_scalars, params + off[0], params + off[1], a.n.s[0], a.n.v[0], st));
-    LGN_TRY(levels_fwd(*d, false, ce, params, off, a.n, p4, mask, st));
-  } else {
-    const InputStage in0{params + off[0], params + off[1]};               // (rides on the first level's kernel)
-    LGN_TRY(levels_fwd(*d, false, ce, params, off, a.n, p4, mask, st, &in0));
-  }
-  LGN_TRY(enc_latent_fwd(d->B, d->N, ce[L], d->tau_s, d->tau_v, d->latent_pool, a.n.s[L], a.n.v[L], params + off[S.out0(false)],
-                         params + off[S.out0(false) + 1], lat_s, lat_v, a.idx, st));
-  return 0;
-}
-
-int lgn_encoder_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* off,
-                        const double* p4, const uint8_t* mask, const double* in_scalars, const double* act, long long act_doubles,
-                        const double* g_lat_s, const double* g_lat_v, double* scratch, long long scratch_doubles, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  LGN_CHECK_ARG(params && grads && off && p4 && mask && act && g_lat_v && scratch && n_params > 0, "encoder_bwd: null pointer");
-  LGN_CHECK_ARG(d->n_in_scalars <= 1 || in_scalars, "encoder_bwd: %d input scalars per node, but in_scalars is NULL", d->n_in_scalars);
-  if (is_generic(*d, false)) {
-    if (int rc = check_generic(*d, false)) return rc;
-    GenAct ga = carve_gen_act(*d, false, const_cast<double*>(act));
-    GenScratch gs = carve_gen_scratch(*d, false, scratch);
-    LGN_CHECK_ARG((long long)ga.total <= act_doubles && (long long)gs.total <= scratch_doubles,
-                  "encoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, ga.total, gs.total);
-    if (int rc = check_mlp_contiguous(*d, false, off)) return rc;
-    LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, gs.zero0, gs.zero_doubles, (hipStream_t)stream));
-    return gen_encoder_bwd(*d, params, grads, off, p4, mask, ga, g_lat_s, g_lat_v, gs, (hipStream_t)stream, in_scalars);
-  }
-  NetAct a = carve_act(*d, false, const_cast<double*>(act));
-  NetScratch sc = carve_scratch(*d, false, scratch);
-  LGN_CHECK_ARG((long long)a.total <= act_doubles && (long long)sc.total <= scratch_doubles,
-                "encoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, a.total, sc.total);
-  if (int rc = check_mlp_contiguous(*d, false, off)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  Work& w = sc.w;
-  const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, B = d->B, N = d->N;
-  const int* ce = d->enc_channels;
-  LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, w.zero0(), w.zero_doubles, st));
-  Deferred dq;
-  dq.parts = w.parts;
-  dq.cap = w.parts_size;
-  RadFinJob fin{};
-  int cur = 0;
-  {
-    const RowLayout rl = enc_latent_rows(*d, N, ce[L]);
-    DQ_NEW(parte, (size_t)B * rl.width);
-    LGN_TRY(enc_latent_bwd(B, N, ce[L], d->tau_s, d->tau_v, d->latent_pool, a.n.s[L], a.n.v[L], params + off[S.out0(false)],
-                           params + off[S.out0(false) + 1], g_lat_s ? g_lat_s : w.g_lat_s, g_lat_v, a.idx, w.gs[cur], w.gv[cur], parte, st));
-    rl.add(dq, parte, B, grads, off);
-  }
-  // without an upstream gradient on the latent scalars the last level's scalars (and its CGMLP) receive none
-  bool in0_done = false;
-  const int K = in_K(*d);      // (several input scalars: the input stage's backward is its own launch, nothing rides)
-  LGN_TRY(levels_bwd(*d, false, ce, params, grads, off, a.n, p4, mask, w, dq, fin, cur, /*has_s_grad=*/g_lat_s != nullptr, st,
-                     K > 1 ? nullptr : &in0_done));
-  if (!in0_done) {
-    const RowLayout ri = enc_input_rows(K, ce[0]);
-    DQ_NEW(part, (size_t)B * ri.width);
-    LGN_TRY(enc_input_bwd(B, N, ce[0], K, p4, in_scalars, w.gs[cur], w.gv[cur], part, st));
-    ri.add(dq, part, B, grads, off);
-  }
-  LGN_CHECK_ARG(dq.off <= dq.cap, "encoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-  // (measured at cfg2, captured module step: the one-launch form is 3 us SLOWER for the encoder alone -- 0.5966 against 0.5937 ms)
-  LGN_TRY(finish_reductions(dq, fin, grads, n_params, nullptr, d->flags, st));
-  return 0;
-}
-
-int lgn_decoder_fwd_f64(const lgn_net_desc* d, const double* params, const int64_t* off, const double* lat_v, double* act,
-                        long long act_doubles, double* recon, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  LGN_CHECK_ARG(params && off && lat_v && act && recon, "decoder_fwd: null pointer");
-  if (is_generic(*d, true)) {
-    if (int rc = check_generic(*d, true)) return rc;
-    GenAct ga = carve_gen_act(*d, true, act);
-    LGN_CHECK_ARG((long long)ga.total <= act_doubles, "decoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, ga.total);
-    LGN_TRY(gen_decoder_fwd(*d, params, off, lat_v, ga, (hipStream_t)stream));
-    const Slots Sg{d->n_levels, d->mlp_nlin};
-    return dec_output_fwd(d->B, d->N, d->dec_channels[d->n_levels], ga.vL, params + off[Sg.out0(true) + 1], recon, (hipStream_t)stream);
-  }
-  NetAct a = carve_act(*d, true, act);
-  LGN_CHECK_ARG((long long)a.total <= act_doubles, "decoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, a.total);
-  hipStream_t st = (hipStream_t)stream;
-  const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels;
-  const int* cd = d->dec_channels;
-  LGN_TRY(dec_input_fwd(d->B, d->N, cd[0], dec_tin(*d), lat_v, params + off[1], params + off[2], params + off[3], a.pdec, a.n.s[0], a.n.v[0], st));
-  LGN_TRY(levels_fwd(*d, true, cd, params, off, a.n, a.pdec, nullptr, st));
-  LGN_TRY(dec_output_fwd(d->B, d->N, cd[L], a.n.v[L], params + off[S.out0(true) + 1], recon, st));
-  return 0;
-}
-
-int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* off,
-                        const double* lat_v, const double* act, long long act_doubles, const double* g_recon, double* g_lat_v,
-                        double* scratch, long long scratch_doubles, void* stream) {
-  if (int rc = check_desc(d)) return rc;
-  LGN_CHECK_ARG(params && grads && off && lat_v && act && g_recon && g_lat_v && scratch && n_params > 0, "decoder_bwd: null pointer");
-  if (is_generic(*d, true)) {
-    if (int rc = check_generic(*d, true)) return rc;
-    hipStream_t gst = (hipStream_t)stream;
-    GenAct ga = carve_gen_act(*d, true, const_cast<double*>(act));
-    GenScratch gs = carve_gen_scratch(*d, true, scratch);
-    LGN_CHECK_ARG((long long)ga.total <= act_doubles && (long long)gs.total <= scratch_doubles,
-                  "decoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, ga.total, gs.total);
-    if (int rc = check_mlp_contiguous(*d, true, off)) return rc;
-    LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, gs.zero0, gs.zero_doubles, gst));
-    const Slots Sg{d->n_levels, d->mlp_nlin};
-    const int CL = d->dec_channels[d->n_levels];
-    Deferred dq;
-    dq.parts = gs.parts;
-    dq.cap = gs.parts_size;
-    RadFinJob fin{};
-    const RowLayout ro = dec_output_rows(*d, CL);
-    DQ_NEW(part, (size_t)d->B * ro.width);
-    LGN_TRY(dec_output_bwd(d->B, d->N, CL, ga.vL, params + off[Sg.out0(true) + 1], g_recon, gs.gv, part, gst));
-    ro.add(dq, part, d->B, grads, off);
-    std::vector<UnpackJob> post;
-    LGN_TRY(gen_decoder_bwd(*d, params, grads, off, lat_v, ga, g_lat_v, gs, dq, fin, post, gst));
-    LGN_CHECK_ARG(dq.off <= dq.cap, "decoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-    LGN_TRY(dq.flush(gst));
-    return run_unpack_jobs(post, gst);
-  }
-  NetAct a = carve_act(*d, true, const_cast<double*>(act));
-  NetScratch sc = carve_scratch(*d, true, scratch);
-  LGN_CHECK_ARG((long long)a.total <= act_doubles && (long long)sc.total <= scratch_doubles,
-                "decoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, a.total, sc.total);
-  if (int rc = check_mlp_contiguous(*d, true, off)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  Work& w = sc.w;
-  const Slots S{d->n_levels, d->mlp_nlin};
-  const int L = d->n_levels, B = d->B, N = d->N, Tin = dec_tin(*d);
-  const int* cd = d->dec_channels;
-  LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, w.zero0(), w.zero_doubles, st));
-  Deferred dq;
-  dq.parts = w.parts;
-  dq.cap = w.parts_size;
-  RadFinJob fin{};
-  int cur = 0;
-  {
-    const RowLayout ro = dec_output_rows(*d, cd[L]);
-    DQ_NEW(part, (size_t)B * ro.width);
-    LGN_TRY(dec_output_bwd(B, N, cd[L], a.n.v[L], params + off[S.out0(true) + 1], g_recon, w.gv[cur], part, st));
-    ro.add(dq, part, B, grads, off);
-  }
-  LGN_TRY(levels_bwd(*d, true, cd, params, grads, off, a.n, a.pdec, nullptr, w, dq, fin, cur, /*has_s_grad=*/false, st));
-  {
-    const RowLayout ri = dec_input_rows(cd[0], N, Tin);
-    DQ_NEW(part, (size_t)B * ri.width);
-    LGN_TRY(dec_input_bwd(B, N, cd[0], Tin, lat_v, params + off[1], params + off[3], a.pdec, w.g_p, w.gs[cur], w.gv[cur], g_lat_v, part, st));
-    ri.add(dq, part, B, grads, off);
-  }
-  LGN_CHECK_ARG(dq.off <= dq.cap, "decoder_bwd: partial-row workspace overflow (%zu > %zu)", dq.off, dq.cap);
-  return finish_reductions(dq, fin, grads, n_params, /*counters=*/nullptr, d->flags, st);
-}
-
-}  // extern "C"
-
-extern "C" {
-
-int lgn_step_param_slots(const lgn_net_desc* d, int decoder) {
-  if (check_desc(d)) return -1;
-  return Slots{d->n_levels, d->mlp_nlin}.count(decoder != 0);
-}
-
-long long lgn_encoder_end_lds_bytes(int N, int C0, int K, int CL, int Ts, int Tv, int pool) {
-  return pool_valid(pool) ? (long long)encoder_end_lds_bytes(N, C0, K < 1 ? 1 : K, CL, Ts, Tv, pool) : -1;
-}
-long long lgn_decoder_end_lds_bytes(int N, int C0, int Tin, int CL) { return (long long)decoder_end_lds_bytes(N, C0, Tin, CL); }
-long long lgn_junction_lds_bytes(int N, int CL, int Ts, int Tv, int pool, int C0) {
-  return pool_valid(pool) ? (long long)junction_lds_bytes(N, CL, Ts, Tv, pool, C0) : -1;
-}
-
-long long lgn_step_workspace_doubles(const lgn_net_desc* d) {
-  if (check_desc(d) || check_latent_match(*d)) return -1;
-  if (is_generic(*d, false) || is_generic(*d, true)) {
-    if (check_generic(*d, false) || check_generic(*d, true)) return -1;
-    return (long long)carve_gen_step(*d, nullptr).total;
-  }
-  return (long long)carve(*d, nullptr).total;
-}
-
-}  // extern "C"
-// forward + backward of a training step, ended by end_step.  Two forms of the same level stacks:
-//   fused: both networks on the same N nodes, the mass the only input scalar -- the encoder's input stage (and the clearing of the
-//          gradients and the zero block) rides on its first level's kernel, the latent stage and the decoder's input stage are one
-//          junction kernel in each direction, the input stage's backward may ride on the first level's backward;
-//   split (step_is_split: jet_features gives the encoder N + 1 nodes, lgn/models/lgn_encoder.py:372-411; data['scalars'] more input
-//          scalars): the four end stages are launches of their own, each on its network's node count, and nothing rides.
-static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                        const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
-                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
-                        const StepTailArgs* tail, const AssignLoss* al = nullptr) {
+// forward + backward of a training step, ended by end_step: argument checks, a carve, autoencoder_fwd, the loss, decoder_bwd and
+// encoder_bwd on one BwdScratch.  In the fused form the first kernel also clears the gradients and the zero block, the loss rides on
+// the decoder's last level where that is one workgroup per jet, and the two stages between the networks are one junction kernel
+// in each direction; in the split form (autoencoder_fwd) every end stage is a launch of its own.
+int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, long long n_params, const int64_t* enc_off,
+                 const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                 double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
+                 const StepTailArgs* tail, const AssignLoss* al = nullptr) {
   if (int rc = check_desc(dp)) return rc;
   const lgn_net_desc& d = *dp;
   LGN_CHECK_ARG(params && grads && enc_off && dec_off && p4 && target && mask && workspace && recon && loss_part && n_params > 0,
@@ -1323,86 +1208,325 @@ static int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* gr
   lgn_net_desc dd = d;               // the decoder's view of the descriptor: the level sequencers read B, N, flags, MLP shape
   dd.N = dec_nodes(d);
   const Slots S{d.n_levels, d.mlp_nlin};
-  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dd.N, Ts = d.tau_s, Tv = d.tau_v, K = in_K(d), Tin = dec_tin(d);
-  const int* ce = d.enc_channels;
-  const int* cd = d.dec_channels;
-  const double* wl0 = params + enc_off[S.out0(false)];
-  const double* wl1 = params + enc_off[S.out0(false) + 1];
-  Deferred dq;
-  dq.parts = w.parts;
-  dq.cap = w.parts_size;
+  const int B = d.B, Nd = dd.N, CL = d.dec_channels[d.n_levels];
+  BwdScratch& k = w.k;
+  Deferred dq(k.parts, k.parts_size);
   RadFinJob fin{};
-
-  // ---------------- forward ----------------
-  // the step returns no latent scalars and the decoder never reads them: neither network's last CGMLP runs, and
-  // the latent stage takes the encoder's last-level scalars as zero (LatentStage)
-  if (split) {
-    LGN_TRY(zero_ranges(grads, (size_t)n_params, w.zero0(), w.zero_doubles, nullptr, 0, st));
-    LGN_TRY(enc_input_fwd(B, Ne, ce[0], K, p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, false, /*last_scalars=*/false));
-    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, st));
-    LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
-                          w.dec.v[0], st));
-  } else {
-    // the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s
-    // (the encoder's input stage and the two clears ride on the first level's kernel: levels_fwd / InputStage)
-    const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, w.zeros_s, w.zero_doubles};
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, false, /*last_scalars=*/false));
-    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.lat_s, w.lat_v, w.idx, cd[0],
-                         params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
-  }
-  // ---------------- loss (and its backward), on the last decoder level's kernel when that is one workgroup per jet ----------
   int cur = 0;
-  {
-    const RowLayout ro = dec_output_rows(d, cd[L]);
-    DQ_NEW(part, (size_t)B * ro.width);
-    const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, w.gv[cur], part};
-    const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);      // (an assignment loss is a launch of its own in every regime)
-    LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &ls : nullptr, false,
-                       /*last_scalars=*/false));
-    if (al)
-      LGN_TRY(dec_output_assign_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, ls.method, *al, recon, loss_part, w.gv[cur], part, st));
-    else if (!rides)
-      LGN_TRY(dec_output_loss(B, Nd, cd[L], w.dec.v[L], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, w.gv[cur], part, st));
-    ro.add(dq, part, B, grads, dec_off);
-  }
+
+  // ---------------- forward, loss (and its backward) ----------------
+  const RowLayout ro = dec_output_rows(d, CL);
+  DQ_NEW(part, (size_t)B * ro.width);
+  const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, k.gv[cur], part};
+  const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);      // (an assignment loss is a launch of its own in every regime)
+  // fused: the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s | tail_cnt
+  const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, k.zeros_s, k.zero_doubles};
+  if (split) LGN_TRY(zero_ranges(grads, (size_t)n_params, k.zero0(), k.zero_doubles, nullptr, 0, st));
+  LGN_TRY(autoencoder_fwd(d, dd, params, enc_off, dec_off, p4, mask, in_scalars, w, in0, rides ? &ls : nullptr, /*eval=*/false,
+                          /*keep_s=*/false, st));
+  if (al)
+    LGN_TRY(dec_output_assign_loss(B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, ls.method, *al, recon, loss_part, k.gv[cur], part, st));
+  else if (!rides)
+    LGN_TRY(dec_output_loss(B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, k.gv[cur], part, st));
+  ro.add(dq, part, B, grads, dec_off);
 
   // ---------------- backward ----------------
-  LGN_TRY(levels_bwd(dd, true, cd, params, grads, dec_off, w.dec, w.pdec, nullptr, w, dq, fin, cur, /*has_s_grad=*/false, st));
-  {
-    const RowLayout ri = dec_input_rows(cd[0], Nd, Tin), rl = enc_latent_rows(d, Ne, ce[L]);
-    DQ_NEW(part, (size_t)B * ri.width);
-    DQ_NEW(parte, (size_t)B * rl.width);
-    // reads the gradient w.r.t. the decoder's level-0 features, writes the one w.r.t. the encoder's last level into the
-    // other buffer pair (jets do not occupy the same slices when the two channel counts differ)
-    const int rd = cur, wr = cur ^ 1;
-    cur = wr;
-    // the decoder never reads the latent scalars: their gradient is the zero block's g_lat_s
-    if (split) {
-      LGN_TRY(dec_input_bwd(B, Nd, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd],
-                            w.g_lat_v, part, st));
-      LGN_TRY(enc_latent_bwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.g_lat_s, w.g_lat_v, w.idx, w.gs[wr],
-                             w.gv[wr], parte, st));
-    } else {
-      LGN_TRY(junction_bwd(B, Ne, cd[0], Tin, w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, w.g_p, w.gs[rd], w.gv[rd], w.g_lat_v,
-                           part, ce[L], Ts, Tv, d.latent_pool, nullptr, w.enc.v[L], wl0, wl1, w.g_lat_s, w.idx, w.gs[wr], w.gv[wr], parte, st));
-    }
-    ri.add(dq, part, B, grads, dec_off);
-    rl.add(dq, parte, B, grads, enc_off);
-  }
+  // fused: the junction kernel reads the gradient w.r.t. the decoder's level-0 features and writes the one w.r.t. the encoder's last
+  // level into the other buffer pair (jets do not occupy the same slices when the two channel counts differ); the split form's two
+  // launches do the same.  The decoder never reads the latent scalars: their gradient is the zero block's g_lat_s.
+  double* part_in = nullptr;
+  LGN_TRY(decoder_bwd(dd, params, grads, dec_off, w.lat_v, w.dec, w.pdec, w.g_lat_v, k, cur, dq, fin, st, split ? nullptr : &part_in));
+  const JunctionBwd jb{d.dec_channels[0], dec_tin(d), w.lat_v, params + dec_off[1], params + dec_off[3], w.pdec, k.g_p, k.gs[cur], k.gv[cur], part_in};
   // the input stage's backward rides on the first level's where it can -- fused form only (split: its own launch, even with K = 1)
-  bool in0_done = false;
-  LGN_TRY(levels_bwd(d, false, ce, params, grads, enc_off, w.enc, p4, mask, w, dq, fin, cur, /*has_s_grad=*/false, st,
-                     split ? nullptr : &in0_done));
-  if (!in0_done) {      // (split, or the three-kernel level backward: N > 40, LGN_AMD_LEVEL_V2)
-    const RowLayout ri = enc_input_rows(K, ce[0]);
-    DQ_NEW(part, (size_t)B * ri.width);
-    LGN_TRY(enc_input_bwd(B, Ne, ce[0], K, p4, split ? in_scalars : nullptr, w.gs[cur], w.gv[cur], part, st));
-    ri.add(dq, part, B, grads, enc_off);
-  }
-  return end_step(dq, fin, grads, n_params, w.tail_cnt, d.flags, tail, st);
+  LGN_TRY(encoder_bwd(d, params, grads, enc_off, p4, mask, split ? in_scalars : nullptr, w.enc, w.idx, nullptr, w.g_lat_v, k, cur ^ 1, dq, fin,
+                      st, /*ride_in0=*/!split, /*last_scalars=*/false, split ? nullptr : &jb));
+  return end_step(dq, fin, grads, n_params, k.tail_cnt, d.flags, tail, st);
 }
+
+// the tail of a call with an optimiser descriptor; refuses what no kernel implements before anything is enqueued
+int optim_tail(const lgn_optim_desc* o, double* params, double* grads, long long n_params, double* state_m, double* state_v,
+               long long* step_dev, int do_step, const double* loss_part, int n_loss, double* loss_out, StepTailArgs& t) {
+  LGN_CHECK_ARG(o, "optimiser descriptor: null pointer");
+  LGN_CHECK_ARG(o->kind == LGN_OPT_ADAM || o->kind == LGN_OPT_RMSPROP, "optimiser descriptor: kind %d is neither LGN_OPT_ADAM nor "
+                "LGN_OPT_RMSPROP", o->kind);
+  LGN_CHECK_ARG(!do_step || (state_m && state_v && step_dev), "optimiser state missing");
+  LGN_CHECK_ARG(o->l2_lambda >= 0.0 && o->eps >= 0.0, "optimiser descriptor: negative l2_lambda or eps");
+  LGN_CHECK_ARG(o->kind != LGN_OPT_RMSPROP || (o->alpha >= 0.0 && o->alpha <= 1.0 && o->momentum >= 0.0),
+                "optimiser descriptor: RMSprop takes 0 <= alpha <= 1 and momentum >= 0");
+  t = StepTailArgs{params, grads, (long)n_params, state_m, state_v, reinterpret_cast<long*>(step_dev), o->l1_lambda, o->lr, o->beta1,
+                   o->beta2, o->eps, do_step, loss_part, n_loss, loss_out, 0, nullptr};
+  t.opt_form = 1;
+  t.kind = o->kind;
+  t.l2 = o->l2_lambda;
+  t.alpha = o->alpha;
+  t.mu = o->momentum;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
+// get_real -> Chamfer [+ jet-feature term] forward only, no L1 (regularization = is_train, utils/train.py:308-314).  Nothing is
+// kept for a backward: two feature buffers per network used in turn, level kernels without the aggregate stores, the CGMLPs on
+// their no-save path, no CGMLP after the decoder's last level, a loss tail that writes no gradient.
+// ---------------------------------------------------------------------------------------------------------
+struct EvalWork : StepNets {        // s / v of level l point to feature buffer l & 1 of the network; smix one buffer for all levels
+  size_t total;
+};
+EvalWork carve_eval(const lgn_net_desc& d, double* base) {
+  EvalWork w{};
+  Bump b{base};
+  const int L = d.n_levels, Nd = dec_nodes(d);
+  const size_t BNe = (size_t)d.B * d.N, BNd = (size_t)d.B * Nd;
+  size_t smix = 0;
+  auto net = [&](NetBuf& n, const int* ch, size_t BN) {
+    const int cmax = *std::max_element(ch, ch + L + 1);
+    double *s[2], *v[2];
+    for (int q = 0; q < 2; ++q) {
+      s[q] = b.take(2 * BN * cmax);
+      v[q] = b.take(8 * BN * cmax);
+    }
+    for (int l = 0; l <= L; ++l) {
+      n.s[l] = s[l & 1];
+      n.v[l] = v[l & 1];
+    }
+    smix = std::max(smix, 2 * BN * cmax);
+  };
+  net(w.enc, d.enc_channels, BNe);
+  net(w.dec, d.dec_channels, BNd);
+  double* sm = b.take(smix);
+  for (int l = 0; l < L; ++l) w.enc.smix[l] = w.dec.smix[l] = sm;
+  w.lat_s = b.take(lat_s_doubles(d));
+  w.lat_v = b.take(lat_v_doubles(d));
+  w.pdec = b.take(8 * BNd);
+  w.idx = reinterpret_cast<int*>(b.take(pool_idx_doubles(d)));
+  w.total = b.off;
+  return w;
+}
+
+// table-driven networks: the training forward (gen_autoencoder_fwd) on activations of their own -- those kernels
+// store what their backward would read; no-keep forms of them are not part of the evaluation step yet
+struct GenEval {
+  GenAct ea, da;
+  double *lat_s, *lat_v;
+  size_t total;
+};
+GenEval carve_gen_eval(const lgn_net_desc& d, double* base) {
+  GenEval g{};
+  Bump b{base};
+  g.ea = carve_gen_act(d, false, b.here()); b.take(g.ea.total);
+  g.da = carve_gen_act(d, true, b.here()); b.take(g.da.total);
+  g.lat_s = b.take(lat_s_doubles(d));
+  g.lat_v = b.take(lat_v_doubles(d));
+  g.total = b.off;
+  return g;
+}
+
+long long eval_workspace(const lgn_net_desc& d) {
+  if (is_generic(d, false) || is_generic(d, true)) {
+    if (check_generic(d, false) || check_generic(d, true)) return -1;
+    return (long long)carve_gen_eval(d, nullptr).total;
+  }
+  return (long long)carve_eval(d, nullptr).total;
+}
+
+int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
+              const double* target, const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
+              double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st,
+              const AssignLoss* al) {
+  // every refusal comes before the first launch
+  if (int rc = check_desc(dp)) return rc;
+  const lgn_net_desc& d = *dp;
+  LGN_CHECK_ARG(params && enc_off && dec_off && p4 && target && mask && workspace && recon_real && loss_part && loss_out,
+                "step_eval: null pointer");
+  LGN_CHECK_ARG(d.n_in_scalars <= 1 || in_scalars, "step_eval: %d input scalars per node, but in_scalars is NULL", d.n_in_scalars);
+  LGN_CHECK_ARG(!lat_s_out == !lat_v_out, "step_eval: give both latent outputs or neither");
+  if (int rc = check_latent_match(d)) return rc;
+  const long long need = eval_workspace(d);
+  if (need < 0) return -1;
+  LGN_CHECK_ARG(need <= workspace_doubles, "step_eval: workspace holds %lld doubles, this configuration needs %lld", workspace_doubles, need);
+  if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
+  if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
+  const int B = d.B, Ne = d.N, Nd = dec_nodes(d), CL = d.dec_channels[d.n_levels];
+  const double* wo1 = params + dec_off[Slots{d.n_levels, d.mlp_nlin}.out0(true) + 1];
+  const double* vL;                  // the decoder's last-level vectors
+  bool rides = false;                // output + loss rode on the decoder's last level
+  if (is_generic(d, false) || is_generic(d, true)) {
+    LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step_eval: encoder and decoder must both be table-driven (or both fused)");
+    LGN_CHECK_ARG(!step_is_split(d), "step_eval: table-driven networks take the mass as the only input scalar and one node count for "
+                  "both networks (n_in_scalars=%d, N=%d, dec_N=%d)", d.n_in_scalars, d.N, d.dec_N);
+    GenEval g = carve_gen_eval(d, workspace);
+    LGN_TRY(gen_autoencoder_fwd(d, params, enc_off, dec_off, p4, mask, g.ea, g.da, lat_s_out ? lat_s_out : g.lat_s,
+                                lat_v_out ? lat_v_out : g.lat_v, st));
+    vL = g.da.vL;
+  } else {
+    EvalWork w = carve_eval(d, workspace);
+    if (lat_s_out) { w.lat_s = lat_s_out; w.lat_v = lat_v_out; }
+    lgn_net_desc dd = d;
+    dd.N = Nd;
+    const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
+    rides = !al && level_fwd_carries_loss(Nd, d.flags);
+    const InputStage in0{params + enc_off[0], params + enc_off[1]};
+    // the latent scalars (the encoder's last CGMLP and what the latent stage makes of its output) only when they are returned
+    LGN_TRY(autoencoder_fwd(d, dd, params, enc_off, dec_off, p4, mask, in_scalars, w, in0, rides ? &loss : nullptr, /*eval=*/true,
+                            /*keep_s=*/lat_s_out != nullptr, st));
+    vL = w.dec.v[d.n_levels];
+  }
+  if (al) LGN_TRY(dec_output_assign_eval(B, Nd, CL, vL, wo1, target, d.get_real, *al, recon_real, loss_part, st));
+  else if (!rides) LGN_TRY(dec_output_eval(B, Nd, CL, vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+  return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
+}
+
+}  // namespace
+}  // namespace lgn
+
+using namespace lgn;
+
 extern "C" {
+
+// ---- one network at a time ----------------------------------------------------------------------------------------------
+long long lgn_net_workspace_doubles(const lgn_net_desc* d, int decoder, int which) {
+  if (check_desc(d)) return -1;
+  if (is_generic(*d, decoder != 0)) {
+    if (check_generic(*d, decoder != 0)) return -1;
+    return which == 0 ? (long long)carve_gen_act(*d, decoder != 0, nullptr).total : (long long)carve_gen_scratch(*d, decoder != 0, nullptr).total;
+  }
+  return which == 0 ? (long long)carve_act(*d, decoder != 0, nullptr).total : (long long)carve_scratch(*d, decoder != 0, nullptr).total;
+}
+
+int lgn_encoder_fwd_f64(const lgn_net_desc* d, const double* params, const int64_t* off, const double* p4, const uint8_t* mask,
+                        const double* in_scalars, double* act, long long act_doubles, double* lat_s, double* lat_v, void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  LGN_CHECK_ARG(params && off && p4 && mask && act && lat_s && lat_v, "encoder_fwd: null pointer");
+  LGN_CHECK_ARG(d->n_in_scalars <= 1 || in_scalars, "encoder_fwd: %d input scalars per node, but in_scalars is NULL", d->n_in_scalars);
+  if (is_generic(*d, false)) {
+    if (int rc = check_generic(*d, false)) return rc;
+    GenAct ga = carve_gen_act(*d, false, act);
+    LGN_CHECK_ARG((long long)ga.total <= act_doubles, "encoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, ga.total);
+    return gen_encoder_fwd(*d, params, off, p4, mask, ga, lat_s, lat_v, (hipStream_t)stream, in_scalars);
+  }
+  NetAct a = carve_act(*d, false, act);
+  LGN_CHECK_ARG((long long)a.total <= act_doubles, "encoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, a.total);
+  // the input stage rides on the first level's kernel; several input scalars: it is a launch of its own
+  const InputStage in0{params + off[0], params + off[1]};
+  return encoder_fwd(*d, params, off, p4, mask, in_scalars, a.n, lat_s, lat_v, a.idx, (hipStream_t)stream, in_K(*d) > 1 ? nullptr : &in0);
+}
+
+int lgn_encoder_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* off,
+                        const double* p4, const uint8_t* mask, const double* in_scalars, const double* act, long long act_doubles,
+                        const double* g_lat_s, const double* g_lat_v, double* scratch, long long scratch_doubles, void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  LGN_CHECK_ARG(params && grads && off && p4 && mask && act && g_lat_v && scratch && n_params > 0, "encoder_bwd: null pointer");
+  LGN_CHECK_ARG(d->n_in_scalars <= 1 || in_scalars, "encoder_bwd: %d input scalars per node, but in_scalars is NULL", d->n_in_scalars);
+  hipStream_t st = (hipStream_t)stream;
+  if (is_generic(*d, false)) {
+    if (int rc = check_generic(*d, false)) return rc;
+    GenAct ga = carve_gen_act(*d, false, const_cast<double*>(act));
+    GenScratch gs = carve_gen_scratch(*d, false, scratch);
+    LGN_CHECK_ARG((long long)ga.total <= act_doubles && (long long)gs.total <= scratch_doubles,
+                  "encoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, ga.total, gs.total);
+    if (int rc = check_mlp_contiguous(*d, false, off)) return rc;
+    LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, gs.zero0, gs.zero_doubles, st));
+    return gen_encoder_bwd(*d, params, grads, off, p4, mask, ga, g_lat_s, g_lat_v, gs, st, in_scalars);
+  }
+  NetAct a = carve_act(*d, false, const_cast<double*>(act));
+  NetScratch sc = carve_scratch(*d, false, scratch);
+  LGN_CHECK_ARG((long long)a.total <= act_doubles && (long long)sc.total <= scratch_doubles,
+                "encoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, a.total, sc.total);
+  if (int rc = check_mlp_contiguous(*d, false, off)) return rc;
+  LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, sc.zero0(), sc.zero_doubles, st));
+  Deferred dq(sc.parts, sc.parts_size);
+  RadFinJob fin{};
+  // (several input scalars: the input stage's backward is its own launch, nothing rides)
+  LGN_TRY(encoder_bwd(*d, params, grads, off, p4, mask, in_scalars, a.n, a.idx, g_lat_s, g_lat_v, sc, /*cur=*/0, dq, fin, st,
+                      /*ride_in0=*/in_K(*d) == 1));
+  // (measured at cfg2, captured module step: the one-launch form is 3 us SLOWER for the encoder alone -- 0.5966 against 0.5937 ms)
+  return finish_reductions(dq, fin, grads, n_params, nullptr, d->flags, st);
+}
+
+int lgn_decoder_fwd_f64(const lgn_net_desc* d, const double* params, const int64_t* off, const double* lat_v, double* act,
+                        long long act_doubles, double* recon, void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  LGN_CHECK_ARG(params && off && lat_v && act && recon, "decoder_fwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int CL = d->dec_channels[d->n_levels];
+  const double* wo1 = params + off[Slots{d->n_levels, d->mlp_nlin}.out0(true) + 1];
+  if (is_generic(*d, true)) {
+    if (int rc = check_generic(*d, true)) return rc;
+    GenAct ga = carve_gen_act(*d, true, act);
+    LGN_CHECK_ARG((long long)ga.total <= act_doubles, "decoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, ga.total);
+    LGN_TRY(gen_decoder_fwd(*d, params, off, lat_v, ga, st));
+    return dec_output_fwd(d->B, d->N, CL, ga.vL, wo1, recon, st);
+  }
+  NetAct a = carve_act(*d, true, act);
+  LGN_CHECK_ARG((long long)a.total <= act_doubles, "decoder_fwd: activation buffer holds %lld doubles, needs %zu", act_doubles, a.total);
+  LGN_TRY(decoder_fwd(*d, params, off, lat_v, a.n, a.pdec, st));
+  return dec_output_fwd(d->B, d->N, CL, a.n.v[d->n_levels], wo1, recon, st);
+}
+
+int lgn_decoder_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* off,
+                        const double* lat_v, const double* act, long long act_doubles, const double* g_recon, double* g_lat_v,
+                        double* scratch, long long scratch_doubles, void* stream) {
+  if (int rc = check_desc(d)) return rc;
+  LGN_CHECK_ARG(params && grads && off && lat_v && act && g_recon && g_lat_v && scratch && n_params > 0, "decoder_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int B = d->B, N = d->N, CL = d->dec_channels[d->n_levels];
+  const double* wo1 = params + off[Slots{d->n_levels, d->mlp_nlin}.out0(true) + 1];
+  const RowLayout ro = dec_output_rows(*d, CL);
+  RadFinJob fin{};
+  if (is_generic(*d, true)) {
+    if (int rc = check_generic(*d, true)) return rc;
+    GenAct ga = carve_gen_act(*d, true, const_cast<double*>(act));
+    GenScratch gs = carve_gen_scratch(*d, true, scratch);
+    LGN_CHECK_ARG((long long)ga.total <= act_doubles && (long long)gs.total <= scratch_doubles,
+                  "decoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, ga.total, gs.total);
+    if (int rc = check_mlp_contiguous(*d, true, off)) return rc;
+    LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, gs.zero0, gs.zero_doubles, st));
+    Deferred dq(gs.parts, gs.parts_size);
+    DQ_NEW(part, (size_t)B * ro.width);
+    LGN_TRY(dec_output_bwd(B, N, CL, ga.vL, wo1, g_recon, gs.gv, part, st));
+    ro.add(dq, part, B, grads, off);
+    std::vector<UnpackJob> post;
+    LGN_TRY(gen_decoder_bwd(*d, params, grads, off, lat_v, ga, g_lat_v, gs, dq, fin, post, st));
+    LGN_TRY(dq.flush(st));
+    return run_unpack_jobs(post, st);
+  }
+  NetAct a = carve_act(*d, true, const_cast<double*>(act));
+  NetScratch sc = carve_scratch(*d, true, scratch);
+  LGN_CHECK_ARG((long long)a.total <= act_doubles && (long long)sc.total <= scratch_doubles,
+                "decoder_bwd: buffers hold %lld / %lld doubles, need %zu / %zu", act_doubles, scratch_doubles, a.total, sc.total);
+  if (int rc = check_mlp_contiguous(*d, true, off)) return rc;
+  LGN_TRY(zero_grads_and_block(grads, (size_t)n_params, sc.zero0(), sc.zero_doubles, st));
+  Deferred dq(sc.parts, sc.parts_size);
+  int cur = 0;
+  DQ_NEW(part, (size_t)B * ro.width);
+  LGN_TRY(dec_output_bwd(B, N, CL, a.n.v[d->n_levels], wo1, g_recon, sc.gv[cur], part, st));
+  ro.add(dq, part, B, grads, off);
+  LGN_TRY(decoder_bwd(*d, params, grads, off, lat_v, a.n, a.pdec, g_lat_v, sc, cur, dq, fin, st));
+  return finish_reductions(dq, fin, grads, n_params, /*counters=*/nullptr, d->flags, st);
+}
+
+// ---- training steps -------------------------------------------------------------------------------------------------------
+int lgn_step_param_slots(const lgn_net_desc* d, int decoder) {
+  if (check_desc(d)) return -1;
+  return Slots{d->n_levels, d->mlp_nlin}.count(decoder != 0);
+}
+
+long long lgn_encoder_end_lds_bytes(int N, int C0, int K, int CL, int Ts, int Tv, int pool) {
+  return pool_valid(pool) ? (long long)encoder_end_lds_bytes(N, C0, K < 1 ? 1 : K, CL, Ts, Tv, pool) : -1;
+}
+long long lgn_decoder_end_lds_bytes(int N, int C0, int Tin, int CL) { return (long long)decoder_end_lds_bytes(N, C0, Tin, CL); }
+long long lgn_junction_lds_bytes(int N, int CL, int Ts, int Tv, int pool, int C0) {
+  return pool_valid(pool) ? (long long)junction_lds_bytes(N, CL, Ts, Tv, pool, C0) : -1;
+}
+
+long long lgn_step_workspace_doubles(const lgn_net_desc* d) {
+  if (check_desc(d) || check_latent_match(*d)) return -1;
+  if (is_generic(*d, false) || is_generic(*d, true)) {
+    if (check_generic(*d, false) || check_generic(*d, true)) return -1;
+    return (long long)carve_gen_step(*d, nullptr).total;
+  }
+  return (long long)carve(*d, nullptr).total;
+}
 
 int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                          const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
@@ -1444,213 +1568,33 @@ int lgn_step_finalize_f64(double* params, double* grads, long long n_params, con
   return 0;
 }
 
-}  // extern "C"
-
-namespace lgn {
-namespace {
-// the tail of a call with an optimiser descriptor; refuses what no kernel implements before anything is enqueued
-int optim_tail(const lgn_optim_desc* o, double* params, double* grads, long long n_params, double* state_m, double* state_v,
-               long long* step_dev, int do_step, const double* loss_part, int n_loss, double* loss_out, StepTailArgs& t) {
-  LGN_CHECK_ARG(o, "optimiser descriptor: null pointer");
-  LGN_CHECK_ARG(o->kind == LGN_OPT_ADAM || o->kind == LGN_OPT_RMSPROP, "optimiser descriptor: kind %d is neither LGN_OPT_ADAM nor "
-                "LGN_OPT_RMSPROP", o->kind);
-  LGN_CHECK_ARG(!do_step || (state_m && state_v && step_dev), "optimiser state missing");
-  LGN_CHECK_ARG(o->l2_lambda >= 0.0 && o->eps >= 0.0, "optimiser descriptor: negative l2_lambda or eps");
-  LGN_CHECK_ARG(o->kind != LGN_OPT_RMSPROP || (o->alpha >= 0.0 && o->alpha <= 1.0 && o->momentum >= 0.0),
-                "optimiser descriptor: RMSprop takes 0 <= alpha <= 1 and momentum >= 0");
-  t = StepTailArgs{params, grads, (long)n_params, state_m, state_v, reinterpret_cast<long*>(step_dev), o->l1_lambda, o->lr, o->beta1,
-                   o->beta2, o->eps, do_step, loss_part, n_loss, loss_out, 0, nullptr};
-  t.opt_form = 1;
-  t.kind = o->kind;
-  t.l2 = o->l2_lambda;
-  t.alpha = o->alpha;
-  t.mu = o->momentum;
-  return 0;
-}
-}  // namespace
-}  // namespace lgn
-
-extern "C" {
-
 int lgn_step_train_opt_f64(const lgn_net_desc* d, double* params, double* grads, long long n_params, const int64_t* enc_off,
                            const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss,
                            const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
                            double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
-  lgn::AssignLoss al;
-  const lgn::AssignLoss* alp;
-  if (int rc = lgn::plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
+  AssignLoss al;
+  const AssignLoss* alp;
+  if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   LGN_CHECK_ARG(loss_out && n_loss > 0, "step_train_opt: null pointer");
-  lgn::StepTailArgs tail{};
-  if (int rc = lgn::optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
+  StepTailArgs tail{};
+  if (int rc = optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
     return rc;
   return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles,
-                           recon, loss_part, stream, &tail, alp);
+                      recon, loss_part, stream, &tail, alp);
 }
 
 int lgn_step_finalize_opt_f64(double* params, double* grads, long long n_params, const double* loss_part, int n_loss,
                               const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
                               double* loss_out, void* stream) {
   LGN_CHECK_ARG(params && grads && loss_part && loss_out && n_params > 0 && n_loss > 0, "step_finalize_opt: null pointer");
-  lgn::StepTailArgs tail{};
-  if (int rc = lgn::optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
+  StepTailArgs tail{};
+  if (int rc = optim_tail(opt, params, grads, n_params, state_m, state_v, step_dev, do_step, loss_part, n_loss, loss_out, tail))
     return rc;
-  return lgn::finalize_step_opt(tail, (hipStream_t)stream);
+  return finalize_step_opt(tail, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------------------
-// evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
-// get_real -> Chamfer [+ jet-feature term] forward only, no L1 (regularization = is_train, utils/train.py:308-314).  Nothing is
-// kept for a backward: two feature buffers per network used in turn, level kernels without the aggregate stores, the CGMLPs on
-// their no-save path, no CGMLP after the decoder's last level, a loss tail that writes no gradient.
-// ---------------------------------------------------------------------------------------------------------
-namespace lgn {
-namespace {
-
-struct EvalWork {
-  NetBuf enc, dec;                  // s / v of level l point to feature buffer l & 1 of the network; smix one buffer for all levels
-  double *lat_s, *lat_v, *pdec;
-  int* idx;
-  size_t total;
-};
-
-EvalWork carve_eval(const lgn_net_desc& d, double* base) {
-  EvalWork w{};
-  Bump b{base};
-  const int L = d.n_levels, Nd = dec_nodes(d);
-  const size_t BNe = (size_t)d.B * d.N, BNd = (size_t)d.B * Nd;
-  size_t smix = 0;
-  auto net = [&](NetBuf& n, const int* ch, size_t BN) {
-    int cmax = 0;
-    for (int l = 0; l <= L; ++l) cmax = cmax > ch[l] ? cmax : ch[l];
-    double *s[2], *v[2];
-    for (int q = 0; q < 2; ++q) {
-      s[q] = b.take(2 * BN * cmax);
-      v[q] = b.take(8 * BN * cmax);
-    }
-    for (int l = 0; l <= L; ++l) {
-      n.s[l] = s[l & 1];
-      n.v[l] = v[l & 1];
-    }
-    smix = std::max(smix, 2 * BN * cmax);
-  };
-  net(w.enc, d.enc_channels, BNe);
-  net(w.dec, d.dec_channels, BNd);
-  double* sm = b.take(smix);
-  for (int l = 0; l < L; ++l) w.enc.smix[l] = w.dec.smix[l] = sm;
-  const int PB = pool_blocks(d.latent_pool);
-  w.lat_s = b.take((size_t)2 * d.B * PB * d.tau_s);
-  w.lat_v = b.take((size_t)2 * d.B * PB * d.tau_v * 4);
-  w.pdec = b.take(8 * BNd);
-  w.idx = reinterpret_cast<int*>(b.take(((size_t)d.B * 2 * (d.tau_s + d.tau_v) * 2 + 1) / 2 + 8));
-  w.total = b.off;
-  return w;
-}
-
-// table-driven networks: the training forward (gen_encoder_fwd / gen_decoder_fwd) on activations of their own -- those kernels
-// store what their backward would read; no-keep forms of them are not part of the evaluation step yet
-struct GenEval {
-  GenAct ea, da;
-  double *lat_s, *lat_v;
-  size_t total;
-};
-GenEval carve_gen_eval(const lgn_net_desc& d, double* base) {
-  GenEval g{};
-  auto at = [&](size_t off) { return base ? base + off : nullptr; };
-  size_t off = 0;
-  g.ea = carve_gen_act(d, false, at(off)); off += (g.ea.total + 15) & ~size_t(15);
-  g.da = carve_gen_act(d, true, at(off)); off += (g.da.total + 15) & ~size_t(15);
-  const int P = pool_blocks(d.latent_pool);
-  g.lat_s = at(off); off += ((size_t)2 * d.B * P * d.tau_s + 15) & ~size_t(15);
-  g.lat_v = at(off); off += ((size_t)2 * d.B * P * d.tau_v * 4 + 15) & ~size_t(15);
-  g.total = off;
-  return g;
-}
-
-long long eval_workspace(const lgn_net_desc& d) {
-  if (is_generic(d, false) || is_generic(d, true)) {
-    if (check_generic(d, false) || check_generic(d, true)) return -1;
-    return (long long)carve_gen_eval(d, nullptr).total;
-  }
-  return (long long)carve_eval(d, nullptr).total;
-}
-
-int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
-              const double* target, const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
-              double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st,
-              const AssignLoss* al) {
-  // every refusal comes before the first launch
-  if (int rc = check_desc(dp)) return rc;
-  const lgn_net_desc& d = *dp;
-  LGN_CHECK_ARG(params && enc_off && dec_off && p4 && target && mask && workspace && recon_real && loss_part && loss_out,
-                "step_eval: null pointer");
-  LGN_CHECK_ARG(d.n_in_scalars <= 1 || in_scalars, "step_eval: %d input scalars per node, but in_scalars is NULL", d.n_in_scalars);
-  LGN_CHECK_ARG(!lat_s_out == !lat_v_out, "step_eval: give both latent outputs or neither");
-  if (int rc = check_latent_match(d)) return rc;
-  const long long need = eval_workspace(d);
-  if (need < 0) return -1;
-  LGN_CHECK_ARG(need <= workspace_doubles, "step_eval: workspace holds %lld doubles, this configuration needs %lld", workspace_doubles, need);
-  if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
-  if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
-  const Slots S{d.n_levels, d.mlp_nlin};
-  const int L = d.n_levels, B = d.B, Ne = d.N, Nd = dec_nodes(d), Ts = d.tau_s, Tv = d.tau_v, Tin = dec_tin(d);
-  const int* ce = d.enc_channels;
-  const int* cd = d.dec_channels;
-  const double* wl0 = params + enc_off[S.out0(false)];
-  const double* wl1 = params + enc_off[S.out0(false) + 1];
-  const double* wo1 = params + dec_off[S.out0(true) + 1];
-
-  if (is_generic(d, false) || is_generic(d, true)) {
-    LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step_eval: encoder and decoder must both be table-driven (or both fused)");
-    LGN_CHECK_ARG(!step_is_split(d), "step_eval: table-driven networks take the mass as the only input scalar and one node count for "
-                  "both networks (n_in_scalars=%d, N=%d, dec_N=%d)", d.n_in_scalars, d.N, d.dec_N);
-    GenEval g = carve_gen_eval(d, workspace);
-    double* ls = lat_s_out ? lat_s_out : g.lat_s;
-    double* lv = lat_v_out ? lat_v_out : g.lat_v;
-    LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, g.ea, ls, lv, st, nullptr, /*with_latent=*/false));
-    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, g.ea.sL, g.ea.vL, wl0, wl1, ls, lv, g.ea.idx, cd[0], params + dec_off[1],
-                         params + dec_off[2], params + dec_off[3], g.da.pdec, g.da.s0, g.da.v0, st));
-    LGN_TRY(gen_decoder_fwd(d, params, dec_off, lv, g.da, st, /*with_input=*/false));
-    if (al) LGN_TRY(dec_output_assign_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, *al, recon_real, loss_part, st));
-    else LGN_TRY(dec_output_eval(B, Ne, cd[L], g.da.vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
-    return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
-  }
-
-  EvalWork w = carve_eval(d, workspace);
-  double* ls = lat_s_out ? lat_s_out : w.lat_s;
-  double* lv = lat_v_out ? lat_v_out : w.lat_v;
-  lgn_net_desc dd = d;
-  dd.N = Nd;
-  const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
-  const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);
-  // the latent scalars (the encoder's last CGMLP and what the latent stage makes of its output) only when they are returned
-  const bool keep_s = lat_s_out != nullptr;
-  const double* sL = keep_s ? w.enc.s[L] : nullptr;
-  if (step_is_split(d)) {            // the four end stages as launches of their own (as in step_fwd_bwd)
-    LGN_TRY(enc_input_fwd(B, Ne, ce[0], in_K(d), p4, in_scalars, params + enc_off[0], params + enc_off[1], w.enc.s[0], w.enc.v[0], st));
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, nullptr, nullptr, /*eval=*/true, keep_s));
-    LGN_TRY(enc_latent_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, sL, w.enc.v[L], wl0, wl1, ls, lv, w.idx, st));
-    LGN_TRY(dec_input_fwd(B, Nd, cd[0], Tin, lv, params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0],
-                          w.dec.v[0], st));
-  } else {                           // input stage riding on the first level, latent + decoder input stage as one junction kernel
-    const InputStage in0{params + enc_off[0], params + enc_off[1]};
-    LGN_TRY(levels_fwd(d, false, ce, params, enc_off, w.enc, p4, mask, st, &in0, nullptr, /*eval=*/true, keep_s));
-    LGN_TRY(junction_fwd(B, Ne, ce[L], Ts, Tv, d.latent_pool, sL, w.enc.v[L], wl0, wl1, ls, lv, w.idx, cd[0],
-                         params + dec_off[1], params + dec_off[2], params + dec_off[3], w.pdec, w.dec.s[0], w.dec.v[0], st));
-  }
-  LGN_TRY(levels_fwd(dd, true, cd, params, dec_off, w.dec, w.pdec, nullptr, st, nullptr, rides ? &loss : nullptr, /*eval=*/true));
-  if (al) LGN_TRY(dec_output_assign_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, *al, recon_real, loss_part, st));
-  else if (!rides) LGN_TRY(dec_output_eval(B, Nd, cd[L], w.dec.v[L], wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
-  return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
-}
-
-}  // namespace
-}  // namespace lgn
-
-extern "C" {
-
+// ---- evaluation step ------------------------------------------------------------------------------------------------------
 long long lgn_eval_workspace_doubles(const lgn_net_desc* d) {
   if (check_desc(d)) return -1;
   return eval_workspace(*d);
