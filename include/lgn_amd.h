@@ -553,6 +553,22 @@ int lgn_roc_auc_f64(const double* scores, long long M, int ld, int K, const doub
  *      R = 1: the reference's score.  Zero-padded particles have no weight.
  *   Refused before any launch (negative return): null pointers, B < 1, n, m or N outside 1 .. LGN_EMD_NMAX, R not a finite positive
  *   number, a missing, short or misaligned workspace.
+ *   lgn_emd_grad_f64, lgn_emd_relative_grad_f64: the same distances (bit for bit) with their gradients, computed in the same launch by
+ *   the wavefront that solved the pair (LP sensitivity: the optimal flow weighs d theta / d position, the potentials are d EMD / d
+ *   weight).  These two only ADD functions: LGN_AMD_ABI_VERSION stays 19 (the rule above lgn_column_stats_f64).  With S0 = sum pT,
+ *   S1 = sum pT', u = dual0, v = dual1, row n and column m the fictitious particles:
+ *      dE/dy_i   =  sum_j f_ij (y_i - y'_j) / (R^2 theta_ij)       dE/dy'_j  = -sum_i (the same term)        (phi alike)
+ *      dE/dpT_i  =  u_i - [S1 > S0] u_n + [S0 > S1] v_m            dE/dpT'_j =  v_j - [S0 > S1] v_m + [S1 > S0] u_n
+ *   An arc with theta_ij = 0 contributes 0; at S0 == S1 neither fictitious term is added; a weightless particle gets a zero position
+ *   gradient and the weight gradient above: every output of a pair without a status bit is finite.  With a status bit every gradient
+ *   of that pair is NaN, like its value; the other pairs are unaffected.
+ *      g0 [B][n][3], g1 [B][m][3] (each nullable, not both): columns (d/dpT, d/dy, d/dphi), like the events
+ *      g_recons [B][N][4], g_target [B][N][4] (nullable): the gradient carried back to the Cartesian jets through w = pT / (jet pT +
+ *             1e-16), y = eta - jet eta, phi = wrap(phi - jet phi) (wrap has derivative 1) and the frame's (pT, eta, phi), with the
+ *             term every particle receives through the jet sum.  The E column is 0.  A particle with pT == 0 gets no direct term (the
+ *             0/0 of the root and of atan2 reads as 0), only the jet-sum term.
+ *   The workspace, the LDS and the refusals are those of lgn_emd_f64 / lgn_emd_relative_f64 (g_recons is required), and one more:
+ *   lgn_emd_grad_f64 with g0 and g1 both null.  Nothing is allocated, nothing waits on the host: capturable.
  *   lgn_emd_debug_max_augmentations: DEBUG ONLY, not part of the stable surface (it may change or go without an ABI bump): the
  *   largest number of augmentations of any pair since the last reset, on the current device only (one counter per device, fed by one
  *   integer atomic max per pair), read with a blocking copy: it waits on the host and is not capturable.  For tools/emd_bench.py. */
@@ -567,6 +583,11 @@ int lgn_emd_f64(const double* ev0, const double* ev1, int B, int n, int m, doubl
                 double* dual0 /*nullable*/, double* dual1 /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
 int lgn_emd_relative_f64(const double* recons, const double* target, int B, int N, double* emd, int* status, void* work,
                          long long work_bytes, void* stream);
+int lgn_emd_grad_f64(const double* ev0, const double* ev1, int B, int n, int m, double R, double* emd, double* g0 /*nullable*/,
+                     double* g1 /*nullable*/, double* flow /*nullable*/, double* dual0 /*nullable*/, double* dual1 /*nullable*/,
+                     int* status, void* work, long long work_bytes, void* stream);
+int lgn_emd_relative_grad_f64(const double* recons, const double* target, int B, int N, double* emd, double* g_recons,
+                              double* g_target /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
 int lgn_emd_debug_max_augmentations(int* out, int reset);
 
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for

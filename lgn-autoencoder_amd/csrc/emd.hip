@@ -1,7 +1,8 @@
 // lgn-autoencoder_amd/csrc/emd.hip -- the energy mover's distance of two events of (pT, y, phi) particles, exactly: the reference's 22nd
 // anomaly score "emd (relative coordinates)" (emd_loss() of utils/jet_analysis/anomaly_detection.py, which calls energyflow.emd.emd per
 // jet with its defaults R = 1, beta = 1, norm = False, Euclidean ground distance, no periodic phi) and the generic batched solver behind it.
-// Entry points: lgn_emd_f64, lgn_emd_relative_f64, lgn_emd_workspace_bytes, lgn_emd_lds_bytes, lgn_emd_debug_max_augmentations.
+// Entry points: lgn_emd_f64, lgn_emd_relative_f64, lgn_emd_grad_f64, lgn_emd_relative_grad_f64, lgn_emd_workspace_bytes,
+// lgn_emd_lds_bytes, lgn_emd_debug_max_augmentations.
 //
 //   theta_ij = sqrt((y_i - y'_j)^2 + (phi_i - phi'_j)^2) / R
 //   EMD      = min over f >= 0 of sum f_ij theta_ij + |sum pT - sum pT'|,  sum_j f_ij <= pT_i, sum_i f_ij <= pT'_j, sum f = min of the sums
@@ -10,6 +11,16 @@
 // the rows (LDS), the second's the columns (registers); row n and column m are the fictitious ones, of which at most one has weight.
 // The flow matrix lives in LDS when it fits EMD_LDS_BUDGET together with the row state, else in the caller's workspace, where a fixed
 // number of resident waves share the pairs.
+//
+// The GRAD variant of the kernel adds the gradient of the EMD as an epilogue of the same wavefront (LP sensitivity: the optimal flow
+// weighs d theta_ij / d position, the potentials are d EMD / d weight).  With S0 = sum pT, S1 = sum pT', u the row and v the column
+// potentials:
+//   dE/dy_i   =  sum_j f_ij (y_i - y'_j) / (R^2 theta_ij)      dE/dy'_j  = -sum_i (the same term)        (phi alike; 0 where theta_ij = 0)
+//   dE/dpT_i  =  u_i - [S1 > S0] u_n + [S0 > S1] v_m           dE/dpT'_j =  v_j - [S0 > S1] v_m + [S1 > S0] u_n
+// Column gradients accumulate per lane over the rows, a row's gradient is one wave reduction; rs.dist and rs.sup, free after the solve,
+// hold the rows' position gradients.  The REL form carries them on to the Cartesian jets through w = pT / (J_pT + 1e-16),
+// y = eta - J_eta, phi = wrap(phi - J_phi) (wrap has derivative 1) and the gradient of p4_polar, with the term every particle
+// receives through the jet sum J.  The forward-only instantiations hold none of it.
 //
 // Floating-point contraction is OFF for this file (pragma below and the Makefile): costs and frames round one operation at a time, as
 // the host restatement computes them, and the relative-polar frame is anomaly.hip's bit for bit.
@@ -65,12 +76,134 @@ inline long long emd_workspace(long long B, int N) {
   return (B < EMD_GLOBAL_WAVES ? B : EMD_GLOBAL_WAVES) * (long long)(N + 1) * (N + 1) * 8;
 }
 
-// REL: a0 = recons, a1 = target [B][n][4] Cartesian jets (n == m), staged into the relative-polar frame as anomaly_scores_kernel
-// stages its components 16..18.  Otherwise a0 [B][n][3], a1 [B][m][3] events of (pT, y, phi).
+struct EmdGradOut {            // the gradient outputs: the one extra kernel argument of the GRAD variant
+  double *g0, *g1;             // [B][n][W], [B][m][W] (each nullable): W = 3 columns (pT, y, phi), REL: W = 4 Cartesian (E, px, py, pz)
+};
+
+// The gradient of p4_polar (polar_dev.hpp): (g_pt, g_eta, g_phi) -> (g_px, g_py, g_pz).  At pt == 0 the 0/0 of the root and of atan2
+// reads as 0: such a particle gets no direct term.
+__device__ __forceinline__ void p4_polar_bwd(double px, double py, double pz, double g_pt, double g_eta, double g_phi, double& gx,
+                                             double& gy, double& gz) {
+  gx = gy = gz = 0.0;
+  const double pt = sqrt(px * px + py * py);
+  if (!(pt > 0.0)) return;
+  const double q = pt + POLAR_EPS, z = pz / q;
+  const double s = 1.0 / sqrt(1.0 + z * z);                    // d asinh(z) / dz
+  const double gt = g_pt - (g_eta * s) * (z / q);              // dz / dpt = -pz / q^2
+  const double X = px + POLAR_EPS, Y = py + POLAR_EPS, r2 = X * X + Y * Y;
+  gx = gt * (px / pt) - g_phi * (Y / r2);
+  gy = gt * (py / pt) + g_phi * (X / r2);
+  gz = (g_eta * s) / q;
+}
+
+// One side of the REL form: the gradients (gw, gy, gp)(k) with respect to the relative-polar frame of particle lane + 64 k of the
+// jet x [n][4], whose sum is J [4], become out [n][4].  Every particle, weightless ones included, receives the jet-sum term.
+template <int K, class GW, class GY, class GP>
+__device__ __forceinline__ void emd_rel_to_cartesian(const double* __restrict__ x, const double* J, int n, int lane, GW gw, GY gy, GP gp,
+                                                     double* __restrict__ out) {
+  double jpT, jeta, jphi;
+  p4_polar(J[1], J[2], J[3], jpT, jeta, jphi);
+  const double q = jpT + POLAR_EPS;
+  double sw = 0.0, sy = 0.0, sp = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = lane + 64 * k;
+    if (i < n) {
+      const double* p = x + 4 * i;
+      sw = sw + gw(k) * sqrt(p[1] * p[1] + p[2] * p[2]);
+      sy = sy + gy(k);
+      sp = sp + gp(k);
+    }
+  }
+  sw = wave_sum(sw), sy = wave_sum(sy), sp = wave_sum(sp);
+  double jx, jy, jz;
+  p4_polar_bwd(J[1], J[2], J[3], -(sw / (q * q)), -sy, -sp, jx, jy, jz);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = lane + 64 * k;
+    if (i < n) {
+      const double* p = x + 4 * i;
+      double dx, dy, dz;
+      p4_polar_bwd(p[1], p[2], p[3], gw(k) / q, gy(k), gp(k), dx, dy, dz);
+      out[4 * i] = 0.0, out[4 * i + 1] = dx + jx, out[4 * i + 2] = dy + jy, out[4 * i + 3] = dz + jz;
+    }
+  }
+}
+
+// The gradient epilogue of one solved pair (the header of this file): F the optimal flow, rs.u and v the finished potentials.  x0, x1:
+// this pair's Cartesian jets, J their sums [2][4] (REL).  g0, g1: this pair's outputs, each nullable.  Overwrites rs.dist and rs.sup.
 template <int K, class Flow, bool REL>
+__device__ __forceinline__ void emd_gradients(const EmdCost<K>& cf, const EmdRows& rs, const Flow& F, const double (&v)[K], int st,
+                                              double S0, double S1, const double* __restrict__ x0, const double* __restrict__ x1,
+                                              const double* J, double* __restrict__ g0, double* __restrict__ g1) {
+  const int n = cf.n, m = cf.m, lane = cf.lane;
+  constexpr int W = REL ? 4 : 3;
+  if (st) {
+    if (g0)
+      for (int t = lane; t < n * W; t += 64) g0[t] = NAN;
+    if (g1)
+      for (int t = lane; t < m * W; t += 64) g1[t] = NAN;
+    return;
+  }
+  double cy[K], cp[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) cy[k] = cp[k] = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double yi = cf.y[i], pi = cf.phi[i];
+    double ry = 0.0, rp = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = lane + 64 * k;
+      if (j < m) {
+        const double f = F.get(i, j);
+        const double dy = yi - cf.qy[k], dp = pi - cf.qphi[k];
+        const double d = sqrt(dy * dy + dp * dp);
+        if (f > 0.0 && d > 0.0) {                              // f / (R d) = f / (R^2 theta)
+          const double t = f / (cf.R * d);
+          const double ty = t * dy, tp = t * dp;
+          ry = ry + ty, rp = rp + tp;
+          cy[k] = cy[k] - ty, cp[k] = cp[k] - tp;
+        }
+      }
+    }
+    ry = wave_sum(ry), rp = wave_sum(rp);
+    if (lane == 0) rs.dist[i] = ry, rs.sup[i] = rp;
+  }
+  wave_sync();
+  // the fictitious particle's weight is the difference of the sums: its potential joins every weight gradient on both sides
+  const double un = rs.u[n], vm = lane_slot<K>(v, m);
+  const double c0 = S1 > S0 ? -un : (S0 > S1 ? vm : 0.0), c1 = S0 > S1 ? -vm : (S1 > S0 ? un : 0.0);
+  if (REL) {
+    // (n == m: a lane's rows are lane + 64 k, k < K, like its columns)
+    if (g0)
+      emd_rel_to_cartesian<K>(x0, J, n, lane, [&](int k) { return rs.u[lane + 64 * k] + c0; }, [&](int k) { return rs.dist[lane + 64 * k]; },
+                              [&](int k) { return rs.sup[lane + 64 * k]; }, g0);
+    if (g1)
+      emd_rel_to_cartesian<K>(x1, J + 4, m, lane, [&](int k) { return v[k] + c1; }, [&](int k) { return cy[k]; },
+                              [&](int k) { return cp[k]; }, g1);
+  } else {
+    if (g0)
+      for (int i = lane; i < n; i += 64) g0[3 * i] = rs.u[i] + c0, g0[3 * i + 1] = rs.dist[i], g0[3 * i + 2] = rs.sup[i];
+    if (g1) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const int j = lane + 64 * k;
+        if (j < m) g1[3 * j] = v[k] + c1, g1[3 * j + 1] = cy[k], g1[3 * j + 2] = cp[k];
+      }
+    }
+  }
+}
+
+// REL: a0 = recons, a1 = target [B][n][4] Cartesian jets (n == m), staged into the relative-polar frame as anomaly_scores_kernel
+// stages its components 16..18.  Otherwise a0 [B][n][3], a1 [B][m][3] events of (pT, y, phi).  The GRAD variant is the one
+// instantiated with a trailing EmdGradOut argument; the forward-only kernels have the argument list they always had.
+template <int K, class Flow, bool REL, class... Grad>
 __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, const double* __restrict__ a1, int B, int n, int m, double R,
                                                  double* __restrict__ emd, double* __restrict__ flow, double* __restrict__ dual0,
-                                                 double* __restrict__ dual1, int* __restrict__ status, double* __restrict__ work) {
+                                                 double* __restrict__ dual1, int* __restrict__ status, double* __restrict__ work,
+                                                 const Grad... go) {
+  constexpr bool GRAD = sizeof...(Grad) == 1;
+  static_assert(sizeof...(Grad) <= 1 && (std::is_same<Grad, EmdGradOut>::value && ...), "at most one EmdGradOut");
   extern __shared__ __align__(16) double lds[];
   const int rows = n + 1, cols = m + 1, lane = threadIdx.x & 63;
   constexpr bool LDS_FLOW = std::is_same<Flow, FlowLds>::value;
@@ -194,12 +327,19 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
         }
       }
       score = wave_sum(part);
-      if (dual1) finish_duals<K>(cf, rows, cols, rs, had, v);
+      if (GRAD || dual1) finish_duals<K>(cf, rows, cols, rs, had, v);
     }
     if (lane == 0) {
       emd[b] = score;
       status[b] = st;
       if (n_aug > 0) atomicMax(&g_emd_max_aug, n_aug);
+    }
+    if constexpr (GRAD) {
+      constexpr int W = REL ? 4 : 3;
+      const size_t jet0 = REL ? (size_t)b * n * 4 : 0;
+      const EmdGradOut g{go...};
+      emd_gradients<K, Flow, REL>(cf, rs, F, v, st, S0, S1, a0 + jet0, a1 + jet0, jet, g.g0 ? g.g0 + (size_t)b * n * W : nullptr,
+                                  g.g1 ? g.g1 + (size_t)b * m * W : nullptr);
     }
     if (flow) {
       double* fo = flow + (size_t)b * rows * cols;
@@ -221,17 +361,17 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
   }
 }
 
-template <int K, class Flow, bool REL>
+template <int K, class Flow, bool REL, class... Grad>
 int launch_emd_kf(const double* a0, const double* a1, int B, int n, int m, double R, double* emd, double* flow, double* dual0, double* dual1,
-                  int* status, double* work, int grid, size_t smem, hipStream_t st) {
-  emd_kernel<K, Flow, REL><<<grid, 64, smem, st>>>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work);
+                  int* status, double* work, int grid, size_t smem, hipStream_t st, Grad... go) {
+  emd_kernel<K, Flow, REL, Grad...><<<grid, 64, smem, st>>>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, go...);
   LGN_CHECK_LAUNCH();
   return 0;
 }
 
-template <bool REL>
+template <bool REL, class... Grad>
 int launch_emd(const double* a0, const double* a1, int B, int n, int m, double R, double* emd, double* flow, double* dual0, double* dual1,
-               int* status, double* work, hipStream_t st) {
+               int* status, double* work, hipStream_t st, Grad... go) {
   const int N = n > m ? n : m;
   const bool in_lds = emd_flow_in_lds(N);
   const size_t smem = (size_t)emd_lds_total(n, m, in_lds);
@@ -239,8 +379,8 @@ int launch_emd(const double* a0, const double* a1, int B, int n, int m, double R
   const int K = (m + 1 + 63) / 64;
 #define LGN_EMD_CASE(KK)                                                                                                               \
   if (K == KK)                                                                                                                         \
-    return in_lds ? launch_emd_kf<KK, FlowLds, REL>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, grid, smem, st)          \
-                  : launch_emd_kf<KK, FlowGlobal, REL>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, grid, smem, st);
+    return in_lds ? launch_emd_kf<KK, FlowLds, REL>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, grid, smem, st, go...)     \
+                  : launch_emd_kf<KK, FlowGlobal, REL>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, grid, smem, st, go...);
   LGN_EMD_CASE(1)
   LGN_EMD_CASE(2)
   LGN_EMD_CASE(3)
@@ -299,6 +439,28 @@ int lgn_emd_relative_f64(const double* recons, const double* target, int B, int 
   if (check_work("emd_relative", B, N, work, work_bytes) != 0) return -1;
   return launch_emd<true>(recons, target, B, N, N, 1.0, emd, nullptr, nullptr, nullptr, status, static_cast<double*>(work),
                           (hipStream_t)stream);
+}
+
+int lgn_emd_grad_f64(const double* ev0, const double* ev1, int B, int n, int m, double R, double* emd, double* g0, double* g1, double* flow,
+                     double* dual0, double* dual1, int* status, void* work, long long work_bytes, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "emd_grad: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(n >= 1 && n <= LGN_EMD_NMAX && m >= 1 && m <= LGN_EMD_NMAX, "emd_grad: n = %d, m = %d outside 1 .. %d", n, m, LGN_EMD_NMAX);
+  LGN_CHECK_ARG(g0 || g1, "emd_grad: no gradient output (g0 and g1 are both null; lgn_emd_f64 is the call without gradients)");
+  LGN_CHECK_ARG(ev0 && ev1 && emd && status, "emd_grad: null pointer (ev0, ev1, emd, status)");
+  LGN_CHECK_ARG(R > 0.0 && R < INFINITY, "emd_grad: R = %g (need a finite R > 0)", R);
+  if (check_work("emd_grad", B, n > m ? n : m, work, work_bytes) != 0) return -1;
+  return launch_emd<false>(ev0, ev1, B, n, m, R, emd, flow, dual0, dual1, status, static_cast<double*>(work), (hipStream_t)stream,
+                           EmdGradOut{g0, g1});
+}
+
+int lgn_emd_relative_grad_f64(const double* recons, const double* target, int B, int N, double* emd, double* g_recons, double* g_target,
+                              int* status, void* work, long long work_bytes, void* stream) {
+  LGN_CHECK_ARG(B >= 1, "emd_relative_grad: B = %d (need B >= 1)", B);
+  LGN_CHECK_ARG(N >= 1 && N <= LGN_EMD_NMAX, "emd_relative_grad: N = %d outside 1 .. %d", N, LGN_EMD_NMAX);
+  LGN_CHECK_ARG(recons && target && emd && g_recons && status, "emd_relative_grad: null pointer (recons, target, emd, g_recons, status)");
+  if (check_work("emd_relative_grad", B, N, work, work_bytes) != 0) return -1;
+  return launch_emd<true>(recons, target, B, N, N, 1.0, emd, nullptr, nullptr, nullptr, status, static_cast<double*>(work),
+                          (hipStream_t)stream, EmdGradOut{g_recons, g_target});
 }
 
 int lgn_emd_debug_max_augmentations(int* out, int reset) {

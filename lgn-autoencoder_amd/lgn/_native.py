@@ -214,6 +214,10 @@ _SIGNATURES.update({
     "lgn_emd_f64": [_vp, _vp, _i, _i, _i, _d] + [_vp] * 6 + [_ll, _vp],
     # (recons, target, B, N, emd, status, work, work_bytes, stream)
     "lgn_emd_relative_f64": [_vp, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp],
+    # (ev0, ev1, B, n, m, R, emd, g0, g1, flow, dual0, dual1, status, work, work_bytes, stream)
+    "lgn_emd_grad_f64": [_vp, _vp, _i, _i, _i, _d] + [_vp] * 8 + [_ll, _vp],
+    # (recons, target, B, N, emd, g_recons, g_target, status, work, work_bytes, stream)
+    "lgn_emd_relative_grad_f64": [_vp, _vp, _i, _i] + [_vp] * 5 + [_ll, _vp],
     "lgn_emd_debug_max_augmentations": [_ip, _i],
     # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
     "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],

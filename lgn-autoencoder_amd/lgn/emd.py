@@ -11,8 +11,14 @@ energyflow's defaults otherwise: beta = 1, norm = False, Euclidean ground distan
 this was written: the definition above, from its documentation, is the specification (include/lgn_amd.h; tests/_emd_ref.py restates it
 as an LP).  What energyflow returns for two weightless events is not known; here that is a status bit and NaN.
 
-There is no CPU fallback.  The EMD *training* losses (--loss-choice emd / hybrid: jetnet's differentiable QP) are a different
-algorithm and stay refused.
+The distance is differentiable here as well: by LP sensitivity the gradient with respect to positions and weights is a closed form
+in the optimal flow and the potentials, which the solving wavefront evaluates as an epilogue of the same launch (``emd_grad``,
+``emd_differentiable``, ``EMDFn`` / ``EMDRelativeFn``; the formulas stand in include/lgn_amd.h).  ``lgn.losses.EMDLoss`` and
+``HybridLoss`` are training losses on top of it for the module-API steps.  What is offered is the exact LP on the relative-polar frame
+of the anomaly score, so that the training loss and the score are one quantity.  What is NOT offered: jetnet's regularised
+differentiable QP, which the reference's ``EMDLoss`` wraps -- and that wrapper unbinds its (eta, phi, pt) columns as (eta, pt, phi),
+handing jetnet an angle ratio as the weight, which is not reproduced; periodic phi, beta != 1 and normalised weights; the names
+``--loss-choice emd`` / ``hybrid`` and the EMD inside the whole-step native calls, which stay refused.  There is no CPU fallback.
 """
 from typing import Optional
 
@@ -89,6 +95,132 @@ def emd(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_flow: bool 
     if return_status:
         res.append(status[0] if single else status)
     return res[0] if len(res) == 1 else tuple(res)
+
+
+def emd_grad(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_status: bool = False, return_flow: bool = False,
+             return_duals: bool = False, need_g0: bool = True, need_g1: bool = True):
+    """emd() with its gradients, in one launch: returns (emd (B,), g0 (B, n, 3), g1 (B, m, 3)[, flow][, dual0, dual1][, status]) --
+    g0 = d emd / d ev0 and g1 = d emd / d ev1 in the events' column order (pT, y, phi); a gradient that is not needed (need_g0 /
+    need_g1 False, not both) is None.  The value is emd()'s bit for bit.  A pair with a status bit has NaN gradients; ValueError and
+    return_status as in emd().  One pair (n, 3) against (m, 3) is accepted like there."""
+    single = ev0.dim() == 2
+    a, b = (ev0.unsqueeze(0), ev1.unsqueeze(0)) if single else (ev0, ev1)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"emd_grad takes events (B, n, 3) and (B, m, 3) of (pT, y, phi); got {tuple(ev0.shape)} and {tuple(ev1.shape)}")
+    B, n, m = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
+    if not (1 <= n <= NMAX and 1 <= m <= NMAX):
+        raise ValueError(f"emd supports 1 <= n, m <= {NMAX} particles per event; got n = {n}, m = {m}")
+    if not (R > 0 and R < float("inf")):
+        raise ValueError(f"emd needs a finite R > 0; got {R}")
+    if not (need_g0 or need_g1):
+        raise ValueError("emd_grad: at least one of the two gradients must be asked for (emd() is the call without gradients)")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError(f"lgn (MI355X build): emd_grad runs only in the HIP kernels of liblgn_amd.so on a GPU device; got tensors "
+                           f"on '{a.device}' and '{b.device}'. There is no CPU fallback.")
+    a, b = N.f64(a.to(torch.float64)), N.f64(b.to(torch.float64))
+    dev = a.device
+    out = torch.empty(B, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    g0 = torch.empty(B, n, 3, device=dev, dtype=torch.float64) if need_g0 else None
+    g1 = torch.empty(B, m, 3, device=dev, dtype=torch.float64) if need_g1 else None
+    flow = torch.empty(B, n + 1, m + 1, device=dev, dtype=torch.float64) if return_flow else None
+    d0 = torch.empty(B, n + 1, device=dev, dtype=torch.float64) if return_duals else None
+    d1 = torch.empty(B, m + 1, device=dev, dtype=torch.float64) if return_duals else None
+    if B > 0:
+        work = _workspace(B, max(n, m), dev)
+        rc = N.lib().lgn_emd_grad_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(g0), N.ptr(g1), N.ptr(flow), N.ptr(d0),
+                                      N.ptr(d1), N.ptr(status), N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_grad_f64")
+    if not return_status:
+        st = status.cpu().numpy()
+        bad = st.nonzero()[0]
+        if len(bad):
+            raise ValueError(f"emd: {status_message(int(st[bad[0]]))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
+    res = [out, g0, g1] + ([flow] if return_flow else []) + ([d0, d1] if return_duals else [])
+    if single:
+        res = [None if x is None else x[0] for x in res]
+    if return_status:
+        res.append(status[0] if single else status)
+    return tuple(res)
+
+
+def emd_relative_grad(recons: torch.Tensor, target: torch.Tensor, need_g_target: bool = False):
+    """emd_relative_tensor() with its gradient with respect to the Cartesian jets, in one launch and with no host sync: returns
+    (emd (B,), g_recons (B, N, 4), g_target (B, N, 4) or None, status (B,) int32).  The E column of the gradients is 0; a jet with a
+    status bit has NaN gradients."""
+    if recons.dim() != 3 or recons.shape[-1] != 4 or recons.shape != target.shape:
+        raise ValueError(f"emd_relative_grad takes two (B, N, 4) Cartesian tensors; got {tuple(recons.shape)} and {tuple(target.shape)}")
+    B, n = int(recons.shape[0]), int(recons.shape[1])
+    if not 1 <= n <= NMAX:
+        raise ValueError(f"the EMD supports 1 <= N <= {NMAX} particles per jet; got N = {n}")
+    if not (recons.is_cuda and target.is_cuda):
+        raise RuntimeError(f"lgn (MI355X build): the EMD runs only in the HIP kernels of liblgn_amd.so on a GPU device; got tensors on "
+                           f"'{recons.device}' and '{target.device}'. There is no CPU fallback.")
+    r, t = N.f64(recons.to(torch.float64)), N.f64(target.to(torch.float64))
+    dev = r.device
+    out = torch.empty(B, device=dev, dtype=torch.float64)
+    status = torch.empty(B, device=dev, dtype=torch.int32)
+    g_r = torch.empty(B, n, 4, device=dev, dtype=torch.float64)
+    g_t = torch.empty(B, n, 4, device=dev, dtype=torch.float64) if need_g_target else None
+    if B > 0:
+        work = _workspace(B, n, dev)
+        rc = N.lib().lgn_emd_relative_grad_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(g_r), N.ptr(g_t), N.ptr(status), N.ptr(work),
+                                               work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_relative_grad_f64")
+    return out, g_r, g_t, status
+
+
+def _per_pair(g, grad):
+    return grad * g.reshape(-1, 1, 1)
+
+
+class EMDFn(torch.autograd.Function):
+    """(ev0 (B,n,3), ev1 (B,m,3), R) -> (B,) distances.  One launch in forward, which also returns the gradients for an upstream
+    gradient of one; backward scales them per pair.  A pair with a status bit is NaN, value and gradients."""
+
+    @staticmethod
+    def forward(ctx, ev0, ev1, R):
+        need1 = bool(ctx.needs_input_grad[1])
+        need0 = bool(ctx.needs_input_grad[0]) or not need1            # (the launch needs one gradient output at least)
+        out, g0, g1, _ = emd_grad(ev0.detach(), ev1.detach(), R, return_status=True, need_g0=need0, need_g1=need1)
+        ctx.has = (g0 is not None, g1 is not None)
+        ctx.save_for_backward(*[g for g in (g0, g1) if g is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = list(ctx.saved_tensors)
+        g0 = saved.pop(0) if ctx.has[0] else None
+        g1 = saved.pop(0) if ctx.has[1] else None
+        return (_per_pair(g, g0) if ctx.needs_input_grad[0] else None), (_per_pair(g, g1) if ctx.needs_input_grad[1] else None), None
+
+
+class EMDRelativeFn(torch.autograd.Function):
+    """(recons (B,N,4), target (B,N,4), owner) -> (B,) distances on the relative-polar frames, emd_relative_tensor()'s bit for bit;
+    the gradient of the target is computed only if the target needs one.  ``owner.status`` receives the (B,) int32 flags."""
+
+    @staticmethod
+    def forward(ctx, recons, target, owner):
+        out, g_r, g_t, status = emd_relative_grad(recons.detach(), target.detach(), need_g_target=ctx.needs_input_grad[1])
+        if owner is not None:
+            owner.status = status
+        ctx.has_target = g_t is not None
+        ctx.save_for_backward(*([g_r, g_t] if g_t is not None else [g_r]))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        return ((_per_pair(g, saved[0]) if ctx.needs_input_grad[0] else None),
+                (_per_pair(g, saved[1]) if ctx.has_target and ctx.needs_input_grad[1] else None), None)
+
+
+def emd_differentiable(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0) -> torch.Tensor:
+    """emd() of (B, n, 3) against (B, m, 3) device tensors as a (B,) tensor with autograd (gradients with respect to pT, y and phi of
+    both events).  No host sync: a pair with a status bit is NaN, value and gradients (emd_grad(return_status=True) shows the flags)."""
+    if ev0.dim() != 3 or ev1.dim() != 3:
+        raise ValueError(f"emd_differentiable takes events (B, n, 3) and (B, m, 3); got {tuple(ev0.shape)} and {tuple(ev1.shape)}")
+    return EMDFn.apply(ev0, ev1, float(R))
 
 
 def emd_relative_tensor(recons: torch.Tensor, target: torch.Tensor, return_status: bool = False):

@@ -9,7 +9,12 @@ decoder's last kernel.
 ``HungarianMSELoss`` is the drop-in of ``utils.losses.HungarianMSELoss`` (utils/losses/hungarian_mse/hungarian_mse.py:8-84): the four
 coordinate frames, the assignment (scipy's ``linear_sum_assignment``, ties included, solved by one wavefront per jet), the MSE of the
 paired rows and its gradient in one HIP kernel (csrc/assign_loss.hip) -- no copy of the cost matrices to the host, no Python loop
-over the jets, capturable into a graph."""
+over the jets, capturable into a graph.
+
+``EMDLoss`` and ``HybridLoss`` have the interface of ``utils.losses.EMDLoss`` and of get_loss()'s hybrid branch, on the exact
+energy mover's distance of lgn.emd (csrc/emd.hip: the transportation LP and its closed-form gradient in one launch) -- not jetnet's
+regularised QP.  No --loss-choice string selects them (``loss_kind`` keeps refusing 'emd' and 'hybrid'): pass an instance as
+``loss_choice`` to the module-API steps of lgn.step."""
 from typing import Optional
 
 import torch
@@ -126,3 +131,57 @@ class HungarianMSELoss(nn.Module):
         if recons.dim() != 3 or recons.shape != target.shape:
             raise ValueError(f"recons {tuple(recons.shape)} and target {tuple(target.shape)} must both be (batch, particles, 4)")
         return HungarianMSEFn.apply(recons, target, bool(abs_coord), bool(polar_coord), self)
+
+
+class EMDLoss(nn.Module):
+    """The energy mover's distance as a training loss, with the interface of the reference's ``utils.losses.EMDLoss``
+    (utils/losses/emd_loss.py): ``EMDLoss(num_particles=..., device=...)`` as get_loss() writes it -- jetnet's constructor arguments
+    are taken and ignored -- and ``forward(p4_recons, p4_target)`` -> the sum over the batch.
+
+    It is NOT that class's algorithm.  The reference wraps jetnet's regularised differentiable QP; this is the exact transportation LP
+    (csrc/emd.hip) on the relative-polar frame of the 22nd anomaly score: the value is ``lgn.emd.emd_relative_tensor(recons,
+    target).sum()`` bit for bit, so that the training loss and the score are one quantity, and the gradient is the closed form in the
+    optimal flow and the potentials (include/lgn_amd.h), from the same launch.  The reference's wrapper also unbinds its (eta, phi, pt)
+    columns as (eta, pt, phi), which hands jetnet an angle ratio as the weight; that mix-up is not reproduced.  After a forward
+    ``status`` holds the (B,) int32 flags (LGN_EMD_*; a flagged jet makes the loss NaN)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+        self.status = None
+
+    def forward(self, p4_recons: torch.Tensor, p4_target: torch.Tensor) -> torch.Tensor:
+        from .emd import EMDRelativeFn
+        if p4_recons.shape[-1] != 4:
+            raise ValueError(f"p4_recons must be a 4-vector. Got: {p4_recons.shape=}")
+        if p4_target.shape[-1] != 4:
+            raise ValueError(f"p4_target must be a 4-vector. Got: {p4_target.shape=}")
+        if p4_recons.device.type != "cuda" or p4_target.device.type != "cuda":
+            raise RuntimeError("lgn (MI355X build): EMDLoss runs only in the HIP kernels of liblgn_amd.so on a GPU device; "
+                               f"got tensors on '{p4_recons.device}' and '{p4_target.device}'. There is no CPU fallback.")
+        if p4_recons.dim() == 2 and p4_target.dim() == 2:       # one unbatched jet
+            p4_recons, p4_target = p4_recons.unsqueeze(0), p4_target.unsqueeze(0)
+        if p4_recons.dim() != 3 or p4_recons.shape != p4_target.shape:
+            raise ValueError(f"p4_recons {tuple(p4_recons.shape)} and p4_target {tuple(p4_target.shape)} must both be "
+                             "(batch, particles, 4)")
+        return EMDRelativeFn.apply(p4_recons, p4_target, self).sum()        # sum over batch
+
+
+class HybridLoss(nn.Module):
+    """The reference's hybrid loss (get_loss(), utils/train.py:446-457) as one module:
+    ``chamfer_loss_weight * ChamferLoss(x, t, jet_features) + EMDLoss(x, t)``, both sums over the jets, with this package's
+    ``ChamferLoss`` and ``EMDLoss`` (the exact LP, not jetnet's QP).  ``status``: the EMD's flags of the last forward."""
+
+    def __init__(self, chamfer_loss_weight: float = 1.0, device: Optional[torch.device] = None):
+        super().__init__()
+        self.chamfer_loss_weight = chamfer_loss_weight
+        self.chamfer, self.emd = ChamferLoss(device=device), EMDLoss()
+
+    @property
+    def status(self):
+        return self.emd.status
+
+    def forward(self, p4_recons: torch.Tensor, p4_target: torch.Tensor, jet_features: bool = False) -> torch.Tensor:
+        if p4_recons.device.type != "cuda" or p4_target.device.type != "cuda":
+            raise RuntimeError("lgn (MI355X build): HybridLoss runs only in the HIP kernels of liblgn_amd.so on a GPU device; "
+                               f"got tensors on '{p4_recons.device}' and '{p4_target.device}'. There is no CPU fallback.")
+        return self.chamfer_loss_weight * self.chamfer(p4_recons, p4_target, jet_features=jet_features) + self.emd(p4_recons, p4_target)

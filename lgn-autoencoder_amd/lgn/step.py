@@ -123,19 +123,23 @@ def torch_optimizer(params, optimizer_choice: str = "adam", lr: float = 5e-4, ep
 class TrainStep:
     """One data-parallel training step of the autoencoder (see module docstring).  ``optimizer_choice`` / ``l2_lambda`` /
     ``rms_alpha`` / ``momentum``: --optimizer and --l2-lambda of the reference, as NativeTrainStep takes them; ``normalize`` /
-    ``normalize_method``: --normalize, the batch is normalised per jet before the encoder sees it (one native launch)."""
+    ``normalize_method``: --normalize, the batch is normalised per jet before the encoder sees it (one native launch).
+    ``loss_choice``: 'chamfer' (the default: the torch restatement ``chamfer_loss``), the other names of get_loss(), or a loss module
+    such as lgn.losses.EMDLoss() / HybridLoss(), used as it is."""
 
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
                  process_group: Optional["dist.ProcessGroup"] = None, optimizer: bool = True, optimizer_choice: str = "adam",
                  l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None, normalize: bool = False,
-                 normalize_method: str = "overall_max"):
+                 normalize_method: str = "overall_max", loss_choice="chamfer"):
         self.encoder, self.decoder = encoder, decoder
+        self.loss_fn = _module_loss(loss_choice, True, False, None, chamfer_loss)     # (no loss here is built for a device)
         self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
         self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.flat = FlatParams(encoder, decoder)
         self.world = _world_size(process_group)
         self.group = process_group
+        self._loss_weight = _loss_weight(loss_choice, self.world)
         # two Adam optimisers with identical hyper-parameters act on disjoint parameters (initialize.py:156-158);
         # one Adam over the flat buffer performs the same element-wise update.
         self.flat_param = torch.nn.Parameter(self.flat.flat)
@@ -152,8 +156,8 @@ class TrainStep:
         recon = self.decoder(latent)
         real = get_real(recon, self.get_real_method)
         target = batch["p4"].to(device=real.device, dtype=real.dtype)
-        loss = chamfer_loss(real, target)
-        loss.backward()
+        loss = self.loss_fn(real, target)
+        (loss if self._loss_weight == 1.0 else loss * self._loss_weight).backward()
         if self.world > 1:
             dist.all_reduce(self.flat.grad, op=dist.ReduceOp.SUM, group=self.group)
         total = loss.detach()
@@ -242,9 +246,14 @@ class ReferenceLoopStep:
 
 def _module_loss(loss_choice, abs_coord, polar_coord, device, chamfer=None, jet_features=False):
     """The loss of the module-API steps as a function (x, target) -> scalar, chosen as get_loss() chooses it (utils/train.py:416-480):
-    lgn.losses.ChamferLoss (or `chamfer`, a restatement), nn.MSELoss, lgn.losses.HungarianMSELoss."""
+    lgn.losses.ChamferLoss (or `chamfer`, a restatement), nn.MSELoss, lgn.losses.HungarianMSELoss.  An nn.Module instance as
+    ``loss_choice`` -- lgn.losses.EMDLoss() or HybridLoss(), which no --loss-choice string selects -- is used as it is."""
     from . import _native as N
     from .losses import ChamferLoss, HungarianMSELoss, loss_kind
+    if isinstance(loss_choice, torch.nn.Module):
+        if jet_features:
+            raise ValueError("chamfer_jet_features is an option of the Chamfer loss chosen by name; a loss module takes its own options")
+        return loss_choice
     kind = loss_kind(loss_choice)
     if kind == N.LOSS_CHAMFER:
         if chamfer is not None:
@@ -264,9 +273,12 @@ def _module_loss(loss_choice, abs_coord, polar_coord, device, chamfer=None, jet_
 def _loss_weight(loss_choice, world: int) -> float:
     """The weight of a rank's loss term in the module-API steps.  Chamfer is a SUM over the jets: the ranks' gradients add up to the
     step of one process on the whole batch.  mse / hungarian are MEANS over the batch: a rank's term is weighted 1 / world before the
-    SUM all-reduce (ranks hold equal shares)."""
+    SUM all-reduce (ranks hold equal shares).  A loss given as a module: lgn.losses.EMDLoss and HybridLoss are sums over the jets
+    like Chamfer, and any other module is taken as one."""
     from . import _native as N
     from .losses import loss_kind
+    if isinstance(loss_choice, torch.nn.Module):
+        return 1.0
     return 1.0 if loss_kind(loss_choice) == N.LOSS_CHAMFER else 1.0 / world
 
 
@@ -410,6 +422,9 @@ def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, decode
     (NotImplementedError) a decoder whose loss stage does not fit a CU's LDS: that configuration runs through the module API."""
     from . import _native as N
     from .losses import loss_kind, loss_columns
+    if isinstance(loss_choice, torch.nn.Module):
+        raise NotImplementedError(f"a loss module ({type(loss_choice).__name__}) is not part of the whole-step native calls; it runs "
+                                  "through the module API (TrainStep, ReferenceLoopStep, CapturedModuleStep, ModuleEvalStep)")
     kind = loss_kind(loss_choice)
     if kind == N.LOSS_CHAMFER:
         return kind, None

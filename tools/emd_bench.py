@@ -3,7 +3,11 @@
 jets, 20 real particles: the flow in LDS) and N = 150 (8,192 jets, 100 real: the flow in a workspace), timed with stream events; also
 the largest number of augmentations any jet needed (the solver's cap is 16 per node).  Each case runs in a child process of its own
 under `timeout -k 10`; the first failure ends the run.  One JSON line per case, printed and appended to profiles/emd_bench.jsonl.
-    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150]"""
+The gradient cases (not run by default): n30_grad / n150_grad -- 4,096 jets, the forward-only launch (emd_relative_tensor) against
+the GRAD launch (emd_relative_grad, reconstruction's gradient alone and with the target's), interleaved over three rounds, the
+fastest round of each; step_cfg2 -- one graph-replayed CapturedModuleStep at cfg2 (512 x 30, maxdim 2) with lgn.losses.EMDLoss()
+against the same step with the Chamfer loss.
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,step_cfg2]]"""
 import argparse
 import json
 import os
@@ -14,6 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "lgn-autoencoder_amd"))
 
 CASES = {"n30": (65536, 30, 20), "n150": (8192, 150, 100)}
+GRAD_CASES = {"n30_grad": (4096, 30, 20), "n150_grad": (4096, 150, 100)}
+ROUNDS = 3
 OUT = os.path.join(ROOT, "profiles", "emd_bench.jsonl")
 
 
@@ -48,6 +54,83 @@ def one(name, steps, warmup):
         f.write(line + "\n")
 
 
+def _emit(res):
+    line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()})
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "a") as f:
+        f.write(line + "\n")
+
+
+def _ms(fn, steps, warmup):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def one_grad(name, steps, warmup):
+    import torch
+    from lgn import emd as M
+    B, n, real = GRAD_CASES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    t = torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    t[..., 0] = t[..., 1:].norm(dim=-1) + 0.1
+    t[:, real:] = 0.0
+    r = t + 0.2 * torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    variants = {"forward": lambda: M.emd_relative_tensor(r, t, return_status=True), "grad": lambda: M.emd_relative_grad(r, t),
+                "grad_both": lambda: M.emd_relative_grad(r, t, need_g_target=True)}
+    ms = {k: [] for k in variants}
+    for _ in range(ROUNDS):                                # interleaved: drift of the clocks hits every variant alike
+        for k, fn in variants.items():
+            ms[k].append(_ms(fn, steps, warmup))
+    st = M.emd_relative_grad(r, t)[3]
+    res = {"case": name, "kind": "emd gradient epilogue", "B": B, "N": n, "real_particles": real, "flow_in_lds": M.flow_in_lds(n),
+           "steps": steps, "rounds": ROUNDS, "status_nonzero": int((st != 0).sum().item())}
+    for k in variants:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
+    res["grad_over_forward"] = res["grad_ms"] / res["forward_ms"]
+    res["grad_both_over_forward"] = res["grad_both_ms"] / res["forward_ms"]
+    _emit(res)
+
+
+def one_step(steps, warmup):
+    import torch
+    import bench
+    import __graft_entry__ as G
+    from lgn.losses import EMDLoss
+    from lgn.step import CapturedModuleStep
+    B, N, ce, cd = 512, 30, (3, 3, 4, 4), (4, 4, 3, 3)
+    dev = torch.device("cuda:0")
+    p4, labels = bench.synthetic_jets(B, N, seed=5)
+    batch = {"p4": p4.to(dev), "labels": labels.to(dev)}
+    emd_loss = EMDLoss()
+    runs = {}
+    for k, loss in (("chamfer", "chamfer"), ("emd", emd_loss)):
+        enc, dec = G._models(N, ce, cd, dev, seed=0, maxdim=2)
+        runs[k] = CapturedModuleStep(enc, dec, B, get_real_method="real", loss_choice=loss)
+        runs[k].load_batch(batch)
+    ms = {k: [] for k in runs}
+    for _ in range(ROUNDS):
+        for k, s in runs.items():
+            ms[k].append(_ms(s.step, steps, warmup))
+    res = {"case": "step_cfg2", "kind": "CapturedModuleStep, graph replay", "B": B, "N": N, "steps": steps, "rounds": ROUNDS,
+           "status_nonzero": int((emd_loss.status != 0).sum().item()), "emd_loss": float(runs["emd"].loss_out[0].item())}
+    for k in runs:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
+    _emit(res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -56,6 +139,10 @@ def main():
     ap.add_argument("--timeout", type=int, default=180, help="seconds per case")
     ap.add_argument("--one", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.one == "step_cfg2":
+        return one_step(args.steps, args.warmup)
+    if args.one in GRAD_CASES:
+        return one_grad(args.one, args.steps, args.warmup)
     if args.one:
         return one(args.one, args.steps, args.warmup)
     for name in args.cases.split(","):
