@@ -199,6 +199,16 @@ __device__ __forceinline__ constexpr T rsqrt2() {
   return T(0.70710678118654752440084436210484903928);
 }
 
+// 2 E^2 - sum p^2 of a real Cartesian 4-vector as the reference's CPU forms it (zonal_functions.py:201-218): four rounded squares,
+// the left-to-right sum, NO fused multiply-add.  For a light particle E^2 and |p|^2 cancel to 1e-7 of their size, so one product
+// fused into the sum moves the mass by 1e-9 of itself, and with it the gradient of input_func_node's scalar weight, which is linear
+// in the mass.
+__device__ __forceinline__ double minkowski_sq_unfused(double pe, double px, double py, double pz) {
+#pragma clang fp contract(off)
+  const double q0 = pe * pe, q1 = px * px, q2 = py * py, q3 = pz * pz;
+  return 2.0 * q0 - (((q0 + q1) + q2) + q3);
+}
+
 // signed pseudo-norm of a real Cartesian 4-vector difference, exactly as the reference forms it:
 // norm_sq = 2 E^2 - sum(p^2) + 1e-16 ; norm = norm_sq / sqrt(|norm_sq|)   (zonal_functions.py:142-144,201-218)
 template <typename T>

@@ -854,9 +854,8 @@ __global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(C <= 4
       }
       if constexpr (!DEC) {
         if (a.part_in0 && wr) {                              // (wave-uniform pointer test; the terms of node jj, channel ch)
-          // 2 E^2 - sum p^2 left to right, canonical momenta: the arithmetic of enc_input_bwd_kernel (net_kernels.hip)
-          const double q0 = pme[0] * pme[0], q1 = pme[1] * pme[1], q2 = pme[2] * pme[2], q3 = pme[3] * pme[3];
-          const double mass = sqrt(fabs(2.0 * q0 - (((q0 + q1) + q2) + q3)));
+          // the mass and the canonical momenta: the arithmetic of enc_input_bwd_kernel (net_kernels.hip)
+          const double mass = sqrt(fabs(minkowski_sq_unfused(pme[0], pme[1], pme[2], pme[3])));
           constexpr double H = 0.70710678118654752440084436210484903928;
           const cx<double> q[4] = {{pme[0], 0.0}, {pme[1] * H, -pme[2] * H}, {pme[3], 0.0}, {-pme[1] * H, -pme[2] * H}};
           cx<double> d1 = {0, 0};

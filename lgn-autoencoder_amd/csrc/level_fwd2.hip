@@ -82,9 +82,7 @@ __global__ __launch_bounds__(2 * BLOCK) void level_fwd2_kernel(LevelArgs<double>
       const int j = e / C, c = e - j * C;
       const double* p = p0 + j * 4;
       const double pe = p[0], px = p[1], py = p[2], pz = p[3];
-      // 2 E^2 - sum p^2 with the left-to-right sum of the reference's CPU reduction (zonal_functions.py:201-218)
-      const double q0 = pe * pe, q1 = px * px, q2 = py * py, q3 = pz * pz;
-      const double mass = sqrt(fabs(2.0 * q0 - (((q0 + q1) + q2) + q3)));
+      const double mass = sqrt(fabs(minkowski_sq_unfused(pe, px, py, pz)));
       constexpr double H = 0.70710678118654752440084436210484903928;
       const cx<double> q[4] = {{pe, 0.0}, {px * H, -py * H}, {pz, 0.0}, {-px * H, -py * H}};     // p_to_rep (zonal_functions.py:251-289)
       const double w0r = a.in_w0[c], w0i = a.in_w0[C + c];

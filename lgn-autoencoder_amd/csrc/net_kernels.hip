@@ -19,9 +19,7 @@ namespace {
 constexpr double H = 0.70710678118654752440084436210484903928;
 
 __device__ __forceinline__ double minkowski_sq_ref(const double* p) {
-  // 2 E^2 - sum p^2 with the left-to-right sum of the reference's CPU reduction (zonal_functions.py:201-218)
-  double q0 = p[0] * p[0], q1 = p[1] * p[1], q2 = p[2] * p[2], q3 = p[3] * p[3];
-  return 2.0 * q0 - (((q0 + q1) + q2) + q3);
+  return minkowski_sq_unfused(p[0], p[1], p[2], p[3]);
 }
 // real Cartesian -> canonical (p_to_rep, zonal_functions.py:251-289)
 __device__ __forceinline__ void canon_real(const double* p, cx<double> (&q)[4]) {

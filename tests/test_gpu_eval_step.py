@@ -30,8 +30,7 @@ def _batch(net):
     return O.synthetic_jets(B, N, seed=N + B, pad=True)
 
 
-def _jet_mse(x, y):
-    return ((x.sum(-2) - y.sum(-2)) ** 2).mean()
+_jet_mse = U.jet_mse
 
 
 def _oracle_eval(enc, dec, p4, labels, method, jet, maxdim):

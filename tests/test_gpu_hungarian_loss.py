@@ -135,12 +135,16 @@ def _oracle_forward(net, method):
     ce = O.NetConfig(num_particles=N, maxdim=maxdim, num_channels=CH[maxdim][0])
     cd = O.NetConfig(num_particles=N, maxdim=maxdim, num_channels=CH[maxdim][1])
     rec = O.decoder_forward(Pd, cd, O.encoder_forward(Pe, ce, p4, labels))
-    return rec, O.get_real(rec, method), list(Pe.values()) + list(Pd.values())
+    return rec, O.get_real(rec, method), {f"{pre}.{k}": q for pre, P in (("enc", Pe), ("dec", Pd)) for k, q in P.items()}
+
+
+def _oracle_grads(loss, leaves):
+    """{name: gradient or None} of the oracle's named leaves."""
+    return dict(zip(leaves, torch.autograd.grad(loss, list(leaves.values()), retain_graph=True, allow_unused=True)))
 
 
 def _oracle_grad(loss, leaves):
-    grads = torch.autograd.grad(loss, leaves, retain_graph=True, allow_unused=True)
-    return torch.cat([(g if g is not None else torch.zeros_like(q)).reshape(-1) for g, q in zip(grads, leaves)])
+    return torch.cat([(g if g is not None else torch.zeros_like(leaves[k])).reshape(-1) for k, g in _oracle_grads(loss, leaves).items()])
 
 
 def _flat_grad(enc, dec):
@@ -183,7 +187,7 @@ def test_native_step_matches_oracle(net, loss, method, use_graph):
     loss_o = _ref_loss(choice, x_o, p4, col, a, p)
     U.assert_close(got, loss_o.detach(), 1e-10, "loss")
     U.assert_close(recon, rec_o.detach(), 1e-10, "recon")
-    U.assert_close(_flat_grad(enc, dec), _oracle_grad(loss_o, leaves), 1e-10, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), _oracle_grads(loss_o, leaves), 1e-10, f"{net} {choice} {a} {p} {method}")
 
 
 @pytest.mark.parametrize("method", ["real", "norm"])

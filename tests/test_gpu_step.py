@@ -541,7 +541,7 @@ def test_native_step_with_input_scalars_matches_module_path(B, N, K, jet):
     lb, rb = b.forward_backward(batch)
     U.assert_close(la, lb, 1e-12, "loss")
     U.assert_close(ra, rb, 1e-12, "recon")
-    U.assert_close(a.flat.grad, b.flat.grad, 1e-9, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), dict(U.named_grads(enc2, dec2)), 1e-9, f"B {B} N {N} K {K} jet {jet}")
     assert torch.isfinite(a.flat.grad).all()
 
 

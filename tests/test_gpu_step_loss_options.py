@@ -30,14 +30,12 @@ def _batch(net):
     return O.synthetic_jets(B, N, seed=N + B, pad=True)
 
 
-def _jet_mse(x, y):
-    """nn.MSELoss()(x.sum(-2), y.sum(-2)) (utils/losses/chamfer_loss/chamfer_loss.py:25-29): all rows, padding included."""
-    return ((x.sum(-2) - y.sum(-2)) ** 2).mean()
+_jet_mse = U.jet_mse
 
 
 @functools.lru_cache(maxsize=None)
 def _oracle(net, method, jet):
-    """(loss, recon, flat gradient in the order of the modules' named_grads) of the CPU oracle."""
+    """(loss, recon, {'enc.<name>' / 'dec.<name>': gradient or None}) of the CPU oracle."""
     from oracle import lgn_oracle as O
     maxdim, N, _ = NETS[net]
     enc, dec = _models(net)
@@ -52,12 +50,7 @@ def _oracle(net, method, jet):
     if jet:
         loss = loss + _jet_mse(x, p4)
     loss.backward()
-    grads = [q.grad if q.grad is not None else torch.zeros_like(q) for q in list(Pe.values()) + list(Pd.values())]
-    return loss.detach(), rec.detach(), torch.cat([g.reshape(-1) for g in grads])
-
-
-def _flat_grad(enc, dec):
-    return torch.cat([g.detach().reshape(-1).cpu() for _, g in list(enc.named_grads()) + list(dec.named_grads())])
+    return loss.detach(), rec.detach(), {f"{pre}.{k}": q.grad for pre, P in (("enc", Pe), ("dec", Pd)) for k, q in P.items()}
 
 
 @pytest.mark.parametrize("use_graph", [False, True])
@@ -74,10 +67,10 @@ def test_native_step_loss_options_match_oracle(method, jet, net, use_graph):
     batch = {"p4": p4.to("cuda:0"), "labels": labels.to("cuda:0")}
     for _ in range(2):                      # (with the graph: capture, then a replay on the same buffers)
         loss, recon = step.step(batch)
-    loss_o, rec_o, grad_o = _oracle(net, method, jet)
+    loss_o, rec_o, grads_o = _oracle(net, method, jet)
     U.assert_close(loss, loss_o, 1e-10, "loss")
     U.assert_close(recon, rec_o, 1e-10, "recon")
-    U.assert_close(_flat_grad(enc, dec), grad_o, 1e-10, "flat gradient")
+    U.assert_named_grads_close(U.named_grads(enc, dec), grads_o, 1e-10, f"{net} {method} jet {jet}")
 
 
 def test_method_names_match_without_regard_to_case_and_unknown_means_real(caplog):
