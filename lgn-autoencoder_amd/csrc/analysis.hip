@@ -18,7 +18,7 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "lds.hpp"
 #include "../../include/lgn_amd.h"
 #include "lsap_wave.hpp"
 #include "polar_dev.hpp"     // p_polar_tensor, wrap_phi
@@ -271,21 +271,14 @@ __global__ __launch_bounds__(64 * RA_WAVES) void match_rel_err_kernel(const RaAr
 template <int K>
 int launch_analysis(const RaArgs& a, hipStream_t st) {
   const size_t smem = ra_lds_bytes(a.N);
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(recon_analysis_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  recon_analysis_kernel<K><<<(a.B + RA_WAVES - 1) / RA_WAVES, 64 * RA_WAVES, smem, st>>>(a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(recon_analysis_kernel<K>, "recon_analysis", dim3((a.B + RA_WAVES - 1) / RA_WAVES), dim3(64 * RA_WAVES), smem, st, a);
 }
 
 template <int K>
 int launch_match(const RaArgs& a, const double* const* fr, hipStream_t st) {
   const size_t smem = ra_lds_bytes(a.N);
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(match_rel_err_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  match_rel_err_kernel<K><<<(a.B + RA_WAVES - 1) / RA_WAVES, 64 * RA_WAVES, smem, st>>>(a, fr[0], fr[1], fr[2], fr[3], fr[4], fr[5]);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(match_rel_err_kernel<K>, "match_rel_err", dim3((a.B + RA_WAVES - 1) / RA_WAVES), dim3(64 * RA_WAVES), smem, st, a, fr[0], fr[1], fr[2],
+                    fr[3], fr[4], fr[5]);
 }
 
 static_assert(NMAX <= LSAP_NMAX, "lsap_wave holds three columns per lane");

@@ -10,7 +10,7 @@
 
 #include <math.h>
 
-#include "common.hpp"
+#include "lds.hpp"
 #include "../../include/lgn_amd.h"
 #include "lsap_wave.hpp"
 #include "polar_dev.hpp"     // p4_polar, wrap_phi: shared with emd.hip
@@ -234,11 +234,8 @@ template <int K>
 int launch_scores(const double* rec, const double* tgt, const double* rec_n, const double* tgt_n, int B, int N, int mask, double* scores,
                   int* col4row, int* status, hipStream_t st) {
   const size_t smem = scores_lds_bytes(N);
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(anomaly_scores_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  anomaly_scores_kernel<K><<<B, 64 * SC_WAVES, smem, st>>>(rec, tgt, rec_n, tgt_n, N, mask, scores, col4row, status, B);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(anomaly_scores_kernel<K>, "anomaly_scores", dim3(B), dim3(64 * SC_WAVES), smem, st, rec, tgt, rec_n, tgt_n, N, mask, scores, col4row,
+                    status, B);
 }
 
 template <int K>

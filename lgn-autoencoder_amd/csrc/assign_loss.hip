@@ -16,6 +16,7 @@
 // The headers of the output stage are included first: their code (the output mix, get_real) contracts as it does in the Chamfer
 // step's kernels, so the reconstruction is that step's bit for bit.  lsap_wave.hpp then switches contraction off for the rest of
 // the file: an FMA in a cost or a reduced cost changes which column wins an exact tie.
+#include "lds.hpp"
 #include "net_dev.hpp"
 #include "net.hpp"
 #include "lsap_wave.hpp"
@@ -235,29 +236,17 @@ inline size_t stage_bytes(int N, int C) {
 }
 inline size_t alone_bytes(int N) { return sizeof(double) * ((size_t)N * 12 + core_doubles(N)); }
 
-#define LGN_ASSIGN_LAUNCH(kernel, what, smem)                                                                                    \
-  LGN_CHECK_ARG((smem) <= LGN_LDS_LIMIT, what ": N=%d needs %zu B of LDS (> %d)", N, (size_t)(smem), LGN_LDS_LIMIT);              \
-  if ((smem) > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem))
-
 template <int K, bool GRAD>
 int launch_stage(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, const AssignLoss& al,
                  double* recon, double* loss_part, double* g_v, double* part, hipStream_t st) {
-  const size_t smem = stage_bytes(N, C);
-  LGN_ASSIGN_LAUNCH((dec_output_assign_loss_kernel<K, GRAD>), "dec_output_assign_loss", smem);
-  hipLaunchKernelGGL((dec_output_assign_loss_kernel<K, GRAD>), dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, method, al.kind,
-                     frame_of(al.kind, al.abs_coord, al.polar_coord), al.scale, recon, loss_part, g_v, part, al.assignment, al.status);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(dec_output_assign_loss_kernel<K, GRAD>, "dec_output_assign_loss", dim3(B), dim3(BLOCK), stage_bytes(N, C), st, B, N, C, v, wo1, target,
+                    method, al.kind, frame_of(al.kind, al.abs_coord, al.polar_coord), al.scale, recon, loss_part, g_v, part, al.assignment, al.status);
 }
 
 template <int K>
 int launch_alone(int B, int N, const double* x, const double* y, const AssignLoss& al, double* loss_part, double* gx, hipStream_t st) {
-  const size_t smem = alone_bytes(N);
-  LGN_ASSIGN_LAUNCH(hungarian_mse_kernel<K>, "hungarian_mse", smem);
-  hipLaunchKernelGGL(hungarian_mse_kernel<K>, dim3(B), dim3(BLOCK), smem, st, N, x, y, al.kind,
-                     frame_of(al.kind, al.abs_coord, al.polar_coord), al.scale, loss_part, gx, al.assignment, al.status);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(hungarian_mse_kernel<K>, "hungarian_mse", dim3(B), dim3(BLOCK), alone_bytes(N), st, N, x, y, al.kind,
+                    frame_of(al.kind, al.abs_coord, al.polar_coord), al.scale, loss_part, gx, al.assignment, al.status);
 }
 
 }  // namespace

@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "lds.hpp"
 #include "../../include/lgn_amd.h"
 #include "emd_wave.hpp"
 #include "polar_dev.hpp"
@@ -364,9 +364,8 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
 template <int K, class Flow, bool REL, class... Grad>
 int launch_emd_kf(const double* a0, const double* a1, int B, int n, int m, double R, double* emd, double* flow, double* dual0, double* dual1,
                   int* status, double* work, int grid, size_t smem, hipStream_t st, Grad... go) {
-  emd_kernel<K, Flow, REL, Grad...><<<grid, 64, smem, st>>>(a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work, go...);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(emd_kernel<K, Flow, REL, Grad...>, "emd", dim3(grid), dim3(64), smem, st, a0, a1, B, n, m, R, emd, flow, dual0, dual1, status, work,
+                    go...);
 }
 
 template <bool REL, class... Grad>

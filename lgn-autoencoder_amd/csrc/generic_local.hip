@@ -10,6 +10,7 @@
 //   out[o][q0_l + m] = sum_{block, c} W_l[o][block*C + c] cat[row(l, block, m)][c]
 #include <stdlib.h>
 
+#include "lds.hpp"
 #include "ops.hpp"
 
 namespace lgn {
@@ -462,11 +463,7 @@ int local_fwd(const LocalArgs& a, hipStream_t st) {
   LGN_CHECK_ARG(a.C * a.Q <= BLOCK && a.C * a.Q * 10 <= PF_U * BLOCK && a.CO * a.Qout <= BLOCK, "local_fwd: C*Q=%d too large", a.C * a.Q);
   LGN_CHECK_ARG(a.Q * 5 < 1024 && a.n_terms > 0, "local_fwd: Q=%d exceeds the packed term code", a.Q);
   const size_t smem = sizeof(double) * ((size_t)a.t.n_rows * a.C * 2 + (size_t)a.C * a.Q * 12) + walk_table_bytes(a.t.n_rows, a.n_terms);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "local_fwd: %zu B of LDS needed", smem);
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(local_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(local_fwd_kernel, dim3(local_partial_rows(a.nodes)), dim3(BLOCK), smem, st, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(local_fwd_kernel, "local_fwd", dim3(local_partial_rows(a.nodes)), dim3(BLOCK), smem, st, a);
 }
 
 int local_bwd(const LocalArgs& a, hipStream_t st) {
@@ -480,11 +477,7 @@ int local_bwd(const LocalArgs& a, hipStream_t st) {
                       sizeof(int) * ((size_t)a.t.n_w + 2 * (size_t)a.t.n_rows + 5 * (size_t)a.Q + 2 + (size_t)a.n_u) +
                       sizeof(double) * (size_t)a.n_u + 8 + walk_table_bytes(a.t.n_rows, a.n_terms);
   LGN_CHECK_ARG(a.Q * 5 < 1024 && a.n_terms > 0, "local_bwd: Q=%d exceeds the packed term code", a.Q);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "local_bwd: %zu B of LDS needed", smem);
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(local_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(local_bwd_kernel, dim3(local_partial_rows(a.nodes)), dim3(BLOCK), smem, st, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(local_bwd_kernel, "local_bwd", dim3(local_partial_rows(a.nodes)), dim3(BLOCK), smem, st, a);
 }
 
 }  // namespace lgn

@@ -17,6 +17,7 @@
 //             bias-gradient terms from those sums (what dec_sep_bwd_tb did from a 147 MB dU).
 // Reference: cg_product aggregate lgn/cg_lib/cg_ops.py:281-297 (sum over j BEFORE the CG matrix: the order kept here), the radial
 // functions of the decoder lgn/nn/position_levels.py:144-149 (masked edges carry the Linear bias).
+#include "lds.hpp"
 #include "local_static_dev.hpp"
 #include <algorithm>
 
@@ -619,16 +620,11 @@ int local_bwd_sep(int kind, int B, int N, int C, int CO, const double* XT, const
   do {                                                                                                                          \
     const size_t smem = sep_lds_bytes<cgs::KIND>();                                                                             \
     LGN_CHECK_ARG(smem <= 80 * 1024, "local_bwd_sep: %zu B of LDS", smem);                                                      \
-    if (smem > 64 * 1024)                                                                                                       \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(local_bwd_sep_kernel<cgs::KIND, COT>),                            \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                                         \
-    hipLaunchKernelGGL((local_bwd_sep_kernel<cgs::KIND, COT>), grid, dim3(128), smem, st, a);                                   \
+    return lds_launch(local_bwd_sep_kernel<cgs::KIND, COT>, "local_bwd_sep", grid, dim3(128), smem, st, a);                     \
   } while (0)
   if (kind == 1) { if (CO <= 4) LGN_LAUNCH(Kind1, 4); else if (CO <= 6) LGN_LAUNCH(Kind1, 6); else LGN_LAUNCH(Kind1, 8); }
   else { if (CO <= 4) LGN_LAUNCH(Kind2, 4); else if (CO <= 6) LGN_LAUNCH(Kind2, 6); else LGN_LAUNCH(Kind2, 8); }
 #undef LGN_LAUNCH
-  LGN_CHECK_LAUNCH();
-  return 0;
 }
 
 // g_p [2][B][N][4] += sum over levels and channels of gpb_l [C_l][M][8]

@@ -16,6 +16,7 @@
 // accumulators stay in registers (the radial part is recomputed per chunk).
 #include <stdlib.h>
 
+#include "lds.hpp"
 #include "pair_dev.hpp"
 #include "ops.hpp"
 
@@ -396,45 +397,21 @@ __global__ __launch_bounds__(BLOCK) void moments_bwd_rad_kernel(GenArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-template <typename K>
-static int set_smem(K kern, size_t smem, const char* what) {
-  if (smem > 160 * 1024) {
-    set_error("%s needs %zu B of LDS (> 160 KiB)", what, smem);
-    return -1;
-  }
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e)); return (int)e; }
-  }
-  return 0;
-}
-
 template <int C, bool DEC>
 static int launch_moments(const GenArgs& a, int which, hipStream_t st) {
   constexpr int PS = DEC ? 8 : 4;
   constexpr int NG = (C + 3) / 4;
   const size_t xs = sizeof(double) * (size_t)a.N * C * a.Q * 2, pos = sizeof(double) * (size_t)a.N * PS + a.N + 16;
-  int rc;
   if (which == 0) {
-    const bool xl = xs + pos <= 160 * 1024;          // (jets whose features do not fit read them from global memory)
+    const bool xl = xs + pos <= LGN_LDS_LIMIT;       // (jets whose features do not fit read them from global memory)
     auto k = xl ? moments_fwd_kernel<C, DEC, true> : moments_fwd_kernel<C, DEC, false>;
-    const size_t smem = (xl ? xs : 0) + pos;
-    if ((rc = set_smem(k, smem, "moments_fwd"))) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(BLOCK), smem, st, a);
-  } else if (which == 1) {
-    auto k = moments_bwd_nodes_kernel<C, DEC>;
-    if ((rc = set_smem(k, pos, "moments_bwd_nodes"))) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(BLOCK), pos, st, a);
-  } else {
-    constexpr int TRSZ = 4 * pair_scratch(NG);
-    const bool xl = xs + pos + sizeof(double) * TRSZ <= 160 * 1024;
-    auto k = xl ? moments_bwd_rad_kernel<C, DEC, true> : moments_bwd_rad_kernel<C, DEC, false>;
-    const size_t smem = (xl ? xs : 0) + pos + sizeof(double) * TRSZ;
-    if ((rc = set_smem(k, smem, "moments_bwd_rad"))) return rc;
-    hipLaunchKernelGGL(k, dim3(a.B), dim3(BLOCK), smem, st, a);
+    return lds_launch(k, "moments_fwd", dim3(a.B), dim3(BLOCK), (xl ? xs : 0) + pos, st, a);
   }
-  LGN_CHECK_LAUNCH();
-  return 0;
+  if (which == 1) return lds_launch(moments_bwd_nodes_kernel<C, DEC>, "moments_bwd_nodes", dim3(a.B), dim3(BLOCK), pos, st, a);
+  constexpr int TRSZ = 4 * pair_scratch(NG);
+  const bool xl = xs + pos + sizeof(double) * TRSZ <= LGN_LDS_LIMIT;
+  auto k = xl ? moments_bwd_rad_kernel<C, DEC, true> : moments_bwd_rad_kernel<C, DEC, false>;
+  return lds_launch(k, "moments_bwd_rad", dim3(a.B), dim3(BLOCK), (xl ? xs : 0) + pos + sizeof(double) * TRSZ, st, a);
 }
 
 bool moments2_fits(const GenArgs& a, int decoder);                                               // generic_moments2.hip

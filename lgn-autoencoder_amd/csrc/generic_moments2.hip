@@ -16,6 +16,7 @@
 //            (the [4C x pairs] . [pairs x 42] matrix-core GEMM of v1, now without the q loop); decoder: bias sums and d p.
 #include <stdlib.h>
 
+#include "lds.hpp"
 #include "pair_dev.hpp"
 #include "ops.hpp"
 
@@ -1009,19 +1010,6 @@ __global__ __launch_bounds__(BLOCK) void moments_rad_reduce2_kernel(GenArgs a, c
   if (wave == 0) rad_rows_sum<C, 4, WaveSum::Pairwise>(red, a.part_rad + (size_t)blockIdx.x * rad_partial_size(C, false), lane);
 }
 
-template <typename K>
-static int set_smem(K kern, size_t smem, const char* what) {
-  if (smem > 160 * 1024) {
-    set_error("%s needs %zu B of LDS (> 160 KiB)", what, smem);
-    return -1;
-  }
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e)); return (int)e; }
-  }
-  return 0;
-}
-
 static size_t base_smem(const GenArgs& a, bool dec, int pitch) {     // pair table (pitch 0: none) + positions + radial constants + mask
   const int PS = dec ? 8 : 4;
   return sizeof(double) * ((size_t)a.N * pitch * 4 + (size_t)a.N * PS + NB * 8 + 4) + a.N + 16;
@@ -1033,38 +1021,17 @@ static int launch(const GenArgs& a, int which, double* Gbuf, hipStream_t st) {
   // encoder: channels are independent -> one workgroup per (jet, channel): 3x .. 6x more workgroups in flight to hide the staging
   // and the barriers; the decoder kernels (pair-sweep cross-check only) accumulate d p and the bias gradients over the channels
   const dim3 grid(a.B, DEC ? 1 : a.C);
-  int rc;
   if (which == 0) {
     // (encoder: the symmetric pair table, N (N + 1) / 2 entries instead of N x pitch)
     const size_t smem = base_smem(a, DEC, row_pitch(a.N)) + xs - (DEC ? 0 : sizeof(double) * 4 * ((size_t)a.N * row_pitch(a.N) - (size_t)(a.N * (a.N + 1) / 2)));
-    if (a.Q <= 8) {
-      auto k = moments_fwd2_kernel<DEC, 2>;
-      if ((rc = set_smem(k, smem, "moments_fwd2"))) return rc;
-      hipLaunchKernelGGL(k, grid, dim3(BLOCK), smem, st, a);
-    } else {
-      auto k = moments_fwd2_kernel<DEC, 5>;
-      if ((rc = set_smem(k, smem, "moments_fwd2"))) return rc;
-      hipLaunchKernelGGL(k, grid, dim3(BLOCK), smem, st, a);
-    }
-  } else if (which == 1) {
-    const size_t smem = base_smem(a, DEC, a.N) + gu + (DEC ? sizeof(double) * 4 * a.N * 8 : 0);
-    if (a.Q <= 8) {
-      auto k = moments_bwd_nodes2_kernel<DEC, 2>;
-      if ((rc = set_smem(k, smem, "moments_bwd_nodes2"))) return rc;
-      hipLaunchKernelGGL(k, grid, dim3(BLOCK), smem, st, a);
-    } else {
-      auto k = moments_bwd_nodes2_kernel<DEC, 5>;
-      if ((rc = set_smem(k, smem, "moments_bwd_nodes2"))) return rc;
-      hipLaunchKernelGGL(k, grid, dim3(BLOCK), smem, st, a);
-    }
-  } else {
-    const size_t smem = base_smem(a, DEC, 0) + sizeof(double) * (size_t)a.N * g2_row_pitch(a.Q) + xs + (DEC ? sizeof(double) * (8 * a.N * 8 + 8 * 2 * 8) : 0);
-    auto k = moments_bwd_G2_kernel<DEC>;
-    if ((rc = set_smem(k, smem, "moments_bwd_G2"))) return rc;
-    hipLaunchKernelGGL(k, grid, dim3(BLOCK), smem, st, a, Gbuf);
+    return lds_launch(a.Q <= 8 ? moments_fwd2_kernel<DEC, 2> : moments_fwd2_kernel<DEC, 5>, "moments_fwd2", grid, dim3(BLOCK), smem, st, a);
   }
-  LGN_CHECK_LAUNCH();
-  return 0;
+  if (which == 1) {
+    const size_t smem = base_smem(a, DEC, a.N) + gu + (DEC ? sizeof(double) * 4 * a.N * 8 : 0);
+    return lds_launch(a.Q <= 8 ? moments_bwd_nodes2_kernel<DEC, 2> : moments_bwd_nodes2_kernel<DEC, 5>, "moments_bwd_nodes2", grid, dim3(BLOCK), smem, st, a);
+  }
+  const size_t smem = base_smem(a, DEC, 0) + sizeof(double) * (size_t)a.N * g2_row_pitch(a.Q) + xs + (DEC ? sizeof(double) * (8 * a.N * 8 + 8 * 2 * 8) : 0);
+  return lds_launch(moments_bwd_G2_kernel<DEC>, "moments_bwd_G2", grid, dim3(BLOCK), smem, st, a, Gbuf);
 }
 
 // encoder backward, both sweeps (moments_bwd_enc2_kernel): LDS = symmetric pair table + padded dU rows + X + jet data
@@ -1075,29 +1042,15 @@ static size_t enc2_smem(const GenArgs& a) {
 static int launch_enc2(const GenArgs& a, double* Gbuf, hipStream_t st) {
   const size_t smem = enc2_smem(a);
   const dim3 grid(a.B, a.C);
-  int rc;
-  if (a.Q <= 8) {
-    auto k = moments_bwd_enc2_kernel<2, 4>;
-    if ((rc = set_smem(k, smem, "moments_bwd_enc2"))) return rc;
-    hipLaunchKernelGGL(k, grid, dim3(256), smem, st, a, Gbuf);
-  } else {
-    auto k = moments_bwd_enc2_kernel<5, 8>;
-    if ((rc = set_smem(k, smem, "moments_bwd_enc2"))) return rc;
-    hipLaunchKernelGGL(k, grid, dim3(512), smem, st, a, Gbuf);
-  }
-  LGN_CHECK_LAUNCH();
-  return 0;
+  if (a.Q <= 8) return lds_launch(moments_bwd_enc2_kernel<2, 4>, "moments_bwd_enc2", grid, dim3(256), smem, st, a, Gbuf);
+  return lds_launch(moments_bwd_enc2_kernel<5, 8>, "moments_bwd_enc2", grid, dim3(512), smem, st, a, Gbuf);
 }
 
 template <int C>
 static int launch_reduce(const GenArgs& a, const double* Gbuf, hipStream_t st) {
   constexpr int NG = (C + 3) / 4;
   const size_t smem = sizeof(double) * ((size_t)a.N * 4 + 4 * 64 * NG * 12) + a.N + 16;
-  auto k = moments_rad_reduce2_kernel<C>;
-  if (int rc = set_smem(k, smem, "moments_rad_reduce2")) return rc;
-  hipLaunchKernelGGL(k, dim3(a.B), dim3(BLOCK), smem, st, a, Gbuf);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(moments_rad_reduce2_kernel<C>, "moments_rad_reduce2", dim3(a.B), dim3(BLOCK), smem, st, a, Gbuf);
 }
 
 }  // namespace m2
@@ -1107,7 +1060,7 @@ bool moments2_fits(const GenArgs& a, int decoder) {
   if (a.N > m2::MAXN || a.C > 8) return false;
   const size_t worst = m2::base_smem(a, decoder != 0, m2::row_pitch(a.N)) + sizeof(double) * ((size_t)a.N * a.Q * 12 + 2 * (size_t)a.N) +
                        (decoder ? sizeof(double) * (8 * a.N * 8 + 8 * 2 * 8) : 0);
-  return worst <= 160 * 1024;
+  return worst <= LGN_LDS_LIMIT;      // (looser than the launchers' largest need, and kept: a tighter bound moves shapes to generic_moments.hip)
 }
 // scratch (doubles) the encoder's i-centric backward needs for the pair gradients
 size_t moments2_gbuf_doubles(int B, int N, int C) { return (size_t)B * N * N * C * 4; }
@@ -1123,17 +1076,10 @@ int moments2_dispatch(const GenArgs& a, int decoder, int which, double* Gbuf, hi
     if (which == 2) return 0;                               // the separable backward does both passes in one launch
     if (const int rc = moments_dec_sep_tb_dispatch(a, which, st); rc != -2) return rc;      // tile-blocked layouts: generic_moments_sep.hip
     const size_t base = sizeof(double) * ((size_t)a.N * 8 + (size_t)a.N * a.Q * 2);
-    if (which == 0) {
-      const size_t smem = base + sizeof(double) * (size_t)a.Q * 10;
-      if (int rc = m2::set_smem(m2::moments_dec_sep_fwd_kernel, smem, "moments_dec_sep_fwd")) return rc;
-      hipLaunchKernelGGL(m2::moments_dec_sep_fwd_kernel, dim3(a.B), dim3(BLOCK), smem, st, a);
-    } else {
-      const size_t smem = base + sizeof(double) * ((size_t)a.N * a.Q * 10 + (size_t)a.Q * 28 + (size_t)a.N * 8 + (size_t)a.Q * 4);
-      if (int rc = m2::set_smem(m2::moments_dec_sep_bwd_kernel, smem, "moments_dec_sep_bwd")) return rc;
-      hipLaunchKernelGGL(m2::moments_dec_sep_bwd_kernel, dim3(a.B), dim3(BLOCK), smem, st, a);
-    }
-    LGN_CHECK_LAUNCH();
-    return 0;
+    if (which == 0)
+      return lds_launch(m2::moments_dec_sep_fwd_kernel, "moments_dec_sep_fwd", dim3(a.B), dim3(BLOCK), base + sizeof(double) * (size_t)a.Q * 10, st, a);
+    const size_t smem = base + sizeof(double) * ((size_t)a.N * a.Q * 10 + (size_t)a.Q * 28 + (size_t)a.N * 8 + (size_t)a.Q * 4);
+    return lds_launch(m2::moments_dec_sep_bwd_kernel, "moments_dec_sep_bwd", dim3(a.B), dim3(BLOCK), smem, st, a);
   }
   // encoder backward: ONE kernel for both sweeps (which = 1; which = 2 is then the radial-parameter reduction alone) unless the
   // caller asks for the two-kernel form (LVL_MOMENTS_SPLIT: cross-check) or has no pair-gradient scratch for pass 1

@@ -15,6 +15,7 @@
 // planar gradient is G_z = G_out * conj(f'(z)).
 #include <stdlib.h>
 
+#include "lds.hpp"
 #include "level_dev.hpp"
 #include <type_traits>
 #include "ops.hpp"
@@ -399,22 +400,6 @@ __global__ __launch_bounds__(64 * RED_RG) void reduce_partials_kernel(const T* _
 // ---------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------
-template <typename K>
-static int ensure_smem(K kern, size_t smem, const char* what) {
-  if (smem > 160 * 1024) {
-    set_error("%s needs %zu B of LDS (> 160 KiB)", what, smem);
-    return -1;
-  }
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
-      return (int)e;
-    }
-  }
-  return 0;
-}
-
 int level_bwd_nodes2_dispatch(const LevelBwdArgs<double>& a, int decoder, hipStream_t stream);   // level_bwd2.hip
 int level_bwd_rad2_dispatch(const LevelBwdArgs<double>& a, hipStream_t stream);
 
@@ -458,11 +443,8 @@ static int launch_level_bwd(const LevelBwdArgs<T>& a, hipStream_t stream) {
   if (use_v3(N, a.flags)) return level_bwd3_dispatch(a, DEC, stream);
   LGN_CHECK_ARG(!a.sep_sums, "level_bwd: N=%d: this form of the backward reads the stored aggregate", N);
   {  // 1. CatMix / power
-    auto kern = level_bwd_mix_kernel<T, C>;
-    size_t smem = sizeof(T) * (4 * CO * 5 * C + 32 * (5 * C * 10) + 32 * CO * 10);
-    if ((rc = ensure_smem(kern, smem, "level_bwd_mix"))) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.B, tiles), dim3(BLOCK), smem, stream, a);
-    LGN_CHECK_LAUNCH();
+    const size_t smem = sizeof(T) * (4 * CO * 5 * C + 32 * (5 * C * 10) + 32 * CO * 10);
+    if ((rc = lds_launch(level_bwd_mix_kernel<T, C>, "level_bwd_mix", dim3(a.B, tiles), dim3(BLOCK), smem, stream, a))) return rc;
   }
   if constexpr (DEC && std::is_same<T, double>::value) {
     if (!dec_pairwise(a.flags)) return level_bwd_dec_sep_dispatch(a, stream);   // 2+3. from jet-level sums, O(N C)
@@ -473,11 +455,8 @@ static int launch_level_bwd(const LevelBwdArgs<T>& a, hipStream_t stream) {
   }
   if ((rc = level_bwd_nodes2_dispatch(a, DEC, stream))) return rc;        // 2. j-centric pass
   if (DEC) {  // 3b
-    auto kern = level_bwd_rad_dec_kernel<T, C>;
-    size_t smem = sizeof(T) * (L::even(N * L::NS) + N * 8 + 32 * GA<C>::SIZE + L::even(2 * C) + (BLOCK / 64) * 2 * C);
-    if ((rc = ensure_smem(kern, smem, "level_bwd_rad_dec"))) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.B, tiles), dim3(BLOCK), smem, stream, a);
-    LGN_CHECK_LAUNCH();
+    const size_t smem = sizeof(T) * (L::even(N * L::NS) + N * 8 + 32 * GA<C>::SIZE + L::even(2 * C) + (BLOCK / 64) * 2 * C);
+    if ((rc = lds_launch(level_bwd_rad_dec_kernel<T, C>, "level_bwd_rad_dec", dim3(a.B, tiles), dim3(BLOCK), smem, stream, a))) return rc;
   } else {    // 3a
     if ((rc = level_bwd_rad2_dispatch(a, stream))) return rc;
   }

@@ -10,6 +10,7 @@
 //                      are one GEMM  [r x pairs] x [pairs x 42 columns]  executed with v_mfma_f64_16x16x4_f64; the
 //                      two operands are produced pair-per-lane and turned into A/B fragments by a 16x16 transpose
 //                      through a wave-private LDS tile (4 writes + 4 reads per lane for A, 12 + 12 for B).
+#include "lds.hpp"
 #include "pair_dev.hpp"
 #include "ops.hpp"
 
@@ -658,10 +659,7 @@ static int launch_sweep_enc_w(const LevelBwdArgs<double>& a, hipStream_t stream)
   if constexpr (C <= 4) {
     if (sym) kern = level_bwd_sweep_enc_kernel<C, NWV, true>;
   }
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(64 * NWV), smem, stream, a, ichunk);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "level_bwd_sweep", dim3(a.B), dim3(64 * NWV), smem, stream, a, ichunk);
 }
 
 // encoder only; reads g_ag and adds into g_s_in / g_v_in (both written by level_bwd_mix_kernel), writes ONE radial partial row per jet
@@ -684,13 +682,9 @@ template <int C, bool DEC>
 static int launch_nodes2(const LevelBwdArgs<double>& a, hipStream_t stream) {
   constexpr int PS = DEC ? 8 : 4;
   const size_t smem = sizeof(double) * ((size_t)a.N * 20 * C + (size_t)a.N * PS) + a.N + 16;
-  LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd_nodes: N=%d C=%d needs %zu B of LDS", a.N, a.C, smem);
-  auto kern = level_bwd_nodes2_kernel<C, DEC>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   // (no per-wave LDS here and <= 168 VGPRs: 12 waves per jet when the batch leaves SIMDs idle)
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(BLOCK * (sweep_wave_factor(a.B, a.N) == 2 ? 3 : 1)), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(level_bwd_nodes2_kernel<C, DEC>, "level_bwd_nodes", dim3(a.B), dim3(BLOCK * (sweep_wave_factor(a.B, a.N) == 2 ? 3 : 1)),
+                    smem, stream, a);
 }
 
 template <int C>
@@ -701,14 +695,8 @@ static int launch_rad2(const LevelBwdArgs<double>& a, hipStream_t stream) {
                              (size_t)nw * pair_scratch(NG)) + a.N + 16;
   };
   int f = sweep_wave_factor(a.B, a.N);
-  if (f == 2 && bytes(8) > 160 * 1024) f = 1;
-  const size_t smem = bytes(4 * f);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd_rad: N=%d C=%d needs %zu B of LDS", a.N, a.C, smem);
-  auto kern = level_bwd_rad2_kernel<C>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(BLOCK * f), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  if (f == 2 && bytes(8) > LGN_LDS_LIMIT) f = 1;
+  return lds_launch(level_bwd_rad2_kernel<C>, "level_bwd_rad", dim3(a.B), dim3(BLOCK * f), bytes(4 * f), stream, a);
 }
 
 int level_bwd_nodes2_dispatch(const LevelBwdArgs<double>& a, int decoder, hipStream_t stream) {

@@ -10,6 +10,7 @@
 //            matrix cores.  Per pair: (a) g_node_j += g_ag_i (x) conj(edge_ij); (b) encoder: dL/d rad of the pair ->
 //            16x16 LDS transposes -> T1|T2|S|dB GEMM on the matrix cores; decoder: bias sums and d p_j
 //   phase 3  decoder only: i-centric sweep for d p_i
+#include "lds.hpp"
 #include "pair_dev.hpp"
 #include "ops.hpp"
 #include "wave_sum.hpp"
@@ -982,8 +983,6 @@ bool level_bwd3_fits(int N) { return N <= 40; }
 
 template <int C, bool DEC, bool SEP, int NWV, bool NOS>
 static int launch_bwd3_w(const LevelBwdArgs<double>& a, int split, hipStream_t stream) {
-  size_t smem = Bwd3<C, DEC, NWV>::smem(a.N, a.CO);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd: N=%d C=%d needs %zu B of LDS", a.N, a.C, smem);
   LGN_CHECK_ARG(a.CO <= 8, "level_bwd: C_out=%d unsupported (1..8)", a.CO);
   LGN_CHECK_ARG(!a.sep_sums || (DEC && SEP), "level_bwd: only the separable decoder backward rebuilds the aggregate from jet sums");
   auto kern = level_bwd3_kernel<C, DEC, SEP, NWV, false, NOS>;
@@ -991,10 +990,7 @@ static int launch_bwd3_w(const LevelBwdArgs<double>& a, int split, hipStream_t s
                                         // C > 4: two lane groups of channels, the second pass would double the spills)
     if (split == 1 && !(a.flags & LVL_BWD_ORDERED)) kern = level_bwd3_kernel<C, DEC, SEP, NWV, true, NOS>;
   }
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(a.B, split), dim3(64 * NWV), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "level_bwd", dim3(a.B, split), dim3(64 * NWV), Bwd3<C, DEC, NWV>::smem(a.N, a.CO), stream, a);
 }
 template <int C, bool DEC, bool SEP>
 static int launch_bwd3(const LevelBwdArgs<double>& a, hipStream_t stream) {

@@ -5,6 +5,7 @@
 // The decoder's edge mask is identically zero, so its radial weights are the per-channel constants R0, R1 and every sum
 // over pairs separates into jet-level sums (derivation and notation: level_fwd2.hip / level_bwd3.hip, SEP).  One workgroup
 // per jet; the (node, channel) terms of the sums go through LDS in slabs of 32 nodes and are added in node order.
+#include "lds.hpp"
 #include "level_dev.hpp"
 #include "ops.hpp"
 
@@ -15,6 +16,16 @@ constexpr int SLAB = 32;
 template <int C> struct GAS {
   static constexpr int A3 = 0, A4 = 2 * C, A1 = 4 * C, A2 = 12 * C, SIZE = 20 * C;
 };
+template <int C> struct DecSepLds {                     // LDS of level_bwd_dec_sep_kernel<C> at N particles
+  size_t pj, tr, sm, bytes;
+  __host__ __device__ explicit DecSepLds(int N) {
+    LdsCarve c;
+    pj = c.take<double>(N * 8);                         // N * 8 centred canonical momenta (re[4], im[4])
+    tr = c.take<double>(SLAB * C * 20);                 // SLAB * C * 20 terms
+    sm = c.take<double>(50 * C);                        // 50 C jet-level sums (layout of level_bwd3.hip)
+    bytes = c.off;
+  }
+};
 }  // namespace
 
 template <int C>
@@ -23,9 +34,8 @@ __global__ __launch_bounds__(BLOCK) void level_bwd_dec_sep_kernel(LevelBwdArgs<d
   const int N = a.N, B = a.B;
   const int b = blockIdx.x, tid = threadIdx.x;
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  double* pj = reinterpret_cast<double*>(smem_raw);     // N * 8 centred canonical momenta (re[4], im[4])
-  double* tr = pj + N * 8;                              // SLAB * C * 20 terms
-  double* sm = tr + SLAB * C * 20;                      // 50 C jet-level sums (layout of level_bwd3.hip)
+  const DecSepLds<C> L(N);
+  double *pj = lds_at<double>(smem_raw, L.pj), *tr = lds_at<double>(smem_raw, L.tr), *sm = lds_at<double>(smem_raw, L.sm);
   const size_t pls = (size_t)B * N * C, plp = (size_t)B * N * 4;
 
   for (int e = tid; e < N * 4; e += BLOCK) {
@@ -206,13 +216,7 @@ __global__ __launch_bounds__(BLOCK) void level_bwd_dec_sep_kernel(LevelBwdArgs<d
 
 template <int C>
 static int launch_dec_sep(const LevelBwdArgs<double>& a, hipStream_t stream) {
-  const size_t smem = sizeof(double) * ((size_t)a.N * 8 + SLAB * C * 20 + 50 * C);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "level_bwd (decoder): N=%d needs %zu B of LDS", a.N, smem);
-  auto kern = level_bwd_dec_sep_kernel<C>;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(a.B), dim3(BLOCK), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(level_bwd_dec_sep_kernel<C>, "level_bwd (decoder)", dim3(a.B), dim3(BLOCK), DecSepLds<C>(a.N).bytes, stream, a);
 }
 
 // neighbour part of the decoder level backward from jet-level sums; one radial partial row per jet

@@ -16,6 +16,7 @@
 //    combined across the 4 lanes of a quad (the 4 neighbours of a tile) with two DPP quad permutes.
 //  * the aggregate of the whole jet is collected in LDS; after one barrier all 256 threads write it out (it is saved
 //    for the backward) and run CatMix over the items (row, out channel, component).
+#include "lds.hpp"
 #include "level_dev.hpp"
 #include "net_dev.hpp"
 #include "ops.hpp"
@@ -558,7 +559,7 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
   const size_t fixed = sizeof(double) * (((size_t)a.N * F::NS + 1 & ~size_t(1)) + (size_t)a.N * F::PS + 4 * a.CO * 5 * C + 20 * C) + a.N + 16;
   // (a batch with no more jets than CUs runs one 8-wave workgroup per CU anyway: it takes the whole LDS)
   const bool wide = a.B <= 320 && a.N >= 64;
-  const size_t row = sizeof(double) * F::AGS, budget1 = 160 * 1024, budget2 = wide ? budget1 : 78 * 1024;
+  const size_t row = sizeof(double) * F::AGS, budget1 = LGN_LDS_LIMIT, budget2 = wide ? budget1 : 78 * 1024;
   const int full = (a.N + 15) & ~15;
   int chunk = full;
   if (fixed + full * row > budget2) {
@@ -575,19 +576,11 @@ static int launch_level_fwd2(const LevelArgs<double>& a, hipStream_t stream) {
   }
   LGN_CHECK_ARG(!a.sep_sums || (DEC && SEP && TRAIN && a.N <= 40),
                 "level_fwd: only the separable decoder forward of a training step (N <= 40) leaves jet sums instead of the aggregate");
-  LGN_CHECK_ARG(smem <= 160 * 1024, "level_fwd: N=%d C=%d needs %zu B of LDS (> 160 KiB)", a.N, a.C, smem);
-  auto kern = level_fwd2_kernel<C, DEC, SEP, TRAIN, NOS>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
-  }
   // 8 waves per jet when the batch has no more jets than the chip has CUs and the jet has enough row groups (cfg4)
   const int nthreads = wide ? 2 * BLOCK : BLOCK;
   // small batches of small jets: several workgroups per jet, each with its own rows (level.hpp: level_jet_split)
   const int split = (SEP || a.N > 40) ? 1 : level_jet_split(a.B, a.N);
-  hipLaunchKernelGGL(kern, dim3(a.B, split), dim3(nthreads), smem, stream, a, chunk);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(level_fwd2_kernel<C, DEC, SEP, TRAIN, NOS>, "level_fwd", dim3(a.B, split), dim3(nthreads), smem, stream, a, chunk);
 }
 
 bool level_fwd_carries_loss(int N, int flags) { return N <= 40 && !(flags & LVL_DEC_PAIRWISE); }

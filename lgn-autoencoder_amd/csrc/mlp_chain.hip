@@ -24,6 +24,7 @@
 //                             the publication), so the one barrier per layer also covers the tiles.
 //   db_l   = row sums of g_pre^T: the owner of a tile row adds up the A fragments it loads anyway (16 adds + 2 shuffles).
 // The hidden activations are recomputed (six more layer steps at the head of the kernel) and stay in registers: 72 doubles.
+#include "lds.hpp"
 #include "ops.hpp"
 
 namespace lgn {
@@ -1490,10 +1491,7 @@ static int launch16s(const MlpArgs<double>& a, bool backward, hipStream_t stream
   if (backward) kern = a.act == 0 ? mlp_chain_bwd16s_kernel<H, D, false> : mlp_chain_bwd16s_kernel<H, D, true>;
   else kern = a.h_saved ? (a.act == 0 ? mlp_chain_fwd16s_kernel<H, D, false, true> : mlp_chain_fwd16s_kernel<H, D, true, true>)
                         : (a.act == 0 ? mlp_chain_fwd16s_kernel<H, D, false, false> : mlp_chain_fwd16s_kernel<H, D, true, false>);
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(backward ? 576 : 320), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "cgmlp (16-row, three chain waves)", dim3(nblk), dim3(backward ? 576 : 320), smem, stream, a);
 }
 
 template <int H, int D>
@@ -1509,10 +1507,7 @@ static int launch16(const MlpArgs<double>& a, bool backward, hipStream_t stream)
                                  : (a.act == 0 ? mlp_chain_bwd16_kernel<H, D, false, false> : mlp_chain_bwd16_kernel<H, D, true, false>);
   else kern = a.h_saved ? (a.act == 0 ? mlp_chain_fwd16_kernel<H, D, false, true> : mlp_chain_fwd16_kernel<H, D, true, true>)
                         : (a.act == 0 ? mlp_chain_fwd16_kernel<H, D, false, false> : mlp_chain_fwd16_kernel<H, D, true, false>);
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(backward ? 256 : 192), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "cgmlp (16-row)", dim3(nblk), dim3(backward ? 256 : 192), smem, stream, a);
 }
 
 // 48 < H <= 96 (C = 5 .. 8): the FORWARD chain only -- its two weight images (up to 150 KB) and ping-ponged activations fit; the
@@ -1520,14 +1515,11 @@ static int launch16(const MlpArgs<double>& a, bool backward, hipStream_t stream)
 template <int H, int D, bool TH>
 static int launch_fwd(const MlpArgs<double>& a, hipStream_t stream) {
   using G = Geo<H, D>;
-  static_assert(G::fwd_bytes() <= 160 * 1024, "LDS budget");
+  static_assert(G::fwd_bytes() <= LGN_LDS_LIMIT, "LDS budget");
   const bool two = !(a.flags & LVL_MLP_BWD1);
   auto kern = two ? (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>)
                   : (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, false, TH> : mlp_chain_fwd_kernel<H, D, true, false, false, TH>);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::fwd_bytes());
-  hipLaunchKernelGGL(kern, dim3(cdiv(a.M, 64)), dim3(two ? 512 : 256), G::fwd_bytes(), stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "cgmlp forward (wide)", dim3(cdiv(a.M, 64)), dim3(two ? 512 : 256), G::fwd_bytes(), stream, a);
 }
 
 template <int H, int D, bool TH>
@@ -1535,33 +1527,24 @@ static int launch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   using G = Geo<H, D>;
   const int nblk = cdiv(a.M, 64);
   const size_t smem = backward ? G::bwd_bytes() : G::fwd_bytes();
-  static_assert(G::bwd_bytes() <= 160 * 1024, "LDS budget");
+  static_assert(G::bwd_bytes() <= LGN_LDS_LIMIT, "LDS budget");
   if (backward) LGN_CHECK_ARG(a.psize == G::psize(), "cgmlp: psize %d, expected %d", a.psize, G::psize());
   LGN_CHECK_ARG(!a.h_saved || a.h_rows >= nblk * 64, "cgmlp: the saved-activation buffer has %d rows per layer, %d rows need %d",
                 a.h_rows, a.M, nblk * 64);
   if (backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {      // (kept activations: the one-role kernel reads them)
     auto k2 = a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false, TH> : mlp_chain_bwd2_kernel<H, D, true, TH>;
     const size_t smem2 = smem - (TH && G::NT == 3 && G::R == 4 ? sizeof(double) * 2 * 1024 : 0);      // (dw_thin3: no quarter sums)
-    if (smem2 > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    hipLaunchKernelGGL(k2, dim3(nblk), dim3(512), smem2, stream, a);
-    LGN_CHECK_LAUNCH();
-    return 0;
+    return lds_launch(k2, "cgmlp backward (two roles)", dim3(nblk), dim3(512), smem2, stream, a);
   }
   if (!backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {
     auto k2 = a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>;
-    if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    hipLaunchKernelGGL(k2, dim3(nblk), dim3(512), smem, stream, a);
-    LGN_CHECK_LAUNCH();
-    return 0;
+    return lds_launch(k2, "cgmlp forward (two roles)", dim3(nblk), dim3(512), smem, stream, a);
   }
   auto kern = a.h_saved ? (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, true, TH> : mlp_chain_fwd_kernel<H, D, false, true, false, TH>)
                                       : (backward ? mlp_chain_bwd_kernel<H, D, true, true, TH> : mlp_chain_fwd_kernel<H, D, true, true, false, TH>))
                         : (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, false, TH> : mlp_chain_fwd_kernel<H, D, false, false, false, TH>)
                                       : (backward ? mlp_chain_bwd_kernel<H, D, true, false, TH> : mlp_chain_fwd_kernel<H, D, true, false, false, TH>));
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(kern, "cgmlp", dim3(nblk), dim3(256), smem, stream, a);
 }
 // the widths whose padded last tile runs as four-neuron blocks (Items) unless LGN_AMD_MLP_FULLTILE asks for the full tile
 template <int H, int D>

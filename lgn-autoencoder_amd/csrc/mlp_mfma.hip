@@ -168,7 +168,7 @@ template <int NT, int KSH, int MT, int NH>
 static int launch_mlp_mfma_mt(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   using G = Geo<NT, MT>;
   const size_t smem = sizeof(double) * (backward ? G::bwd_doubles() : G::fwd_doubles());
-  static_assert(sizeof(double) * G::bwd_doubles() <= 160 * 1024, "LDS budget");
+  static_assert(sizeof(double) * G::bwd_doubles() <= LGN_LDS_LIMIT, "LDS budget");
   // (the other depths -- mlp_depth 3 .. 5, round 5 -- share the instantiation with the activation switch)
   constexpr bool GEN = NH != 6;
   return backward ? launch_tile_kernel(mlp_bwd_mfma_kernel<NT, NH, KSH, MT, GEN>, mlp_bwd_mfma_kernel<NT, NH, KSH, MT, true>, a,

@@ -25,10 +25,10 @@ struct Geo : TileGeo<NT, MT> {
   static constexpr int MTB = 4;                         // M-tiles of a backward workgroup (64 rows)
   //                                          image   X, G tiles       input tiles    column sums
   static constexpr size_t bwd_doubles() { return T::WSIZE + 2 * MTB * T::TSIZE + MTB * T::T0SIZE + MTB * T::HP; }
-  static constexpr bool ONE_PASS = sizeof(double) * (T::WSIZE + 2 * MTB * T::TSIZE + MTB * T::T0SIZE + MTB * T::HP) <= 160 * 1024;
+  static constexpr bool ONE_PASS = sizeof(double) * (T::WSIZE + 2 * MTB * T::TSIZE + MTB * T::T0SIZE + MTB * T::HP) <= LGN_LDS_LIMIT;
   // two-pass backward (NT = 6): the activations of the first NHL hidden layers stay in LDS tiles of their own
   static constexpr int BWD_BASE = T::WSIZE + 2 * MT * T::TSIZE + MT * T::T0SIZE + MT * T::HP;
-  static constexpr int NHL_FIT = (160 * 1024 / 8 - BWD_BASE) / (MT * T::TSIZE);
+  static constexpr int NHL_FIT = (LGN_LDS_LIMIT / 8 - BWD_BASE) / (MT * T::TSIZE);
   static constexpr int NHL = NHL_FIT > 5 ? 5 : NHL_FIT;
   static constexpr size_t bwd2p_doubles() { return BWD_BASE + NHL * MT * T::TSIZE; }
 };
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(64 * MT * NT) void mlp_bwd_wide_2pass_kernel(MlpArg
 template <int NT, int NH = 6>
 static int launch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   using G = Geo<NT>;
-  static_assert(sizeof(double) * G::bwd2p_doubles() <= 160 * 1024 && sizeof(double) * G::fwd_doubles() <= 160 * 1024, "LDS budget");
+  static_assert(sizeof(double) * G::bwd2p_doubles() <= LGN_LDS_LIMIT && sizeof(double) * G::fwd_doubles() <= LGN_LDS_LIMIT, "LDS budget");
   // (mlp_depth 3 .. 5 share the instantiation with the activation switch)
   constexpr bool GEN = NH != 6;
   if (!backward)

@@ -21,6 +21,7 @@
 //
 // Everything a piece branches on is a template argument or a value the unrolled layer loops make a constant; none of them stamps.
 #pragma once
+#include "lds.hpp"
 #include "ops.hpp"
 
 namespace lgn {
@@ -302,11 +303,7 @@ __device__ __forceinline__ v4d slope_mul(const v4d& gin, const v4d& h, int act) 
 using MlpKernel = void (*)(MlpArgs<double>);
 inline int launch_tile_kernel(MlpKernel leaky, MlpKernel gen, const MlpArgs<double>& a, int nblk, int threads, size_t smem,
                               hipStream_t stream) {
-  const MlpKernel kern = a.act == 0 ? leaky : gen;
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(kern, dim3(nblk), dim3(threads), smem, stream, a);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(a.act == 0 ? leaky : gen, "cgmlp (tile)", dim3(nblk), dim3(threads), smem, stream, a);
 }
 
 }  // namespace tile

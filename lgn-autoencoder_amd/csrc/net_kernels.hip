@@ -6,6 +6,7 @@
 //                   + ChamferLoss (utils/losses/chamfer_loss/chamfer_loss.py:17-23) forward AND backward
 //   L1 + Adam       (utils/train.py:484-487, utils/initialize.py:156-158)
 // Each forward/backward pair is one workgroup per jet; weight-gradient partials are one row per jet.
+#include "lds.hpp"
 #include "net.hpp"
 #include "net_dev.hpp"
 #include "tail_dev.hpp"
@@ -1223,9 +1224,6 @@ __global__ __launch_bounds__(BLOCK) void l1_adam_kernel(long n, double* w, doubl
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-#define LGN_LDS_LAUNCH(kernel, what, smem)                                                                            \
-  LGN_CHECK_ARG((smem) <= 160 * 1024, what ": needs %zu B of LDS", (size_t)(smem));                                    \
-  if ((smem) > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem))
 static int grid_for(size_t total) {
   size_t g = (total + BLOCK - 1) / BLOCK;
   return (int)(g < 2048 ? (g ? g : 1) : 2048);
@@ -1243,64 +1241,43 @@ int enc_input_bwd(int B, int N, int C, int K, const double* p4, const double* xs
                   hipStream_t st) {
   LGN_CHECK_ARG(K >= 1 && (K == 1 || xs), "enc_input: %d input scalars need the extra-scalar array", K);
   const size_t smem = sizeof(double) * N * C * (2 * K + 2);
-  LGN_LDS_LAUNCH(enc_input_bwd_kernel, "enc_input_bwd", smem);
-  hipLaunchKernelGGL(enc_input_bwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, K, p4, xs, g_s, g_v, part);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(enc_input_bwd_kernel, "enc_input_bwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, K, p4, xs, g_s, g_v, part);
 }
 int enc_latent_fwd(int B, int N, int C, int Ts, int Tv, int pool, const double* s, const double* v, const double* wl0, const double* wl1,
                    double* lat_s, double* lat_v, int* idx, hipStream_t st) {
   LGN_CHECK_ARG(pool_valid(pool), "enc_latent_fwd: bad latent pooling code %d", pool);
   const size_t smem = sizeof(double) * lat_fwd_doubles(N, C, Ts, Tv, pool_canon(pool));
-  LGN_LDS_LAUNCH(enc_latent_fwd_kernel, "enc_latent_fwd", smem);
-  hipLaunchKernelGGL(enc_latent_fwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, Ts, Tv, pool_canon(pool), s, v, wl0, wl1, lat_s, lat_v, idx);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(enc_latent_fwd_kernel, "enc_latent_fwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, Ts, Tv, pool_canon(pool), s, v, wl0, wl1, lat_s, lat_v, idx);
 }
 int enc_latent_bwd(int B, int N, int C, int Ts, int Tv, int pool, const double* s, const double* v, const double* wl0, const double* wl1,
                    const double* g_lat_s, const double* g_lat_v, const int* idx, double* g_s, double* g_v, double* part,
                    hipStream_t st) {
   LGN_CHECK_ARG(pool_valid(pool), "enc_latent_bwd: bad latent pooling code %d", pool);
   const size_t smem = sizeof(double) * lat_bwd_doubles(N, C, Ts, Tv, pool_canon(pool));
-  LGN_LDS_LAUNCH(enc_latent_bwd_kernel, "enc_latent_bwd", smem);
-  hipLaunchKernelGGL(enc_latent_bwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, Ts, Tv, pool_canon(pool), s, v, wl0, wl1, g_lat_s, g_lat_v, idx,
+  return lds_launch(enc_latent_bwd_kernel, "enc_latent_bwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, Ts, Tv, pool_canon(pool), s, v, wl0, wl1, g_lat_s, g_lat_v, idx,
                      g_s, g_v, part);
-  LGN_CHECK_LAUNCH();
-  return 0;
 }
 int dec_input_fwd(int B, int N, int C, int Tin, const double* lat_v, const double* wg1, const double* w0, const double* w1,
                   double* pdec, double* s0, double* v0, hipStream_t st) {
   const size_t smem = sizeof(double) * dec_in_fwd_doubles(N, C, Tin);
-  LGN_LDS_LAUNCH(dec_input_fwd_kernel, "dec_input_fwd", smem);
-  hipLaunchKernelGGL(dec_input_fwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, Tin, lat_v, wg1, w0, w1, pdec, s0, v0);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(dec_input_fwd_kernel, "dec_input_fwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, Tin, lat_v, wg1, w0, w1, pdec, s0, v0);
 }
 int dec_input_bwd(int B, int N, int C, int Tin, const double* lat_v, const double* wg1, const double* w1, const double* pdec,
                   const double* g_p, const double* g_s0, const double* g_v0, double* g_lat_v, double* part, hipStream_t st) {
   const size_t smem = sizeof(double) * dec_in_bwd_doubles(N, C, Tin);
-  LGN_LDS_LAUNCH(dec_input_bwd_kernel, "dec_input_bwd", smem);
-  hipLaunchKernelGGL(dec_input_bwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, Tin, lat_v, wg1, w1, pdec, g_p,
+  return lds_launch(dec_input_bwd_kernel, "dec_input_bwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, Tin, lat_v, wg1, w1, pdec, g_p,
                      g_s0, g_v0, g_lat_v, part);
-  LGN_CHECK_LAUNCH();
-  return 0;
 }
 int dec_output_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, double loss_scale, int method,
                     double jscale, double* recon, double* loss_part, double* g_v, double* part, hipStream_t st) {
   const size_t smem = dec_out_loss_bytes(N, C);
-  LGN_LDS_LAUNCH(dec_output_loss_kernel, "dec_output_loss", smem);
-  hipLaunchKernelGGL(dec_output_loss_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, loss_scale, method, jscale, recon,
+  return lds_launch(dec_output_loss_kernel, "dec_output_loss", dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, loss_scale, method, jscale, recon,
                      loss_part, g_v, part);
-  LGN_CHECK_LAUNCH();
-  return 0;
 }
 int dec_output_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, double jscale,
                     double* recon_real, double* loss_part, hipStream_t st) {
   const size_t smem = dec_out_loss_bytes(N, C);
-  LGN_LDS_LAUNCH(dec_output_eval_kernel, "dec_output_eval", smem);
-  hipLaunchKernelGGL(dec_output_eval_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, method, jscale, recon_real, loss_part);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(dec_output_eval_kernel, "dec_output_eval", dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, target, method, jscale, recon_real, loss_part);
 }
 int eval_loss_sum(int B, int N, const uint8_t* mask, const double* loss_part, double* loss_out, hipStream_t st) {
   hipLaunchKernelGGL(eval_loss_sum_kernel, dim3(1), dim3(BLOCK), 0, st, B, N, mask, loss_part, loss_out);
@@ -1315,10 +1292,7 @@ int dec_output_fwd(int B, int N, int C, const double* v, const double* wo1, doub
 int chamfer_fwd(int B, int N, int M, const double* x, const double* y, int jet_features, double* loss_part, double* gx, double* gy,
                 hipStream_t st) {
   const size_t smem = sizeof(double) * ((size_t)(N + M) * 4 + BLOCK / 64 + 8) + sizeof(int) * (size_t)(N + M);
-  LGN_LDS_LAUNCH(chamfer_kernel, "chamfer", smem);
-  hipLaunchKernelGGL(chamfer_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, M, x, y, jet_features, loss_part, gx, gy);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(chamfer_kernel, "chamfer", dim3(B), dim3(BLOCK), smem, st, B, N, M, x, y, jet_features, loss_part, gx, gy);
 }
 // Plan-time fit queries (lgn_encoder_end_lds_bytes / lgn_decoder_end_lds_bytes / lgn_junction_lds_bytes): the LDS the per-jet end
 // stages of a network need, from the same expressions as the launchers above -- so that the callers choose the per-operator path
@@ -1339,43 +1313,40 @@ size_t decoder_end_lds_bytes(int N, int C0, int Tin, int CL) {
   m = o > m ? o : m;
   return ob > m ? ob : m;
 }
+// The two stages of a junction keep their LDS blocks side by side (all fetches up front) while that stays within 64 KB per
+// workgroup; larger jets run them in turn on shared LDS.  One statement of that decision and of the sizes, for the two launchers
+// and the plan-time query (pool: canonical).
+struct JunctionLds {
+  bool overlap_fwd, overlap_bwd;
+  size_t fwd, bwd;
+  JunctionLds(int N, int CL, int Ts, int Tv, int pool, int C0) {
+    const int Tin = pool_blocks(pool) * Tv;
+    const size_t nl = lat_fwd_doubles(N, CL, Ts, Tv, pool), nd = dec_in_fwd_doubles(N, C0, Tin), ny = lat_y_doubles(N, Ts, Tv, pool);
+    overlap_fwd = sizeof(double) * (nl + nd) <= 64 * 1024;
+    fwd = sizeof(double) * (overlap_fwd ? nl + nd : ny + (nl - ny > nd ? nl - ny : nd) + (pool_is_mix(pool) ? (size_t)Tin * 8 : 0));
+    const size_t bd = dec_in_bwd_doubles(N, C0, Tin), bl = lat_bwd_doubles(N, CL, Ts, Tv, pool);
+    overlap_bwd = sizeof(double) * (bd + bl + (size_t)Tin * 8) <= 64 * 1024;
+    bwd = sizeof(double) * ((overlap_bwd ? bd + bl : (bd > bl ? bd : bl)) + (size_t)Tin * 8);
+  }
+};
 size_t junction_lds_bytes(int N, int CL, int Ts, int Tv, int pool, int C0) {
-  pool = pool_canon(pool);
-  const int Tin = pool_blocks(pool) * Tv;
-  const size_t nl = lat_fwd_doubles(N, CL, Ts, Tv, pool), nd = dec_in_fwd_doubles(N, C0, Tin), ny = lat_y_doubles(N, Ts, Tv, pool);
-  const bool ov = sizeof(double) * (nl + nd) <= 64 * 1024;
-  const size_t fwd = sizeof(double) * (ov ? nl + nd : ny + (nl - ny > nd ? nl - ny : nd) + (pool_is_mix(pool) ? (size_t)Tin * 8 : 0));
-  const size_t bd = dec_in_bwd_doubles(N, C0, Tin), bl = lat_bwd_doubles(N, CL, Ts, Tv, pool);
-  const bool ovb = sizeof(double) * (bd + bl + (size_t)Tin * 8) <= 64 * 1024;
-  const size_t bwd = sizeof(double) * ((ovb ? bd + bl : (bd > bl ? bd : bl)) + (size_t)Tin * 8);
-  return fwd > bwd ? fwd : bwd;
+  const JunctionLds L(N, CL, Ts, Tv, pool_canon(pool), C0);
+  return L.fwd > L.bwd ? L.fwd : L.bwd;
 }
 
 int dec_output_bwd(int B, int N, int C, const double* v, const double* wo1, const double* g_recon, double* g_v, double* part,
                    hipStream_t st) {
   const size_t smem = sizeof(double) * ((size_t)N * 8 + (size_t)N * C * 2);
-  LGN_CHECK_ARG(smem <= 160 * 1024, "dec_output_bwd: needs %zu B of LDS", smem);
-  if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dec_output_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  hipLaunchKernelGGL(dec_output_bwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, g_recon, g_v, part);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  return lds_launch(dec_output_bwd_kernel, "dec_output_bwd", dim3(B), dim3(BLOCK), smem, st, B, N, C, v, wo1, g_recon, g_v, part);
 }
-// The two stages of a junction keep their LDS blocks side by side (all fetches up front) while that stays within 64 KB per
-// workgroup; larger jets run them in turn on shared LDS.
 int junction_fwd(int B, int N, int CL, int Ts, int Tv, int pool, const double* s, const double* v, const double* wl0, const double* wl1,
                  double* lat_s, double* lat_v, int* idx, int C0, const double* wg1, const double* w0, const double* w1, double* pdec,
                  double* s0, double* v0, hipStream_t st) {
   LGN_CHECK_ARG(pool_valid(pool), "junction_fwd: bad latent pooling code %d", pool);
   pool = pool_canon(pool);
-  const size_t nl = lat_fwd_doubles(N, CL, Ts, Tv, pool), nd = dec_in_fwd_doubles(N, C0, pool_blocks(pool) * Tv), ny = lat_y_doubles(N, Ts, Tv, pool);
-  const int overlap = sizeof(double) * (nl + nd) <= 64 * 1024;
-  const size_t smem = sizeof(double) * (overlap ? nl + nd : ny + (nl - ny > nd ? nl - ny : nd) +
-                                                            (pool_is_mix(pool) ? (size_t)pool_blocks(pool) * Tv * 8 : 0));
-  LGN_LDS_LAUNCH(junction_fwd_kernel, "junction_fwd", smem);
-  hipLaunchKernelGGL(junction_fwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, CL, Ts, Tv, s, v, wl0, wl1, lat_s, lat_v, idx, C0, wg1,
-                     w0, w1, pdec, s0, v0, overlap, pool);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  const JunctionLds L(N, CL, Ts, Tv, pool, C0);
+  return lds_launch(junction_fwd_kernel, "junction_fwd", dim3(B), dim3(BLOCK), L.fwd, st, B, N, CL, Ts, Tv, s, v, wl0, wl1, lat_s, lat_v, idx, C0, wg1,
+                    w0, w1, pdec, s0, v0, (int)L.overlap_fwd, pool);
 }
 int junction_bwd(int B, int N, int C0, int Tin, const double* lat_v, const double* wg1, const double* w1, const double* pdec,
                  const double* g_p, const double* g_s0, const double* g_v0, double* g_lat_v, double* part_dec, int CL, int Ts, int Tv,
@@ -1385,14 +1356,9 @@ int junction_bwd(int B, int N, int C0, int Tin, const double* lat_v, const doubl
   pool = pool_canon(pool);
   LGN_CHECK_ARG(Tin == pool_blocks(pool) * Tv, "junction_bwd: the decoder takes the %d pooled latent vectors, got Tin = %d",
                 pool_blocks(pool) * Tv, Tin);
-  const size_t nd = dec_in_bwd_doubles(N, C0, Tin), nl = lat_bwd_doubles(N, CL, Ts, Tv, pool);
-  const int overlap = sizeof(double) * (nd + nl + (size_t)Tin * 8) <= 64 * 1024;
-  const size_t smem = sizeof(double) * ((overlap ? nd + nl : (nd > nl ? nd : nl)) + (size_t)Tin * 8);
-  LGN_LDS_LAUNCH(junction_bwd_kernel, "junction_bwd", smem);
-  hipLaunchKernelGGL(junction_bwd_kernel, dim3(B), dim3(BLOCK), smem, st, B, N, C0, Tin, lat_v, wg1, w1, pdec, g_p, g_s0, g_v0, g_lat_v,
-                     part_dec, CL, Ts, Tv, s, v, wl0, wl1, g_lat_s, idx, g_s, g_v, part_enc, overlap, pool);
-  LGN_CHECK_LAUNCH();
-  return 0;
+  const JunctionLds L(N, CL, Ts, Tv, pool, C0);
+  return lds_launch(junction_bwd_kernel, "junction_bwd", dim3(B), dim3(BLOCK), L.bwd, st, B, N, C0, Tin, lat_v, wg1, w1, pdec, g_p, g_s0, g_v0, g_lat_v,
+                    part_dec, CL, Ts, Tv, s, v, wl0, wl1, g_lat_s, idx, g_s, g_v, part_enc, (int)L.overlap_bwd, pool);
 }
 
 // loss_out: 3 results followed by LGN_FINALIZE_SCRATCH doubles of scratch (per-workgroup |w| partials)

@@ -22,7 +22,7 @@
 #pragma clang fp contract(off)
 #include <math.h>
 
-#include "common.hpp"
+#include "lds.hpp"
 #include "../../include/lgn_amd.h"
 #include "polar_dev.hpp"     // wrap_phi
 #include "sort_dev.hpp"
@@ -594,16 +594,9 @@ int lgn_jet_images_f64(const double* jets, const double* frame_jets, int B, int 
                                                                                               any_far);
   }
   const size_t smem = ji_lds_bytes(N, npix);
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(jet_image_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) {
-      set_error("jet_images: %zu bytes of LDS per workgroup (N = %d, npix = %d) were refused: %s", smem, N, npix, hipGetErrorString(e));
-      return (int)e;
-    }
-  }
-  jet_image_kernel<<<(l.parts + JW - 1) / JW, 64 * JW, smem, s>>>(jets, mode ? frame : nullptr, any_far, B, N, npix, maxR,
-                                                                first_n < B ? first_n : B, l.parts, images, part);
+  if (const int rc = lds_launch(jet_image_kernel, "jet_images", dim3((l.parts + JW - 1) / JW), dim3(64 * JW), smem, s, jets, mode ? frame : nullptr,
+                                any_far, B, N, npix, maxR, first_n < B ? first_n : B, l.parts, images, part))
+    return rc;
   jet_average_kernel<<<(npix * npix + 255) / 256, 256, 0, s>>>(part, l.parts, npix * npix, B, average);
   LGN_CHECK_LAUNCH();
   return 0;

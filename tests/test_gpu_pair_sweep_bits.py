@@ -6,7 +6,10 @@ each case gave the same hashes in two runs and none was left out: profiles/r11_p
 generators with fixed seeds.  Shapes (C, CO, N, B) are the smallest that reach each instantiation: 257 jets of 9 particles = whole
 jets per workgroup with a padded third group (symmetric backward: tiles above, on and below the diagonal); 2 jets of 9 =
 level_jet_split with the rs = 2 and rs = 4 receiver split; N = 41 = level_bwd_mix + level_bwd_sweep_enc with four waves; N = 150,
-one jet = eight waves and several receiver chunks; N = 33 at maxdim 3 = the moments kernels of generic_moments.hip by size."""
+one jet = eight waves and several receiver chunks; N = 33 at maxdim 3 = the moments kernels of generic_moments.hip by size; five packed
+components (":q5") = the two-components-per-thread instantiations of generic_moments2.hip; N = 150 at maxdim 3 = the smallest round
+shape whose features exceed the LDS, read from global memory by generic_moments.hip.  (The q5 and N = 150 moments cases were
+recorded from the library as it was before the kernels' launches went through csrc/lds.hpp, each the same in two runs.)"""
 import json
 import os
 
@@ -21,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 ORDERED = {"LGN_AMD_BWD_ORDERED": "1"}
-# id -> (kind, decoder, C, CO, N, B, environment switches)
+# id -> (kind, decoder, C, CO, N, B, environment switches); moments cases: CO = packed components per node (0: Q3, maxdim = 3)
 CASES = {
     "enc:4,4,9,257": ("level", False, 4, 4, 9, 257, {}),
     "enc:4,4,9,257:ordered": ("level", False, 4, 4, 9, 257, ORDERED),
@@ -45,6 +48,11 @@ CASES = {
     "m3:dec:4,9,2:pairwise": ("moments", True, 4, 0, 9, 2, {"LGN_AMD_DEC_PAIRWISE": "1"}),
     "m3:enc:4,33,1": ("moments", False, 4, 0, 33, 1, {}),
     "m3:dec:4,33,1": ("moments", True, 4, 0, 33, 1, {}),
+    "m3:enc:4,9,2:q5": ("moments", False, 4, 5, 9, 2, {}),
+    "m3:enc:4,9,2:q5:split": ("moments", False, 4, 5, 9, 2, {"LGN_AMD_MOMENTS_SPLIT": "1"}),
+    "m3:dec:4,9,2:q5:pairwise": ("moments", True, 4, 5, 9, 2, {"LGN_AMD_DEC_PAIRWISE": "1"}),
+    "m3:enc:4,150,1": ("moments", False, 4, 0, 150, 1, {}),
+    "m3:dec:4,150,1": ("moments", True, 4, 0, 150, 1, {}),
     # the dead-scalar (NOS) form of the symmetric backward: the last encoder level of a training step on whole-jet workgroups
     "step:257x9": ("step", False, 0, 0, 9, 257, {}),
 }
@@ -90,13 +98,14 @@ def level_bits(decoder, C, CO, N, B):
     return U.sha(bufs)
 
 
-def moments_bits(decoder, C, N, B):
+def moments_bits(decoder, C, N, B, Q=0):
     from lgn import _native as Nn
-    g = torch.Generator().manual_seed(3000 + 10 * C + N + int(decoder))
+    g = torch.Generator().manual_seed(3000 + 10 * C + N + int(decoder) + 100 * Q)
+    Q = Q or Q3
     rn = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=g)      # noqa: E731
     rad = _radial(decoder, C, g)
-    X = rn(2, B, N, C, Q3).to(DEV)
-    gU, gX = rn(B, N, C, Q3, 5, 2).to(DEV), rn(2, B, N, C, Q3).to(DEV)
+    X = rn(2, B, N, C, Q).to(DEV)
+    gU, gX = rn(B, N, C, Q, 5, 2).to(DEV), rn(2, B, N, C, Q).to(DEV)
     p, mask = _momenta(decoder, N, B, C, g)
     Um = Nn.moments_fwd(decoder, X, p, mask, rad)
     g_p = torch.zeros_like(p) if decoder else None
@@ -128,7 +137,7 @@ def case_bits(case):
     if kind == "level":
         return level_bits(decoder, C, CO, N, B)
     if kind == "moments":
-        return moments_bits(decoder, C, N, B)
+        return moments_bits(decoder, C, N, B, CO)
     return step_bits(N, B)
 
 
