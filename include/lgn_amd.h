@@ -590,6 +590,45 @@ int lgn_emd_relative_grad_f64(const double* recons, const double* target, int B,
                               double* g_target /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
 int lgn_emd_debug_max_augmentations(int* out, int reset);
 
+/* ---- matrices of EMDs and energyflow's options (csrc/emd_pairs.hip, csrc/emd_plan.hpp): energyflow.emd.emds and the R, beta, norm and
+ * periodic_phi arguments of energyflow.emd.emd, around the solver above (one wavefront per pair; a persistent grid strides over the
+ * pair numbers p in [0, P), 64-bit).  These only ADD functions: LGN_AMD_ABI_VERSION stays 19.
+ *   mode   LGN_EMD_PAIRS_FULL     p = i B1 + j: ev0[i] against ev1[j], P = B0 B1; emd, status [B0][B1]
+ *          LGN_EMD_PAIRS_UPPER    one set against itself (ev1 NULL or ev0, n == m, B1 == B0 = B): only i < j is solved, row-major over
+ *                                 the upper triangle, P = B (B - 1) / 2; emd, status [B][B], [i][j] and [j][i] get the same value, the
+ *                                 diagonal is +0.0 with status 0 whatever the event holds.  B == 1 solves nothing and writes the one zero.
+ *          LGN_EMD_PAIRS_ALIGNED  B1 == B0, p = i: ev0[i] against ev1[i] as lgn_emd_f64 pairs them; emd, status [B0]; flow, dual0, dual1
+ *                                 (each nullable) in the layouts of lgn_emd_f64.  In the other modes a non-null one is refused.
+ *   lgn_emd_pairs_decode: the pair (i, j) of pair number p, on the host (the kernel decodes with the same function): integer-exact.
+ *   opts   NULL: R = 1, beta = 1, norm = 0, periodic_phi = 0, at which every result has the bits lgn_emd_f64 gives for the same pair.
+ *          energyflow is not available to this project: the definition here is the specification.  Every step is one rounded operation:
+ *            dphi   = phi_i - phi'_j;  periodic_phi: dphi = pi - |pi - |phi_i - phi'_j|| with pi the double M_PI (the minimum image
+ *                     for |phi_i - phi'_j| <= 2 pi; applied as written outside that)
+ *            theta  = sqrt(dy^2 + dphi^2), divided by R unless R == 1
+ *            cost   = theta for beta == 1, theta * theta for beta == 2, pow(theta, beta) otherwise.  The fictitious particle's cost
+ *                     stays 1: the term |sum pT - sum pT'| is not raised to beta.
+ *            norm   each event's weights are divided by that event's sum (summed as staged); the fictitious particle gets no weight;
+ *                     the rounding difference of the two normalised sums is dropped under the leftover tolerance of lgn_emd_f64,
+ *                     computed from the normalised sums; flow, dual0 and dual1 refer to the normalised weights.  With norm an event
+ *                     without weight on either side of a pair is LGN_EMD_EMPTY (without: only both sides weightless, as above).
+ *   status is per pair: an invalid event (NaN, +-inf, a negative weight) marks every pair it takes part in and no other.
+ *   work   at least lgn_emd_workspace_bytes(min(P, INT_MAX), max(n, m)) bytes, 8-byte aligned (0 bytes: may be NULL).
+ *   Refused before any launch (negative return): null ev0, emd or status (ev1 outside UPPER); B0 or B1 < 1; n or m outside
+ *   1 .. LGN_EMD_NMAX; an unknown mode; UPPER with n != m, B0 != B1 or an ev1 that is neither NULL nor ev0; ALIGNED with B0 != B1; R or
+ *   beta not a finite positive number; flow or duals outside ALIGNED; a short, missing or misaligned workspace.  Nothing is allocated,
+ *   nothing waits on the host, no buffer is cleared by a memset: capturable.  Gradients under the options are not offered. */
+#define LGN_EMD_PAIRS_FULL 0
+#define LGN_EMD_PAIRS_UPPER 1
+#define LGN_EMD_PAIRS_ALIGNED 2
+typedef struct lgn_emd_opts {
+  double R, beta;
+  int norm, periodic_phi;
+} lgn_emd_opts;
+int lgn_emd_pairs_decode(int mode, long long p, int B0, int B1, int* i, int* j);
+int lgn_emd_pairs_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/, int B0, int B1, int n, int m, int mode,
+                      const lgn_emd_opts* opts /*nullable*/, double* emd, double* flow /*nullable*/, double* dual0 /*nullable*/,
+                      double* dual1 /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
+
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */

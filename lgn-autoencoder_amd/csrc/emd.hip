@@ -32,14 +32,14 @@
 
 #include "lds.hpp"
 #include "../../include/lgn_amd.h"
+#include "emd_plan.hpp"
 #include "emd_wave.hpp"
 #include "polar_dev.hpp"
 
 namespace lgn {
 namespace {
 
-constexpr int EMD_LDS_BUDGET = 64 * 1024;      // plan-time budget of one wave's LDS (no opt-in launch attribute below it)
-constexpr int EMD_GLOBAL_WAVES = 2048;         // resident waves of the workspace path: 8 per CU
+// (the LDS and workspace sizes the launchers below plan with: emd_plan.hpp, shared with emd_pairs.hip)
 constexpr int EMD_AUG_PER_NODE = 16;           // cap of the augmentations of one problem per node
 
 static_assert(EMD_NMAX == LGN_EMD_NMAX, "include/lgn_amd.h and emd_wave.hpp agree on the largest event");
@@ -63,18 +63,6 @@ struct EmdCost {               // c[i][j] = theta_ij, 1 to or from the fictitiou
 };
 
 __device__ __forceinline__ bool finite(double x) { return fabs(x) < INFINITY; }      // false for NaN and +-inf
-
-__host__ __device__ constexpr long long emd_lds_doubles(int n, int m, bool lds_flow) {
-  return 5ll * (n + 1) + 8 + (lds_flow ? (long long)(n + 1) * (m + 1) : 0);
-}
-__host__ __device__ constexpr long long emd_lds_total(int n, int m, bool lds_flow) {
-  return 8 * emd_lds_doubles(n, m, lds_flow) + 8ll * (n + 1);
-}
-inline bool emd_flow_in_lds(int N) { return emd_lds_total(N, N, true) <= EMD_LDS_BUDGET; }
-inline long long emd_workspace(long long B, int N) {
-  if (emd_flow_in_lds(N)) return 0;
-  return (B < EMD_GLOBAL_WAVES ? B : EMD_GLOBAL_WAVES) * (long long)(N + 1) * (N + 1) * 8;
-}
 
 struct EmdGradOut {            // the gradient outputs: the one extra kernel argument of the GRAD variant
   double *g0, *g1;             // [B][n][W], [B][m][W] (each nullable): W = 3 columns (pT, y, phi), REL: W = 4 Cartesian (E, px, py, pz)
@@ -388,15 +376,6 @@ int launch_emd(const double* a0, const double* a1, int B, int n, int m, double R
   return -1;
 }
 
-int check_work(const char* who, int B, int N, const void* work, long long work_bytes) {
-  const long long need = emd_workspace(B, N);
-  if (need == 0) return 0;
-  LGN_CHECK_ARG(work, "%s: N = %d keeps the flow in a workspace: null work (lgn_emd_workspace_bytes: %lld bytes)", who, N, need);
-  LGN_CHECK_ARG(work_bytes >= need, "%s: workspace of %lld bytes is too short (%lld needed)", who, work_bytes, need);
-  LGN_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 7) == 0, "%s: the workspace must be 8-byte aligned", who);
-  return 0;
-}
-
 }  // namespace
 }  // namespace lgn
 
@@ -426,7 +405,7 @@ int lgn_emd_f64(const double* ev0, const double* ev1, int B, int n, int m, doubl
   LGN_CHECK_ARG(n >= 1 && n <= LGN_EMD_NMAX && m >= 1 && m <= LGN_EMD_NMAX, "emd: n = %d, m = %d outside 1 .. %d", n, m, LGN_EMD_NMAX);
   LGN_CHECK_ARG(ev0 && ev1 && emd && status, "emd: null pointer (ev0, ev1, emd, status)");
   LGN_CHECK_ARG(R > 0.0 && R < INFINITY, "emd: R = %g (need a finite R > 0)", R);
-  if (check_work("emd", B, n > m ? n : m, work, work_bytes) != 0) return -1;
+  if (emd_check_work("emd", B, n > m ? n : m, work, work_bytes) != 0) return -1;
   return launch_emd<false>(ev0, ev1, B, n, m, R, emd, flow, dual0, dual1, status, static_cast<double*>(work), (hipStream_t)stream);
 }
 
@@ -435,7 +414,7 @@ int lgn_emd_relative_f64(const double* recons, const double* target, int B, int 
   LGN_CHECK_ARG(B >= 1, "emd_relative: B = %d (need B >= 1)", B);
   LGN_CHECK_ARG(N >= 1 && N <= LGN_EMD_NMAX, "emd_relative: N = %d outside 1 .. %d", N, LGN_EMD_NMAX);
   LGN_CHECK_ARG(recons && target && emd && status, "emd_relative: null pointer (recons, target, emd, status)");
-  if (check_work("emd_relative", B, N, work, work_bytes) != 0) return -1;
+  if (emd_check_work("emd_relative", B, N, work, work_bytes) != 0) return -1;
   return launch_emd<true>(recons, target, B, N, N, 1.0, emd, nullptr, nullptr, nullptr, status, static_cast<double*>(work),
                           (hipStream_t)stream);
 }
@@ -447,7 +426,7 @@ int lgn_emd_grad_f64(const double* ev0, const double* ev1, int B, int n, int m, 
   LGN_CHECK_ARG(g0 || g1, "emd_grad: no gradient output (g0 and g1 are both null; lgn_emd_f64 is the call without gradients)");
   LGN_CHECK_ARG(ev0 && ev1 && emd && status, "emd_grad: null pointer (ev0, ev1, emd, status)");
   LGN_CHECK_ARG(R > 0.0 && R < INFINITY, "emd_grad: R = %g (need a finite R > 0)", R);
-  if (check_work("emd_grad", B, n > m ? n : m, work, work_bytes) != 0) return -1;
+  if (emd_check_work("emd_grad", B, n > m ? n : m, work, work_bytes) != 0) return -1;
   return launch_emd<false>(ev0, ev1, B, n, m, R, emd, flow, dual0, dual1, status, static_cast<double*>(work), (hipStream_t)stream,
                            EmdGradOut{g0, g1});
 }
@@ -457,7 +436,7 @@ int lgn_emd_relative_grad_f64(const double* recons, const double* target, int B,
   LGN_CHECK_ARG(B >= 1, "emd_relative_grad: B = %d (need B >= 1)", B);
   LGN_CHECK_ARG(N >= 1 && N <= LGN_EMD_NMAX, "emd_relative_grad: N = %d outside 1 .. %d", N, LGN_EMD_NMAX);
   LGN_CHECK_ARG(recons && target && emd && g_recons && status, "emd_relative_grad: null pointer (recons, target, emd, g_recons, status)");
-  if (check_work("emd_relative_grad", B, N, work, work_bytes) != 0) return -1;
+  if (emd_check_work("emd_relative_grad", B, N, work, work_bytes) != 0) return -1;
   return launch_emd<true>(recons, target, B, N, N, 1.0, emd, nullptr, nullptr, nullptr, status, static_cast<double*>(work),
                           (hipStream_t)stream, EmdGradOut{g_recons, g_target});
 }

@@ -159,6 +159,11 @@ class OptimDesc(C.Structure):
                 ("beta1", C.c_double), ("beta2", C.c_double), ("alpha", C.c_double), ("momentum", C.c_double)]
 
 
+class EmdOpts(C.Structure):
+    """lgn_emd_opts of include/lgn_amd.h."""
+    _fields_ = [("R", C.c_double), ("beta", C.c_double), ("norm", C.c_int), ("periodic_phi", C.c_int)]
+
+
 OPT_ADAM, OPT_RMSPROP = 0, 1
 LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
 ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
@@ -219,6 +224,10 @@ _SIGNATURES.update({
     # (recons, target, B, N, emd, g_recons, g_target, status, work, work_bytes, stream)
     "lgn_emd_relative_grad_f64": [_vp, _vp, _i, _i] + [_vp] * 5 + [_ll, _vp],
     "lgn_emd_debug_max_augmentations": [_ip, _i],
+    # (mode, p, B0, B1, i [host], j [host])
+    "lgn_emd_pairs_decode": [_i, _ll, _i, _i, _ip, _ip],
+    # (ev0, ev1, B0, B1, n, m, mode, opts, emd, flow, dual0, dual1, status, work, work_bytes, stream)
+    "lgn_emd_pairs_f64": [_vp, _vp] + [_i] * 5 + [C.POINTER(EmdOpts)] + [_vp] * 6 + [_ll, _vp],
     # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
     "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],
     # (counts, max_bins, edges, max_edges, n_edges [host], cols, fwhm, stream)
@@ -256,6 +265,7 @@ ROC_TILE, ROC_MAX_COLS = 2048, 65535        # LGN_ROC_TILE, LGN_ROC_MAX_COLS of 
 ROC_NONFINITE, ROC_SINGLE_CLASS, ROC_BAD_LABEL, ROC_NAN = 1, 2, 4, 8    # LGN_ROC_* status bits
 EMD_NMAX = 191                              # LGN_EMD_NMAX of include/lgn_amd.h
 EMD_INVALID, EMD_EMPTY, EMD_ITER, EMD_INFEASIBLE = 1, 2, 4, 8    # LGN_EMD_* status bits
+EMD_PAIRS_FULL, EMD_PAIRS_UPPER, EMD_PAIRS_ALIGNED = 0, 1, 2     # LGN_EMD_PAIRS_* modes
 HIST_MAX_EDGES, HIST_MAX_COLS = 1025, 16    # LGN_HIST_MAX_EDGES, LGN_HIST_MAX_COLS of include/lgn_amd.h
 # LGN_STATS_*, LGN_STAT_* (the positions in a column's statistics, the reference's dict order) and LGN_JET_IMAGE_* of include/lgn_amd.h
 STATS_TILE, STATS_MAX_COLS, STATS_EMPTY, STATS_NONFINITE = 2048, 16, 1, 2

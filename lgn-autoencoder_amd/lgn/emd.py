@@ -7,9 +7,12 @@ utils/jet_analysis/anomaly_detection.py, which calls ``energyflow.emd.emd`` per 
     EMD      = min over f >= 0 of sum f_ij theta_ij + |sum pT - sum pT'|
                with sum_j f_ij <= pT_i, sum_i f_ij <= pT'_j, sum f_ij = min(sum pT, sum pT')
 
-energyflow's defaults otherwise: beta = 1, norm = False, Euclidean ground distance, no periodic phi.  energyflow was not available when
-this was written: the definition above, from its documentation, is the specification (include/lgn_amd.h; tests/_emd_ref.py restates it
-as an LP).  What energyflow returns for two weightless events is not known; here that is a status bit and NaN.
+at energyflow's defaults beta = 1, norm = False, no periodic phi; ``emd`` takes those three as keywords and ``emds`` is
+energyflow.emd.emds, the matrix of distances between every event of one set and every event of another or of one set with itself, in
+one launch that reads each event where it lies (csrc/emd_pairs.hip).  The ground distance is Euclidean in (y, phi).  energyflow was not
+available when this was written: the definitions in include/lgn_amd.h, from its documentation, are the specification (tests/_emd_ref.py
+and tests/_emd_pairs_ref.py restate them as LPs).  What energyflow returns for two weightless events is not known; here that is a status
+bit and NaN.
 
 The distance is differentiable here as well: by LP sensitivity the gradient with respect to positions and weights is a closed form
 in the optimal flow and the potentials, which the solving wavefront evaluates as an epilogue of the same launch (``emd_grad``,
@@ -17,8 +20,10 @@ in the optimal flow and the potentials, which the solving wavefront evaluates as
 ``HybridLoss`` are training losses on top of it for the module-API steps.  What is offered is the exact LP on the relative-polar frame
 of the anomaly score, so that the training loss and the score are one quantity.  What is NOT offered: jetnet's regularised
 differentiable QP, which the reference's ``EMDLoss`` wraps -- and that wrapper unbinds its (eta, phi, pt) columns as (eta, pt, phi),
-handing jetnet an angle ratio as the weight, which is not reproduced; periodic phi, beta != 1 and normalised weights; the names
-``--loss-choice emd`` / ``hybrid`` and the EMD inside the whole-step native calls, which stay refused.  There is no CPU fallback.
+handing jetnet an angle ratio as the weight, which is not reproduced; gradients under beta != 1, norm or periodic phi (``emd_grad``,
+``emd_differentiable`` and the losses are the default options only) and gradients of ``emds``; energyflow's gdim, spherical measure,
+coords and mask; the names ``--loss-choice emd`` / ``hybrid`` and the EMD inside the whole-step native calls, which stay refused.
+There is no CPU fallback.
 """
 from typing import Optional
 
@@ -30,11 +35,14 @@ NMAX = N.EMD_NMAX
 INVALID, EMPTY, ITER, INFEASIBLE = N.EMD_INVALID, N.EMD_EMPTY, N.EMD_ITER, N.EMD_INFEASIBLE
 
 
-def status_message(s: int) -> str:
+FULL, UPPER, ALIGNED = N.EMD_PAIRS_FULL, N.EMD_PAIRS_UPPER, N.EMD_PAIRS_ALIGNED
+
+
+def status_message(s: int, norm: bool = False) -> str:
     if s & INVALID:
         return "events hold NaN, infinity or a negative weight"
     if s & EMPTY:
-        return "both events are weightless"
+        return "an event is weightless and cannot be normalised" if norm else "both events are weightless"
     if s & ITER:
         return "the cap of the solver's augmentations was hit"
     return "the weights left over exceed the rounding of the two sums"
@@ -55,14 +63,67 @@ def flow_in_lds(n: int) -> bool:
     return nbytes >= 8 * (n + 1) * (n + 1)
 
 
+def _options(who: str, R, beta, norm, periodic_phi) -> "N.EmdOpts":
+    if not (R > 0 and R < float("inf")):
+        raise ValueError(f"{who} needs a finite R > 0; got {R}")
+    if not (beta > 0 and beta < float("inf")):
+        raise ValueError(f"{who} needs a finite beta > 0; got {beta}")
+    return N.EmdOpts(float(R), float(beta), int(bool(norm)), int(bool(periodic_phi)))
+
+
+def _pairs_workspace(P: int, n: int, dev) -> Optional[torch.Tensor]:
+    return _workspace(min(P, 2 ** 31 - 1), n, dev)
+
+
+def emds(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, R: float = 1.0, beta: float = 1.0, norm: bool = False,
+         periodic_phi: bool = False, return_status: bool = False):
+    """energyflow.emd.emds: the (B0, B1) fp64 device tensor of the EMDs of every event of X0 (B0, n, 3) against every event of X1
+    (B1, m, 3), zero-padded events of (pT, y, phi), in one launch and without a gathered copy of the events.  X1=None is the symmetric
+    form, X0 against itself: the pairs i < j are solved and mirrored, the diagonal is 0.  R, beta, norm and periodic_phi as in emd().
+    Raises ValueError at the first pair with a status bit; return_status=True returns the (B0, B1) int32 status as well (the distance
+    of such a pair is NaN) and does not wait for the device.  No gradients."""
+    sym = X1 is None
+    a, b = X0, (X0 if sym else X1)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3:
+        raise ValueError(f"emds takes events (B0, n, 3) and (B1, m, 3) of (pT, y, phi); got {tuple(a.shape)} and {tuple(b.shape)}")
+    B0, B1, n, m = int(a.shape[0]), int(b.shape[0]), int(a.shape[1]), int(b.shape[1])
+    if not (1 <= n <= NMAX and 1 <= m <= NMAX):
+        raise ValueError(f"emd supports 1 <= n, m <= {NMAX} particles per event; got n = {n}, m = {m}")
+    opts = _options("emds", R, beta, norm, periodic_phi)
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError(f"lgn (MI355X build): emds runs only in the HIP kernels of liblgn_amd.so on a GPU device; got tensors on "
+                           f"'{a.device}' and '{b.device}'. There is no CPU fallback.")
+    a = N.f64(a.to(torch.float64))
+    b = a if sym else N.f64(b.to(torch.float64))
+    dev = a.device
+    out = torch.empty(B0, B1, device=dev, dtype=torch.float64)
+    status = torch.empty(B0, B1, device=dev, dtype=torch.int32)
+    if B0 > 0 and B1 > 0:
+        P = B0 * (B0 - 1) // 2 if sym else B0 * B1
+        work = _pairs_workspace(max(P, 1), max(n, m), dev)
+        rc = N.lib().lgn_emd_pairs_f64(N.ptr(a), None if sym else N.ptr(b), B0, B1, n, m, UPPER if sym else FULL, opts, N.ptr(out), None,
+                                       None, None, N.ptr(status), N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_pairs_f64")
+    if not return_status:
+        bad = status.nonzero().cpu().numpy()
+        if len(bad):
+            i, j = int(bad[0][0]), int(bad[0][1])
+            raise ValueError(f"emds: {status_message(int(status[i, j].item()), bool(norm))} (pair ({i}, {j}), {len(bad)} pair(s) in all)")
+    return (out, status) if return_status else out
+
+
 def emd(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_flow: bool = False, return_duals: bool = False,
-        return_status: bool = False):
+        return_status: bool = False, beta: float = 1.0, norm: bool = False, periodic_phi: bool = False):
     """EMD of events of (pT, y, phi) particles: ev0 (B, n, 3) against ev1 (B, m, 3) device tensors (or one (n, 3) against one (m, 3)),
     n != m allowed, 1 <= n, m <= 191.  Returns the (B,) fp64 device tensor of distances (a 0-dim tensor for one pair); with
     return_flow also the optimal flow (B, n + 1, m + 1), with return_duals also the potentials (B, n + 1) and (B, m + 1) -- row n and
     column m are the fictitious particle that carries the weight difference.  Raises ValueError when a pair has a status bit (NaN,
     infinity or a negative weight; both events weightless; ...); return_status=True returns the (B,) int32 status last instead (the
-    distance of such a pair is NaN) and does not wait for the device."""
+    distance of such a pair is NaN) and does not wait for the device.
+    beta, norm, periodic_phi: energyflow's arguments, as include/lgn_amd.h defines them -- the angular cost is theta^beta (the term of
+    the weight difference is not raised), norm divides each event's weights by that event's sum (flow and potentials then refer to the
+    normalised weights; an event without weight is a status bit), periodic_phi takes the minimum image of the phi difference.  At
+    their defaults the call is the one it always was; otherwise the pairs kernel solves (csrc/emd_pairs.hip)."""
     single = ev0.dim() == 2
     a, b = (ev0.unsqueeze(0), ev1.unsqueeze(0)) if single else (ev0, ev1)
     if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3 or a.shape[0] != b.shape[0]:
@@ -79,16 +140,23 @@ def emd(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_flow: bool 
     flow = torch.empty(B, n + 1, m + 1, device=dev, dtype=torch.float64) if return_flow else None
     d0 = torch.empty(B, n + 1, device=dev, dtype=torch.float64) if return_duals else None
     d1 = torch.empty(B, m + 1, device=dev, dtype=torch.float64) if return_duals else None
+    optioned = beta != 1.0 or bool(norm) or bool(periodic_phi)
+    opts = _options("emd", R, beta, norm, periodic_phi) if optioned else None
     if B > 0:
         work = _workspace(B, max(n, m), dev)
-        rc = N.lib().lgn_emd_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(flow), N.ptr(d0), N.ptr(d1), N.ptr(status),
-                                 N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
-        N._check(rc, "lgn_emd_f64")
+        if optioned:
+            rc = N.lib().lgn_emd_pairs_f64(N.ptr(a), N.ptr(b), B, B, n, m, ALIGNED, opts, N.ptr(out), N.ptr(flow), N.ptr(d0), N.ptr(d1),
+                                           N.ptr(status), N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_pairs_f64")
+        else:
+            rc = N.lib().lgn_emd_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(flow), N.ptr(d0), N.ptr(d1), N.ptr(status),
+                                     N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_f64")
     if not return_status:
         st = status.cpu().numpy()
         bad = st.nonzero()[0]
         if len(bad):
-            raise ValueError(f"emd: {status_message(int(st[bad[0]]))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
+            raise ValueError(f"emd: {status_message(int(st[bad[0]]), bool(norm))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
     res = [out] + ([flow] if return_flow else []) + ([d0, d1] if return_duals else [])
     if single:
         res = [x[0] for x in res]

@@ -7,7 +7,12 @@ The gradient cases (not run by default): n30_grad / n150_grad -- 4,096 jets, the
 the GRAD launch (emd_relative_grad, reconstruction's gradient alone and with the target's), interleaved over three rounds, the
 fastest round of each; step_cfg2 -- one graph-replayed CapturedModuleStep at cfg2 (512 x 30, maxdim 2) with lgn.losses.EMDLoss()
 against the same step with the Chamfer loss.
-    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,step_cfg2]]"""
+The pairs cases (not run by default): pairs_full -- lgn.emd.emds of 512 x 512 events of 30 particles (20 real; the jets of the cases
+above as (pT, eta, phi) events), 262,144 pairs in one launch, against what there was before it for the same job: index_select the
+pairs into two (P, 30, 3) tensors, then one emd() call, the gather and the solve timed apart; pairs_upper -- the symmetric form on
+the same 512 events (130,816 pairs); pairs_full_n150 -- 64 x 64 events of 150 particles (100 real), the flow in the workspace.  Interleaved over five rounds; the fastest round, every round and the spread are reported, and
+the results of the two ways are compared bit for bit.
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,step_cfg2,pairs_full,pairs_upper,pairs_full_n150]]"""
 import argparse
 import json
 import os
@@ -19,7 +24,9 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "lgn-autoencoder
 
 CASES = {"n30": (65536, 30, 20), "n150": (8192, 150, 100)}
 GRAD_CASES = {"n30_grad": (4096, 30, 20), "n150_grad": (4096, 150, 100)}
+PAIRS_CASES = {"pairs_full": (512, 30, 20), "pairs_upper": (512, 30, 20), "pairs_full_n150": (64, 150, 100)}
 ROUNDS = 3
+PAIRS_ROUNDS = 5
 OUT = os.path.join(ROOT, "profiles", "emd_bench.jsonl")
 
 
@@ -103,6 +110,60 @@ def one_grad(name, steps, warmup):
     _emit(res)
 
 
+def _events(B, n, real, seed, dev):
+    """(B, n, 3) events of (pT, eta, phi) from the jet-like 4-vectors of the cases above, zero padded"""
+    import torch
+    g = torch.Generator(device=dev).manual_seed(seed)
+    t = torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    pt = t[..., 1:3].norm(dim=-1)
+    ev = torch.stack([pt, torch.asinh(t[..., 3] / pt), torch.atan2(t[..., 2], t[..., 1])], -1)
+    ev[:, real:] = 0.0
+    return ev
+
+
+def one_pairs(name, steps, warmup):
+    import torch
+    from lgn import emd as M
+    B, n, real = PAIRS_CASES[name]
+    dev = torch.device("cuda:0")
+    X0, X1 = _events(B, n, real, 1, dev), _events(B, n, real, 2, dev)
+    upper = name == "pairs_upper"
+    if upper:
+        iu = torch.triu_indices(B, B, offset=1, device=dev)
+        i, j, X1 = iu[0].contiguous(), iu[1].contiguous(), X0
+    else:
+        i, j = torch.arange(B, device=dev).repeat_interleave(B), torch.arange(B, device=dev).repeat(B)
+    npairs = int(i.numel())
+    gathered = [X0.index_select(0, i), X1.index_select(0, j)]
+
+    def gather():
+        gathered[0], gathered[1] = X0.index_select(0, i), X1.index_select(0, j)
+
+    variants = {"emds": lambda: M.emds(X0, None if upper else X1, return_status=True), "gather": gather,
+                "solve": lambda: M.emd(gathered[0], gathered[1], return_status=True)}
+    ms = {k: [] for k in variants}
+    for _ in range(PAIRS_ROUNDS):                          # interleaved: drift of the clocks hits every variant alike
+        for k, fn in variants.items():
+            ms[k].append(_ms(fn, steps, warmup))
+    out, st = M.emds(X0, None if upper else X1, return_status=True)
+    ref, ref_st = M.emd(gathered[0], gathered[1], return_status=True)
+    same = bool(torch.equal(out[i, j].view(torch.int64), ref.view(torch.int64)) and torch.equal(st[i, j], ref_st))
+    res = {"case": name, "kind": "emds, one launch, against gather + emd", "B0": B, "B1": B, "N": n, "real_particles": real, "pairs": npairs,
+           "flow_in_lds": M.flow_in_lds(n), "steps": steps, "rounds": PAIRS_ROUNDS, "status_nonzero": int((st != 0).sum().item()),
+           "same_bits_as_gather_and_emd": same}
+    for k in variants:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
+        res[f"{k}_spread"] = (max(ms[k]) - min(ms[k])) / min(ms[k])
+    res["emds_pairs_per_s"] = npairs / (res["emds_ms"] * 1e-3)
+    res["solve_pairs_per_s"] = npairs / (res["solve_ms"] * 1e-3)
+    res["emds_over_solve"] = res["emds_ms"] / res["solve_ms"]
+    res["emds_over_gather_plus_solve"] = res["emds_ms"] / (res["gather_ms"] + res["solve_ms"])
+    if os.environ.get("LGN_AMD_LIB"):
+        res["library"] = os.path.basename(os.environ["LGN_AMD_LIB"])
+    _emit(res)
+
+
 def one_step(steps, warmup):
     import torch
     import bench
@@ -143,6 +204,8 @@ def main():
         return one_step(args.steps, args.warmup)
     if args.one in GRAD_CASES:
         return one_grad(args.one, args.steps, args.warmup)
+    if args.one in PAIRS_CASES:
+        return one_pairs(args.one, args.steps, args.warmup)
     if args.one:
         return one(args.one, args.steps, args.warmup)
     for name in args.cases.split(","):
