@@ -616,7 +616,7 @@ int lgn_emd_debug_max_augmentations(int* out, int reset);
  *   Refused before any launch (negative return): null ev0, emd or status (ev1 outside UPPER); B0 or B1 < 1; n or m outside
  *   1 .. LGN_EMD_NMAX; an unknown mode; UPPER with n != m, B0 != B1 or an ev1 that is neither NULL nor ev0; ALIGNED with B0 != B1; R or
  *   beta not a finite positive number; flow or duals outside ALIGNED; a short, missing or misaligned workspace.  Nothing is allocated,
- *   nothing waits on the host, no buffer is cleared by a memset: capturable.  Gradients under the options are not offered. */
+ *   nothing waits on the host, no buffer is cleared by a memset: capturable.  Gradients under the options: the section below. */
 #define LGN_EMD_PAIRS_FULL 0
 #define LGN_EMD_PAIRS_UPPER 1
 #define LGN_EMD_PAIRS_ALIGNED 2
@@ -628,6 +628,41 @@ int lgn_emd_pairs_decode(int mode, long long p, int B0, int B1, int* i, int* j);
 int lgn_emd_pairs_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/, int B0, int B1, int n, int m, int mode,
                       const lgn_emd_opts* opts /*nullable*/, double* emd, double* flow /*nullable*/, double* dual0 /*nullable*/,
                       double* dual1 /*nullable*/, int* status, void* work, long long work_bytes, void* stream);
+
+/* ---- gradients of the EMD under the options (csrc/emd_grad_opts.hip): the GRAD calls above with an lgn_emd_opts, computed like them by
+ * the wavefront that solved the pair.  These only ADD functions: LGN_AMD_ABI_VERSION stays 19.  The value (and flow, dual0, dual1) is the
+ * ALIGNED mode's of the pairs call above under the same options, bit for bit.  With dy = y_i - y'_j, D = phi_i - phi'_j, dphi and
+ * theta_ij as defined above, f the optimal flow in the units of the staged weights (normalised under norm), u = dual0, v = dual1,
+ * S0 = sum pT, S1 = sum pT' as given, row n and column m the fictitious particles:
+ *      s_ij      = 1 without periodic_phi;  sign(D) sign(pi - |D|) with it (0 at D = 0 and at |D| = pi)
+ *      k_ij      = f_ij beta theta_ij^(beta - 2) / R^2   where theta_ij > 0, else 0 (at every beta)
+ *      dE/dy_i   =  sum_j k_ij dy             dE/dy'_j   = -sum_i k_ij dy
+ *      dE/dphi_i =  sum_j k_ij dphi s_ij      dE/dphi'_j = -sum_i k_ij dphi s_ij
+ *      norm off:  dE/dpT_i = u_i - [S1 > S0] u_n + [S0 > S1] v_m          dE/dpT'_j = v_j - [S0 > S1] v_m + [S1 > S0] u_n
+ *      norm on :  dE/dpT_i = (u_i - sum_k a_k u_k) / S0, a = pT / S0      dE/dpT'_j = (v_j - sum_k b_k v_k) / S1, b = pT' / S1
+ *   The norm form does not change under the shift (u + c, v - c) a balanced problem leaves free.  An arc with theta_ij = 0 contributes 0
+ *   at every beta (for beta < 1 the true derivative is unbounded there: a convention); a weightless particle gets a zero position
+ *   gradient and the weight gradient above with its finished potential: every output of a pair without a status bit is finite.  With a
+ *   status bit (with norm: LGN_EMD_EMPTY when either event is weightless) value and gradients of that pair are NaN, the other pairs
+ *   are unaffected.
+ *   lgn_emd_grad_opts_f64: the arguments of lgn_emd_grad_f64 with opts (nullable) in the place of R.
+ *   lgn_emd_relative_opts_f64: recons, target [B][N][4] Cartesian jets staged into their relative-polar frames as lgn_emd_relative_f64
+ *      stages them, solved under opts, the gradients (g_w, g_y, g_phi) carried back to the Cartesian jets as lgn_emd_relative_grad_f64
+ *      carries them.  g_recons NULL: the value only, the score under the options (g_target must then be NULL too).
+ *   opts NULL, or R = 1, beta = 1, norm = 0, periodic_phi = 0: every output has the bits of lgn_emd_grad_f64, lgn_emd_relative_grad_f64
+ *   or (g_recons NULL) lgn_emd_relative_f64, which then run.  Workspace and LDS are those of lgn_emd_f64.
+ *   Refused before any launch (negative return): null ev0, ev1, recons, target, emd or status; B < 1; n, m or N outside
+ *   1 .. LGN_EMD_NMAX; R or beta not a finite positive number; g0 and g1 both null; g_target without g_recons; a short, missing or
+ *   misaligned workspace.  Nothing is allocated, nothing waits on the host, no buffer is cleared by a memset: capturable.
+ *   Not offered: energyflow's gdim, spherical measure, coords and mask; gradients of the FULL and UPPER matrices in one launch (the
+ *   Python package composes them from this call); the EMD inside the whole-step calls. */
+int lgn_emd_grad_opts_f64(const double* ev0, const double* ev1, int B, int n, int m, const lgn_emd_opts* opts /*nullable*/, double* emd,
+                          double* g0 /*nullable*/, double* g1 /*nullable, not both*/, double* flow /*nullable*/,
+                          double* dual0 /*nullable*/, double* dual1 /*nullable*/, int* status, void* work, long long work_bytes,
+                          void* stream);
+int lgn_emd_relative_opts_f64(const double* recons, const double* target, int B, int N, const lgn_emd_opts* opts /*nullable*/,
+                              double* emd, double* g_recons /*nullable: value only*/, double* g_target /*nullable*/, int* status,
+                              void* work, long long work_bytes, void* stream);
 
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.

@@ -228,6 +228,10 @@ _SIGNATURES.update({
     "lgn_emd_pairs_decode": [_i, _ll, _i, _i, _ip, _ip],
     # (ev0, ev1, B0, B1, n, m, mode, opts, emd, flow, dual0, dual1, status, work, work_bytes, stream)
     "lgn_emd_pairs_f64": [_vp, _vp] + [_i] * 5 + [C.POINTER(EmdOpts)] + [_vp] * 6 + [_ll, _vp],
+    # (ev0, ev1, B, n, m, opts, emd, g0, g1, flow, dual0, dual1, status, work, work_bytes, stream)
+    "lgn_emd_grad_opts_f64": [_vp, _vp, _i, _i, _i, C.POINTER(EmdOpts)] + [_vp] * 8 + [_ll, _vp],
+    # (recons, target, B, N, opts, emd, g_recons, g_target, status, work, work_bytes, stream)
+    "lgn_emd_relative_opts_f64": [_vp, _vp, _i, _i, C.POINTER(EmdOpts)] + [_vp] * 5 + [_ll, _vp],
     # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
     "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],
     # (counts, max_bins, edges, max_edges, n_edges [host], cols, fwhm, stream)

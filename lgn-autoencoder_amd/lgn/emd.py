@@ -18,10 +18,13 @@ The distance is differentiable here as well: by LP sensitivity the gradient with
 in the optimal flow and the potentials, which the solving wavefront evaluates as an epilogue of the same launch (``emd_grad``,
 ``emd_differentiable``, ``EMDFn`` / ``EMDRelativeFn``; the formulas stand in include/lgn_amd.h).  ``lgn.losses.EMDLoss`` and
 ``HybridLoss`` are training losses on top of it for the module-API steps.  What is offered is the exact LP on the relative-polar frame
-of the anomaly score, so that the training loss and the score are one quantity.  What is NOT offered: jetnet's regularised
-differentiable QP, which the reference's ``EMDLoss`` wraps -- and that wrapper unbinds its (eta, phi, pt) columns as (eta, pt, phi),
-handing jetnet an angle ratio as the weight, which is not reproduced; gradients under beta != 1, norm or periodic phi (``emd_grad``,
-``emd_differentiable`` and the losses are the default options only) and gradients of ``emds``; energyflow's gdim, spherical measure,
+of the anomaly score, so that the training loss and the score are one quantity.  The gradients exist under R, beta, norm and
+periodic_phi as well (csrc/emd_grad_opts.hip: the same epilogue under the option cost and weights): ``emd_grad``,
+``emd_differentiable``, ``emd_relative_grad``, ``emd_relative_tensor`` and the losses take the options as keywords, and at their
+defaults make the calls they always made.  ``emds_differentiable`` is ``emds`` with autograd, composed from ``emd_grad``.  What is NOT
+offered: jetnet's regularised differentiable QP, which the reference's ``EMDLoss`` wraps -- and that wrapper unbinds its (eta, phi, pt)
+columns as (eta, pt, phi), handing jetnet an angle ratio as the weight, which is not reproduced; a native kernel for the gradients of
+a matrix of distances (``emds_differentiable`` solves its pairs a second time in backward); energyflow's gdim, spherical measure,
 coords and mask; the names ``--loss-choice emd`` / ``hybrid`` and the EMD inside the whole-step native calls, which stay refused.
 There is no CPU fallback.
 """
@@ -81,7 +84,7 @@ def emds(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, R: float = 1.0, be
     (B1, m, 3), zero-padded events of (pT, y, phi), in one launch and without a gathered copy of the events.  X1=None is the symmetric
     form, X0 against itself: the pairs i < j are solved and mirrored, the diagonal is 0.  R, beta, norm and periodic_phi as in emd().
     Raises ValueError at the first pair with a status bit; return_status=True returns the (B0, B1) int32 status as well (the distance
-    of such a pair is NaN) and does not wait for the device.  No gradients."""
+    of such a pair is NaN) and does not wait for the device.  No gradients: emds_differentiable() is the form with autograd."""
     sym = X1 is None
     a, b = X0, (X0 if sym else X1)
     if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3:
@@ -166,11 +169,15 @@ def emd(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_flow: bool 
 
 
 def emd_grad(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_status: bool = False, return_flow: bool = False,
-             return_duals: bool = False, need_g0: bool = True, need_g1: bool = True):
+             return_duals: bool = False, need_g0: bool = True, need_g1: bool = True, beta: float = 1.0, norm: bool = False,
+             periodic_phi: bool = False):
     """emd() with its gradients, in one launch: returns (emd (B,), g0 (B, n, 3), g1 (B, m, 3)[, flow][, dual0, dual1][, status]) --
     g0 = d emd / d ev0 and g1 = d emd / d ev1 in the events' column order (pT, y, phi); a gradient that is not needed (need_g0 /
     need_g1 False, not both) is None.  The value is emd()'s bit for bit.  A pair with a status bit has NaN gradients; ValueError and
-    return_status as in emd().  One pair (n, 3) against (m, 3) is accepted like there."""
+    return_status as in emd().  One pair (n, 3) against (m, 3) is accepted like there.
+    beta, norm, periodic_phi as in emd(): at their defaults the call is the one it always was, otherwise lgn_emd_grad_opts_f64 solves
+    and differentiates under the options (include/lgn_amd.h has the formulas; under norm the weight gradients are those of the given,
+    unnormalised pT, and flow and potentials refer to the normalised weights)."""
     single = ev0.dim() == 2
     a, b = (ev0.unsqueeze(0), ev1.unsqueeze(0)) if single else (ev0, ev1)
     if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3 or a.shape[0] != b.shape[0]:
@@ -182,6 +189,8 @@ def emd_grad(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_status
         raise ValueError(f"emd needs a finite R > 0; got {R}")
     if not (need_g0 or need_g1):
         raise ValueError("emd_grad: at least one of the two gradients must be asked for (emd() is the call without gradients)")
+    optioned = beta != 1.0 or bool(norm) or bool(periodic_phi)
+    opts = _options("emd_grad", R, beta, norm, periodic_phi) if optioned else None
     if not (a.is_cuda and b.is_cuda):
         raise RuntimeError(f"lgn (MI355X build): emd_grad runs only in the HIP kernels of liblgn_amd.so on a GPU device; got tensors "
                            f"on '{a.device}' and '{b.device}'. There is no CPU fallback.")
@@ -196,14 +205,21 @@ def emd_grad(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_status
     d1 = torch.empty(B, m + 1, device=dev, dtype=torch.float64) if return_duals else None
     if B > 0:
         work = _workspace(B, max(n, m), dev)
-        rc = N.lib().lgn_emd_grad_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(g0), N.ptr(g1), N.ptr(flow), N.ptr(d0),
-                                      N.ptr(d1), N.ptr(status), N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
-        N._check(rc, "lgn_emd_grad_f64")
+        if opts is not None:
+            rc = N.lib().lgn_emd_grad_opts_f64(N.ptr(a), N.ptr(b), B, n, m, opts, N.ptr(out), N.ptr(g0), N.ptr(g1), N.ptr(flow), N.ptr(d0),
+                                               N.ptr(d1), N.ptr(status), N.ptr(work), work.numel() if work is not None else 0,
+                                               N.stream_ptr())
+            N._check(rc, "lgn_emd_grad_opts_f64")
+        else:
+            rc = N.lib().lgn_emd_grad_f64(N.ptr(a), N.ptr(b), B, n, m, float(R), N.ptr(out), N.ptr(g0), N.ptr(g1), N.ptr(flow),
+                                          N.ptr(d0), N.ptr(d1), N.ptr(status), N.ptr(work), work.numel() if work is not None else 0,
+                                          N.stream_ptr())
+            N._check(rc, "lgn_emd_grad_f64")
     if not return_status:
         st = status.cpu().numpy()
         bad = st.nonzero()[0]
         if len(bad):
-            raise ValueError(f"emd: {status_message(int(st[bad[0]]))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
+            raise ValueError(f"emd: {status_message(int(st[bad[0]]), bool(norm))} (pair {int(bad[0])}, {len(bad)} pair(s) in all)")
     res = [out, g0, g1] + ([flow] if return_flow else []) + ([d0, d1] if return_duals else [])
     if single:
         res = [None if x is None else x[0] for x in res]
@@ -212,10 +228,20 @@ def emd_grad(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, return_status
     return tuple(res)
 
 
-def emd_relative_grad(recons: torch.Tensor, target: torch.Tensor, need_g_target: bool = False):
+def _relative_options(who: str, R, beta, norm, periodic_phi) -> Optional["N.EmdOpts"]:
+    """None at the defaults (the calls without options then run), else the checked lgn_emd_opts"""
+    if R == 1.0 and beta == 1.0 and not norm and not periodic_phi:
+        return None
+    return _options(who, R, beta, norm, periodic_phi)
+
+
+def emd_relative_grad(recons: torch.Tensor, target: torch.Tensor, need_g_target: bool = False, R: float = 1.0, beta: float = 1.0,
+                      norm: bool = False, periodic_phi: bool = False):
     """emd_relative_tensor() with its gradient with respect to the Cartesian jets, in one launch and with no host sync: returns
     (emd (B,), g_recons (B, N, 4), g_target (B, N, 4) or None, status (B,) int32).  The E column of the gradients is 0; a jet with a
-    status bit has NaN gradients."""
+    status bit has NaN gradients.  R, beta, norm, periodic_phi as in emd(), applied to the relative-polar frames; at their defaults
+    the call is the one it always was, otherwise lgn_emd_relative_opts_f64 runs."""
+    opts = _relative_options("emd_relative_grad", R, beta, norm, periodic_phi)
     if recons.dim() != 3 or recons.shape[-1] != 4 or recons.shape != target.shape:
         raise ValueError(f"emd_relative_grad takes two (B, N, 4) Cartesian tensors; got {tuple(recons.shape)} and {tuple(target.shape)}")
     B, n = int(recons.shape[0]), int(recons.shape[1])
@@ -232,9 +258,14 @@ def emd_relative_grad(recons: torch.Tensor, target: torch.Tensor, need_g_target:
     g_t = torch.empty(B, n, 4, device=dev, dtype=torch.float64) if need_g_target else None
     if B > 0:
         work = _workspace(B, n, dev)
-        rc = N.lib().lgn_emd_relative_grad_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(g_r), N.ptr(g_t), N.ptr(status), N.ptr(work),
-                                               work.numel() if work is not None else 0, N.stream_ptr())
-        N._check(rc, "lgn_emd_relative_grad_f64")
+        if opts is not None:
+            rc = N.lib().lgn_emd_relative_opts_f64(N.ptr(r), N.ptr(t), B, n, opts, N.ptr(out), N.ptr(g_r), N.ptr(g_t), N.ptr(status),
+                                                   N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_relative_opts_f64")
+        else:
+            rc = N.lib().lgn_emd_relative_grad_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(g_r), N.ptr(g_t), N.ptr(status),
+                                                   N.ptr(work), work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_relative_grad_f64")
     return out, g_r, g_t, status
 
 
@@ -243,14 +274,15 @@ def _per_pair(g, grad):
 
 
 class EMDFn(torch.autograd.Function):
-    """(ev0 (B,n,3), ev1 (B,m,3), R) -> (B,) distances.  One launch in forward, which also returns the gradients for an upstream
-    gradient of one; backward scales them per pair.  A pair with a status bit is NaN, value and gradients."""
+    """(ev0 (B,n,3), ev1 (B,m,3), R[, beta, norm, periodic_phi]) -> (B,) distances.  One launch in forward, which also returns the
+    gradients for an upstream gradient of one; backward scales them per pair.  A pair with a status bit is NaN, value and gradients."""
 
     @staticmethod
-    def forward(ctx, ev0, ev1, R):
+    def forward(ctx, ev0, ev1, R, beta=1.0, norm=False, periodic_phi=False):
         need1 = bool(ctx.needs_input_grad[1])
         need0 = bool(ctx.needs_input_grad[0]) or not need1            # (the launch needs one gradient output at least)
-        out, g0, g1, _ = emd_grad(ev0.detach(), ev1.detach(), R, return_status=True, need_g0=need0, need_g1=need1)
+        out, g0, g1, _ = emd_grad(ev0.detach(), ev1.detach(), R, return_status=True, need_g0=need0, need_g1=need1, beta=beta, norm=norm,
+                                  periodic_phi=periodic_phi)
         ctx.has = (g0 is not None, g1 is not None)
         ctx.save_for_backward(*[g for g in (g0, g1) if g is not None])
         return out
@@ -260,16 +292,19 @@ class EMDFn(torch.autograd.Function):
         saved = list(ctx.saved_tensors)
         g0 = saved.pop(0) if ctx.has[0] else None
         g1 = saved.pop(0) if ctx.has[1] else None
-        return (_per_pair(g, g0) if ctx.needs_input_grad[0] else None), (_per_pair(g, g1) if ctx.needs_input_grad[1] else None), None
+        return ((_per_pair(g, g0) if ctx.needs_input_grad[0] else None), (_per_pair(g, g1) if ctx.needs_input_grad[1] else None), None,
+                None, None, None)
 
 
 class EMDRelativeFn(torch.autograd.Function):
-    """(recons (B,N,4), target (B,N,4), owner) -> (B,) distances on the relative-polar frames, emd_relative_tensor()'s bit for bit;
-    the gradient of the target is computed only if the target needs one.  ``owner.status`` receives the (B,) int32 flags."""
+    """(recons (B,N,4), target (B,N,4), owner[, R, beta, norm, periodic_phi]) -> (B,) distances on the relative-polar frames,
+    emd_relative_tensor()'s bit for bit; the gradient of the target is computed only if the target needs one.  ``owner.status``
+    receives the (B,) int32 flags."""
 
     @staticmethod
-    def forward(ctx, recons, target, owner):
-        out, g_r, g_t, status = emd_relative_grad(recons.detach(), target.detach(), need_g_target=ctx.needs_input_grad[1])
+    def forward(ctx, recons, target, owner, R=1.0, beta=1.0, norm=False, periodic_phi=False):
+        out, g_r, g_t, status = emd_relative_grad(recons.detach(), target.detach(), need_g_target=ctx.needs_input_grad[1], R=R, beta=beta,
+                                                  norm=norm, periodic_phi=periodic_phi)
         if owner is not None:
             owner.status = status
         ctx.has_target = g_t is not None
@@ -280,37 +315,105 @@ class EMDRelativeFn(torch.autograd.Function):
     def backward(ctx, g):
         saved = ctx.saved_tensors
         return ((_per_pair(g, saved[0]) if ctx.needs_input_grad[0] else None),
-                (_per_pair(g, saved[1]) if ctx.has_target and ctx.needs_input_grad[1] else None), None)
+                (_per_pair(g, saved[1]) if ctx.has_target and ctx.needs_input_grad[1] else None), None, None, None, None, None)
 
 
-def emd_differentiable(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0) -> torch.Tensor:
+def emd_differentiable(ev0: torch.Tensor, ev1: torch.Tensor, R: float = 1.0, beta: float = 1.0, norm: bool = False,
+                       periodic_phi: bool = False) -> torch.Tensor:
     """emd() of (B, n, 3) against (B, m, 3) device tensors as a (B,) tensor with autograd (gradients with respect to pT, y and phi of
-    both events).  No host sync: a pair with a status bit is NaN, value and gradients (emd_grad(return_status=True) shows the flags)."""
+    both events), under emd()'s options.  No host sync: a pair with a status bit is NaN, value and gradients
+    (emd_grad(return_status=True) shows the flags)."""
     if ev0.dim() != 3 or ev1.dim() != 3:
         raise ValueError(f"emd_differentiable takes events (B, n, 3) and (B, m, 3); got {tuple(ev0.shape)} and {tuple(ev1.shape)}")
-    return EMDFn.apply(ev0, ev1, float(R))
+    if beta == 1.0 and not norm and not periodic_phi:
+        return EMDFn.apply(ev0, ev1, float(R))
+    return EMDFn.apply(ev0, ev1, float(R), float(beta), bool(norm), bool(periodic_phi))
 
 
-def emd_relative_tensor(recons: torch.Tensor, target: torch.Tensor, return_status: bool = False):
+def emd_relative_tensor(recons: torch.Tensor, target: torch.Tensor, return_status: bool = False, R: float = 1.0, beta: float = 1.0,
+                        norm: bool = False, periodic_phi: bool = False):
     """The reference's score "emd (relative coordinates)" of (B, N, 4) Cartesian device tensors as a (B,) fp64 device tensor, with no
     host sync (chain it after NativeEvalStep.run()): each jet is staged into its relative-polar frame (pT / (jet pT + 1e-16), eta - jet
     eta, wrapped phi - jet phi) exactly as the other 21 scores stage it, then energyflow.emd.emd(target_rel, recons_rel).  A jet with
-    a status bit (see emd()) gets NaN; return_status=True also returns the (B,) int32 status."""
+    a status bit (see emd()) gets NaN; return_status=True also returns the (B,) int32 status.  R, beta, norm, periodic_phi: emd()'s
+    options on the frames (the score itself is the defaults, at which the call is the one it always was)."""
     if recons.dim() != 3 or recons.shape[-1] != 4 or recons.shape != target.shape:
         raise ValueError(f"emd_relative_tensor takes two (B, N, 4) Cartesian tensors; got {tuple(recons.shape)} and {tuple(target.shape)}")
     B, n = int(recons.shape[0]), int(recons.shape[1])
     if not 1 <= n <= NMAX:
         raise ValueError(f"the EMD score supports 1 <= N <= {NMAX} particles per jet; got N = {n}")
+    opts = _relative_options("emd_relative_tensor", R, beta, norm, periodic_phi)
     r, t = N.f64(recons.to(torch.float64)), N.f64(target.to(torch.float64))
     dev = r.device
     out = torch.empty(B, device=dev, dtype=torch.float64)
     status = torch.empty(B, device=dev, dtype=torch.int32)
     if B > 0:
         work = _workspace(B, n, dev)
-        rc = N.lib().lgn_emd_relative_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(status), N.ptr(work),
-                                          work.numel() if work is not None else 0, N.stream_ptr())
-        N._check(rc, "lgn_emd_relative_f64")
+        if opts is not None:
+            rc = N.lib().lgn_emd_relative_opts_f64(N.ptr(r), N.ptr(t), B, n, opts, N.ptr(out), None, None, N.ptr(status), N.ptr(work),
+                                                   work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_relative_opts_f64")
+        else:
+            rc = N.lib().lgn_emd_relative_f64(N.ptr(r), N.ptr(t), B, n, N.ptr(out), N.ptr(status), N.ptr(work),
+                                              work.numel() if work is not None else 0, N.stream_ptr())
+            N._check(rc, "lgn_emd_relative_f64")
     return (out, status) if return_status else out
+
+
+class EMDsFn(torch.autograd.Function):
+    """emds() with autograd: forward is emds(); backward solves the pairs once more, in chunks of whole rows of the matrix, through
+    emd_grad() and sums each side in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, X0, X1, sym, R, beta, norm, periodic_phi, chunk_pairs):
+        a = X0.detach()
+        out, _ = emds(a, None if sym else X1.detach(), R=R, beta=beta, norm=norm, periodic_phi=periodic_phi, return_status=True)
+        ctx.save_for_backward(a, a if sym else X1.detach())
+        ctx.conf = (sym, R, beta, norm, periodic_phi, chunk_pairs)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        a, b = ctx.saved_tensors
+        sym, R, beta, norm, periodic_phi, chunk_pairs = ctx.conf
+        B0, B1, n, m = a.shape[0], b.shape[0], a.shape[1], b.shape[1]
+        G = G.to(torch.float64)
+        need0, need1 = ctx.needs_input_grad[0], (not sym and ctx.needs_input_grad[1])
+        g_a = torch.zeros_like(a) if need0 else None
+        g_b = torch.zeros(B1, m, 3, device=b.device, dtype=torch.float64) if (need1 or (sym and need0)) else None
+        rows = max(1, chunk_pairs // max(B1, 1))
+        for r0 in range(0, B0, rows):
+            r1 = min(B0, r0 + rows)
+            k = r1 - r0
+            ea = a[r0:r1].unsqueeze(1).expand(k, B1, n, 3).reshape(k * B1, n, 3)
+            eb = b.unsqueeze(0).expand(k, B1, m, 3).reshape(k * B1, m, 3)
+            _, g0, g1, _ = emd_grad(ea, eb, R, return_status=True, need_g0=g_a is not None, need_g1=g_b is not None, beta=beta, norm=norm,
+                                    periodic_phi=periodic_phi)
+            w = G[r0:r1].reshape(k * B1, 1, 1)
+            t0, t1 = (None if g0 is None else g0 * w), (None if g1 is None else g1 * w)
+            if sym:                  # the diagonal is the constant 0 whatever the event holds: it gives nothing (not even a NaN)
+                eye = (torch.arange(r0, r1, device=a.device).unsqueeze(1) == torch.arange(B1, device=a.device).unsqueeze(0)).view(-1, 1, 1)
+                t0, t1 = t0.masked_fill(eye, 0.0), t1.masked_fill(eye, 0.0)
+            if g_a is not None:
+                g_a[r0:r1] = t0.reshape(k, B1, n, 3).sum(1)
+            if g_b is not None:
+                g_b += t1.reshape(k, B1, m, 3).sum(0)
+        if sym:
+            return (g_a + g_b if need0 else None), None, None, None, None, None, None, None
+        return g_a, (g_b if need1 else None), None, None, None, None, None, None
+
+
+def emds_differentiable(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, R: float = 1.0, beta: float = 1.0, norm: bool = False,
+                        periodic_phi: bool = False, chunk_pairs: int = 65536) -> torch.Tensor:
+    """emds() as a (B0, B1) tensor with autograd (gradients with respect to pT, y and phi of every event); forward is emds(), same
+    bits, with no host sync (a pair with a status bit is NaN, value and gradients).  There is no kernel for the gradient of a matrix:
+    backward costs one more solve per pair -- the pairs are solved again through emd_grad(), whole rows of the matrix at a time, at
+    most max(chunk_pairs, B1) pairs per chunk, whose gathered events and whose gradients take that many times (n + m) * 3 doubles of
+    scratch each -- and each side is summed with one reshaped sum per chunk (over the columns for X0, over the rows for X1), an order
+    that does not depend on the run: two runs give the same bits.  X1=None is the symmetric form: every pair i != j is solved in both
+    orders, X0 receives its share from both of its roles, the diagonal gives nothing."""
+    sym = X1 is None
+    return EMDsFn.apply(X0, X0 if sym else X1, sym, float(R), float(beta), bool(norm), bool(periodic_phi), int(chunk_pairs))
 
 
 def max_augmentations(reset: bool = True) -> int:

@@ -13,7 +13,7 @@ over the jets, capturable into a graph.
 
 ``EMDLoss`` and ``HybridLoss`` have the interface of ``utils.losses.EMDLoss`` and of get_loss()'s hybrid branch, on the exact
 energy mover's distance of lgn.emd (csrc/emd.hip: the transportation LP and its closed-form gradient in one launch) -- not jetnet's
-regularised QP.  No --loss-choice string selects them (``loss_kind`` keeps refusing 'emd' and 'hybrid'): pass an instance as
+regularised QP.  Both take energyflow's R, beta, norm and periodic_phi as keywords (csrc/emd_grad_opts.hip).  No --loss-choice string selects them (``loss_kind`` keeps refusing 'emd' and 'hybrid'): pass an instance as
 ``loss_choice`` to the module-API steps of lgn.step."""
 from typing import Optional
 
@@ -143,10 +143,18 @@ class EMDLoss(nn.Module):
     target).sum()`` bit for bit, so that the training loss and the score are one quantity, and the gradient is the closed form in the
     optimal flow and the potentials (include/lgn_amd.h), from the same launch.  The reference's wrapper also unbinds its (eta, phi, pt)
     columns as (eta, pt, phi), which hands jetnet an angle ratio as the weight; that mix-up is not reproduced.  After a forward
-    ``status`` holds the (B,) int32 flags (LGN_EMD_*; a flagged jet makes the loss NaN)."""
+    ``status`` holds the (B,) int32 flags (LGN_EMD_*; a flagged jet makes the loss NaN).
 
-    def __init__(self, *args, **kwargs):
+    ``R``, ``beta``, ``norm`` and ``periodic_phi`` (keywords only) are energyflow's options as lgn.emd.emd() defines them, applied to
+    the relative-polar frames: beta = 2 is the squared ground distance, norm = True compares the shapes of the two jets and drops the
+    |sum pT - sum pT'| term.  The value is then ``emd_relative_tensor(recons, target, **options).sum()``; at the defaults the loss is
+    the one described above, bit for bit."""
+
+    def __init__(self, *args, R: float = 1.0, beta: float = 1.0, norm: bool = False, periodic_phi: bool = False, **kwargs):
         super().__init__()
+        from .emd import _options
+        _options("EMDLoss", R, beta, norm, periodic_phi)
+        self.R, self.beta, self.norm, self.periodic_phi = float(R), float(beta), bool(norm), bool(periodic_phi)
         self.status = None
 
     def forward(self, p4_recons: torch.Tensor, p4_target: torch.Tensor) -> torch.Tensor:
@@ -163,18 +171,19 @@ class EMDLoss(nn.Module):
         if p4_recons.dim() != 3 or p4_recons.shape != p4_target.shape:
             raise ValueError(f"p4_recons {tuple(p4_recons.shape)} and p4_target {tuple(p4_target.shape)} must both be "
                              "(batch, particles, 4)")
-        return EMDRelativeFn.apply(p4_recons, p4_target, self).sum()        # sum over batch
+        return EMDRelativeFn.apply(p4_recons, p4_target, self, self.R, self.beta, self.norm, self.periodic_phi).sum()    # sum over batch
 
 
 class HybridLoss(nn.Module):
     """The reference's hybrid loss (get_loss(), utils/train.py:446-457) as one module:
     ``chamfer_loss_weight * ChamferLoss(x, t, jet_features) + EMDLoss(x, t)``, both sums over the jets, with this package's
-    ``ChamferLoss`` and ``EMDLoss`` (the exact LP, not jetnet's QP).  ``status``: the EMD's flags of the last forward."""
+    ``ChamferLoss`` and ``EMDLoss`` (the exact LP, not jetnet's QP).  ``status``: the EMD's flags of the last forward.
+    ``emd_options`` (R, beta, norm, periodic_phi) go to the ``EMDLoss``."""
 
-    def __init__(self, chamfer_loss_weight: float = 1.0, device: Optional[torch.device] = None):
+    def __init__(self, chamfer_loss_weight: float = 1.0, device: Optional[torch.device] = None, **emd_options):
         super().__init__()
         self.chamfer_loss_weight = chamfer_loss_weight
-        self.chamfer, self.emd = ChamferLoss(device=device), EMDLoss()
+        self.chamfer, self.emd = ChamferLoss(device=device), EMDLoss(**emd_options)
 
     @property
     def status(self):

@@ -7,12 +7,15 @@ The gradient cases (not run by default): n30_grad / n150_grad -- 4,096 jets, the
 the GRAD launch (emd_relative_grad, reconstruction's gradient alone and with the target's), interleaved over three rounds, the
 fastest round of each; step_cfg2 -- one graph-replayed CapturedModuleStep at cfg2 (512 x 30, maxdim 2) with lgn.losses.EMDLoss()
 against the same step with the Chamfer loss.
+The option-gradient cases (not run by default): n30_grad_opts / n150_grad_opts -- the same 4,096 jets under beta = 2, under norm and
+under R = 0.8, beta = 2, norm, periodic phi: the gradient launch against the value-only launch under the same options, for the generic
+form on the jets' (pT, eta, phi) events and for the relative form, with the default options timed in the same rounds as the control.
 The pairs cases (not run by default): pairs_full -- lgn.emd.emds of 512 x 512 events of 30 particles (20 real; the jets of the cases
 above as (pT, eta, phi) events), 262,144 pairs in one launch, against what there was before it for the same job: index_select the
 pairs into two (P, 30, 3) tensors, then one emd() call, the gather and the solve timed apart; pairs_upper -- the symmetric form on
 the same 512 events (130,816 pairs); pairs_full_n150 -- 64 x 64 events of 150 particles (100 real), the flow in the workspace.  Interleaved over five rounds; the fastest round, every round and the spread are reported, and
 the results of the two ways are compared bit for bit.
-    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,step_cfg2,pairs_full,pairs_upper,pairs_full_n150]]"""
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,n30_grad_opts,n150_grad_opts,step_cfg2,pairs_full,pairs_upper,pairs_full_n150]]"""
 import argparse
 import json
 import os
@@ -24,6 +27,7 @@ sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "lgn-autoencoder
 
 CASES = {"n30": (65536, 30, 20), "n150": (8192, 150, 100)}
 GRAD_CASES = {"n30_grad": (4096, 30, 20), "n150_grad": (4096, 150, 100)}
+GRAD_OPTS_CASES = {"n30_grad_opts": (4096, 30, 20), "n150_grad_opts": (4096, 150, 100)}
 PAIRS_CASES = {"pairs_full": (512, 30, 20), "pairs_upper": (512, 30, 20), "pairs_full_n150": (64, 150, 100)}
 ROUNDS = 3
 PAIRS_ROUNDS = 5
@@ -107,6 +111,53 @@ def one_grad(name, steps, warmup):
         res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
     res["grad_over_forward"] = res["grad_ms"] / res["forward_ms"]
     res["grad_both_over_forward"] = res["grad_both_ms"] / res["forward_ms"]
+    _emit(res)
+
+
+OPTIONS = {"beta2": dict(beta=2.0), "norm": dict(norm=True), "all": dict(R=0.8, beta=2.0, norm=True, periodic_phi=True)}
+
+
+def one_grad_opts(name, steps, warmup):
+    """The gradients under the options against the value-only calls under the same options, on the jets of one_grad: the generic
+    form on their (pT, eta, phi) events (emd_grad with the first event's gradient against emd(), whose pairs kernel is the value-only
+    launch) and the relative form (emd_relative_grad against emd_relative_tensor), with the default options as the control."""
+    import torch
+    from lgn import emd as M
+    B, n, real = GRAD_OPTS_CASES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    t = torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+    t[..., 0] = t[..., 1:].norm(dim=-1) + 0.1
+    t[:, real:] = 0.0
+    r = t + 0.2 * torch.randn(B, n, 4, device=dev, dtype=torch.float64, generator=g)
+
+    def events(x):
+        pt = x[..., 1:3].norm(dim=-1)
+        ev = torch.stack([pt, torch.asinh(x[..., 3] / pt), torch.atan2(x[..., 2], x[..., 1])], -1)
+        ev[pt == 0] = 0.0                                  # (the target's zero padding)
+        return ev.contiguous()
+    er, et = events(r), events(t)
+    variants = {"control_forward": lambda: M.emd_relative_tensor(r, t, return_status=True), "control_grad": lambda: M.emd_relative_grad(r, t)}
+    for k, o in OPTIONS.items():
+        variants[f"{k}_value"] = lambda o=o: M.emd(er, et, return_status=True, **o)
+        variants[f"{k}_grad"] = lambda o=o: M.emd_grad(er, et, return_status=True, need_g1=False, **o)
+        variants[f"{k}_rel_value"] = lambda o=o: M.emd_relative_tensor(r, t, return_status=True, **o)
+        variants[f"{k}_rel_grad"] = lambda o=o: M.emd_relative_grad(r, t, **o)
+    ms = {k: [] for k in variants}
+    for _ in range(ROUNDS):                                # interleaved: drift of the clocks hits every variant alike
+        for k, fn in variants.items():
+            ms[k].append(_ms(fn, steps, warmup))
+    bad = sum(int((M.emd_grad(er, et, return_status=True, **o)[3] != 0).sum().item()) +
+              int((M.emd_relative_grad(r, t, **o)[3] != 0).sum().item()) for o in OPTIONS.values())
+    res = {"case": name, "kind": "emd gradient epilogue under options", "B": B, "N": n, "real_particles": real,
+           "flow_in_lds": M.flow_in_lds(n), "steps": steps, "rounds": ROUNDS, "status_nonzero": bad}
+    for k in variants:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_spread"] = (max(ms[k]) - min(ms[k])) / min(ms[k])
+    res["control_grad_over_forward"] = res["control_grad_ms"] / res["control_forward_ms"]
+    for k in OPTIONS:
+        res[f"{k}_grad_over_value"] = res[f"{k}_grad_ms"] / res[f"{k}_value_ms"]
+        res[f"{k}_rel_grad_over_value"] = res[f"{k}_rel_grad_ms"] / res[f"{k}_rel_value_ms"]
     _emit(res)
 
 
@@ -204,6 +255,8 @@ def main():
         return one_step(args.steps, args.warmup)
     if args.one in GRAD_CASES:
         return one_grad(args.one, args.steps, args.warmup)
+    if args.one in GRAD_OPTS_CASES:
+        return one_grad_opts(args.one, args.steps, args.warmup)
     if args.one in PAIRS_CASES:
         return one_pairs(args.one, args.steps, args.warmup)
     if args.one:
