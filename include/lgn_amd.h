@@ -654,8 +654,8 @@ int lgn_emd_pairs_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/, int 
  *   Refused before any launch (negative return): null ev0, ev1, recons, target, emd or status; B < 1; n, m or N outside
  *   1 .. LGN_EMD_NMAX; R or beta not a finite positive number; g0 and g1 both null; g_target without g_recons; a short, missing or
  *   misaligned workspace.  Nothing is allocated, nothing waits on the host, no buffer is cleared by a memset: capturable.
- *   Not offered: energyflow's gdim, spherical measure, coords and mask; gradients of the FULL and UPPER matrices in one launch (the
- *   Python package composes them from this call); the EMD inside the whole-step calls. */
+ *   Not offered: energyflow's gdim, spherical measure, coords and mask; the EMD inside the whole-step calls.  Gradients of the FULL
+ *   and UPPER matrices: the section after this one. */
 int lgn_emd_grad_opts_f64(const double* ev0, const double* ev1, int B, int n, int m, const lgn_emd_opts* opts /*nullable*/, double* emd,
                           double* g0 /*nullable*/, double* g1 /*nullable, not both*/, double* flow /*nullable*/,
                           double* dual0 /*nullable*/, double* dual1 /*nullable*/, int* status, void* work, long long work_bytes,
@@ -663,6 +663,44 @@ int lgn_emd_grad_opts_f64(const double* ev0, const double* ev1, int B, int n, in
 int lgn_emd_relative_opts_f64(const double* recons, const double* target, int B, int N, const lgn_emd_opts* opts /*nullable*/,
                               double* emd, double* g_recons /*nullable: value only*/, double* g_target /*nullable*/, int* status,
                               void* work, long long work_bytes, void* stream);
+
+/* ---- gradients of a matrix of EMDs (csrc/emd_pairs_grad.hip): d sum_ij G[i][j] E[i][j] / d events for the FULL and UPPER matrices of
+ * lgn_emd_pairs_f64, each pair solved once.  These only ADD functions: LGN_AMD_ABI_VERSION stays 19.  Two calls work on a range of
+ * whole rows [row_begin, row_begin + row_count) of the matrix: its pairs are the pair numbers p_begin .. p_begin + P - 1 of the mode
+ * (FULL: P = row_count B1; UPPER: the rows' pairs i < j, row i holds B - 1 - i), and pair p_begin + q is row q of the two slabs.
+ *   lgn_emd_pairs_grad_f64: one wavefront per pair on the persistent grid of lgn_emd_pairs_f64 stages ev0[i] and ev1[j] where they lie
+ *      (no gathered copies), solves the pair and writes
+ *        emd, status [B0][B1] (each nullable): the value and the status of the pair, with the bits of lgn_emd_pairs_f64 under the same
+ *               opts; UPPER mirrors them to [j][i] and writes +0.0 / 0 on the diagonal of the rows of the range.
+ *        s0 [P][n][3], s1 [P][m][3]: d E[i][j] / d ev0[i] and d E[i][j] / d ev1[j] as (d/dpT, d/dy, d/dphi), with the bits
+ *               lgn_emd_grad_opts_f64 gives g0 and g1 for the aligned pair (ev0[i], ev1[j]) under the same opts (the formulas of the
+ *               section above).  A pair with a status bit has value NaN and NaN in both of its slab rows.
+ *      work: at least lgn_emd_workspace_bytes(min(max(P, 1), INT_MAX), max(n, m)) bytes, 8-byte aligned (0 bytes: may be NULL); what
+ *      the whole matrix needs is enough for every range.
+ *   lgn_emd_pairs_grad_slab_bytes: the bytes of s0 and s1 together for a row range, P (n + m) 24 (s0 takes P n 24 of them); negative
+ *      for a shape or a range the calls refuse.
+ *   lgn_emd_pairs_grad_reduce_f64: the slabs of a row range, weighted by G [B0][B1] (nullable: every weight 1), summed into
+ *      g0 [B0][n][3] and g1 [B1][m][3] (each nullable, not both).  One thread owns one output double and sums sequentially, one rounded
+ *      product then one rounded sum per pair -- no FMA, no atomics, no tree -- in this order:
+ *        FULL   g0[i], i in the range:  acc = +0.0, then acc = acc + G[i][j] s0[i, j] for j ascending (complete in one call; other rows
+ *               of g0 are not touched).  g1[j]: acc = acc + G[i][j] s1[i, j] for the rows i of the range ascending.
+ *        UPPER  (g1 must be NULL) g0[e], every e: the weight of pair i < j is w = G[i][j] + G[j][i] (one rounded sum; 2 without G);
+ *               partners ascending: first the rows k < e of the range with w s1[k, e], then, if row e is in the range, k > e with
+ *               w s0[e, k].  The diagonal gives nothing.
+ *      g1 (UPPER: g0) starts at +0.0 in a call with row_begin == 0 and continues from what is stored otherwise: ranges that cover the
+ *      matrix, processed in ascending order, give bits that do not depend on where they were cut, on the grid or on the run.  NaN
+ *      propagates: a pair with a status bit makes the gradients of both its events NaN whatever G holds there.
+ *   Refused before any launch (negative return): null ev0, s0 or s1 (ev1 in FULL); B0 or B1 < 1; n or m outside 1 .. LGN_EMD_NMAX;
+ *   ALIGNED or an unknown mode; UPPER with n != m, B0 != B1, an ev1 that is neither NULL nor ev0, or a non-null g1; a row range
+ *   outside the matrix (row_count < 1 included); R or beta not a finite positive number; a short, missing or misaligned workspace; g0
+ *   and g1 both null.  Nothing is allocated, nothing waits on the host, no buffer is cleared by a memset: capturable.
+ *   Not offered: the matrix of the relative (Cartesian jet) form. */
+long long lgn_emd_pairs_grad_slab_bytes(int mode, int B0, int B1, int n, int m, int row_begin, int row_count);
+int lgn_emd_pairs_grad_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/, int B0, int B1, int n, int m, int mode,
+                           const lgn_emd_opts* opts /*nullable*/, int row_begin, int row_count, double* emd /*nullable*/, double* s0,
+                           double* s1, int* status /*nullable*/, void* work, long long work_bytes, void* stream);
+int lgn_emd_pairs_grad_reduce_f64(const double* s0, const double* s1, const double* G /*nullable*/, int B0, int B1, int n, int m, int mode,
+                                  int row_begin, int row_count, double* g0 /*nullable*/, double* g1 /*nullable*/, void* stream);
 
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.

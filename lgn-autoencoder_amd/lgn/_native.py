@@ -232,6 +232,10 @@ _SIGNATURES.update({
     "lgn_emd_grad_opts_f64": [_vp, _vp, _i, _i, _i, C.POINTER(EmdOpts)] + [_vp] * 8 + [_ll, _vp],
     # (recons, target, B, N, opts, emd, g_recons, g_target, status, work, work_bytes, stream)
     "lgn_emd_relative_opts_f64": [_vp, _vp, _i, _i, C.POINTER(EmdOpts)] + [_vp] * 5 + [_ll, _vp],
+    # (ev0, ev1, B0, B1, n, m, mode, opts, row_begin, row_count, emd, s0, s1, status, work, work_bytes, stream)
+    "lgn_emd_pairs_grad_f64": [_vp, _vp] + [_i] * 5 + [C.POINTER(EmdOpts), _i, _i] + [_vp] * 5 + [_ll, _vp],
+    # (s0, s1, G, B0, B1, n, m, mode, row_begin, row_count, g0, g1, stream)
+    "lgn_emd_pairs_grad_reduce_f64": [_vp] * 3 + [_i] * 7 + [_vp] * 3,
     # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
     "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],
     # (counts, max_bins, edges, max_edges, n_edges [host], cols, fwhm, stream)
@@ -261,6 +265,8 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_roc_workspace_bytes": [_ll, _i],
     "lgn_emd_workspace_bytes": [_i, _i],
     "lgn_emd_lds_bytes": [_i],
+    # (mode, B0, B1, n, m, row_begin, row_count)
+    "lgn_emd_pairs_grad_slab_bytes": [_i] * 7,
     "lgn_column_stats_workspace_bytes": [_ll, _i],
     "lgn_jet_images_workspace_bytes": [_i, _i],
     "lgn_rep_deviation_workspace_bytes": [_i, _i, _i, _ip, _ip, _ip],

@@ -21,10 +21,11 @@ in the optimal flow and the potentials, which the solving wavefront evaluates as
 of the anomaly score, so that the training loss and the score are one quantity.  The gradients exist under R, beta, norm and
 periodic_phi as well (csrc/emd_grad_opts.hip: the same epilogue under the option cost and weights): ``emd_grad``,
 ``emd_differentiable``, ``emd_relative_grad``, ``emd_relative_tensor`` and the losses take the options as keywords, and at their
-defaults make the calls they always made.  ``emds_differentiable`` is ``emds`` with autograd, composed from ``emd_grad``.  What is NOT
+defaults make the calls they always made.  ``emds_differentiable`` is ``emds`` with autograd, composed from ``emd_grad`` or, with
+``backward="native"``, on the matrix-gradient kernels (csrc/emd_pairs_grad.hip): ``emds_pair_grads`` solves every pair once and returns
+its gradients, ``emds_grad`` sums them under an upstream matrix in a fixed order, chunk after chunk of rows.  What is NOT
 offered: jetnet's regularised differentiable QP, which the reference's ``EMDLoss`` wraps -- and that wrapper unbinds its (eta, phi, pt)
-columns as (eta, pt, phi), handing jetnet an angle ratio as the weight, which is not reproduced; a native kernel for the gradients of
-a matrix of distances (``emds_differentiable`` solves its pairs a second time in backward); energyflow's gdim, spherical measure,
+columns as (eta, pt, phi), handing jetnet an angle ratio as the weight, which is not reproduced; energyflow's gdim, spherical measure,
 coords and mask; the names ``--loss-choice emd`` / ``hybrid`` and the EMD inside the whole-step native calls, which stay refused.
 There is no CPU fallback.
 """
@@ -403,17 +404,198 @@ class EMDsFn(torch.autograd.Function):
         return g_a, (g_b if need1 else None), None, None, None, None, None, None
 
 
+class _Matrix:
+    """The checked arguments of a matrix call: emds()'s shape and option checks, with its messages."""
+
+    def __init__(self, who: str, X0, X1, R, beta, norm, periodic_phi):
+        self.sym = X1 is None
+        a, b = X0, (X0 if self.sym else X1)
+        if a.dim() != 3 or b.dim() != 3 or a.shape[-1] != 3 or b.shape[-1] != 3:
+            raise ValueError(f"emds takes events (B0, n, 3) and (B1, m, 3) of (pT, y, phi); got {tuple(a.shape)} and {tuple(b.shape)}")
+        self.B0, self.B1, self.n, self.m = int(a.shape[0]), int(b.shape[0]), int(a.shape[1]), int(b.shape[1])
+        if not (1 <= self.n <= NMAX and 1 <= self.m <= NMAX):
+            raise ValueError(f"emd supports 1 <= n, m <= {NMAX} particles per event; got n = {self.n}, m = {self.m}")
+        self.opts = _options("emds", R, beta, norm, periodic_phi)
+        if not (a.is_cuda and b.is_cuda):
+            raise RuntimeError(f"lgn (MI355X build): {who} runs only in the HIP kernels of liblgn_amd.so on a GPU device; got tensors "
+                               f"on '{a.device}' and '{b.device}'. There is no CPU fallback.")
+        self.a = N.f64(a.to(torch.float64))
+        self.b = self.a if self.sym else N.f64(b.to(torch.float64))
+        self.dev = self.a.device
+        self.mode = UPPER if self.sym else FULL
+        self.norm = bool(norm)
+
+    def row_pairs(self, i: int) -> int:
+        return self.B0 - 1 - i if self.sym else self.B1
+
+    def pairs(self, r0: int, k: int) -> int:
+        """the pairs of the rows [r0, r0 + k) of the matrix, by the library's plan-time query"""
+        nbytes = N.lib().lgn_emd_pairs_grad_slab_bytes(self.mode, self.B0, self.B1, self.n, self.m, r0, k)
+        if nbytes < 0:
+            raise ValueError(N.last_error())
+        return nbytes // (24 * (self.n + self.m))
+
+    def chunks(self, max_slab_bytes: int):
+        """whole rows in ascending order, as many per chunk as keep its two slabs within max_slab_bytes (one row at least)"""
+        out, r0, per_pair = [], 0, 24 * (self.n + self.m)
+        while r0 < self.B0:
+            k, P = 1, self.row_pairs(r0)
+            while r0 + k < self.B0 and (P + self.row_pairs(r0 + k)) * per_pair <= max_slab_bytes:
+                P += self.row_pairs(r0 + k)
+                k += 1
+            out.append((r0, k))
+            r0 += k
+        return out
+
+    def slabs(self, P: int):
+        """(s0, s1) for P pairs (never zero-sized: the library refuses null pointers)"""
+        return (torch.empty(max(P, 1), self.n, 3, device=self.dev, dtype=torch.float64),
+                torch.empty(max(P, 1), self.m, 3, device=self.dev, dtype=torch.float64))
+
+    def solve(self, r0, k, E, s0, s1, status, work):
+        rc = N.lib().lgn_emd_pairs_grad_f64(N.ptr(self.a), None if self.sym else N.ptr(self.b), self.B0, self.B1, self.n, self.m, self.mode,
+                                            self.opts, r0, k, N.ptr(E), N.ptr(s0), N.ptr(s1), N.ptr(status), N.ptr(work),
+                                            work.numel() if work is not None else 0, N.stream_ptr())
+        N._check(rc, "lgn_emd_pairs_grad_f64")
+
+    def reduce(self, r0, k, s0, s1, G, g0, g1):
+        rc = N.lib().lgn_emd_pairs_grad_reduce_f64(N.ptr(s0), N.ptr(s1), N.ptr(G), self.B0, self.B1, self.n, self.m, self.mode, r0, k,
+                                                   N.ptr(g0), N.ptr(g1), N.stream_ptr())
+        N._check(rc, "lgn_emd_pairs_grad_reduce_f64")
+
+    def outputs(self, need0: bool = True, need1: bool = True):
+        """(g0, g1): what the reduction writes; g1 is None in the symmetric form.  Without pairs the sums are empty: zeros."""
+        make = torch.zeros if self.B0 * self.B1 == 0 else torch.empty
+        g0 = make(self.B0, self.n, 3, device=self.dev, dtype=torch.float64) if need0 else None
+        g1 = make(self.B1, self.m, 3, device=self.dev, dtype=torch.float64) if (need1 and not self.sym) else None
+        return g0, g1
+
+    def solve_and_reduce(self, G, E, status, g0, g1, max_slab_bytes: int):
+        """row chunk after row chunk in ascending order: solve into one pair of slabs, sum them into g0 and g1"""
+        if self.B0 * self.B1 == 0:
+            return
+        chunks = self.chunks(max_slab_bytes)
+        P = max(self.pairs(r0, k) for r0, k in chunks)
+        s0, s1 = self.slabs(P)
+        work = _pairs_workspace(max(P, 1), max(self.n, self.m), self.dev)
+        for r0, k in chunks:
+            self.solve(r0, k, E, s0, s1, status, work)
+            self.reduce(r0, k, s0, s1, G, g0, g1)
+
+
+def _upstream(who: str, G, M: "_Matrix") -> Optional[torch.Tensor]:
+    if G is None:
+        return None
+    if tuple(G.shape) != (M.B0, M.B1):
+        raise ValueError(f"{who}: the upstream matrix G is {tuple(G.shape)}; the matrix of distances is ({M.B0}, {M.B1})")
+    if not G.is_cuda:
+        raise RuntimeError(f"lgn (MI355X build): {who} runs only in the HIP kernels of liblgn_amd.so on a GPU device; got G on "
+                           f"'{G.device}'. There is no CPU fallback.")
+    return N.f64(G.to(torch.float64))
+
+
+def emds_pair_grads(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, R: float = 1.0, beta: float = 1.0, norm: bool = False,
+                    periodic_phi: bool = False):
+    """emds() with the gradient of every pair, each pair solved once in one launch (csrc/emd_pairs_grad.hip): returns
+    (E (B0, B1), s0 (P, n, 3), s1 (P, m, 3), status (B0, B1) int32).  Row p of the slabs is pair number p of the matrix -- p = i B1 + j,
+    or, with X1=None, the pairs i < j row-major over the upper triangle -- and holds d E[i, j] / d X0[i] and d E[i, j] / d X1[j] in the
+    column order (pT, y, phi), with the bits emd_grad() gives for that ordered pair; E has emds()'s bits.  A pair with a status bit is
+    NaN, value and gradients.  No host sync.  The slabs take P (n + m) 24 bytes: emds_grad() sums them in chunks of rows."""
+    M = _Matrix("emds_pair_grads", X0, X1, R, beta, norm, periodic_phi)
+    E = torch.empty(M.B0, M.B1, device=M.dev, dtype=torch.float64)
+    status = torch.empty(M.B0, M.B1, device=M.dev, dtype=torch.int32)
+    P = M.pairs(0, M.B0) if M.B0 * M.B1 else 0
+    s0, s1 = M.slabs(P)
+    if M.B0 * M.B1:
+        M.solve(0, M.B0, E, s0, s1, status, _pairs_workspace(max(P, 1), max(M.n, M.m), M.dev))
+    return E, s0[:P], s1[:P], status
+
+
+def emds_grad(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, G: Optional[torch.Tensor] = None, R: float = 1.0, beta: float = 1.0,
+              norm: bool = False, periodic_phi: bool = False, return_status: bool = False, max_slab_bytes: int = 2 ** 30):
+    """emds() with the gradient of sum(G * E): returns (E (B0, B1), g0 (B0, n, 3), g1 (B1, m, 3)[, status]), g0 = d sum(G E) / d X0 and
+    g1 = d sum(G E) / d X1; G (B0, B1) is the upstream matrix, None is all ones.  X1=None is the symmetric form: g1 is None and g0
+    holds an event's share from both of its roles (pair i < j weighs G[i, j] + G[j, i]; the diagonal gives nothing).  Every pair is
+    solved once; whole rows of the matrix are solved and summed at a time, as many as keep the per-pair gradients within
+    max_slab_bytes (one row at least).  The sums run in a fixed order, one rounded product and one rounded sum per pair, partners
+    ascending (include/lgn_amd.h): the bits do not depend on max_slab_bytes or on the run.  A pair with a status bit is NaN in E and
+    makes the gradients of both its events NaN whatever G holds there; ValueError and return_status as in emds()."""
+    M = _Matrix("emds_grad", X0, X1, R, beta, norm, periodic_phi)
+    G = _upstream("emds_grad", G, M)
+    E = torch.empty(M.B0, M.B1, device=M.dev, dtype=torch.float64)
+    status = torch.empty(M.B0, M.B1, device=M.dev, dtype=torch.int32)
+    g0, g1 = M.outputs()
+    M.solve_and_reduce(G, E, status, g0, g1, int(max_slab_bytes))
+    if not return_status:
+        bad = status.nonzero().cpu().numpy()
+        if len(bad):
+            i, j = int(bad[0][0]), int(bad[0][1])
+            raise ValueError(f"emds_grad: {status_message(int(status[i, j].item()), M.norm)} (pair ({i}, {j}), {len(bad)} pair(s) in all)")
+    return (E, g0, g1, status) if return_status else (E, g0, g1)
+
+
+class EMDsNativeFn(torch.autograd.Function):
+    """emds() with autograd on the matrix-gradient kernels.  When the per-pair gradients of the whole matrix fit keep_bytes, forward
+    is the launch that solves and differentiates every pair and backward is the weighted sum alone; otherwise forward is emds() and
+    backward solves and sums chunk after chunk of rows."""
+
+    @staticmethod
+    def forward(ctx, X0, X1, sym, R, beta, norm, periodic_phi, keep_bytes, max_slab_bytes):
+        a = X0.detach()
+        b = None if sym else X1.detach()
+        M = _Matrix("emds_differentiable", a, b, R, beta, norm, periodic_phi)
+        ctx.conf = (sym, R, beta, norm, periodic_phi, max_slab_bytes)
+        ctx.kept = 24 * (M.n + M.m) * (M.pairs(0, M.B0) if M.B0 * M.B1 else 0) <= keep_bytes
+        if ctx.kept:
+            out, s0, s1, _ = emds_pair_grads(a, b, R=R, beta=beta, norm=norm, periodic_phi=periodic_phi)
+            ctx.save_for_backward(M.a, M.b, s0, s1)
+        else:
+            out, _ = emds(a, b, R=R, beta=beta, norm=norm, periodic_phi=periodic_phi, return_status=True)
+            ctx.save_for_backward(M.a, M.b)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        sym, R, beta, norm, periodic_phi, max_slab_bytes = ctx.conf
+        saved = ctx.saved_tensors
+        M = _Matrix("emds_differentiable", saved[0], None if sym else saved[1], R, beta, norm, periodic_phi)
+        G = N.f64(G.to(torch.float64))
+        g0, g1 = M.outputs(bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1]))
+        if g0 is None and g1 is None:
+            return (None,) * 9
+        if ctx.kept:
+            if M.B0 * M.B1:
+                s0, s1 = M.slabs(0) if saved[2].shape[0] == 0 else (saved[2], saved[3])
+                M.reduce(0, M.B0, s0, s1, G, g0, g1)
+        else:
+            M.solve_and_reduce(G, None, None, g0, g1, max_slab_bytes)
+        return (g0, g1) + (None,) * 7
+
+
 def emds_differentiable(X0: torch.Tensor, X1: Optional[torch.Tensor] = None, R: float = 1.0, beta: float = 1.0, norm: bool = False,
-                        periodic_phi: bool = False, chunk_pairs: int = 65536) -> torch.Tensor:
-    """emds() as a (B0, B1) tensor with autograd (gradients with respect to pT, y and phi of every event); forward is emds(), same
-    bits, with no host sync (a pair with a status bit is NaN, value and gradients).  There is no kernel for the gradient of a matrix:
-    backward costs one more solve per pair -- the pairs are solved again through emd_grad(), whole rows of the matrix at a time, at
-    most max(chunk_pairs, B1) pairs per chunk, whose gathered events and whose gradients take that many times (n + m) * 3 doubles of
-    scratch each -- and each side is summed with one reshaped sum per chunk (over the columns for X0, over the rows for X1), an order
-    that does not depend on the run: two runs give the same bits.  X1=None is the symmetric form: every pair i != j is solved in both
-    orders, X0 receives its share from both of its roles, the diagonal gives nothing."""
+                        periodic_phi: bool = False, chunk_pairs: int = 65536, backward: str = "rows",
+                        keep_bytes: int = 2 ** 30) -> torch.Tensor:
+    """emds() as a (B0, B1) tensor with autograd (gradients with respect to pT, y and phi of every event); the value has emds()'s
+    bits, with no host sync (a pair with a status bit is NaN, value and gradients).  X1=None is the symmetric form: X0 receives its
+    share from both of its roles, the diagonal gives nothing.  ``backward`` chooses how the gradient is made:
+    "rows" (the default) is the composition over emd_grad(): forward is emds(), backward solves the pairs again, whole rows of the
+    matrix at a time, at most max(chunk_pairs, B1) pairs per chunk, whose gathered events and whose gradients take that many times
+    (n + m) * 3 doubles of scratch each, and sums each side with one reshaped sum per chunk (over the columns for X0, over the rows for
+    X1), an order that does not depend on the run.  The symmetric form solves every pair i != j in both orders.
+    "native" runs the matrix-gradient kernels (emds_pair_grads(), emds_grad()): no gathered events, every pair solved in one order
+    only.  When the per-pair gradients of the whole matrix, P (n + m) 24 bytes, fit keep_bytes, forward solves and differentiates
+    every pair in one launch and keeps them, and backward is the weighted sum alone: one solve per pair in all.  Otherwise forward is
+    emds() and backward solves and sums at most max(chunk_pairs, one row) pairs at a time: two solves per pair and chunk_pairs
+    (n + m) 24 bytes of scratch.  Its sums run in emds_grad()'s fixed order: the bits depend neither on keep_bytes, nor on
+    chunk_pairs, nor on the run."""
     sym = X1 is None
-    return EMDsFn.apply(X0, X0 if sym else X1, sym, float(R), float(beta), bool(norm), bool(periodic_phi), int(chunk_pairs))
+    if backward == "rows":
+        return EMDsFn.apply(X0, X0 if sym else X1, sym, float(R), float(beta), bool(norm), bool(periodic_phi), int(chunk_pairs))
+    if backward != "native":
+        raise ValueError(f"emds_differentiable: backward is 'rows' or 'native'; got {backward!r}")
+    per_pair = 24 * (int(X0.shape[-2]) + int((X0 if sym else X1).shape[-2])) if X0.dim() == 3 and (sym or X1.dim() == 3) else 0
+    return EMDsNativeFn.apply(X0, X0 if sym else X1, sym, float(R), float(beta), bool(norm), bool(periodic_phi), int(keep_bytes),
+                              int(chunk_pairs) * per_pair)
 
 
 def max_augmentations(reset: bool = True) -> int:

@@ -15,7 +15,12 @@ above as (pT, eta, phi) events), 262,144 pairs in one launch, against what there
 pairs into two (P, 30, 3) tensors, then one emd() call, the gather and the solve timed apart; pairs_upper -- the symmetric form on
 the same 512 events (130,816 pairs); pairs_full_n150 -- 64 x 64 events of 150 particles (100 real), the flow in the workspace.  Interleaved over five rounds; the fastest round, every round and the spread are reported, and
 the results of the two ways are compared bit for bit.
-    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,n30_grad_opts,n150_grad_opts,step_cfg2,pairs_full,pairs_upper,pairs_full_n150]]"""
+The matrix-gradient cases (not run by default): pairs_grad_full -- forward + backward of lgn.emd.emds_differentiable on 64 x 64 events
+of 30 particles (4,096 pairs, as the gradient cases) under a random upstream matrix: backward="rows" (the composition over emd_grad,
+the control) against backward="native" with kept slabs and with keep_bytes=0; pairs_grad_upper -- the symmetric form on 91 events
+(4,095 pairs); pairs_grad_full_n150 -- 64 x 64 events of 150 particles, the flow in the workspace.  Interleaved over three rounds;
+the fastest round, every round and the spread are reported.
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,n30_grad_opts,n150_grad_opts,step_cfg2,pairs_full,pairs_upper,pairs_full_n150,pairs_grad_full,pairs_grad_upper,pairs_grad_full_n150]]"""
 import argparse
 import json
 import os
@@ -29,6 +34,7 @@ CASES = {"n30": (65536, 30, 20), "n150": (8192, 150, 100)}
 GRAD_CASES = {"n30_grad": (4096, 30, 20), "n150_grad": (4096, 150, 100)}
 GRAD_OPTS_CASES = {"n30_grad_opts": (4096, 30, 20), "n150_grad_opts": (4096, 150, 100)}
 PAIRS_CASES = {"pairs_full": (512, 30, 20), "pairs_upper": (512, 30, 20), "pairs_full_n150": (64, 150, 100)}
+PAIRS_GRAD_CASES = {"pairs_grad_full": (64, 30, 20), "pairs_grad_upper": (91, 30, 20), "pairs_grad_full_n150": (64, 150, 100)}
 ROUNDS = 3
 PAIRS_ROUNDS = 5
 OUT = os.path.join(ROOT, "profiles", "emd_bench.jsonl")
@@ -215,6 +221,55 @@ def one_pairs(name, steps, warmup):
     _emit(res)
 
 
+def one_pairs_grad(name, steps, warmup):
+    """Forward + backward of emds_differentiable under a random upstream matrix: the composition (backward="rows", the parent's code,
+    unchanged) as the control against backward="native" with kept slabs and with keep_bytes=0.  The gradients of the variants are
+    compared: native kept against native keep_bytes=0 bit for bit, native against the composition by the largest relative deviation."""
+    import torch
+    from lgn import emd as M
+    B, n, real = PAIRS_GRAD_CASES[name]
+    dev = torch.device("cuda:0")
+    upper = name == "pairs_grad_upper"
+    X0 = _events(B, n, real, 1, dev).requires_grad_(True)
+    X1 = None if upper else _events(B, n, real, 2, dev).requires_grad_(True)
+    npairs = B * (B - 1) // 2 if upper else B * B
+    W = torch.randn(B, B, device=dev, dtype=torch.float64, generator=torch.Generator(device=dev).manual_seed(3))
+    grads = {}
+
+    def run(key, **kw):
+        def fn():
+            X0.grad = None
+            if X1 is not None:
+                X1.grad = None
+            out = M.emds_differentiable(X0, X1, **kw)
+            out.backward(W)
+            grads[key] = (X0.grad, None if upper else X1.grad)
+        return fn
+
+    variants = {"rows": run("rows", backward="rows"), "native_kept": run("native_kept", backward="native"),
+                "native_nokeep": run("native_nokeep", backward="native", keep_bytes=0)}
+    ms = {k: [] for k in variants}
+    for _ in range(ROUNDS):                                # interleaved: drift of the clocks hits every variant alike
+        for k, fn in variants.items():
+            ms[k].append(_ms(fn, steps, warmup))
+    st = M.emds(X0.detach(), None if upper else X1.detach(), return_status=True)[1]
+    same = all(b is None or bool(torch.equal(a, b)) for a, b in zip(grads["native_kept"], grads["native_nokeep"]))
+    # (the particles with weight: at zero weight the distance has a kink in that weight, and the two orders of a pair, which the
+    # composition's symmetric form solves, may return different subgradients there)
+    dev_rows = max(float((a[:, :real] - b[:, :real]).abs().max() / b[:, :real].abs().max())
+                   for a, b in zip(grads["native_kept"], grads["rows"]) if b is not None)
+    res = {"case": name, "kind": "emds_differentiable forward + backward", "B0": B, "B1": B, "N": n, "real_particles": real,
+           "pairs": npairs, "flow_in_lds": M.flow_in_lds(n), "steps": steps, "rounds": ROUNDS,
+           "status_nonzero": int((st != 0).sum().item()), "kept_and_nokeep_same_bits": same, "native_against_rows_max_rel_weighted_particles": dev_rows}
+    for k in variants:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
+        res[f"{k}_spread"] = (max(ms[k]) - min(ms[k])) / min(ms[k])
+    res["native_kept_over_rows"] = res["native_kept_ms"] / res["rows_ms"]
+    res["native_nokeep_over_rows"] = res["native_nokeep_ms"] / res["rows_ms"]
+    _emit(res)
+
+
 def one_step(steps, warmup):
     import torch
     import bench
@@ -259,6 +314,8 @@ def main():
         return one_grad_opts(args.one, args.steps, args.warmup)
     if args.one in PAIRS_CASES:
         return one_pairs(args.one, args.steps, args.warmup)
+    if args.one in PAIRS_GRAD_CASES:
+        return one_pairs_grad(args.one, args.steps, args.warmup)
     if args.one:
         return one(args.one, args.steps, args.warmup)
     for name in args.cases.split(","):
