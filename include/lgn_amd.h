@@ -274,10 +274,14 @@ typedef struct lgn_net_desc {
  *   loss_part[b] is then NaN, its assignment row is -1, and the stage hands on exact zeros for the jet (d loss / d x, the gradient
  *   into the last level's vectors and its dWo1 partial row); where the jet's activations themselves are NaN, the level backwards
  *   after the stage still turn 0 * NaN into NaN parameter gradients.
+ *   LGN_LOSS_EMD        the energy mover's distance of (x, t) on their relative-polar frames (lgn/losses.py: EMDLoss, HybridLoss): the
+ *                       `loss` argument then points at the first member of an lgn_emd_loss_desc, which is defined with the EMD
+ *                       calls below, where its stage is described.
  * Workspace sizes do not depend on the loss. */
 #define LGN_LOSS_CHAMFER 0
 #define LGN_LOSS_MSE 1
 #define LGN_LOSS_HUNGARIAN 2
+#define LGN_LOSS_EMD 3
 typedef struct lgn_loss_desc {
   int kind;                /* LGN_LOSS_* */
   int abs_coord;           /* Hungarian: --hungarian-abs-coord */
@@ -654,8 +658,8 @@ int lgn_emd_pairs_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/, int 
  *   Refused before any launch (negative return): null ev0, ev1, recons, target, emd or status; B < 1; n, m or N outside
  *   1 .. LGN_EMD_NMAX; R or beta not a finite positive number; g0 and g1 both null; g_target without g_recons; a short, missing or
  *   misaligned workspace.  Nothing is allocated, nothing waits on the host, no buffer is cleared by a memset: capturable.
- *   Not offered: energyflow's gdim, spherical measure, coords and mask; the EMD inside the whole-step calls.  Gradients of the FULL
- *   and UPPER matrices: the section after this one. */
+ *   Not offered: energyflow's gdim, spherical measure, coords and mask.  Gradients of the FULL and UPPER matrices: the section after
+ *   this one.  The EMD as the loss of the whole-step calls: LGN_LOSS_EMD, after that. */
 int lgn_emd_grad_opts_f64(const double* ev0, const double* ev1, int B, int n, int m, const lgn_emd_opts* opts /*nullable*/, double* emd,
                           double* g0 /*nullable*/, double* g1 /*nullable, not both*/, double* flow /*nullable*/,
                           double* dual0 /*nullable*/, double* dual1 /*nullable*/, int* status, void* work, long long work_bytes,
@@ -663,6 +667,43 @@ int lgn_emd_grad_opts_f64(const double* ev0, const double* ev1, int B, int n, in
 int lgn_emd_relative_opts_f64(const double* recons, const double* target, int B, int N, const lgn_emd_opts* opts /*nullable*/,
                               double* emd, double* g_recons /*nullable: value only*/, double* g_target /*nullable*/, int* status,
                               void* work, long long work_bytes, void* stream);
+
+/* ---- the EMD as the loss stage of the whole-step calls (csrc/emd_loss.hip): lgn/losses.py's EMDLoss and HybridLoss inside
+ * lgn_step_fwd_bwd_f64, lgn_step_train_f64, lgn_step_train_opt_f64 and lgn_step_eval_f64.  This only ADDS a kind, a struct and a
+ * function: LGN_AMD_ABI_VERSION stays 19 and no existing struct or signature changes.  A `loss` whose kind is LGN_LOSS_EMD is read as
+ * an lgn_emd_loss_desc, whose first member it is (pass &desc.base).  With x = get_real(reconstruction) and t = target, per jet b:
+ *      E_b          = the value of lgn_emd_relative_opts_f64(x, t) under opts, bit for bit (at default options: lgn_emd_relative_f64's)
+ *      loss_part[b] = base.scale * E_b                                   chamfer_weight == 0 (EMDLoss)
+ *                   = chamfer_weight * Chamfer_b + base.scale * E_b      chamfer_weight  > 0 (HybridLoss), each product rounded
+ *   and the gradient is that call's g_recons (times base.scale) carried through get_real and the output mix like every other loss
+ *   gradient.  The loss is a SUM over the jets, like Chamfer.  One launch of its own after the decoder's last level, one workgroup per
+ *   jet; one wavefront of it solves the jet with the device functions of the calls above (csrc/emd_dev.hpp).  Under the hybrid loss the
+ *   step's Chamfer stage runs first, exactly as without a `loss` (riding on the decoder's last level where it does), with
+ *   chamfer_weight as its gradient scale; the EMD stage then recomputes x (the same bits) and adds its gradient into the last level's
+ *   vectors, its dWo1 partial row and its term of loss_part[b] to what that stage wrote -- the owning thread's read-modify-write, in a
+ *   fixed order, no atomics.  The reconstruction is the Chamfer step's bit for bit.
+ *   base.abs_coord = base.polar_coord = 0.  `assignment` is ignored; status [B] int32 (nullable) receives the LGN_EMD_* bits.  A
+ *   flagged jet follows the contract of lgn_loss_desc: loss_part[b] is NaN and the stage hands on exact zeros for the jet (under the
+ *   hybrid loss: it adds nothing, the jet's Chamfer gradient stays).  Without norm "both events weightless" (LGN_EMD_EMPTY) needs a
+ *   reconstruction without any pT; with norm a target without weight -- an all-padded jet -- is LGN_EMD_EMPTY.  lgn_step_eval_f64 sums
+ *   loss_part over the jets that have an unmasked particle: it selects, so the NaN of an all-masked pad jet does not reach loss_out.
+ *   The flow matrix lives in LDS only, so the workspace sizes still do not depend on the loss.
+ *   lgn_emd_loss_lds_bytes(N, C): the dynamic LDS of the stage at N decoder particles and C channels of the decoder's last level, the one
+ *   place that counts it (-1 for N < 1 or C < 1):
+ *      8 * (20 N + 10 N C + 2 C)              the output stage's block (that of lgn_assign_loss_lds_bytes without the assignment's own)
+ *      + 8 * (5 (N + 1) + 8 + (N + 1)^2)      one wavefront's rows, jets and flow: lgn_emd_lds_bytes' count with the flow in LDS
+ *      + 8 * (N + 1)                          its two int arrays
+ *   Refused before any launch (negative return): R or beta not a finite positive number; chamfer_weight negative or not finite;
+ *   base.scale not positive and finite; d->jet_loss_scale != 0; Nd outside 1 .. LGN_EMD_NMAX; lgn_emd_loss_lds_bytes(Nd, C) above
+ *   LGN_LDS_LIMIT (a flow in a global workspace is not offered here).
+ *   Layout: sizeof(lgn_emd_loss_desc) = 56; offsets base 0 (kind 0, abs_coord 4, polar_coord 8, scale 16), opts 24 (R 24, beta 32,
+ *   norm 40, periodic_phi 44), chamfer_weight 48. */
+typedef struct lgn_emd_loss_desc {
+  lgn_loss_desc base;      /* kind = LGN_LOSS_EMD, abs_coord = polar_coord = 0, scale = weight of the EMD term (1) */
+  lgn_emd_opts opts;
+  double chamfer_weight;   /* 0: the EMD alone; > 0: chamfer_weight * Chamfer + EMD (HybridLoss) */
+} lgn_emd_loss_desc;
+long long lgn_emd_loss_lds_bytes(int N, int C);
 
 /* ---- gradients of a matrix of EMDs (csrc/emd_pairs_grad.hip): d sum_ij G[i][j] E[i][j] / d events for the FULL and UPPER matrices of
  * lgn_emd_pairs_f64, each pair solved once.  These only ADD functions: LGN_AMD_ABI_VERSION stays 19.  Two calls work on a range of

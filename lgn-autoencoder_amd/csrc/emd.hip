@@ -33,16 +33,12 @@
 #include "lds.hpp"
 #include "../../include/lgn_amd.h"
 #include "emd_plan.hpp"
-#include "emd_wave.hpp"
-#include "polar_dev.hpp"
+#include "emd_dev.hpp"      // the relative staging, p4_polar_bwd, emd_rel_to_cartesian: shared with emd_grad_opts.hip and emd_loss.hip
 
 namespace lgn {
 namespace {
 
 // (the LDS and workspace sizes the launchers below plan with: emd_plan.hpp, shared with emd_pairs.hip)
-constexpr int EMD_AUG_PER_NODE = 16;           // cap of the augmentations of one problem per node
-
-static_assert(EMD_NMAX == LGN_EMD_NMAX, "include/lgn_amd.h and emd_wave.hpp agree on the largest event");
 static_assert(EMD_ITER == LGN_EMD_ITER && EMD_INFEASIBLE == LGN_EMD_INFEASIBLE, "status bits of include/lgn_amd.h");
 
 __device__ int g_emd_max_aug;                  // the largest augmentation count of any problem since the last reset (tools/emd_bench.py)
@@ -62,61 +58,9 @@ struct EmdCost {               // c[i][j] = theta_ij, 1 to or from the fictitiou
   }
 };
 
-__device__ __forceinline__ bool finite(double x) { return fabs(x) < INFINITY; }      // false for NaN and +-inf
-
 struct EmdGradOut {            // the gradient outputs: the one extra kernel argument of the GRAD variant
   double *g0, *g1;             // [B][n][W], [B][m][W] (each nullable): W = 3 columns (pT, y, phi), REL: W = 4 Cartesian (E, px, py, pz)
 };
-
-// The gradient of p4_polar (polar_dev.hpp): (g_pt, g_eta, g_phi) -> (g_px, g_py, g_pz).  At pt == 0 the 0/0 of the root and of atan2
-// reads as 0: such a particle gets no direct term.
-__device__ __forceinline__ void p4_polar_bwd(double px, double py, double pz, double g_pt, double g_eta, double g_phi, double& gx,
-                                             double& gy, double& gz) {
-  gx = gy = gz = 0.0;
-  const double pt = sqrt(px * px + py * py);
-  if (!(pt > 0.0)) return;
-  const double q = pt + POLAR_EPS, z = pz / q;
-  const double s = 1.0 / sqrt(1.0 + z * z);                    // d asinh(z) / dz
-  const double gt = g_pt - (g_eta * s) * (z / q);              // dz / dpt = -pz / q^2
-  const double X = px + POLAR_EPS, Y = py + POLAR_EPS, r2 = X * X + Y * Y;
-  gx = gt * (px / pt) - g_phi * (Y / r2);
-  gy = gt * (py / pt) + g_phi * (X / r2);
-  gz = (g_eta * s) / q;
-}
-
-// One side of the REL form: the gradients (gw, gy, gp)(k) with respect to the relative-polar frame of particle lane + 64 k of the
-// jet x [n][4], whose sum is J [4], become out [n][4].  Every particle, weightless ones included, receives the jet-sum term.
-template <int K, class GW, class GY, class GP>
-__device__ __forceinline__ void emd_rel_to_cartesian(const double* __restrict__ x, const double* J, int n, int lane, GW gw, GY gy, GP gp,
-                                                     double* __restrict__ out) {
-  double jpT, jeta, jphi;
-  p4_polar(J[1], J[2], J[3], jpT, jeta, jphi);
-  const double q = jpT + POLAR_EPS;
-  double sw = 0.0, sy = 0.0, sp = 0.0;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int i = lane + 64 * k;
-    if (i < n) {
-      const double* p = x + 4 * i;
-      sw = sw + gw(k) * sqrt(p[1] * p[1] + p[2] * p[2]);
-      sy = sy + gy(k);
-      sp = sp + gp(k);
-    }
-  }
-  sw = wave_sum(sw), sy = wave_sum(sy), sp = wave_sum(sp);
-  double jx, jy, jz;
-  p4_polar_bwd(J[1], J[2], J[3], -(sw / (q * q)), -sy, -sp, jx, jy, jz);
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int i = lane + 64 * k;
-    if (i < n) {
-      const double* p = x + 4 * i;
-      double dx, dy, dz;
-      p4_polar_bwd(p[1], p[2], p[3], gw(k) / q, gy(k), gp(k), dx, dy, dz);
-      out[4 * i] = 0.0, out[4 * i + 1] = dx + jx, out[4 * i + 2] = dy + jy, out[4 * i + 3] = dz + jz;
-    }
-  }
-}
 
 // The gradient epilogue of one solved pair (the header of this file): F the optimal flow, rs.u and v the finished potentials.  x0, x1:
 // this pair's Cartesian jets, J their sums [2][4] (REL).  g0, g1: this pair's outputs, each nullable.  Overwrites rs.dist and rs.sup.
@@ -218,53 +162,14 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
     double p0 = 0.0, p1 = 0.0;
     if (REL) {
       const size_t base = (size_t)b * n * 4;
-      if (lane < 8) {                      // jet sums, rows in order 0 .. N-1
-        const double* x = (lane < 4 ? a0 : a1) + base + (lane & 3);
-        double s = 0.0;
-        for (int r = 0; r < n; ++r) s = s + x[4 * r];
-        jet[lane] = s;
-      }
-      wave_sync();
-      double jpT0, jeta0, jphi0, jpT1, jeta1, jphi1;
-      p4_polar(jet[1], jet[2], jet[3], jpT0, jeta0, jphi0);
-      p4_polar(jet[5], jet[6], jet[7], jpT1, jeta1, jphi1);
-      for (int i = lane; i < rows; i += 64) {
-        double w = 0.0, y = 0.0, ph = 0.0;
-        if (i < n) {
-          const double* x = a0 + base + 4 * i;
-          double pT, eta, phi;
-          p4_polar(x[1], x[2], x[3], pT, eta, phi);
-          w = pT / (jpT0 + POLAR_EPS);
-          y = eta - jeta0;
-          ph = wrap_phi(phi - jphi0);
-          bad |= !finite(w) || !finite(y) || !finite(ph) || !finite(x[0]) || w < 0.0;
-        }
-        rs.sup[i] = w, ry[i] = y, rphi[i] = ph;
-        p0 = p0 + w;
-      }
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int j = lane + 64 * k;
-        double w = 0.0, y = 0.0, ph = 0.0;
-        if (j < m) {
-          const double* x = a1 + base + 4 * j;
-          double pT, eta, phi;
-          p4_polar(x[1], x[2], x[3], pT, eta, phi);
-          w = pT / (jpT1 + POLAR_EPS);
-          y = eta - jeta1;
-          ph = wrap_phi(phi - jphi1);
-          bad |= !finite(w) || !finite(y) || !finite(ph) || !finite(x[0]) || w < 0.0;
-        }
-        dem[k] = w, cf.qy[k] = y, cf.qphi[k] = ph;
-        p1 = p1 + w;
-      }
+      emd_stage_rel<K>(a0 + base, a1 + base, n, m, lane, rs.sup, ry, rphi, jet, dem, cf.qy, cf.qphi, bad, p0, p1);
     } else {
       for (int i = lane; i < rows; i += 64) {
         double w = 0.0, y = 0.0, ph = 0.0;
         if (i < n) {
           const double* x = a0 + ((size_t)b * n + i) * 3;
           w = x[0], y = x[1], ph = x[2];
-          bad |= !finite(w) || !finite(y) || !finite(ph) || w < 0.0;
+          bad |= !emd_finite(w) || !emd_finite(y) || !emd_finite(ph) || w < 0.0;
         }
         rs.sup[i] = w, ry[i] = y, rphi[i] = ph;
         p0 = p0 + w;
@@ -276,7 +181,7 @@ __global__ __launch_bounds__(64) void emd_kernel(const double* __restrict__ a0, 
         if (j < m) {
           const double* x = a1 + ((size_t)b * m + j) * 3;
           w = x[0], y = x[1], ph = x[2];
-          bad |= !finite(w) || !finite(y) || !finite(ph) || w < 0.0;
+          bad |= !emd_finite(w) || !emd_finite(y) || !emd_finite(ph) || w < 0.0;
         }
         dem[k] = w, cf.qy[k] = y, cf.qphi[k] = ph;
         p1 = p1 + w;

@@ -66,6 +66,28 @@ int dec_output_assign_eval(int B, int N, int C, const double* v, const double* w
                            double* recon_real, double* loss_part, hipStream_t);
 int hungarian_mse(int B, int N, const double* x, const double* y, const AssignLoss& al, double* loss_part, double* gx, hipStream_t);
 size_t assign_loss_lds_bytes(int N, int C);
+// The energy mover's distance of (get_real(recon), target) on their relative-polar frames (emd_loss.hip; lgn_emd_loss_desc of
+// include/lgn_amd.h) as the step's last stage: the same sandwich around the solver of emd_wave.hpp.  chamfer_weight > 0 (the hybrid
+// loss): the stage ACCUMULATES -- the step's Chamfer loss has run with chamfer_weight as its gradient scale and left g_v, part and the
+// unweighted loss_part; the stage adds its own g_v and part and makes loss_part[b] = chamfer_weight * loss_part[b] + scale * EMD_b.
+// A flagged jet (status [B], LGN_EMD_* bits): loss_part[b] NaN, exact zeros handed on (accumulating: g_v and part left as they are).
+struct EmdLoss {
+  lgn_emd_opts opts;
+  double scale, chamfer_weight;
+  int* status;
+};
+int check_emd_loss(const EmdLoss& el, int N);
+int dec_output_emd_loss(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, const EmdLoss& el,
+                        double* recon, double* loss_part /*[B]*/, double* g_v, double* part /*[B][2C]*/, hipStream_t);
+int dec_output_emd_eval(int B, int N, int C, const double* v, const double* wo1, const double* target, int method, const EmdLoss& el,
+                        double* recon_real, double* loss_part, hipStream_t);
+long long emd_loss_lds_bytes(int N, int C);        // -1 for bad arguments: lgn_emd_loss_lds_bytes
+// the loss stage of a whole step that is a launch of its own, by kind: al (LGN_LOSS_MSE, LGN_LOSS_HUNGARIAN) or emd (LGN_LOSS_EMD)
+struct StageLoss {
+  int kind;
+  AssignLoss al;
+  EmdLoss emd;
+};
 // loss_out[0] = sum of loss_part over the jets with an unmasked particle (mask [B][N]), in a fixed order
 int eval_loss_sum(int B, int N, const uint8_t* mask, const double* loss_part, double* loss_out, hipStream_t);
 // Chamfer loss per jet and its gradients (module API: lgn/losses.py); loss_part [B], gx [B][N][4], gy [B][M][4]

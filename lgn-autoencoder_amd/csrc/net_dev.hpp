@@ -283,7 +283,10 @@ __device__ __forceinline__ void dec_out_forward(int B, int N, int C, const doubl
   }
   __syncthreads();
 }
-// gx [N][4] = d loss / d x (in LDS, synchronised) -> g_v [2][B][N][C][4] and the jet's dWo1 partial row [2][C]
+// gx [N][4] = d loss / d x (in LDS, synchronised) -> g_v [2][B][N][C][4] and the jet's dWo1 partial row [2][C].  ACC: both are added to
+// what another loss stage of the same jet left there (the hybrid loss: Chamfer first, then the EMD stage of emd_loss.hip) -- a plain
+// read-modify-write by the thread that owns the element, so the sum has one order.
+template <bool ACC = false>
 __device__ __forceinline__ void dec_out_backward(int B, int N, int C, int method, double* g_v, double* part, const DecOutLds& s) {
   double *x = s.x, *gx = s.gx, *ycl = s.ycl, *vl = s.vl, *tmp = s.tmp, *wol = s.wol;
   const int b = blockIdx.x;
@@ -312,8 +315,14 @@ __device__ __forceinline__ void dec_out_backward(int B, int N, int C, int method
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       cx<double> r = cmulc(gc[m], w);
-      g_v[base * 4 + m] = r.r;
-      g_v[pl * 4 + base * 4 + m] = r.i;
+      if constexpr (ACC) {
+        const double o_r = g_v[base * 4 + m], o_i = g_v[pl * 4 + base * 4 + m];
+        g_v[base * 4 + m] = o_r + r.r;
+        g_v[pl * 4 + base * 4 + m] = o_i + r.i;
+      } else {
+        g_v[base * 4 + m] = r.r;
+        g_v[pl * 4 + base * 4 + m] = r.i;
+      }
       cfmac(d, gc[m], cx<double>{vl[e * 8 + m], vl[e * 8 + 4 + m]});
     }
     tmp[e * 2] = d.r;
@@ -325,7 +334,8 @@ __device__ __forceinline__ void dec_out_backward(int B, int N, int C, int method
     double acc = 0.0;
 #pragma unroll 6
     for (int n = 0; n < N; ++n) acc += tmp[(n * C + c) * 2 + k];
-    part[(size_t)b * 2 * C + k * C + c] = acc;
+    if constexpr (ACC) part[(size_t)b * 2 * C + k * C + c] = part[(size_t)b * 2 * C + k * C + c] + acc;
+    else part[(size_t)b * 2 * C + k * C + c] = acc;
   }
 }
 

@@ -264,21 +264,57 @@ struct JunctionBwd {
   double* part_dec;
 };
 
-// The loss argument of the whole-step calls: nullptr for Chamfer, else the assignment loss the step's last stage
-// runs (net.hpp: AssignLoss).  Every refusal is made here, before anything is enqueued.
-int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, AssignLoss& al, const AssignLoss** out) {
+// The loss argument of the whole-step calls: nullptr for Chamfer, else the loss stage that is a launch of its own after the
+// decoder's last level (net.hpp: StageLoss) -- an assignment loss, or the EMD, whose descriptor is an lgn_emd_loss_desc read through
+// its first member.  The one planner of any non-Chamfer stage: every refusal is made here, before anything is enqueued.
+int plan_assign_loss(const lgn_net_desc* d, const lgn_loss_desc* loss, int* assignment, int* status, StageLoss& al, const StageLoss** out) {
   *out = nullptr;
   if (!loss || loss->kind == LGN_LOSS_CHAMFER) return 0;
   if (int rc = check_desc(d)) return rc;
-  al = AssignLoss{loss->kind, loss->abs_coord, loss->polar_coord, loss->scale, assignment, status};
   const int Nd = dec_nodes(*d), CL = d->dec_channels[d->n_levels];
-  if (int rc = check_assign_loss(al, Nd)) return rc;
+  al = StageLoss{};
+  al.kind = loss->kind;
+  if (loss->kind == LGN_LOSS_EMD) {
+    const lgn_emd_loss_desc* e = reinterpret_cast<const lgn_emd_loss_desc*>(loss);
+    al.emd = EmdLoss{e->opts, loss->scale, e->chamfer_weight, status};
+    al.emd.opts.norm = e->opts.norm != 0, al.emd.opts.periodic_phi = e->opts.periodic_phi != 0;
+    if (int rc = check_emd_loss(al.emd, Nd)) return rc;
+    LGN_CHECK_ARG(loss->abs_coord == 0 && loss->polar_coord == 0, "step: LGN_LOSS_EMD takes abs_coord = polar_coord = 0 (the frame is "
+                  "the relative polar one)");
+  } else {
+    al.al = AssignLoss{loss->kind, loss->abs_coord, loss->polar_coord, loss->scale, assignment, status};
+    if (int rc = check_assign_loss(al.al, Nd)) return rc;
+  }
   LGN_CHECK_ARG(d->jet_loss_scale == 0.0, "step: jet_loss_scale=%g with loss kind %d: the jet-feature term is a Chamfer option "
                 "(--chamfer-jet-features)", d->jet_loss_scale, loss->kind);
-  const size_t need = assign_loss_lds_bytes(Nd, CL);
-  LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the assignment-loss stage at N=%d needs %zu B of LDS (> %d)", Nd, need, LGN_LDS_LIMIT);
+  if (loss->kind == LGN_LOSS_EMD) {
+    const long long need = emd_loss_lds_bytes(Nd, CL);
+    LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the EMD loss stage at N=%d needs %lld B of LDS (lgn_emd_loss_lds_bytes; > %d)", Nd, need,
+                  LGN_LDS_LIMIT);
+  } else {
+    const size_t need = assign_loss_lds_bytes(Nd, CL);
+    LGN_CHECK_ARG(need <= LGN_LDS_LIMIT, "step: the assignment-loss stage at N=%d needs %zu B of LDS (> %d)", Nd, need, LGN_LDS_LIMIT);
+  }
   *out = &al;
   return 0;
+}
+
+// What the step's Chamfer stage does next to a StageLoss: nothing beside an assignment loss or the EMD alone; under the hybrid loss
+// (LGN_LOSS_EMD with chamfer_weight > 0) it runs exactly as without one, its gradient scale times chamfer_weight, and the EMD stage
+// after it accumulates.
+bool stage_keeps_chamfer(const StageLoss* al) { return !al || (al->kind == LGN_LOSS_EMD && al->emd.chamfer_weight > 0.0); }
+double chamfer_scale(const StageLoss* al) { return al ? al->emd.chamfer_weight : 1.0; }
+
+// the training / evaluation launch of a StageLoss, by kind
+int stage_loss_train(const StageLoss& L, int B, int N, int C, const double* v, const double* wo1, const double* target, int method,
+                     double* recon, double* loss_part, double* g_v, double* part, hipStream_t st) {
+  if (L.kind == LGN_LOSS_EMD) return dec_output_emd_loss(B, N, C, v, wo1, target, method, L.emd, recon, loss_part, g_v, part, st);
+  return dec_output_assign_loss(B, N, C, v, wo1, target, method, L.al, recon, loss_part, g_v, part, st);
+}
+int stage_loss_eval(const StageLoss& L, int B, int N, int C, const double* v, const double* wo1, const double* target, int method,
+                    double* recon_real, double* loss_part, hipStream_t st) {
+  if (L.kind == LGN_LOSS_EMD) return dec_output_emd_eval(B, N, C, v, wo1, target, method, L.emd, recon_real, loss_part, st);
+  return dec_output_assign_eval(B, N, C, v, wo1, target, method, L.al, recon_real, loss_part, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1125,7 +1161,7 @@ int gen_autoencoder_fwd(const lgn_net_desc& d, const double* params, const int64
 int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                      const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, double* workspace,
                      long long workspace_doubles, double* recon, double* loss_part, hipStream_t st, const StepTailArgs* tail,
-                     const AssignLoss* al) {
+                     const StageLoss* al) {
   LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step: encoder and decoder must both be table-driven (or both fused)");
   if (int rc = check_generic(d, false)) return rc;
   if (int rc = check_generic(d, true)) return rc;
@@ -1143,12 +1179,12 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   {
     const RowLayout ro = dec_output_rows(d, CL);
     DQ_NEW(part, (size_t)B * ro.width);
+    if (stage_keeps_chamfer(al))
+      LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, chamfer_scale(al), d.get_real,
+                              d.jet_loss_scale, recon, loss_part, g.ds.gv, part, st));
     if (al)
-      LGN_TRY(dec_output_assign_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, d.get_real, *al, recon, loss_part,
-                                     g.ds.gv, part, st));
-    else
-      LGN_TRY(dec_output_loss(B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon,
-                              loss_part, g.ds.gv, part, st));
+      LGN_TRY(stage_loss_train(*al, B, N, CL, g.da.vL, params + dec_off[S.out0(true) + 1], target, d.get_real, recon, loss_part, g.ds.gv,
+                               part, st));
     ro.add(dq, part, B, grads, dec_off);
   }
   std::vector<UnpackJob> post;
@@ -1182,7 +1218,7 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
 int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, long long n_params, const int64_t* enc_off,
                  const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                  double* workspace, long long workspace_doubles, double* recon, double* loss_part, void* stream,
-                 const StepTailArgs* tail, const AssignLoss* al = nullptr) {
+                 const StepTailArgs* tail, const StageLoss* al = nullptr) {
   if (int rc = check_desc(dp)) return rc;
   const lgn_net_desc& d = *dp;
   LGN_CHECK_ARG(params && grads && enc_off && dec_off && p4 && target && mask && workspace && recon && loss_part && n_params > 0,
@@ -1217,17 +1253,19 @@ int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, lo
   // ---------------- forward, loss (and its backward) ----------------
   const RowLayout ro = dec_output_rows(d, CL);
   DQ_NEW(part, (size_t)B * ro.width);
-  const LossStage ls{params + dec_off[S.out0(true) + 1], target, 1.0, d.get_real, d.jet_loss_scale, recon, loss_part, k.gv[cur], part};
-  const bool rides = !al && level_fwd_carries_loss(Nd, d.flags);      // (an assignment loss is a launch of its own in every regime)
+  const bool chamfer = stage_keeps_chamfer(al);
+  const LossStage ls{params + dec_off[S.out0(true) + 1], target, chamfer_scale(al), d.get_real, d.jet_loss_scale, recon, loss_part, k.gv[cur], part};
+  const bool rides = chamfer && level_fwd_carries_loss(Nd, d.flags);  // (a StageLoss is a launch of its own in every regime)
   // fused: the first kernel also zeroes the gradient buffer (dead parameters keep an exact zero) and zeros_s | g_p | g_lat_s | tail_cnt
   const InputStage in0{params + enc_off[0], params + enc_off[1], grads, (size_t)n_params, k.zeros_s, k.zero_doubles};
   if (split) LGN_TRY(zero_ranges(grads, (size_t)n_params, k.zero0(), k.zero_doubles, nullptr, 0, st));
   LGN_TRY(autoencoder_fwd(d, dd, params, enc_off, dec_off, p4, mask, in_scalars, w, in0, rides ? &ls : nullptr, /*eval=*/false,
                           /*keep_s=*/false, st));
+  if (chamfer && !rides)
+    LGN_TRY(dec_output_loss(B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, chamfer_scale(al), ls.method, ls.jscale, recon, loss_part,
+                            k.gv[cur], part, st));
   if (al)
-    LGN_TRY(dec_output_assign_loss(B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, ls.method, *al, recon, loss_part, k.gv[cur], part, st));
-  else if (!rides)
-    LGN_TRY(dec_output_loss(B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, 1.0, ls.method, ls.jscale, recon, loss_part, k.gv[cur], part, st));
+    LGN_TRY(stage_loss_train(*al, B, Nd, CL, w.dec.v[d.n_levels], ls.wo1, target, ls.method, recon, loss_part, k.gv[cur], part, st));
   ro.add(dq, part, B, grads, dec_off);
 
   // ---------------- backward ----------------
@@ -1332,7 +1370,7 @@ long long eval_workspace(const lgn_net_desc& d) {
 int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
               const double* target, const uint8_t* mask, const double* in_scalars, double* workspace, long long workspace_doubles,
               double* recon_real, double* lat_s_out, double* lat_v_out, double* loss_part, double* loss_out, hipStream_t st,
-              const AssignLoss* al) {
+              const StageLoss* al) {
   // every refusal comes before the first launch
   if (int rc = check_desc(dp)) return rc;
   const lgn_net_desc& d = *dp;
@@ -1350,6 +1388,7 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
   const double* wo1 = params + dec_off[Slots{d.n_levels, d.mlp_nlin}.out0(true) + 1];
   const double* vL;                  // the decoder's last-level vectors
   bool rides = false;                // output + loss rode on the decoder's last level
+  const bool chamfer = stage_keeps_chamfer(al);
   if (is_generic(d, false) || is_generic(d, true)) {
     LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step_eval: encoder and decoder must both be table-driven (or both fused)");
     LGN_CHECK_ARG(!step_is_split(d), "step_eval: table-driven networks take the mass as the only input scalar and one node count for "
@@ -1364,15 +1403,15 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
     lgn_net_desc dd = d;
     dd.N = Nd;
     const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
-    rides = !al && level_fwd_carries_loss(Nd, d.flags);
+    rides = chamfer && level_fwd_carries_loss(Nd, d.flags);
     const InputStage in0{params + enc_off[0], params + enc_off[1]};
     // the latent scalars (the encoder's last CGMLP and what the latent stage makes of its output) only when they are returned
     LGN_TRY(autoencoder_fwd(d, dd, params, enc_off, dec_off, p4, mask, in_scalars, w, in0, rides ? &loss : nullptr, /*eval=*/true,
                             /*keep_s=*/lat_s_out != nullptr, st));
     vL = w.dec.v[d.n_levels];
   }
-  if (al) LGN_TRY(dec_output_assign_eval(B, Nd, CL, vL, wo1, target, d.get_real, *al, recon_real, loss_part, st));
-  else if (!rides) LGN_TRY(dec_output_eval(B, Nd, CL, vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+  if (chamfer && !rides) LGN_TRY(dec_output_eval(B, Nd, CL, vL, wo1, target, d.get_real, d.jet_loss_scale, recon_real, loss_part, st));
+  if (al) LGN_TRY(stage_loss_eval(*al, B, Nd, CL, vL, wo1, target, d.get_real, recon_real, loss_part, st));
   return eval_loss_sum(B, Ne, mask, loss_part, loss_out, st);
 }
 
@@ -1532,8 +1571,8 @@ int lgn_step_fwd_bwd_f64(const lgn_net_desc* d, const double* params, double* gr
                          const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
                          double* workspace, long long workspace_doubles, double* recon, double* loss_part, const lgn_loss_desc* loss,
                          int* assignment, int* status, void* stream) {
-  AssignLoss al;
-  const AssignLoss* alp;
+  StageLoss al;
+  const StageLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   return step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles, recon,
                       loss_part, stream, nullptr, alp);
@@ -1544,8 +1583,8 @@ int lgn_step_train_f64(const lgn_net_desc* d, double* params, double* grads, lon
                        double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss, double l1_lambda,
                        double* adam_m, double* adam_v, long long* step_dev, double lr, double beta1, double beta2, double eps,
                        int do_adam, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
-  AssignLoss al;
-  const AssignLoss* alp;
+  StageLoss al;
+  const StageLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   LGN_CHECK_ARG(loss_out && n_loss > 0, "step_train: null pointer");
   LGN_CHECK_ARG(!do_adam || (adam_m && adam_v && step_dev), "step_train: Adam state missing");
@@ -1573,8 +1612,8 @@ int lgn_step_train_opt_f64(const lgn_net_desc* d, double* params, double* grads,
                            double* workspace, long long workspace_doubles, double* recon, double* loss_part, int n_loss,
                            const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
                            double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
-  AssignLoss al;
-  const AssignLoss* alp;
+  StageLoss al;
+  const StageLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   LGN_CHECK_ARG(loss_out && n_loss > 0, "step_train_opt: null pointer");
   StepTailArgs tail{};
@@ -1604,8 +1643,8 @@ int lgn_step_eval_f64(const lgn_net_desc* d, const double* params, const int64_t
                       const double* p4_scaled, const double* p4_target, const uint8_t* mask, const double* in_scalars,
                       double* workspace, long long workspace_doubles, double* recon_real, double* lat_s, double* lat_v,
                       double* loss_part, double* loss_out, const lgn_loss_desc* loss, int* assignment, int* status, void* stream) {
-  AssignLoss al;
-  const AssignLoss* alp;
+  StageLoss al;
+  const StageLoss* alp;
   if (int rc = plan_assign_loss(d, loss, assignment, status, al, &alp)) return rc;
   return step_eval(d, params, enc_off, dec_off, p4_scaled, p4_target, mask, in_scalars, workspace, workspace_doubles, recon_real, lat_s,
                    lat_v, loss_part, loss_out, (hipStream_t)stream, alp);

@@ -164,8 +164,22 @@ class EmdOpts(C.Structure):
     _fields_ = [("R", C.c_double), ("beta", C.c_double), ("norm", C.c_int), ("periodic_phi", C.c_int)]
 
 
+class EMDLossDesc(C.Structure):
+    """lgn_emd_loss_desc of include/lgn_amd.h: the `loss` of a whole-step call whose kind is LOSS_EMD (passed as a pointer to its
+    first member: ``loss_ref``)."""
+    _fields_ = [("base", LossDesc), ("opts", EmdOpts), ("chamfer_weight", C.c_double)]
+
+
+def loss_ref(desc):
+    """The `loss` argument of the whole-step calls for a LossDesc, an EMDLossDesc (the C prefix idiom: a pointer to its first member,
+    which is the struct's own address) or None (Chamfer: NULL)."""
+    if desc is None:
+        return None
+    return C.byref(desc.base) if isinstance(desc, EMDLossDesc) else C.byref(desc)
+
+
 OPT_ADAM, OPT_RMSPROP = 0, 1
-LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN = 0, 1, 2
+LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN, LOSS_EMD = 0, 1, 2, 3
 ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
 _dp = C.POINTER(NetDesc)
 _lp = C.POINTER(LossDesc)
@@ -265,6 +279,7 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_roc_workspace_bytes": [_ll, _i],
     "lgn_emd_workspace_bytes": [_i, _i],
     "lgn_emd_lds_bytes": [_i],
+    "lgn_emd_loss_lds_bytes": [_i, _i],
     # (mode, B0, B1, n, m, row_begin, row_count)
     "lgn_emd_pairs_grad_slab_bytes": [_i] * 7,
     "lgn_column_stats_workspace_bytes": [_ll, _i],

@@ -271,8 +271,9 @@ class EpochRunner:
             self._graph = None               # the parameter blocks moved: the step re-planned, its calls have new arguments
         tail = self.count - (self.steps - 1) * self.B          # jets of the last batch
         # the means of an evaluation step (jet-feature MSE, mse / hungarian) run over the real jets: its short batch is a call of its
-        # own descriptors, outside any graph
-        eager_tail = not self.training and tail < self.B and (s.chamfer_jet_features or s.loss_desc is not None)
+        # own descriptors, outside any graph (the EMD loss stage is a sum over the jets, like Chamfer: no such call)
+        eager_tail = not self.training and tail < self.B and (s.chamfer_jet_features or
+                                                              s.loss_kind in (s.N.LOSS_MSE, s.N.LOSS_HUNGARIAN))
         if self.single_graph and self._graph is None:
             self._capture()
         self._reset()

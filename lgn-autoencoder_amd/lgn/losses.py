@@ -14,7 +14,10 @@ over the jets, capturable into a graph.
 ``EMDLoss`` and ``HybridLoss`` have the interface of ``utils.losses.EMDLoss`` and of get_loss()'s hybrid branch, on the exact
 energy mover's distance of lgn.emd (csrc/emd.hip: the transportation LP and its closed-form gradient in one launch) -- not jetnet's
 regularised QP.  Both take energyflow's R, beta, norm and periodic_phi as keywords (csrc/emd_grad_opts.hip).  No --loss-choice string selects them (``loss_kind`` keeps refusing 'emd' and 'hybrid'): pass an instance as
-``loss_choice`` to the module-API steps of lgn.step."""
+``loss_choice`` to the module-API steps of lgn.step, or -- with ``native_emd=True`` -- to NativeTrainStep / NativeEvalStep /
+native_train_step / native_eval_step, where the EMD then runs as the step's loss stage (csrc/emd_loss.hip: the same per-jet value bit
+for bit; HybridLoss on top of the step's own Chamfer loss) and the module's ``status`` is the step's status buffer.  ``native_emd``
+defaults to False only because tests pin the refusal of loss modules by the native steps; a later change flips it."""
 from typing import Optional
 
 import torch

@@ -416,13 +416,56 @@ def _step_desc(encoder, decoder, B: int, split: bool, get_real_method: str, jet_
     return d, keep
 
 
-def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, decoder):
+def _share_status(loss_choice, status):
+    """A loss module that runs as the native step's loss stage (native_emd) shows the step's status buffer as its own ``status``: the
+    buffer is static, every step (and graph replay) fills it with the LGN_EMD_* flags of its jets."""
+    if isinstance(loss_choice, torch.nn.Module) and status is not None:
+        getattr(loss_choice, "emd", loss_choice).status = status
+
+
+def _emd_loss_desc(module, jet_features, decoder):
+    """(LOSS_EMD, lgn_emd_loss_desc) of an lgn.losses.EMDLoss or HybridLoss instance: its options and chamfer_loss_weight as the loss
+    stage of a whole step (csrc/emd_loss.hip).  The loss is a sum over the jets: scale = 1 whatever the batch or the world size."""
+    from . import _native as N
+    from .losses import EMDLoss, HybridLoss
+    if isinstance(module, HybridLoss):
+        emd, weight = module.emd, float(module.chamfer_loss_weight)
+        if jet_features:
+            raise NotImplementedError("the native hybrid loss stage does not take chamfer_jet_features (the jet-feature term of its Chamfer "
+                                      "part); that combination runs through the module API")
+        if not (0.0 <= weight < float("inf")):
+            raise ValueError(f"HybridLoss: chamfer_loss_weight={module.chamfer_loss_weight!r} must be finite and >= 0")
+    elif isinstance(module, EMDLoss):
+        emd, weight = module, 0.0
+        if jet_features:
+            raise ValueError("chamfer_jet_features is an option of the Chamfer loss; it cannot be combined with an EMDLoss")
+    else:
+        raise NotImplementedError(f"a loss module ({type(module).__name__}) is not part of the whole-step native calls (native_emd takes "
+                                  "lgn.losses.EMDLoss and HybridLoss); it runs through the module API (TrainStep, ReferenceLoopStep, "
+                                  "CapturedModuleStep, ModuleEvalStep)")
+    Nd = decoder.num_output_particles
+    need = N.lib().lgn_emd_loss_lds_bytes(Nd, decoder.num_channels[-1])
+    if Nd > N.EMD_NMAX or not 0 <= need <= N.LDS_LIMIT:
+        raise NotImplementedError(f"the native EMD loss stage at {Nd} particles needs {need} B of LDS (lgn_emd_loss_lds_bytes; limit "
+                                  f"{N.LDS_LIMIT}, at most {N.EMD_NMAX} particles); this configuration runs through the module API")
+    ld = N.EMDLossDesc()
+    ld.base.kind, ld.base.abs_coord, ld.base.polar_coord, ld.base.scale = N.LOSS_EMD, 0, 0, 1.0
+    ld.opts.R, ld.opts.beta, ld.opts.norm, ld.opts.periodic_phi = emd.R, emd.beta, int(emd.norm), int(emd.periodic_phi)
+    ld.chamfer_weight = weight
+    return N.LOSS_EMD, ld
+
+
+def _loss_desc(loss_choice, abs_coord, polar_coord, jet_features, n_jets, decoder, native_emd: bool = False):
     """(kind, lgn_loss_desc or None) of a whole step: None for Chamfer -- the native calls then take NULL for it.
     scale = 1 / (n_jets N D), n_jets the GLOBAL batch (the mean of nn.MSELoss over everything the ranks hold together).  Refuses
-    (NotImplementedError) a decoder whose loss stage does not fit a CU's LDS: that configuration runs through the module API."""
+    (NotImplementedError) a decoder whose loss stage does not fit a CU's LDS: that configuration runs through the module API.
+    ``native_emd``: an lgn.losses.EMDLoss / HybridLoss instance becomes an lgn_emd_loss_desc (_emd_loss_desc) instead of being
+    refused.  The default is False only because tests pin the refusal of loss modules; a later change flips it."""
     from . import _native as N
     from .losses import loss_kind, loss_columns
     if isinstance(loss_choice, torch.nn.Module):
+        if native_emd:
+            return _emd_loss_desc(loss_choice, jet_features, decoder)
         raise NotImplementedError(f"a loss module ({type(loss_choice).__name__}) is not part of the whole-step native calls; it runs "
                                   "through the module API (TrainStep, ReferenceLoopStep, CapturedModuleStep, ModuleEvalStep)")
     kind = loss_kind(loss_choice)
@@ -635,6 +678,14 @@ class NativeTrainStep:
     D), so each rank scales by 1 / (batch_size world N D).  ``assignment`` is the (B, N) int32 buffer the last step filled with every
     jet's col (static: graph replays keep filling it), ``status`` its (B,) int32 companion.
 
+    ``native_emd=True`` with an lgn.losses.EMDLoss or HybridLoss instance as ``loss_choice``: the exact EMD runs as the step's loss
+    stage (lgn_emd_loss_desc, csrc/emd_loss.hip) with the module's R / beta / norm / periodic_phi, under HybridLoss after the step's
+    own Chamfer stage weighted by chamfer_loss_weight.  The loss is a sum over the jets (no 1 / world).  ``status`` is the (B,) int32
+    buffer of LGN_EMD_* flags, which the module shows as its own ``status``; a flagged jet's term is NaN and it hands on no gradient.
+    HybridLoss with ``chamfer_jet_features`` and a decoder whose stage does not fit the LDS (lgn_emd_loss_lds_bytes) raise
+    NotImplementedError; any other module raises as before.  The default is False only because tests pin the refusal of loss
+    modules here; a later change flips it.
+
     ``optimizer_choice`` (--optimizer, matched as utils/initialize.py:153-173 matches it: 'adam' or 'rmsprop' in any case, anything
     else raises NotImplementedError) and ``l2_lambda`` (--l2-lambda: + l2_lambda * sum w^2 on the loss, utils/train.py:489-492; None
     or <= 0 is off) run in the step's tail as L1 + Adam do, same launch count (include/lgn_amd.h: lgn_optim_desc).  RMSprop takes
@@ -652,7 +703,7 @@ class NativeTrainStep:
                  force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
-                 momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max"):
+                 momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max", native_emd: bool = False):
         import ctypes as C
         from . import _native as N
         self.N = N
@@ -661,7 +712,7 @@ class NativeTrainStep:
         self.world = _world_size(process_group)
         self.loss_choice = loss_choice
         self.loss_kind, self.loss_desc = _loss_desc(loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features,
-                                                    batch_size * self.world, decoder)
+                                                    batch_size * self.world, decoder, native_emd=native_emd)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
         self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet loss terms
@@ -708,7 +759,8 @@ class NativeTrainStep:
         self._net_args = (C.byref(d), N.ptr(self.flat.flat), N.ptr(self.flat.grad), n, self.enc_off, self.dec_off, N.ptr(i.p4),
                           N.ptr(i.target), N.ptr(i.mask), N.ptr(i.in_scalars), N.ptr(self.workspace), nws, N.ptr(self.recon),
                           N.ptr(self.loss_part))
-        self._loss_args = (C.byref(self.loss_desc) if self.loss_desc is not None else None, N.ptr(i.assignment), N.ptr(i.status))
+        self._loss_args = (N.loss_ref(self.loss_desc), N.ptr(i.assignment), N.ptr(i.status))
+        _share_status(loss_choice, i.status)
 
     # -- raw native calls on the current stream
     def _fwd_bwd(self):
@@ -922,7 +974,10 @@ _STEP_KEYWORDS = {cls: set(inspect.signature(cls.__init__).parameters) - {"self"
 
 def native_train_step(encoder, decoder, batch_size: int, **kw):
     """NativeTrainStep where lgn_step_fwd_bwd_f64 covers the configuration (one native call per step), else CapturedModuleStep
-    (the module-API step captured into one graph).  Keyword arguments the two do not share go to the one that takes them."""
+    (the module-API step captured into one graph).  Keyword arguments the two do not share go to the one that takes them.
+    ``native_emd=True`` with an lgn.losses.EMDLoss / HybridLoss as ``loss_choice``: the native step where its loss stage plans (the
+    decoder fits the stage's LDS, no chamfer_jet_features), else the module route as for every other refusal.  The default is False
+    only because tests pin the refusal of loss modules; a later change flips it."""
     import warnings
     takes = _STEP_KEYWORDS
     unknown = set(kw) - takes[NativeTrainStep] - takes[CapturedModuleStep]
@@ -937,7 +992,8 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
         return NativeTrainStep(encoder, decoder, batch_size, **only(NativeTrainStep))
     except NotImplementedError:
         pass
-    dropped = sorted(k for k in kw if k not in takes[CapturedModuleStep])
+    # (native_emd only chooses between the two routes: the module route runs a loss module anyway)
+    dropped = sorted(k for k in kw if k not in takes[CapturedModuleStep] and k != "native_emd")
     if dropped:
         warnings.warn(f"native_train_step: this configuration runs as CapturedModuleStep, which does not take {dropped}; ignored")
     return CapturedModuleStep(encoder, decoder, batch_size, **only(CapturedModuleStep))
@@ -962,6 +1018,10 @@ class NativeEvalStep:
     A short last batch (B' < batch_size jets) is padded with all-masked jets; loss and outputs cover the B' real ones, and the
     jet-feature MSE, like the mse / hungarian loss, is the mean over those B' jets (nn.MSELoss on that batch).
 
+    ``native_emd=True`` with an lgn.losses.EMDLoss / HybridLoss as ``loss_choice``: the EMD loss stage, as in NativeTrainStep; ``status``
+    holds the jets' LGN_EMD_* flags (an all-masked pad jet is EMPTY under norm and is left out of the loss).  Default False only
+    because tests pin the refusal of loss modules; a later change flips it.
+
     ``normalize`` / ``normalize_method`` (--normalize): the batch is normalised per jet while it is staged (one native launch), the
     loss is taken in the normalised space, and one more kernel right behind lgn_step_eval_f64 -- inside the graph -- multiplies
     reconstruction and target back: ``run`` then also returns 'recon_denorm' and 'target_denorm' (what validate() collects,
@@ -969,13 +1029,14 @@ class NativeEvalStep:
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
                  keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
-                 hungarian_polar_coord: bool = False, normalize: bool = False, normalize_method: str = "overall_max"):
+                 hungarian_polar_coord: bool = False, normalize: bool = False, normalize_method: str = "overall_max",
+                 native_emd: bool = False):
         from . import _native as N
         self.N = N
         self.split = _check_native_pair(encoder, decoder)
         self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
         self._loss_opts = (loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features)
-        self.loss_kind, self.loss_desc = _loss_desc(*self._loss_opts, self.B, decoder)
+        self.loss_kind, self.loss_desc = _loss_desc(*self._loss_opts, self.B, decoder, native_emd=native_emd)
         self.get_real_method, self.chamfer_jet_features = get_real_method, bool(chamfer_jet_features)
         self.keep_latent, self.use_graph = bool(keep_latent), use_graph
         self._plan()
@@ -999,6 +1060,7 @@ class NativeEvalStep:
         self._graph = None
         self.n_real = d.B
         self._bind()
+        _share_status(loss_choice, i.status)
 
     def _plan(self):
         """Descriptor and parameter offsets for where the two flat blocks are now (offsets count from the lower block)."""
@@ -1024,7 +1086,7 @@ class NativeEvalStep:
         self._args = (C.byref(self.desc), self._base, self.enc_off, self.dec_off, N.ptr(self.p4), N.ptr(self.target), N.ptr(self.mask),
                       N.ptr(self.in_scalars), N.ptr(self.workspace), self.workspace.numel(), N.ptr(self.recon), N.ptr(self.lat_s),
                       N.ptr(self.lat_v), N.ptr(self.loss_part), N.ptr(self.loss_out),
-                      C.byref(self.loss_desc) if self.loss_desc is not None else None, N.ptr(self.assignment), N.ptr(self.status))
+                      N.loss_ref(self.loss_desc), N.ptr(self.assignment), N.ptr(self.status))
 
     def _eval(self, desc=None, loss_desc=None):
         """The native call on the current stream; desc / loss_desc: descriptors of the caller's for this call (a short batch)."""
@@ -1033,7 +1095,7 @@ class NativeEvalStep:
         if desc is not None:
             args[0] = C.byref(desc)
         if loss_desc is not None:
-            args[-3] = C.byref(loss_desc)
+            args[-3] = N.loss_ref(loss_desc)
         N._check(N.lib().lgn_step_eval_f64(*args, N.stream_ptr()), "lgn_step_eval_f64")
         if self.normalize:      # p4_recons * norm_factor, p4_target * norm_factor (utils/train.py:294-297): static pointers, capturable
             _denormalize(self.norm_factor, self.recon, self.recon_denorm, self.target, self.target_denorm)
@@ -1078,9 +1140,10 @@ class NativeEvalStep:
             self.load_batch(batch)
         self._follow_params()
         n = self.n_real
-        if n < self.B and (self.chamfer_jet_features or self.loss_desc is not None):
+        if n < self.B and (self.chamfer_jet_features or self.loss_kind in (self.N.LOSS_MSE, self.N.LOSS_HUNGARIAN)):
             # the means (nn.MSELoss of the jet features; mse / hungarian) run over the B' real jets: descriptors of this call's own,
-            # one call outside the graph
+            # one call outside the graph.  (The EMD stage is a sum over the jets like Chamfer: the full batch's descriptor serves,
+            # and lgn_step_eval_f64 leaves the all-masked pad jets -- NaN under norm -- out of the sum.)
             d = type(self.desc).from_buffer_copy(self.desc)
             d.jet_loss_scale = 1.0 / (4.0 * n) if self.chamfer_jet_features else 0.0
             self._eval(d, _loss_desc(*self._loss_opts, n, self.decoder)[1])
@@ -1132,8 +1195,10 @@ class ModuleEvalStep:
 
 
 def native_eval_step(encoder, decoder, batch_size: int, **kw):
-    """NativeEvalStep where lgn_step_eval_f64 covers the configuration, else ModuleEvalStep (the module API under no_grad)."""
+    """NativeEvalStep where lgn_step_eval_f64 covers the configuration, else ModuleEvalStep (the module API under no_grad).
+    ``native_emd=True``: an lgn.losses.EMDLoss / HybridLoss as ``loss_choice`` runs as the native step's loss stage where that plans
+    (default False only because tests pin the refusal of loss modules; a later change flips it)."""
     try:
         return NativeEvalStep(encoder, decoder, batch_size, **kw)
     except NotImplementedError:
-        return ModuleEvalStep(encoder, decoder, batch_size, **kw)
+        return ModuleEvalStep(encoder, decoder, batch_size, **{k: v for k, v in kw.items() if k != "native_emd"})

@@ -6,7 +6,9 @@ under `timeout -k 10`; the first failure ends the run.  One JSON line per case, 
 The gradient cases (not run by default): n30_grad / n150_grad -- 4,096 jets, the forward-only launch (emd_relative_tensor) against
 the GRAD launch (emd_relative_grad, reconstruction's gradient alone and with the target's), interleaved over three rounds, the
 fastest round of each; step_cfg2 -- one graph-replayed CapturedModuleStep at cfg2 (512 x 30, maxdim 2) with lgn.losses.EMDLoss()
-against the same step with the Chamfer loss.
+against the same step with the Chamfer loss; step_cfg2_native -- the same shape through NativeTrainStep(native_emd=True), whose loss
+stage is the EMD (csrc/emd_loss.hip), against CapturedModuleStep with the same loss and against the Chamfer native step, with the
+stage's LDS (--one step_cfg2_trace:<route>: that route's steps alone, eager, for a kernel trace of its launches).
 The option-gradient cases (not run by default): n30_grad_opts / n150_grad_opts -- the same 4,096 jets under beta = 2, under norm and
 under R = 0.8, beta = 2, norm, periodic phi: the gradient launch against the value-only launch under the same options, for the generic
 form on the jets' (pT, eta, phi) events and for the relative form, with the default options timed in the same rounds as the control.
@@ -20,7 +22,7 @@ of 30 particles (4,096 pairs, as the gradient cases) under a random upstream mat
 the control) against backward="native" with kept slabs and with keep_bytes=0; pairs_grad_upper -- the symmetric form on 91 events
 (4,095 pairs); pairs_grad_full_n150 -- 64 x 64 events of 150 particles, the flow in the workspace.  Interleaved over three rounds;
 the fastest round, every round and the spread are reported.
-    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,n30_grad_opts,n150_grad_opts,step_cfg2,pairs_full,pairs_upper,pairs_full_n150,pairs_grad_full,pairs_grad_upper,pairs_grad_full_n150]]"""
+    python tools/emd_bench.py [--steps K] [--warmup W] [--cases n30,n150[,n30_grad,n150_grad,n30_grad_opts,n150_grad_opts,step_cfg2,step_cfg2_native,pairs_full,pairs_upper,pairs_full_n150,pairs_grad_full,pairs_grad_upper,pairs_grad_full_n150]]"""
 import argparse
 import json
 import os
@@ -298,6 +300,73 @@ def one_step(steps, warmup):
     _emit(res)
 
 
+def _native_routes(B, Np, cd):
+    """the three routes of step_cfg2_native: name -> (encoder, decoder) -> step, and the loss modules by name"""
+    from lgn.losses import EMDLoss
+    from lgn.step import CapturedModuleStep, NativeTrainStep
+    mods = {"native_emd": EMDLoss(), "captured_module_emd": EMDLoss()}
+    make = {"native_emd": lambda e, d, **kw: NativeTrainStep(e, d, B, get_real_method="real", loss_choice=mods["native_emd"],
+                                                              native_emd=True, **kw),
+            "captured_module_emd": lambda e, d, **kw: CapturedModuleStep(e, d, B, get_real_method="real",
+                                                                         loss_choice=mods["captured_module_emd"], **kw),
+            "native_chamfer": lambda e, d, **kw: NativeTrainStep(e, d, B, get_real_method="real", **kw)}
+    return make, mods
+
+
+def one_step_trace(route, steps):
+    """step_cfg2_trace:<route>: `steps` eager (uncaptured) steps of one route of step_cfg2_native on a staged batch and nothing else on
+    the device, for a kernel trace of its launches:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/emd_bench.py --one
+    step_cfg2_trace:native_emd --steps 10  (the calls per kernel over `steps` are the launches per step)."""
+    import torch
+    import bench
+    import __graft_entry__ as G
+    B, Np, ce, cd = 512, 30, (3, 3, 4, 4), (4, 4, 3, 3)
+    dev = torch.device("cuda:0")
+    p4, labels = bench.synthetic_jets(B, Np, seed=5)
+    enc, dec = G._models(Np, ce, cd, dev, seed=0, maxdim=2)
+    step = _native_routes(B, Np, cd)[0][route](enc, dec, use_graph=False)
+    step.load_batch({"p4": p4.to(dev), "labels": labels.to(dev)})
+    torch.cuda.synchronize()
+    for _ in range(steps):
+        step.step()
+    torch.cuda.synchronize()
+    print(json.dumps({"case": f"step_cfg2_trace:{route}", "steps": steps, "loss": float(step.loss_out[0].item())}), flush=True)
+
+
+def one_step_native(steps, warmup):
+    """step_cfg2_native: the EMD loss as the loss stage of the native step (NativeTrainStep(native_emd=True)) against the module-API
+    step captured into one graph (CapturedModuleStep) with the same loss, and the Chamfer native step, at cfg2 (512 x 30, fp64):
+    interleaved over three rounds, every round reported."""
+    import torch
+    import bench
+    import __graft_entry__ as G
+    from lgn import _native as N
+    B, Np, ce, cd = 512, 30, (3, 3, 4, 4), (4, 4, 3, 3)
+    dev = torch.device("cuda:0")
+    p4, labels = bench.synthetic_jets(B, Np, seed=5)
+    batch = {"p4": p4.to(dev), "labels": labels.to(dev)}
+    make, mods = _native_routes(B, Np, cd)
+    runs = {}
+    for k, fn in make.items():
+        enc, dec = G._models(Np, ce, cd, dev, seed=0, maxdim=2)
+        runs[k] = fn(enc, dec)
+        runs[k].load_batch(batch)
+    ms = {k: [] for k in runs}
+    for _ in range(ROUNDS):
+        for k, s in runs.items():
+            ms[k].append(_ms(s.step, steps, warmup))
+    res = {"case": "step_cfg2_native", "kind": "one training step, graph replay", "B": B, "N": Np, "steps": steps, "rounds": ROUNDS,
+           "status_nonzero": {k: int((m.status != 0).sum().item()) for k, m in mods.items()},
+           "loss": {k: float(s.loss_out[0].item()) for k, s in runs.items()},
+           "stage_lds_bytes": int(N.lib().lgn_emd_loss_lds_bytes(Np, cd[-1]))}
+    for k in runs:
+        res[f"{k}_ms"] = min(ms[k])
+        res[f"{k}_ms_rounds"] = [round(x, 4) for x in ms[k]]
+        res[f"{k}_spread_ms"] = max(ms[k]) - min(ms[k])
+    res["native_over_captured"] = res["native_emd_ms"] / res["captured_module_emd_ms"]
+    _emit(res)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=3)
@@ -308,6 +377,10 @@ def main():
     args = ap.parse_args()
     if args.one == "step_cfg2":
         return one_step(args.steps, args.warmup)
+    if args.one == "step_cfg2_native":
+        return one_step_native(args.steps, args.warmup)
+    if args.one and args.one.startswith("step_cfg2_trace:"):
+        return one_step_trace(args.one.split(":", 1)[1], args.steps)
     if args.one in GRAD_CASES:
         return one_grad(args.one, args.steps, args.warmup)
     if args.one in GRAD_OPTS_CASES:
