@@ -234,17 +234,19 @@ typedef struct lgn_net_desc {
   int activation;          /* LGN_ACT_* of every CGMLP of both networks (the reference builds them from one --activation) */
   int n_in_scalars;        /* encoder: input scalars per node, K (0 or 1: the mass alone).  K > 1 -- jet_features and / or
                               data['scalars'], lgn/models/lgn_encoder.py:372-411: the mass, then K - 1 values per node the caller
-                              passes as in_scalars [B][N][K - 1] -- to the per-network calls and (ABI 17, maxdim = 2 networks) the
-                              whole-step calls */
+                              passes as in_scalars [B][N][K - 1] -- to the per-network calls and (ABI 17) the whole-step calls, on
+                              maxdim = 2 and table-driven networks alike; K <= 8 */
   int latent_pool;         /* encoder: how the latent channels are pooled over the particles (aggregate(), lgn/models/
                               lgn_encoder.py:419-496): 0 = 'min&max' (the reference default), else LGN_POOL(...).  With P output
                               blocks (one per pooling under '&', one in all under '+') the latent space is lat_s [2][B][P tau_s],
                               lat_v [2][B][P tau_v][4], and the decoder of a whole step takes Tin = P tau_v vectors */
   int dec_N;               /* whole-step call only: particles the decoder reconstructs when that differs from the encoder's node count N
                               (jet_features: the encoder works on N = particles + 1 nodes, lgn_encoder.py:372-411); 0 = N.  With
-                              dec_N != N or n_in_scalars > 1 the step runs its four end stages as launches of their own (maxdim = 2
-                              networks; table-driven networks refuse).  Checked at plan time: >= 0, and the decoder's end stages
-                              at dec_N particles fit LGN_LDS_LIMIT */
+                              dec_N != N or n_in_scalars > 1 the step runs its four end stages as launches of their own, each on
+                              its network's node count -- maxdim = 2 and table-driven networks alike (both kinds take dec_N and
+                              n_in_scalars; a table-driven network's layout and kernels are chosen per network on that network's
+                              node count).  Checked at plan time: >= 0, and the decoder's end stages at dec_N particles fit
+                              LGN_LDS_LIMIT */
   /* Loss options of the whole-step call (ABI 18; a zero-initialised descriptor is the 'sum' / no-jet-term step of ABI 17): */
   int get_real;            /* LGN_REAL_*: how the real reconstruction x is taken from the two planes (utils/utils.py:194-207) */
   double jet_loss_scale;   /* >= 0; adds jet_loss_scale * sum_mu (sum_i x_i - sum_j t_j)_mu^2 per jet, sums over all N rows, padding

@@ -123,6 +123,13 @@ inline int dec_nodes(const lgn_net_desc& d) { return d.dec_N > 0 ? d.dec_N : d.N
 // the step takes the two-kernel junction and the riding input stage only when both networks work on the same nodes and the mass is
 // the only input scalar; otherwise the four end stages are launches of their own
 inline bool step_is_split(const lgn_net_desc& d) { return dec_nodes(d) != d.N || d.n_in_scalars > 1; }
+// the decoder's view of a whole step's descriptor: the level sequencers, the carves and the layout predicates of a network read B, N,
+// flags and the MLP shape off the descriptor they are given -- the decoder's carries its own node count
+inline lgn_net_desc dec_view(const lgn_net_desc& d) {
+  lgn_net_desc dd = d;
+  dd.N = dec_nodes(d);
+  return dd;
+}
 // latent vectors per jet the decoder's input stage reads: its own tau_v_in, or the encoder's pooled ones
 inline int dec_tin(const lgn_net_desc& d) { return d.tau_v_in > 0 ? d.tau_v_in : pool_blocks(d.latent_pool) * d.tau_v; }
 
@@ -1132,13 +1139,15 @@ struct GenStep {
   double *lat_s, *lat_v, *g_lat_v;
   size_t total;
 };
+// (each network's activations, scratch and partial rows on its own node count: the decoder's through dd = dec_view(d))
 GenStep carve_gen_step(const lgn_net_desc& d, double* base) {
   GenStep g{};
   Bump b{base};
+  const lgn_net_desc dd = dec_view(d);
   g.ea = carve_gen_act(d, false, b.here()); b.take(g.ea.total);
-  g.da = carve_gen_act(d, true, b.here()); b.take(g.da.total);
+  g.da = carve_gen_act(dd, true, b.here()); b.take(g.da.total);
   g.es = carve_gen_scratch(d, false, b.here()); b.take(g.es.total);
-  g.ds = carve_gen_scratch(d, true, b.here()); b.take(g.ds.total);
+  g.ds = carve_gen_scratch(dd, true, b.here()); b.take(g.ds.total);
   g.lat_s = b.take(lat_s_doubles(d));
   g.lat_v = b.take(lat_v_doubles(d));        // (= the dec_tin(d) vectors the decoder reads: check_latent_match)
   g.g_lat_v = b.take(lat_v_doubles(d));
@@ -1146,11 +1155,18 @@ GenStep carve_gen_step(const lgn_net_desc& d, double* base) {
   return g;
 }
 
-// forward of a whole table-driven step up to the decoder's unpacked last-level features, training and evaluation alike: the encoder's
-// latent stage + the decoder's input stage of a jet are ONE launch (the junction kernel of the maxdim-2 step)
-int gen_autoencoder_fwd(const lgn_net_desc& d, const double* params, const int64_t* enc_off, const int64_t* dec_off, const double* p4,
-                        const uint8_t* mask, GenAct& ea, GenAct& da, double* lat_s, double* lat_v, hipStream_t st) {
+// forward of a whole table-driven step up to the decoder's unpacked last-level features, training and evaluation alike.  Two forms,
+// as autoencoder_fwd has them: the encoder's latent stage + the decoder's input stage of a jet as ONE launch (the junction kernel of
+// the maxdim-2 step), or, split (step_is_split: two node counts, several input scalars), as launches of their own, each on its
+// network's node count.  dd: the decoder's view of the descriptor (dec_view)
+int gen_autoencoder_fwd(const lgn_net_desc& d, const lgn_net_desc& dd, const double* params, const int64_t* enc_off, const int64_t* dec_off,
+                        const double* p4, const uint8_t* mask, const double* in_scalars, GenAct& ea, GenAct& da, double* lat_s,
+                        double* lat_v, hipStream_t st) {
   const Slots S{d.n_levels, d.mlp_nlin};
+  if (step_is_split(d)) {
+    LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, ea, lat_s, lat_v, st, in_scalars, /*with_latent=*/true));
+    return gen_decoder_fwd(dd, params, dec_off, lat_v, da, st, /*with_input=*/true);
+  }
   LGN_TRY(gen_encoder_fwd(d, params, enc_off, p4, mask, ea, lat_s, lat_v, st, nullptr, /*with_latent=*/false));
   LGN_TRY(junction_fwd(d.B, d.N, d.enc_channels[d.n_levels], d.tau_s, d.tau_v, d.latent_pool, ea.sL, ea.vL, params + enc_off[S.out0(false)],
                        params + enc_off[S.out0(false) + 1], lat_s, lat_v, ea.idx, d.dec_channels[0], params + dec_off[1], params + dec_off[2],
@@ -1159,9 +1175,9 @@ int gen_autoencoder_fwd(const lgn_net_desc& d, const double* params, const int64
 }
 
 int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads, long long n_params, const int64_t* enc_off,
-                     const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, double* workspace,
-                     long long workspace_doubles, double* recon, double* loss_part, hipStream_t st, const StepTailArgs* tail,
-                     const StageLoss* al) {
+                     const int64_t* dec_off, const double* p4, const double* target, const uint8_t* mask, const double* in_scalars,
+                     double* workspace, long long workspace_doubles, double* recon, double* loss_part, hipStream_t st,
+                     const StepTailArgs* tail, const StageLoss* al) {
   LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step: encoder and decoder must both be table-driven (or both fused)");
   if (int rc = check_generic(d, false)) return rc;
   if (int rc = check_generic(d, true)) return rc;
@@ -1171,9 +1187,11 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
   if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
   const Slots S{d.n_levels, d.mlp_nlin};
-  const int L = d.n_levels, B = d.B, N = d.N, CL = d.dec_channels[L];
+  const lgn_net_desc dd = dec_view(d);       // (the carve made the same one)
+  const bool split = step_is_split(d);
+  const int L = d.n_levels, B = d.B, N = dd.N, CL = d.dec_channels[L];       // N: the decoder's nodes -- what the loss stages run on
   LGN_TRY(zero_ranges(grads, (size_t)n_params, g.es.zero0, g.es.zero_doubles, g.ds.zero0, g.ds.zero_doubles, st));
-  LGN_TRY(gen_autoencoder_fwd(d, params, enc_off, dec_off, p4, mask, g.ea, g.da, g.lat_s, g.lat_v, st));
+  LGN_TRY(gen_autoencoder_fwd(d, dd, params, enc_off, dec_off, p4, mask, in_scalars, g.ea, g.da, g.lat_s, g.lat_v, st));
   Deferred dq(g.ds.parts, g.ds.parts_size);
   RadFinJob fin{};
   {
@@ -1189,25 +1207,29 @@ int gen_step_fwd_bwd(const lgn_net_desc& d, const double* params, double* grads,
   }
   std::vector<UnpackJob> post;
   double* part_in = nullptr;
-  LGN_TRY(gen_decoder_bwd(d, params, grads, dec_off, g.lat_v, g.da, g.g_lat_v, g.ds, dq, fin, post, st, &part_in));
+  // split: the decoder's input stage backward is gen_decoder_bwd's own launch (part_in stays null), the latent stage's the encoder's
+  LGN_TRY(gen_decoder_bwd(dd, params, grads, dec_off, g.lat_v, g.da, g.g_lat_v, g.ds, dq, fin, post, st, split ? nullptr : &part_in));
   const int Tin = dec_tin(d), C0d = d.dec_channels[0];
   const JunctionBwd jb{C0d, Tin, g.lat_v, params + dec_off[1], params + dec_off[3], g.da.pdec, g.ds.g_p, g.ds.gs, g.ds.gv, part_in};
   // Round 6: the static levels leave their CatMix partial rows in PARAMETER layout (nothing to unpack after the reduction), so the
   // two networks' reductions wait for ONE launch at the end of the step -- with `tail` (single process) the fused tail of the
   // maxdim-2 step (step_tail.hip: reductions + radial finalisation + L1 + Adam + loss), else reduce_segments + rad_finalize_batch.
   // Run-time-table levels (LGN_NET_NO_STATIC) keep packed rows and the round-5 sequence.
-  if (!post.empty() || !is_static(d, false) || !is_static(d, true)) {
+  // (split: either network alone may be on run-time tables -- the encoder's one node more crosses N = 32 first)
+  if (!post.empty() || !is_static(d, false) || !is_static(dd, true)) {
     // (the decoder's reductions run now: its input stage's backward must have written its partial rows -- no junction kernel here)
-    LGN_TRY(dec_input_bwd(B, N, C0d, Tin, g.lat_v, params + dec_off[1], params + dec_off[3], g.da.pdec, g.ds.g_p, g.ds.gs, g.ds.gv, g.g_lat_v,
-                          part_in, st));
+    if (!split)
+      LGN_TRY(dec_input_bwd(B, N, C0d, Tin, g.lat_v, params + dec_off[1], params + dec_off[3], g.da.pdec, g.ds.g_p, g.ds.gs, g.ds.gv, g.g_lat_v,
+                            part_in, st));
     LGN_TRY(dq.flush(st));
     LGN_TRY(run_unpack_jobs(post, st));
     // the decoder never reads the latent scalars: no gradient on them
-    LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st));
+    LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st, split ? in_scalars : nullptr));
     if (tail) LGN_TRY(finalize_tail(*tail, st));
     return 0;
   }
-  LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st, nullptr, &dq, &fin, &jb));
+  LGN_TRY(gen_encoder_bwd(d, params, grads, enc_off, p4, mask, g.ea, nullptr, g.g_lat_v, g.es, st, split ? in_scalars : nullptr, &dq, &fin,
+                          split ? nullptr : &jb));
   return end_step(dq, fin, grads, n_params, /*counters=*/nullptr, d.flags, tail, st);
 }
 
@@ -1228,10 +1250,8 @@ int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, lo
   hipStream_t st = (hipStream_t)stream;
   const bool split = step_is_split(d);
   if (is_generic(d, false) || is_generic(d, true)) {
-    LGN_CHECK_ARG(!split, "step_fwd_bwd: table-driven networks take the mass as the only input scalar and one node count "
-                  "for both networks (n_in_scalars=%d, N=%d, dec_N=%d): use the per-network calls", d.n_in_scalars, d.N, d.dec_N);
-    return gen_step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, workspace, workspace_doubles, recon,
-                            loss_part, st, tail, al);
+    return gen_step_fwd_bwd(d, params, grads, n_params, enc_off, dec_off, p4, target, mask, in_scalars, workspace, workspace_doubles,
+                            recon, loss_part, st, tail, al);
   }
   Work w = carve(d, workspace);
   // the layout depends on run-time switches (LGN_AMD_DEC_PAIRWISE / LGN_AMD_LEVEL_V2 change the partial-row counts):
@@ -1241,8 +1261,7 @@ int step_fwd_bwd(const lgn_net_desc* dp, const double* params, double* grads, lo
   // MLP parameter blocks must be contiguous (W_0, b_0, W_1, b_1, ...) for the single-reduce path
   if (int rc = check_mlp_contiguous(d, false, enc_off)) return rc;
   if (int rc = check_mlp_contiguous(d, true, dec_off)) return rc;
-  lgn_net_desc dd = d;               // the decoder's view of the descriptor: the level sequencers read B, N, flags, MLP shape
-  dd.N = dec_nodes(d);
+  const lgn_net_desc dd = dec_view(d);
   const Slots S{d.n_levels, d.mlp_nlin};
   const int B = d.B, Nd = dd.N, CL = d.dec_channels[d.n_levels];
   BwdScratch& k = w.k;
@@ -1352,7 +1371,7 @@ GenEval carve_gen_eval(const lgn_net_desc& d, double* base) {
   GenEval g{};
   Bump b{base};
   g.ea = carve_gen_act(d, false, b.here()); b.take(g.ea.total);
-  g.da = carve_gen_act(d, true, b.here()); b.take(g.da.total);
+  g.da = carve_gen_act(dec_view(d), true, b.here()); b.take(g.da.total);
   g.lat_s = b.take(lat_s_doubles(d));
   g.lat_v = b.take(lat_v_doubles(d));
   g.total = b.off;
@@ -1391,17 +1410,14 @@ int step_eval(const lgn_net_desc* dp, const double* params, const int64_t* enc_o
   const bool chamfer = stage_keeps_chamfer(al);
   if (is_generic(d, false) || is_generic(d, true)) {
     LGN_CHECK_ARG(is_generic(d, false) && is_generic(d, true), "step_eval: encoder and decoder must both be table-driven (or both fused)");
-    LGN_CHECK_ARG(!step_is_split(d), "step_eval: table-driven networks take the mass as the only input scalar and one node count for "
-                  "both networks (n_in_scalars=%d, N=%d, dec_N=%d)", d.n_in_scalars, d.N, d.dec_N);
     GenEval g = carve_gen_eval(d, workspace);
-    LGN_TRY(gen_autoencoder_fwd(d, params, enc_off, dec_off, p4, mask, g.ea, g.da, lat_s_out ? lat_s_out : g.lat_s,
+    LGN_TRY(gen_autoencoder_fwd(d, dec_view(d), params, enc_off, dec_off, p4, mask, in_scalars, g.ea, g.da, lat_s_out ? lat_s_out : g.lat_s,
                                 lat_v_out ? lat_v_out : g.lat_v, st));
     vL = g.da.vL;
   } else {
     EvalWork w = carve_eval(d, workspace);
     if (lat_s_out) { w.lat_s = lat_s_out; w.lat_v = lat_v_out; }
-    lgn_net_desc dd = d;
-    dd.N = Nd;
+    const lgn_net_desc dd = dec_view(d);
     const LossStage loss{wo1, target, 1.0, d.get_real, d.jet_loss_scale, recon_real, loss_part, nullptr, nullptr};
     rides = chamfer && level_fwd_carries_loss(Nd, d.flags);
     const InputStage in0{params + enc_off[0], params + enc_off[1]};

@@ -125,7 +125,9 @@ class EpochRunner:
     shuffle / generator: every ``run_epoch()`` draws ``torch.randperm(len(dataset), generator=generator)``; without shuffle the order
     is 0 .. M - 1.  ``index`` (here or per ``run_epoch``): an explicit order, checked on the host once (``check_index``).  The order
     in force is ``self.order`` (dataset positions); ``self.index`` holds the data rows (``dataset.perm[order]``), int32, on the device.
-    collect: names out of ``COLLECTABLE`` the step has.  remainder: see ``epoch_steps``.
+    collect: names out of ``COLLECTABLE`` the step has.  remainder: see ``epoch_steps``.  A split step (``step.split``: jet_features /
+    extra input scalars -- a maxdim-2 pair, or a table-driven one built with ``table_split=True``) gets its jet node, jet-mass scalar
+    and the dataset's ``scalars`` from the same gather launch.
 
     Where the step is one graph (a single process with ``use_graph``), gather, step and collect are captured together: one launch per
     batch.  Otherwise -- the data-parallel forms with the all-reduce between two graphs, ``use_graph=False``, and the short last batch

@@ -357,9 +357,11 @@ def get_real_code(method: str) -> int:
     return code
 
 
-def _check_native_pair(encoder, decoder) -> bool:
+def _check_native_pair(encoder, decoder, table_split: bool = False) -> bool:
     """Plan-time refusals (NotImplementedError) shared by NativeTrainStep and NativeEvalStep: the configurations the whole-step
-    calls of csrc/step.hip do not cover.  Returns whether the step is the split form (jet_features / extra input scalars)."""
+    calls of csrc/step.hip do not cover.  Returns whether the step is the split form (jet_features / extra input scalars).
+    ``table_split``: plan the split form for table-driven (maxdim 3) networks too, which the C calls take as they take it for
+    maxdim-2 networks; without it such a pair is refused (the module route)."""
     from . import _native as N
     from .ops import native_kind as _kind
     if _kind(encoder) is None or _kind(encoder) != _kind(decoder):
@@ -372,10 +374,14 @@ def _check_native_pair(encoder, decoder) -> bool:
             f"maxdim={encoder.level_maxdim} map_to_latent={encoder.map_to_latent!r} mlp={encoder.mlp} mlp_depth="
             f"{encoder.mlp_depth}, decoder maxdim={decoder.level_maxdim} mlp={decoder.mlp}")
     # jet_features (the encoder works on one node more than the decoder reconstructs) and data['scalars']: the whole-step call
-    # takes them for maxdim = 2 networks (lgn_net_desc.dec_N / n_in_scalars, ABI 17), its four end stages then run as launches
-    # of their own; table-driven networks keep the module route
+    # takes them (lgn_net_desc.dec_N / n_in_scalars, ABI 17), its four end stages then run as launches of their own, each on its
+    # network's node count; table-driven networks keep the module route unless the caller asks for the split form (table_split)
     split = getattr(encoder, "tau_input_scalars", 1) != 1 or bool(getattr(encoder, "jet_features", False))
-    if split and (_kind(encoder) != "fused" or encoder.tau_input_scalars > 8):
+    if split and encoder.tau_input_scalars > 8 and (table_split or _kind(encoder) == "fused"):
+        raise NotImplementedError(f"the native step takes up to K = 8 input scalars per node (the mass, the jet-mass term of jet_features, "
+                                  f"data['scalars']); this encoder has K = {encoder.tau_input_scalars}: it runs through the module API "
+                                  "(CapturedModuleStep / native_train_step capture that step into one graph)")
+    if split and _kind(encoder) != "fused" and not table_split:
         raise NotImplementedError("the native step of table-driven (maxdim 3) networks takes the particle masses as the only input "
                                   "scalars: jet_features / extra input scalars run through the module API there (CapturedModuleStep "
                                   "/ native_train_step capture that step into one graph)")
@@ -696,19 +702,28 @@ class NativeTrainStep:
     ``normalize`` / ``normalize_method`` (--normalize / --normalize-method, utils/train.py:281-283): every batch is divided per jet
     -- by 'component_max', 'overall_max' or 'jet_E', names matched as utils/normalize_p4.py matches them -- before the encoder's
     scale and jet features, and the loss is taken against the normalised batch.  load_batch is then one native launch
-    (lgn_stage_batch_f64) in place of the torch copies; ``norm_factor`` (B, 4) holds the last batch's factors."""
+    (lgn_stage_batch_f64) in place of the torch copies; ``norm_factor`` (B, 4) holds the last batch's factors.
+
+    ``table_split=True``: a table-driven (maxdim 3) pair with ``jet_features`` and / or extra input scalars (K <= 8 per node) is
+    planned as the split form of the whole-step call, as a maxdim-2 pair always is: the encoder on its own node count and K input
+    scalars, the decoder and the loss stage on the particles it reconstructs, the four end stages as launches of their own, and
+    every option above -- get_real / chamfer_jet_features, the mse, Hungarian and EMD loss stages, normalize, RMSprop and L2,
+    enqueue() under an EpochRunner -- as for any other pair.  The keyword changes nothing for any other configuration.  The default
+    is False only because tests pin the refusal of such a pair here and its fall-back to the module route in the choosers; a later
+    change flips it."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
                  betas=(0.9, 0.999), eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  force_collective: bool = False, graph_collective: Optional[bool] = None, get_real_method: str = "sum",
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
-                 momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max", native_emd: bool = False):
+                 momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max", native_emd: bool = False,
+                 table_split: bool = False):
         import ctypes as C
         from . import _native as N
         self.N = N
         optimizer_kind(optimizer_choice)
-        self.split = _check_native_pair(encoder, decoder)
+        self.split = _check_native_pair(encoder, decoder, table_split)
         self.world = _world_size(process_group)
         self.loss_choice = loss_choice
         self.loss_kind, self.loss_desc = _loss_desc(loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features,
@@ -860,7 +875,7 @@ class NativeTrainStep:
 
 class CapturedModuleStep:
     """The training step for every configuration the MODULES run but lgn_step_fwd_bwd_f64 refuses -- ``jet_features`` / extra
-    input scalars of maxdim-3 networks, mixed maxdim-2 / maxdim-3 networks,
+    input scalars of maxdim-3 networks (unless planned with ``table_split=True``), mixed maxdim-2 / maxdim-3 networks,
     ``map_to_latent='sum'``, levels without CGMLP: ``encoder(batch) -> decoder(latent) -> lgn.losses.ChamferLoss -> backward()``
     under autograd (one native call per network and direction where the configuration allows it, per operator otherwise), then
     lgn_step_finalize_f64 (L1 sub-gradient, loss assembly, Adam) -- all of it, input preparation included, captured ONCE into a
@@ -977,7 +992,9 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
     (the module-API step captured into one graph).  Keyword arguments the two do not share go to the one that takes them.
     ``native_emd=True`` with an lgn.losses.EMDLoss / HybridLoss as ``loss_choice``: the native step where its loss stage plans (the
     decoder fits the stage's LDS, no chamfer_jet_features), else the module route as for every other refusal.  The default is False
-    only because tests pin the refusal of loss modules; a later change flips it."""
+    only because tests pin the refusal of loss modules; a later change flips it.
+    ``table_split=True``: a table-driven (maxdim 3) pair with jet_features / extra input scalars (K <= 8) gets NativeTrainStep too (its
+    split form); the default is False only because tests pin the module route for such a pair, a later change flips it."""
     import warnings
     takes = _STEP_KEYWORDS
     unknown = set(kw) - takes[NativeTrainStep] - takes[CapturedModuleStep]
@@ -992,8 +1009,8 @@ def native_train_step(encoder, decoder, batch_size: int, **kw):
         return NativeTrainStep(encoder, decoder, batch_size, **only(NativeTrainStep))
     except NotImplementedError:
         pass
-    # (native_emd only chooses between the two routes: the module route runs a loss module anyway)
-    dropped = sorted(k for k in kw if k not in takes[CapturedModuleStep] and k != "native_emd")
+    # (native_emd / table_split only choose between the two routes: the module route runs a loss module and such a pair anyway)
+    dropped = sorted(k for k in kw if k not in takes[CapturedModuleStep] and k not in ("native_emd", "table_split"))
     if dropped:
         warnings.warn(f"native_train_step: this configuration runs as CapturedModuleStep, which does not take {dropped}; ignored")
     return CapturedModuleStep(encoder, decoder, batch_size, **only(CapturedModuleStep))
@@ -1025,15 +1042,18 @@ class NativeEvalStep:
     ``normalize`` / ``normalize_method`` (--normalize): the batch is normalised per jet while it is staged (one native launch), the
     loss is taken in the normalised space, and one more kernel right behind lgn_step_eval_f64 -- inside the graph -- multiplies
     reconstruction and target back: ``run`` then also returns 'recon_denorm' and 'target_denorm' (what validate() collects,
-    utils/train.py:294-297) and 'norm_factors' in the reference's shape, (B', 1, 4) for component_max, else (B', 1, 1)."""
+    utils/train.py:294-297) and 'norm_factors' in the reference's shape, (B', 1, 4) for component_max, else (B', 1, 1).
+
+    ``table_split=True``: a table-driven (maxdim 3) pair with ``jet_features`` / extra input scalars (K <= 8) runs here as the split
+    form, as in NativeTrainStep.  Default False only because tests pin the refusal and the module route; a later change flips it."""
 
     def __init__(self, encoder, decoder, batch_size: int, get_real_method: str = "real", chamfer_jet_features: bool = False,
                  keep_latent: bool = False, use_graph: bool = True, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, normalize: bool = False, normalize_method: str = "overall_max",
-                 native_emd: bool = False):
+                 native_emd: bool = False, table_split: bool = False):
         from . import _native as N
         self.N = N
-        self.split = _check_native_pair(encoder, decoder)
+        self.split = _check_native_pair(encoder, decoder, table_split)
         self.encoder, self.decoder, self.B = encoder, decoder, int(batch_size)
         self._loss_opts = (loss_choice, hungarian_abs_coord, hungarian_polar_coord, chamfer_jet_features)
         self.loss_kind, self.loss_desc = _loss_desc(*self._loss_opts, self.B, decoder, native_emd=native_emd)
@@ -1197,8 +1217,10 @@ class ModuleEvalStep:
 def native_eval_step(encoder, decoder, batch_size: int, **kw):
     """NativeEvalStep where lgn_step_eval_f64 covers the configuration, else ModuleEvalStep (the module API under no_grad).
     ``native_emd=True``: an lgn.losses.EMDLoss / HybridLoss as ``loss_choice`` runs as the native step's loss stage where that plans
-    (default False only because tests pin the refusal of loss modules; a later change flips it)."""
+    (default False only because tests pin the refusal of loss modules; a later change flips it).
+    ``table_split=True``: a table-driven (maxdim 3) pair with jet_features / extra input scalars (K <= 8) gets NativeEvalStep too
+    (default False only because tests pin the module route for such a pair; a later change flips it)."""
     try:
         return NativeEvalStep(encoder, decoder, batch_size, **kw)
     except NotImplementedError:
-        return ModuleEvalStep(encoder, decoder, batch_size, **{k: v for k, v in kw.items() if k != "native_emd"})
+        return ModuleEvalStep(encoder, decoder, batch_size, **{k: v for k, v in kw.items() if k not in ("native_emd", "table_split")})
