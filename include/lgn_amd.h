@@ -987,7 +987,8 @@ int lgn_denormalize_f64(const double* x0, const double* x1 /*nullable*/, const d
  * lgn_epoch_collect_f64 runs once behind the step: with n_valid = min(B, count - cursor * B) it copies rows b < n_valid of each of the
  * n <= LGN_EPOCH_MAX_COLLECT sources src[k] [B][row_doubles[k]] to dst[k] [count][row_doubles[k]] at jet cursor * B + b, adds *loss to
  * epoch[0], counts the step and -- its last act, one thread -- advances the cursor.  src / dst / row_doubles are HOST arrays read during
- * the call (n = 0: all three may be NULL).  Only tensors whose batch axis leads can be collected (not the latent). */
+ * the call (n = 0: all three may be NULL).  Only tensors whose batch axis leads can be collected (the latent: lgn_epoch_collect_planes_f64
+ * below). */
 #define LGN_EPOCH_MAX_COLLECT 4
 #define LGN_EPOCH_BAD_INDEX 1
 int lgn_stage_gather_f64(const double* p4, const uint8_t* labels /*nullable*/, const double* scalars /*nullable*/, long long M,
@@ -997,6 +998,26 @@ int lgn_stage_gather_f64(const double* p4, const uint8_t* labels /*nullable*/, c
 int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, long long count, int B, int n,
                           const double* const* src /*host*/, double* const* dst /*host*/, const int* row_doubles /*host*/, void* stream);
 int lgn_epoch_reset(long long* cursor, double* epoch, int* status, void* stream);
+/* The same two calls for a SECOND plan of another batch size replayed behind the first in the same epoch -- the short last batch of a
+ * training epoch: B jets per replay of the first plan, then r = count mod B jets in one replay of a plan built for r -- and for
+ * tensors whose batch axis is the second one (the latent, [2][B][...]).  Both add functions only (ABI 19 stands).
+ *
+ * lgn_stage_gather_at_f64 is lgn_stage_gather_f64 with row b taken from index[base + cursor * B_pad + b], 0 <= base <= count.  With
+ * `full` batches of B done, the cursor holds `full`, and a plan of B_pad = r jets reads from position full * B with
+ * base = full * (B - r).  base = 0 writes the bits of lgn_stage_gather_f64.
+ *
+ * lgn_epoch_collect_planes_f64 is lgn_epoch_collect_f64 with a per-tensor planes[k] >= 1 and the same base: source k is
+ * [planes[k]][B][row_doubles[k]], its destination [planes[k]][count][row_doubles[k]]; with row0 = base + cursor * B and
+ * n_valid = min(B, count - row0), every plane is one contiguous run of n_valid * row_doubles[k] doubles written at row row0 of its
+ * plane (16-byte vectors where both ends are aligned).  Loss sum, step count, ticket and cursor as lgn_epoch_collect_f64; planes is
+ * a HOST array like the other three.  planes = 1 everywhere and base = 0 write the bits of lgn_epoch_collect_f64. */
+int lgn_stage_gather_at_f64(const double* p4, const uint8_t* labels /*nullable*/, const double* scalars /*nullable*/, long long M,
+                            const int* index, long long count, long long base, const long long* cursor, int B_pad, int N, int method,
+                            double scale, int jet_features, int K, double* p4_in, double* target, uint8_t* mask,
+                            double* in_scalars /*nullable*/, double* factor, int* status, void* stream);
+int lgn_epoch_collect_planes_f64(const double* loss, double* epoch, long long* cursor, long long count, long long base, int B, int n,
+                                 const double* const* src /*host*/, double* const* dst /*host*/, const int* row_doubles /*host*/,
+                                 const int* planes /*host*/, void* stream);
 
 #ifdef __cplusplus
 }

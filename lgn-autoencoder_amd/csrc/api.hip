@@ -300,9 +300,10 @@ int lgn_denormalize_f64(const double* x0, const double* x1, const double* factor
   return denormalize(x0, x1, factor, B, N, out0, out1, (hipStream_t)stream);
 }
 
-int lgn_stage_gather_f64(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
-                         const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K, double* p4_in,
-                         double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, void* stream) {
+// the refusals lgn_stage_gather_f64 and lgn_stage_gather_at_f64 share
+static int stage_gather_check(const double* p4, const double* scalars, long long M, const int* index, long long count,
+                              const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K,
+                              double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor, int* status) {
   LGN_CHECK_ARG(method >= LGN_NORM_NONE && method <= LGN_NORM_JET_E, "stage_gather: unknown method code %d", method);
   LGN_CHECK_ARG(M >= 1, "stage_gather: M = %lld (need M >= 1)", M);
   LGN_CHECK_ARG(count >= 1, "stage_gather: count = %lld (need count >= 1)", count);
@@ -319,12 +320,34 @@ int lgn_stage_gather_f64(const double* p4, const uint8_t* labels, const double* 
                 "stage_gather: p4, p4_in, target and factor must be 16-byte aligned");
   LGN_CHECK_ARG((reinterpret_cast<uintptr_t>(index) & 3) == 0 && (reinterpret_cast<uintptr_t>(cursor) & 7) == 0 &&
                     (reinterpret_cast<uintptr_t>(status) & 3) == 0, "stage_gather: misaligned index, cursor or status");
+  return 0;
+}
+
+int lgn_stage_gather_f64(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                         const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K, double* p4_in,
+                         double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, void* stream) {
+  if (const int rc = stage_gather_check(p4, scalars, M, index, count, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target,
+                                        mask, in_scalars, factor, status))
+    return rc;
   return stage_gather(p4, labels, scalars, M, index, count, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target, mask,
                       in_scalars, factor, status, (hipStream_t)stream);
 }
 
-int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
-                          double* const* dst, const int* row_doubles, void* stream) {
+int lgn_stage_gather_at_f64(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index,
+                            long long count, long long base, const long long* cursor, int B_pad, int N, int method, double scale,
+                            int jet_features, int K, double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor,
+                            int* status, void* stream) {
+  if (const int rc = stage_gather_check(p4, scalars, M, index, count, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target,
+                                        mask, in_scalars, factor, status))
+    return rc;
+  LGN_CHECK_ARG(base >= 0 && base <= count, "stage_gather_at: base = %lld (need 0 <= base <= count = %lld)", base, count);
+  return stage_gather_at(p4, labels, scalars, M, index, count, base, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target,
+                         mask, in_scalars, factor, status, (hipStream_t)stream);
+}
+
+// the refusals lgn_epoch_collect_f64 and lgn_epoch_collect_planes_f64 share
+static int epoch_collect_check(const double* loss, double* epoch, long long* cursor, long long count, int B, int n,
+                               const double* const* src, double* const* dst, const int* row_doubles) {
   LGN_CHECK_ARG(count >= 1, "epoch_collect: count = %lld (need count >= 1)", count);
   LGN_CHECK_ARG(B >= 1, "epoch_collect: B = %d (need B >= 1)", B);
   LGN_CHECK_ARG(n >= 0 && n <= LGN_EPOCH_MAX_COLLECT, "epoch_collect: %d tensors to collect (0 .. %d)", n, LGN_EPOCH_MAX_COLLECT);
@@ -338,7 +361,24 @@ int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, 
     LGN_CHECK_ARG(((reinterpret_cast<uintptr_t>(src[k]) | reinterpret_cast<uintptr_t>(dst[k])) & 7) == 0,
                   "epoch_collect: src and dst of tensor %d must be 8-byte aligned", k);
   }
+  return 0;
+}
+
+int lgn_epoch_collect_f64(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
+                          double* const* dst, const int* row_doubles, void* stream) {
+  if (const int rc = epoch_collect_check(loss, epoch, cursor, count, B, n, src, dst, row_doubles)) return rc;
   return epoch_collect(loss, epoch, cursor, count, B, n, src, dst, row_doubles, (hipStream_t)stream);
+}
+
+int lgn_epoch_collect_planes_f64(const double* loss, double* epoch, long long* cursor, long long count, long long base, int B, int n,
+                                 const double* const* src, double* const* dst, const int* row_doubles, const int* planes,
+                                 void* stream) {
+  if (const int rc = epoch_collect_check(loss, epoch, cursor, count, B, n, src, dst, row_doubles)) return rc;
+  LGN_CHECK_ARG(base >= 0 && base <= count, "epoch_collect_planes: base = %lld (need 0 <= base <= count = %lld)", base, count);
+  LGN_CHECK_ARG(n == 0 || planes, "epoch_collect_planes: null planes array with n = %d", n);
+  for (int k = 0; k < n; ++k)
+    LGN_CHECK_ARG(planes[k] >= 1, "epoch_collect_planes: planes = %d of tensor %d (need planes >= 1)", planes[k], k);
+  return epoch_collect_planes(loss, epoch, cursor, count, base, B, n, src, dst, row_doubles, planes, (hipStream_t)stream);
 }
 
 int lgn_epoch_reset(long long* cursor, double* epoch, int* status, void* stream) {

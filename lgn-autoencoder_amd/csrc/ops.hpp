@@ -251,6 +251,12 @@ int stage_gather(const double* p4, const uint8_t* labels, const double* scalars,
 int epoch_collect(const double* loss, double* epoch, long long* cursor, long long count, int B, int n, const double* const* src,
                   double* const* dst, const int* row_doubles, hipStream_t st);
 int epoch_reset(long long* cursor, double* epoch, int* status, hipStream_t st);
+// the same two for a second plan behind the first (rows from `base` on) and for tensors of several planes, [planes][B][rd]
+int stage_gather_at(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                    long long base, const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K,
+                    double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, hipStream_t st);
+int epoch_collect_planes(const double* loss, double* epoch, long long* cursor, long long count, long long base, int B, int n,
+                         const double* const* src, double* const* dst, const int* row_doubles, const int* planes, hipStream_t st);
 int gen_pack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* s, const double* v, double* X, hipStream_t st);
 int gen_unpack(size_t nodes_x_C, int Q, int q_s, int q_v, const double* X, double* s, double* v, hipStream_t st);
 // the same with the packed tensor tile-blocked: XT [tile][C][Q][2][64]  (M nodes; whole tiles are written, padding lanes zero)

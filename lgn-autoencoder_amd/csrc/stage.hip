@@ -14,6 +14,9 @@
 // Device-resident epochs: stage_gather_kernel is the same staging with each row's jet picked by index from a resident dataset at a
 // cursor kept on the device, epoch_collect_kernel the bookkeeping behind the step (loss sum, step count, collected rows, cursor
 // advance), epoch_reset_kernel their state's clear -- [gather | step | collect] is one linear graph, replayed once per batch.
+// stage_gather_at_kernel and epoch_collect_planes_kernel are the two with a base row (a second plan of another batch size replayed
+// behind the first: the short last batch of a training epoch) and with tensors of several planes, [planes][B][rd] (the latent); they
+// run the device code of the first two -- stage_jet and gather_jet, LGN_COLLECT_RUN and collect_arrive.
 //
 // Contraction is off: p / f * scale, the products of normsq4 and the sums round one operation at a time, as torch's do.
 #pragma clang fp contract(off)
@@ -150,6 +153,18 @@ struct GatherArgs {
   int* status;
 };
 
+// The jet at position pos of the epoch's order (pos >= count: a padding jet), with the check of its index -- the lookup of both
+// gather kernels.
+__device__ __forceinline__ long gather_jet(const GatherArgs& g, const long long pos, const int lane) {
+  long src_jet = -1;
+  if (pos < g.count) {
+    const long long j = g.index[pos];
+    if (j >= 0 && j < g.M) src_jet = (long)j;
+    else if (lane == 0) g.status[0] = LGN_EPOCH_BAD_INDEX;      // (every wave that stores, stores the same word)
+  }
+  return src_jet;
+}
+
 __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_gather_kernel(const StageArgs a, const GatherArgs g) {
   const int lane = threadIdx.x & 63;
   const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
@@ -157,13 +172,18 @@ __global__ __launch_bounds__(64 * STAGE_WAVES) void stage_gather_kernel(const St
   const long long c = g.cursor[0];
   // (a cursor outside the epoch -- negative, or so large that the product would wrap -- stages padding jets only)
   const long long pos = (c >= 0 && c <= g.count / a.B_pad) ? c * a.B_pad + b : g.count;
-  long src_jet = -1;
-  if (pos < g.count) {
-    const long long j = g.index[pos];
-    if (j >= 0 && j < g.M) src_jet = (long)j;
-    else if (lane == 0) g.status[0] = LGN_EPOCH_BAD_INDEX;      // (every wave that stores, stores the same word)
-  }
-  stage_jet(a, b, src_jet, lane);
+  stage_jet(a, b, gather_jet(g, pos, lane), lane);
+}
+
+// The gather of a second plan of another batch size behind the first (the short last batch of a training epoch): position
+// base + cursor * B_pad + b, 0 <= base <= count.  base = 0 is the kernel above.
+__global__ __launch_bounds__(64 * STAGE_WAVES) void stage_gather_at_kernel(const StageArgs a, const GatherArgs g, const long long base) {
+  const int lane = threadIdx.x & 63;
+  const long b = (long)blockIdx.x * STAGE_WAVES + (threadIdx.x >> 6);
+  if (b >= a.B_pad) return;
+  const long long c = g.cursor[0];
+  const long long pos = (c >= 0 && c <= (g.count - base) / a.B_pad) ? base + c * a.B_pad + b : g.count;
+  stage_jet(a, b, gather_jet(g, pos, lane), lane);
 }
 
 // out[b][i][mu] = x[b][i][mu] * factor[b][mu] for reconstruction and target at once: one thread per row of each tensor
@@ -202,24 +222,23 @@ struct CollectArgs {
   int rd[LGN_EPOCH_MAX_COLLECT];
 };
 
-__global__ __launch_bounds__(BLOCK) void epoch_collect_kernel(const CollectArgs a) {
-  const long long c = a.cursor[0];
-  long long n_valid = 0;
-  if (c >= 0 && c <= a.count / a.B) n_valid = a.count - c * a.B < a.B ? a.count - c * a.B : a.B;
-  const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nth = (long)gridDim.x * BLOCK;
-  for (int k = 0; k < a.n && n_valid > 0; ++k) {
-    const double* __restrict__ s = a.src[k];
-    double* __restrict__ d = a.dst[k] + c * a.B * a.rd[k];
-    const long total = (long)n_valid * a.rd[k];
-    if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {
-      const dbl2* __restrict__ s2 = reinterpret_cast<const dbl2*>(s);
-      dbl2* __restrict__ d2 = reinterpret_cast<dbl2*>(d);
-      for (long e = tid; e < total / 2; e += nth) d2[e] = s2[e];
-      if ((total & 1) && tid == 0) d[total - 1] = s[total - 1];
-    } else {
-      for (long e = tid; e < total; e += nth) d[e] = s[e];
-    }
-  }
+// One run of `total` doubles from s to d by the whole grid, 16-byte vectors where both ends are aligned: the copy of both collect
+// kernels.  It is a macro, not a function: as an inlined function the same statements leave epoch_collect_kernel with another order
+// of its scalar address arithmetic, and that kernel's code is to stay what it was, instruction for instruction.
+#define LGN_COLLECT_RUN(s, d, total, tid, nth)                                                  \
+  do {                                                                                          \
+    if (((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {        \
+      const dbl2* __restrict__ s2 = reinterpret_cast<const dbl2*>(s);                           \
+      dbl2* __restrict__ d2 = reinterpret_cast<dbl2*>(d);                                       \
+      for (long e = tid; e < total / 2; e += nth) d2[e] = s2[e];                                \
+      if ((total & 1) && tid == 0) d[total - 1] = s[total - 1];                                 \
+    } else {                                                                                    \
+      for (long e = tid; e < total; e += nth) d[e] = s[e];                                      \
+    }                                                                                           \
+  } while (0)
+
+// The arrival ticket of both collect kernels: the last workgroup to arrive books the step and advances the cursor from c.
+__device__ __forceinline__ void collect_arrive(const CollectArgs& a, const long long c) {
   __syncthreads();                     // every thread of this workgroup has read the cursor
   if (threadIdx.x == 0) {
     __threadfence();
@@ -232,6 +251,48 @@ __global__ __launch_bounds__(BLOCK) void epoch_collect_kernel(const CollectArgs 
     }
   }
 }
+
+__global__ __launch_bounds__(BLOCK) void epoch_collect_kernel(const CollectArgs a) {
+  const long long c = a.cursor[0];
+  long long n_valid = 0;
+  if (c >= 0 && c <= a.count / a.B) n_valid = a.count - c * a.B < a.B ? a.count - c * a.B : a.B;
+  const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nth = (long)gridDim.x * BLOCK;
+  for (int k = 0; k < a.n && n_valid > 0; ++k) {
+    const double* __restrict__ s = a.src[k];
+    double* __restrict__ d = a.dst[k] + c * a.B * a.rd[k];
+    const long total = (long)n_valid * a.rd[k];
+    LGN_COLLECT_RUN(s, d, total, tid, nth);
+  }
+  collect_arrive(a, c);
+}
+
+// The same bookkeeping for tensors whose batch axis is the SECOND one (the latent, [2][B][rd]) and for a second plan behind the
+// first: source k is [planes[k]][B][rd], its destination [planes[k]][count][rd], a plane ONE run of n_valid * rd doubles at row
+// row0 = base + cursor * B with n_valid = min(B, count - row0).  planes = 1 and base = 0 is the kernel above.
+struct PlaneArgs {
+  long long base;
+  int planes[LGN_EPOCH_MAX_COLLECT];
+};
+
+__global__ __launch_bounds__(BLOCK) void epoch_collect_planes_kernel(const CollectArgs a, const PlaneArgs p) {
+  const long long c = a.cursor[0];
+  long long n_valid = 0, row0 = 0;
+  if (c >= 0 && c <= (a.count - p.base) / a.B) {       // (so that row0 <= count, whatever the cursor holds)
+    row0 = p.base + c * a.B;
+    n_valid = a.count - row0 < a.B ? a.count - row0 : a.B;
+  }
+  const long tid = (long)blockIdx.x * BLOCK + threadIdx.x, nth = (long)gridDim.x * BLOCK;
+  for (int k = 0; k < a.n && n_valid > 0; ++k)
+    for (int q = 0; q < p.planes[k]; ++q) {
+      const double* __restrict__ s = a.src[k] + (long long)q * a.B * a.rd[k];
+      double* __restrict__ d = a.dst[k] + ((long long)q * a.count + row0) * a.rd[k];
+      const long total = (long)n_valid * a.rd[k];
+      LGN_COLLECT_RUN(s, d, total, tid, nth);
+    }
+  collect_arrive(a, c);
+}
+
+#undef LGN_COLLECT_RUN
 
 __global__ void epoch_reset_kernel(long long* cursor, double* epoch, int* status) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -280,6 +341,32 @@ int epoch_collect(const double* loss, double* epoch, long long* cursor, long lon
   // a thread moves about four 16-byte vectors of the largest tensor; a few workgroups saturate what a step's outputs need
   const long blocks = std::min<long>(std::max<long>((most / 2 + 4 * BLOCK - 1) / (4 * BLOCK), 1), 64);
   epoch_collect_kernel<<<(unsigned)blocks, BLOCK, 0, st>>>(a);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int stage_gather_at(const double* p4, const uint8_t* labels, const double* scalars, long long M, const int* index, long long count,
+                    long long base, const long long* cursor, int B_pad, int N, int method, double scale, int jet_features, int K,
+                    double* p4_in, double* target, uint8_t* mask, double* in_scalars, double* factor, int* status, hipStream_t st) {
+  const StageArgs a{p4, labels, scalars, B_pad, B_pad, N, method, jet_features ? 1 : 0, K, scale, p4_in, target, mask, in_scalars, factor};
+  const GatherArgs g{index, cursor, count, M, status};
+  stage_gather_at_kernel<<<cdiv(B_pad, STAGE_WAVES), 64 * STAGE_WAVES, 0, st>>>(a, g, base);
+  LGN_CHECK_LAUNCH();
+  return 0;
+}
+
+int epoch_collect_planes(const double* loss, double* epoch, long long* cursor, long long count, long long base, int B, int n,
+                         const double* const* src, double* const* dst, const int* row_doubles, const int* planes, hipStream_t st) {
+  CollectArgs a{loss, epoch, cursor, count, B, n, {}, {}, {}};
+  PlaneArgs p{base, {}};
+  long most = 0;
+  for (int k = 0; k < n; ++k) {
+    a.src[k] = src[k]; a.dst[k] = dst[k]; a.rd[k] = row_doubles[k]; p.planes[k] = planes[k];
+    most = std::max(most, (long)B * row_doubles[k] * planes[k]);
+  }
+  // (the grid of epoch_collect, sized by the largest tensor over all its planes)
+  const long blocks = std::min<long>(std::max<long>((most / 2 + 4 * BLOCK - 1) / (4 * BLOCK), 1), 64);
+  epoch_collect_planes_kernel<<<(unsigned)blocks, BLOCK, 0, st>>>(a, p);
   LGN_CHECK_LAUNCH();
   return 0;
 }

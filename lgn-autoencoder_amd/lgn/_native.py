@@ -227,6 +227,11 @@ _SIGNATURES.update({
     # (loss, epoch, cursor, count, B, n, src [host], dst [host], row_doubles [host], stream)
     "lgn_epoch_collect_f64": [_vp] * 3 + [_ll, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _ip, _vp],
     "lgn_epoch_reset": [_vp] * 4,
+    # (p4, labels, scalars, M, index, count, base, cursor, B_pad, N, method, scale, jet_features, K, p4_in, target, mask, in_scalars,
+    #  factor, status, stream)
+    "lgn_stage_gather_at_f64": [_vp] * 3 + [_ll, _vp, _ll, _ll, _vp] + [_i] * 3 + [_d, _i, _i] + [_vp] * 7,
+    # (loss, epoch, cursor, count, base, B, n, src [host], dst [host], row_doubles [host], planes [host], stream)
+    "lgn_epoch_collect_planes_f64": [_vp] * 3 + [_ll, _ll, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _ip, _ip, _vp],
     # (scores, M, ld, K, labels, fpr, tpr, thresholds, length, auc, flipped, status, workspace, workspace_bytes, stream)
     "lgn_roc_auc_f64": [_vp, _ll, _i, _i] + [_vp] * 9 + [_ll, _vp],
     # (ev0, ev1, B, n, m, R, emd, flow, dual0, dual1, status, work, work_bytes, stream)

@@ -83,6 +83,19 @@ class FlatParams:
         self.grad.zero_()
 
 
+class _SharedFlat:
+    """A FlatParams' buffers as a second plan of fewer jets sees them (NativeTrainStep.short_step): the same parameters and
+    gradients, the first ``grad_tail`` per-jet loss terms.  Nothing is re-homed or allocated."""
+
+    def __init__(self, flat: FlatParams, grad_tail: int):
+        total = flat.flat.numel()
+        self.flat, self.grad, self.params = flat.flat, flat.grad, flat.params
+        self.grad_buf = flat.grad_buf[:total + grad_tail]
+        self.tail = self.grad_buf[total:]
+
+    zero_grad = FlatParams.zero_grad
+
+
 OPTIMIZER_CHOICES = ("adam", "rmsprop")
 
 
@@ -544,14 +557,19 @@ class _OptimState:
     _force_opt = False      # tests: Adam without L2 through the lgn_optim_desc calls as well (same bits)
 
     def __init__(self, flat: FlatParams, l1_lambda, lr, betas, eps, optimizer_choice: str = "adam", l2_lambda=0.0,
-                 rms_alpha: float = 0.99, momentum: float = 0.9):
+                 rms_alpha: float = 0.99, momentum: float = 0.9, share: Optional["_OptimState"] = None):
+        """share: another plan's state on the same parameters -- its two state tensors and its step counter are this one's (a short
+        batch's step updates what the full batch's does); the loss block is this plan's own, zero-filled like any new one."""
         from . import _native as N
         self.N, self.flat = N, flat
         self.kind, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.eps = optimizer_eps(self.kind, eps, flat.flat.dtype)
-        self.adam_m, self.adam_v = torch.zeros_like(flat.flat), torch.zeros_like(flat.flat)
+        if share is not None:
+            self.adam_m, self.adam_v, self.step_dev = share.adam_m, share.adam_v, share.step_dev
+        else:
+            self.adam_m, self.adam_v = torch.zeros_like(flat.flat), torch.zeros_like(flat.flat)
+            self.step_dev = torch.zeros(1, device=flat.flat.device, dtype=torch.int64)
         self.momentum_buf, self.square_avg = self.adam_m, self.adam_v
-        self.step_dev = torch.zeros(1, device=flat.flat.device, dtype=torch.int64)
         self.opt_form = self._force_opt or self.kind != "adam" or self.l2_lambda > 0.0
         dev, dt = flat.flat.device, flat.flat.dtype
         if self.opt_form:
@@ -710,7 +728,10 @@ class NativeTrainStep:
     every option above -- get_real / chamfer_jet_features, the mse, Hungarian and EMD loss stages, normalize, RMSprop and L2,
     enqueue() under an EpochRunner -- as for any other pair.  The keyword changes nothing for any other configuration.  The default
     is False only because tests pin the refusal of such a pair here and its fall-back to the module route in the choosers; a later
-    change flips it."""
+    change flips it.
+
+    ``short_step(n)``: the step of a short last batch of n < batch_size jets -- a second plan with the same options and the means
+    over n, on this step's parameters and optimiser state (what lgn.epoch.EpochRunner replays under ``remainder='short'``)."""
 
     def __init__(self, encoder, decoder, batch_size: int, lr: float = 5e-4, l1_lambda: float = 1e-8,
                  betas=(0.9, 0.999), eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
@@ -718,11 +739,18 @@ class NativeTrainStep:
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
                  momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max", native_emd: bool = False,
-                 table_split: bool = False):
+                 table_split: bool = False, _share: Optional["NativeTrainStep"] = None):
         import ctypes as C
         from . import _native as N
         self.N = N
         optimizer_kind(optimizer_choice)
+        # what short_step(n) builds its plans with: this step's own options (a second plan is a single process's)
+        self._options = dict(lr=lr, l1_lambda=l1_lambda, betas=betas, eps=eps, optimizer=optimizer, use_graph=use_graph,
+                             get_real_method=get_real_method, chamfer_jet_features=chamfer_jet_features, loss_choice=loss_choice,
+                             hungarian_abs_coord=hungarian_abs_coord, hungarian_polar_coord=hungarian_polar_coord,
+                             optimizer_choice=optimizer_choice, l2_lambda=l2_lambda, rms_alpha=rms_alpha, momentum=momentum,
+                             normalize=normalize, normalize_method=normalize_method, native_emd=native_emd, table_split=table_split)
+        self._short = {}
         self.split = _check_native_pair(encoder, decoder, table_split)
         self.world = _world_size(process_group)
         self.loss_choice = loss_choice
@@ -730,7 +758,8 @@ class NativeTrainStep:
                                                     batch_size * self.world, decoder, native_emd=native_emd)
         self.encoder, self.decoder = encoder, decoder
         self.l1_lambda, self.lr, self.betas, self.eps = l1_lambda, lr, betas, eps
-        self.flat = FlatParams(encoder, decoder, grad_tail=batch_size)   # gradients | per-jet loss terms
+        # gradients | per-jet loss terms; a short batch's plan (_share) works in the buffers of the step it belongs to
+        self.flat = FlatParams(encoder, decoder, grad_tail=batch_size) if _share is None else _SharedFlat(_share.flat, batch_size)
         self.group = process_group
         # force_collective: take the two-graph + all-reduce branch even with one rank (exercises the capture boundaries and
         # the RCCL call on the flat buffer on a single GPU; a 1-rank SUM leaves the buffer unchanged)
@@ -761,7 +790,8 @@ class NativeTrainStep:
         self.workspace = torch.empty(nws, device=dev, dtype=dt)
         self.recon = torch.empty(2, d.B, decoder.num_output_particles, 4, device=dev, dtype=dt)
         self.loss_part = self.flat.tail
-        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum)
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum,
+                                         share=None if _share is None else _share.opt_state)
         _adopt_optim_state(self, o)
         self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True,
                                         normalize=normalize, normalize_method=normalize_method)
@@ -775,7 +805,26 @@ class NativeTrainStep:
                           N.ptr(i.target), N.ptr(i.mask), N.ptr(i.in_scalars), N.ptr(self.workspace), nws, N.ptr(self.recon),
                           N.ptr(self.loss_part))
         self._loss_args = (N.loss_ref(self.loss_desc), N.ptr(i.assignment), N.ptr(i.status))
-        _share_status(loss_choice, i.status)
+        if _share is None:                  # (a loss module keeps showing the full batch's status)
+            _share_status(loss_choice, i.status)
+
+    def short_step(self, n: int) -> "NativeTrainStep":
+        """The step of a short last batch of 1 <= n < batch_size jets, as the reference's DataLoader hands it to the loop: a second
+        plan with this step's own options whose means run over n -- jet_loss_scale = 1 / (4 n), loss scale = 1 / (n N D), n per-jet
+        terms -- on static buffers, workspace and loss block of its own, working on THIS step's parameters, gradients, optimiser state
+        tensors and step counter.  What it computes is what a fresh NativeTrainStep(batch_size=n) with the same options computes
+        on those jets from the same state: the same native call on a descriptor of n jets, not a padded batch.  Cached per n; use its
+        load_batch / step / enqueue / loss_out like this step's.  ValueError for a data-parallel step (the n jets would have to be
+        split over the ranks)."""
+        n = int(n)
+        if not 1 <= n < self.desc.B:
+            raise ValueError(f"short_step: a short batch of this step has 1 .. {self.desc.B - 1} jets; got {n}")
+        if self.collective:
+            raise ValueError("short_step: a data-parallel step takes whole batches only (a short batch would have to be split over the "
+                             "ranks)")
+        if n not in self._short:
+            self._short[n] = NativeTrainStep(self.encoder, self.decoder, n, **self._options, _share=self)
+        return self._short[n]
 
     # -- raw native calls on the current stream
     def _fwd_bwd(self):
@@ -851,7 +900,7 @@ class NativeTrainStep:
         """Stage a batch into the static input buffers (_StaticInputs.stage)."""
         if tuple(batch["p4"].shape) != tuple(self.target.shape):
             raise ValueError(f"NativeTrainStep was built for batches of shape {tuple(self.target.shape)}, got {tuple(batch['p4'].shape)} "
-                             "(static buffers / captured graph: pad or drop the last short batch)")
+                             "(static buffers / captured graph: drop the last short batch, or step it with short_step(n))")
         self.inputs.stage(batch)
 
     def step(self, batch: Optional[Dict[str, torch.Tensor]] = None):
@@ -984,7 +1033,7 @@ class CapturedModuleStep:
         return self.loss_out[0], self.recon
 
 
-_STEP_KEYWORDS = {cls: set(inspect.signature(cls.__init__).parameters) - {"self"} for cls in (NativeTrainStep, CapturedModuleStep)}
+_STEP_KEYWORDS = {cls: set(inspect.signature(cls.__init__).parameters) - {"self", "_share"} for cls in (NativeTrainStep, CapturedModuleStep)}
 
 
 def native_train_step(encoder, decoder, batch_size: int, **kw):
