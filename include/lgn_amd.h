@@ -745,6 +745,70 @@ int lgn_emd_pairs_grad_f64(const double* ev0, const double* ev1 /*NULL: UPPER*/,
 int lgn_emd_pairs_grad_reduce_f64(const double* s0, const double* s1, const double* G /*nullable*/, int B0, int B1, int n, int m, int mode,
                                   int row_begin, int row_count, double* g0 /*nullable*/, double* g1 /*nullable*/, void* stream);
 
+/* ---- entropic optimal transport and the Sinkhorn divergence (csrc/sinkhorn.hip): the regularised, smooth relative of the EMD above,
+ * solved by Sinkhorn iterations in the log domain, one wavefront per pair.  These only ADD functions, a struct and a status bit:
+ * LGN_AMD_ABI_VERSION stays 19.  energyflow, POT and geomloss are not available to this project: the definition here is the
+ * specification (tests/_sinkhorn_ref.py restates it in numpy).
+ *   Inputs   ev0 [B][n][3], ev1 [B][m][3], columns (pT, y, phi); opts.base gives cost and staging exactly as lgn_emd_pairs_f64 defines
+ *            them (R, beta, norm, periodic_phi); epsilon > 0, max_iter >= 1, tol >= 0, debias 0 or 1.
+ *   Extended problem: the EMD's.  Without norm the lighter event gets a fictitious particle (row n or column m) of weight |S0 - S1| at
+ *            cost 1 to every particle of the other event (0 to the other fictitious one); with norm each event's weights are divided
+ *            by that event's sum and there is none.  a [n + 1], b [m + 1] are the extended weights, S = max(sum a, sum b) (the two sums
+ *            agree to rounding), C [n + 1][m + 1] the cost.
+ *   Objective  OT_eps(a, b) = min over P of <P, C> + eps KL(P | a (x) b / S).
+ *   Iteration k = 1, 2, ..., from g = 0:
+ *            f_i <- -eps log sum_j (b_j / S) exp((g_j - C_ij) / eps)
+ *            g_j <- -eps log sum_i (a_i / S) exp((f_i - C_ij) / eps)
+ *            evaluated on F = f / eps, G = g / eps, Cs = C / eps as F_i = -(M + log sum_j exp(t_j - M)), t_j = (log(b_j / S) + G_j) - Cs_ij,
+ *            M = max_j t_j.  Terms of weightless particles are skipped; a weightless particle still gets its potential.  Every sum runs
+ *            in index order in one lane; err, the value and the mean potentials of the norm form are per-lane sums in index order
+ *            (indices l, l + 64, ...) reduced by a fixed butterfly: the same bits run to run, whatever B and the pair's place in it.
+ *   Stopping, at no extra pass: when iteration k + 1 has computed f_new, err = sum_i a_i |1 - exp((f_i - f_new_i) / eps)|, the
+ *            row-marginal violation of the current (f, g) (its column marginals are exact after a g-update).  With tol > 0 and
+ *            err <= tol S the iteration stops and keeps (f, g): f_new is not applied.  After max_iter iterations one more f evaluation
+ *            gives the final err and is not applied either.  tol > 0 and a final err > tol S set LGN_SINKHORN_ITER; value and gradients
+ *            are delivered all the same (the value is a valid lower bound of OT_eps).  tol = 0 always runs max_iter iterations and never
+ *            sets the bit.  LGN_EMD_INVALID and LGN_EMD_EMPTY as in lgn_emd_pairs_f64: such a pair's outputs are NaN (iters 0).
+ *   Outputs per pair: value E = <a, f> + <b, g>; f [n + 1], g [m + 1]; plan [n + 1][m + 1], P_ij = (a_i b_j / S) exp(F_i + G_j - Cs_ij)
+ *            (0 where a_i b_j = 0); iters, the iterations applied; err.  Each but value and status is nullable.
+ *   Gradients (g0 [B][n][3], g1 [B][m][3], each nullable; both null: the value only, the same bits): the envelope theorem at the
+ *            returned state, which is the closed form of lgn_emd_grad_opts_f64 above with the flow replaced by P and (u, v) by (f, g):
+ *            k_ij = P_ij beta theta_ij^(beta - 2) / R^2 where theta_ij > 0, else 0; the same position sums, the same s_ij under
+ *            periodic_phi, the same fictitious-particle and norm forms of the weight terms.  P is never stored for this.
+ *   debias   value = OT_eps(ev0, ev1) - OT_eps(ev0, ev0) / 2 - OT_eps(ev1, ev1) / 2: zero for equal events.  A self term is the same
+ *            routine on the event's own staged (under norm: normalised) weights, without a fictitious particle, its reference
+ *            measure a (x) a / S0; d / d a_i = f_i + g_i, its position terms count as row and as column, and its weight terms take the
+ *            norm form like the cross term's.  The self term of a weightless event is 0.  status, iters, err, f, g and plan refer to
+ *            the cross term; a self term that misses tol sets LGN_SINKHORN_ITER as well.
+ *   lgn_sinkhorn_relative_f64: recons, target [B][N][4] Cartesian jets, staged into their relative-polar frames and the gradients
+ *            carried back exactly as lgn_emd_relative_opts_f64 does it.  g_recons NULL: the value only (g_target must be NULL too).
+ *   lgn_sinkhorn_lds_bytes(n, m): the dynamic LDS of ONE wavefront, the one place that counts it (-1 outside 1 .. LGN_EMD_NMAX): with
+ *            R = max(n, m) + 1 and ld = R | 1 (odd: both walks of the matrix are free of bank conflicts)
+ *               8 * (16 R + 8)      sixteen arrays of R doubles (weights, their logs, coordinates, potentials, gradients), two jets
+ *               + 8 * R * ld        C / eps, when the sum stays within 64 KiB (max(n, m) <= 81); else the cost is recomputed from the
+ *                                   staged coordinates in every sweep.  There is no global workspace.
+ *            A workgroup holds min(4, 64 KiB / that) wavefronts, one pair each.
+ *   Refused before any launch (negative return): null ev0, ev1, recons, target, opts, value or status; B < 1; n, m or N outside
+ *   1 .. LGN_EMD_NMAX; R, beta or epsilon not a finite positive number; tol negative or not finite; max_iter < 1; g_target without
+ *   g_recons.  Nothing is allocated, nothing waits on the host, no buffer is cleared by a memset, no atomics: capturable.
+ *   Not offered: a LGN_LOSS_SINKHORN stage inside the whole-step calls; epsilon scaling (annealing); an all-pairs matrix form;
+ *   unbalanced (KL-relaxed) marginals.
+ *   Layout: sizeof(lgn_sinkhorn_opts) = 48; offsets base 0 (R 0, beta 8, norm 16, periodic_phi 20), epsilon 24, tol 32, max_iter 40,
+ *   debias 44. */
+#define LGN_SINKHORN_ITER 16
+typedef struct lgn_sinkhorn_opts {
+  lgn_emd_opts base;
+  double epsilon, tol;
+  int max_iter, debias;
+} lgn_sinkhorn_opts;
+long long lgn_sinkhorn_lds_bytes(int n, int m);
+int lgn_sinkhorn_f64(const double* ev0, const double* ev1, int B, int n, int m, const lgn_sinkhorn_opts* opts, double* value,
+                     double* g0 /*nullable*/, double* g1 /*nullable*/, double* f /*nullable*/, double* g /*nullable*/,
+                     double* plan /*nullable*/, int* iters /*nullable*/, double* err /*nullable*/, int* status, void* stream);
+int lgn_sinkhorn_relative_f64(const double* recons, const double* target, int B, int N, const lgn_sinkhorn_opts* opts, double* value,
+                              double* g_recons /*nullable: value only*/, double* g_target /*nullable*/, int* iters /*nullable*/,
+                              double* err /*nullable*/, int* status, void* stream);
+
 /* ---- batched linear sum assignment: cost [B][n][n] -> col4row [B][n] int32, scipy.optimize.linear_sum_assignment(cost[b])[1] for
  * every b, ties broken as scipy breaks them (csrc/anomaly.hip).  One wavefront per problem; 1 <= n <= LGN_ANOMALY_NMAX.
  *   status [B] int32: 1 -- the matrix holds NaN or -inf; 256 -- infeasible (+inf entries); col4row is then -1. */

@@ -164,6 +164,11 @@ class EmdOpts(C.Structure):
     _fields_ = [("R", C.c_double), ("beta", C.c_double), ("norm", C.c_int), ("periodic_phi", C.c_int)]
 
 
+class SinkhornOpts(C.Structure):
+    """lgn_sinkhorn_opts of include/lgn_amd.h."""
+    _fields_ = [("base", EmdOpts), ("epsilon", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int), ("debias", C.c_int)]
+
+
 class EMDLossDesc(C.Structure):
     """lgn_emd_loss_desc of include/lgn_amd.h: the `loss` of a whole-step call whose kind is LOSS_EMD (passed as a pointer to its
     first member: ``loss_ref``)."""
@@ -255,6 +260,10 @@ _SIGNATURES.update({
     "lgn_emd_pairs_grad_f64": [_vp, _vp] + [_i] * 5 + [C.POINTER(EmdOpts), _i, _i] + [_vp] * 5 + [_ll, _vp],
     # (s0, s1, G, B0, B1, n, m, mode, row_begin, row_count, g0, g1, stream)
     "lgn_emd_pairs_grad_reduce_f64": [_vp] * 3 + [_i] * 7 + [_vp] * 3,
+    # (ev0, ev1, B, n, m, opts, value, g0, g1, f, g, plan, iters, err, status, stream)
+    "lgn_sinkhorn_f64": [_vp, _vp, _i, _i, _i, C.POINTER(SinkhornOpts)] + [_vp] * 10,
+    # (recons, target, B, N, opts, value, g_recons, g_target, iters, err, status, stream)
+    "lgn_sinkhorn_relative_f64": [_vp, _vp, _i, _i, C.POINTER(SinkhornOpts)] + [_vp] * 7,
     # (x, rows, ld, cols, mask, mask_keep, alpha, num_edges, stats, edges, kept, status, workspace, workspace_bytes, stream)
     "lgn_column_stats_f64": [_vp, _ll, _i, _i, _vp, _i, _d, _i] + [_vp] * 5 + [_ll, _vp],
     # (counts, max_bins, edges, max_edges, n_edges [host], cols, fwhm, stream)
@@ -287,6 +296,7 @@ _LL_SIGNATURES = {          # entry points that return a long long
     "lgn_emd_loss_lds_bytes": [_i, _i],
     # (mode, B0, B1, n, m, row_begin, row_count)
     "lgn_emd_pairs_grad_slab_bytes": [_i] * 7,
+    "lgn_sinkhorn_lds_bytes": [_i, _i],
     "lgn_column_stats_workspace_bytes": [_ll, _i],
     "lgn_jet_images_workspace_bytes": [_i, _i],
     "lgn_rep_deviation_workspace_bytes": [_i, _i, _i, _ip, _ip, _ip],
@@ -296,6 +306,7 @@ ROC_NONFINITE, ROC_SINGLE_CLASS, ROC_BAD_LABEL, ROC_NAN = 1, 2, 4, 8    # LGN_RO
 EMD_NMAX = 191                              # LGN_EMD_NMAX of include/lgn_amd.h
 EMD_INVALID, EMD_EMPTY, EMD_ITER, EMD_INFEASIBLE = 1, 2, 4, 8    # LGN_EMD_* status bits
 EMD_PAIRS_FULL, EMD_PAIRS_UPPER, EMD_PAIRS_ALIGNED = 0, 1, 2     # LGN_EMD_PAIRS_* modes
+SINKHORN_ITER = 16                          # LGN_SINKHORN_ITER: the status bit of lgn_sinkhorn_f64 next to EMD_INVALID and EMD_EMPTY
 HIST_MAX_EDGES, HIST_MAX_COLS = 1025, 16    # LGN_HIST_MAX_EDGES, LGN_HIST_MAX_COLS of include/lgn_amd.h
 # LGN_STATS_*, LGN_STAT_* (the positions in a column's statistics, the reference's dict order) and LGN_JET_IMAGE_* of include/lgn_amd.h
 STATS_TILE, STATS_MAX_COLS, STATS_EMPTY, STATS_NONFINITE = 2048, 16, 1, 2

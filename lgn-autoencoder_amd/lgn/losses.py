@@ -17,7 +17,11 @@ regularised QP.  Both take energyflow's R, beta, norm and periodic_phi as keywor
 ``loss_choice`` to the module-API steps of lgn.step, or -- with ``native_emd=True`` -- to NativeTrainStep / NativeEvalStep /
 native_train_step / native_eval_step, where the EMD then runs as the step's loss stage (csrc/emd_loss.hip: the same per-jet value bit
 for bit; HybridLoss on top of the step's own Chamfer loss) and the module's ``status`` is the step's status buffer.  ``native_emd``
-defaults to False only because tests pin the refusal of loss modules by the native steps; a later change flips it."""
+defaults to False only because tests pin the refusal of loss modules by the native steps; a later change flips it.
+
+``SinkhornLoss`` has ``EMDLoss``'s interface on the entropic relative of that distance (lgn.sinkhorn, csrc/sinkhorn.hip: Sinkhorn
+iterations in the log domain, by default the debiased Sinkhorn divergence): a smooth loss for the module-API steps.  It is not a stage
+of the whole-step native calls: the native step classes refuse it and ``native_train_step`` returns a CapturedModuleStep for it."""
 from typing import Optional
 
 import torch
@@ -197,3 +201,45 @@ class HybridLoss(nn.Module):
             raise RuntimeError("lgn (MI355X build): HybridLoss runs only in the HIP kernels of liblgn_amd.so on a GPU device; "
                                f"got tensors on '{p4_recons.device}' and '{p4_target.device}'. There is no CPU fallback.")
         return self.chamfer_loss_weight * self.chamfer(p4_recons, p4_target, jet_features=jet_features) + self.emd(p4_recons, p4_target)
+
+
+class SinkhornLoss(nn.Module):
+    """The Sinkhorn divergence as a training loss, with ``EMDLoss``'s interface: jetnet's constructor arguments
+    (``num_particles=..., device=...``) are taken and ignored, and ``forward(p4_recons, p4_target)`` returns the sum over the jets.
+
+    Per jet the value is ``lgn.sinkhorn.sinkhorn_relative_tensor(recons, target, **options)``, bit for bit: the entropic transport
+    problem on the relative-polar frames of the EMD score (include/lgn_amd.h defines it), by default debiased --
+    OT_eps(x, t) - OT_eps(x, x) / 2 - OT_eps(t, t) / 2, zero for equal jets -- with the envelope gradient from the same launch.  Where
+    the exact LP of ``EMDLoss`` has a gradient that jumps between optimal bases, this loss is smooth.  ``R``, ``beta``, ``norm`` and
+    ``periodic_phi`` are the EMD's options.  After a forward ``status`` (LGN_EMD_INVALID, LGN_EMD_EMPTY, LGN_SINKHORN_ITER), ``iters``
+    and ``err`` hold the (B,) flags, iteration counts and marginal errors of the cross terms; a jet flagged INVALID or EMPTY makes the
+    loss NaN, a jet that only missed ``tol`` within ``max_iter`` iterations still contributes its value and gradient.
+
+    The defaults (epsilon = 0.02, max_iter = 200, tol = 1e-6) are a starting point, not a measured optimum: epsilon sets both the
+    smoothing and the number of iterations a jet needs, and no training run has tuned them."""
+
+    def __init__(self, *args, epsilon: float = 0.02, max_iter: int = 200, tol: float = 1e-6, debias: bool = True, R: float = 1.0,
+                 beta: float = 1.0, norm: bool = False, periodic_phi: bool = False, **kwargs):
+        super().__init__()
+        from .sinkhorn import _options
+        _options("SinkhornLoss", epsilon, max_iter, tol, debias, R, beta, norm, periodic_phi)
+        self.epsilon, self.max_iter, self.tol, self.debias = float(epsilon), int(max_iter), float(tol), bool(debias)
+        self.R, self.beta, self.norm, self.periodic_phi = float(R), float(beta), bool(norm), bool(periodic_phi)
+        self.status = self.iters = self.err = None
+
+    def forward(self, p4_recons: torch.Tensor, p4_target: torch.Tensor) -> torch.Tensor:
+        from .sinkhorn import SinkhornRelativeFn
+        if p4_recons.shape[-1] != 4:
+            raise ValueError(f"p4_recons must be a 4-vector. Got: {p4_recons.shape=}")
+        if p4_target.shape[-1] != 4:
+            raise ValueError(f"p4_target must be a 4-vector. Got: {p4_target.shape=}")
+        if p4_recons.device.type != "cuda" or p4_target.device.type != "cuda":
+            raise RuntimeError("lgn (MI355X build): SinkhornLoss runs only in the HIP kernels of liblgn_amd.so on a GPU device; "
+                               f"got tensors on '{p4_recons.device}' and '{p4_target.device}'. There is no CPU fallback.")
+        if p4_recons.dim() == 2 and p4_target.dim() == 2:       # one unbatched jet
+            p4_recons, p4_target = p4_recons.unsqueeze(0), p4_target.unsqueeze(0)
+        if p4_recons.dim() != 3 or p4_recons.shape != p4_target.shape:
+            raise ValueError(f"p4_recons {tuple(p4_recons.shape)} and p4_target {tuple(p4_target.shape)} must both be "
+                             "(batch, particles, 4)")
+        conf = (self.epsilon, self.max_iter, self.tol, self.debias, self.R, self.beta, self.norm, self.periodic_phi)
+        return SinkhornRelativeFn.apply(p4_recons, p4_target, self, conf).sum()    # sum over batch
