@@ -329,7 +329,15 @@ typedef struct lgn_loss_desc {
 #define LGN_NET_LIVE_SCALARS 4096 /* LGN_AMD_LIVE_SCALARS=1: the last level of either network, whose scalar output nobody reads and whose scalars carry
                                     no gradient, runs the level kernels with live scalars -- on the zero block, as before those kernels had a
                                     form without them; cross-check (bit-identical) */
-#define LGN_NET_SPLIT_TAIL 128   /* LGN_AMD_SPLIT_TAIL=1: the tail of a step (deferred reductions, radial finalisation, L1 + Adam) as the
+#define LGN_NET_MLP_KEEP 8192    /* not a cross-check but a workspace request, SET by default (lgn/_native.py: net_flags; LGN_AMD_MLP_RECOMPUTE=1
+                                    clears it): the training step and the per-network calls keep the six hidden activations of a CGMLP
+                                    of H <= 48 for its backward also beyond 8 128 rows, where the 64-row two-role kernels of
+                                    csrc/mlp_chain.hip then store and re-read them instead of recomputing them at the head of the backward --
+                                    6 x rows (rounded up to 64) x 48 doubles per CGMLP with a backward, 141.6 MB at 512 jets of 30 particles.
+                                    Without the bit the workspace is the one of before (tests/golden/workspace_doubles.json) and those batches
+                                    recompute; bit-identical results either way.  The evaluation step keeps nothing.  A new bit of `flags`
+                                    changes no struct or signature: LGN_AMD_ABI_VERSION stays 19 */
+#define LGN_NET_SPLIT_TAIL 128  /* LGN_AMD_SPLIT_TAIL=1: the tail of a step (deferred reductions, radial finalisation, L1 + Adam) as the
                                     three separate launches instead of csrc/step_tail.hip's one (cross-check; bit-identical) */
 
 /* Plan-time fit queries: bytes of LDS the largest per-jet end stage needs (one workgroup per jet; the limit is LGN_LDS_LIMIT).

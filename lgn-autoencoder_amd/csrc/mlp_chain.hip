@@ -23,7 +23,8 @@
 //                             64-row workgroup as before.  dW_l runs one step BEHIND the chain (after the barrier that follows
 //                             the publication), so the one barrier per layer also covers the tiles.
 //   db_l   = row sums of g_pre^T: the owner of a tile row adds up the A fragments it loads anyway (16 adds + 2 shuffles).
-// The hidden activations are recomputed (six more layer steps at the head of the kernel) and stay in registers: 72 doubles.
+// The hidden activations stay in registers: 72 doubles.  They are the forward's copy where the step keeps one (MlpArgs::h_saved, below)
+// and recomputed otherwise (six more layer steps at the head of the kernel).
 #include "lds.hpp"
 #include "ops.hpp"
 
@@ -350,18 +351,40 @@ __device__ __forceinline__ void fin_last(FinF fin, int r) {
   }
 }
 
-// Hidden activations kept for the backward (MlpArgs::h_saved): an opaque register image,
-// [64-row block][wave][layer][tile][lane][register] -- a lane's four registers of a tile are 32 contiguous bytes, moved as two
-// 16-byte pieces, a wave's piece = every other 16 bytes of a 2 KB run -- of exactly mlp_saved_doubles(M, H, 7) doubles.  Written and
-// read by these kernels only (same H, same lane mapping).  The forward stores layer q - 1 under layer q's matrix instructions; the
-// backward requests layer l - 1 TWO steps before the step that needs it (as it does for the weight images): loaded all at once in
-// the prologue, the 35 MB of a 512-jet batch were a burst of ~6 us in front of every backward -- what the six recomputed layers cost.
+// Hidden activations kept for the backward (MlpArgs::h_saved): an opaque register image of exactly mlp_saved_doubles(M, H, 7)
+// doubles, written and read by these kernels only (same H, same lane mapping), moved as pieces of 16 bytes per lane (two registers
+// of a tile).  The forward stores layer q - 1 under layer q's matrix instructions; the backward requests layer l - 1 TWO steps
+// before the step that needs it (as it does for the weight images): loaded all at once in the prologue, the 35 MB of a 512-jet
+// batch were a burst of ~6 us in front of every backward -- what the six recomputed layers cost.
+//   16-row kernels (saved_ptr16, save_piece / load_piece): [16-row block][layer][tile][lane][register] -- a lane's four registers of
+//     a tile are 32 contiguous bytes, a wave's piece = every other 16 bytes of a 2 KB run.
+//   64-row kernels (line_ptr, save_line / load_line): [64-row block][wave][layer][piece = 2 tile + half][lane][2 registers] -- one
+//     store or load instruction of a wave covers 1 KB of whole 128-byte lines.  (In the interleaved image every store wrote half of
+//     each line it touched, and the 35 MB of a 512-jet batch left as half-line writes: round 5, forward 11.5 -> 19.2 us.)
 template <class G>
-__device__ __forceinline__ double* saved_ptr(const MlpArgs<double>& a, int wave, int lane) {
-  return a.h_saved + ((size_t)blockIdx.x * 4 + wave) * (G::NH * G::NT * 256) + lane * 4;
+__device__ __forceinline__ double* line_ptr(const MlpArgs<double>& a, int wave, int lane) {
+  return a.h_saved + ((size_t)blockIdx.x * 4 + wave) * (G::NH * G::NT * 256) + lane * 2;
+}
+template <class G, int NTI>
+__device__ __forceinline__ void save_line(double* hs, int l, const v4d (&h)[NTI], int j) {
+  const v2d v = {h[j >> 1][2 * (j & 1)], h[j >> 1][2 * (j & 1) + 1]};
+  __builtin_nontemporal_store(v, reinterpret_cast<v2d*>(hs + (l * 2 * G::NT + j) * 128));
+}
+template <class G>
+__device__ __forceinline__ void load_line(const double* hs, int l, v4d (&h)[G::NT], int j) {
+  const v2d v = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(hs + (l * 2 * G::NT + j) * 128));
+  h[j >> 1][2 * (j & 1)] = v[0];
+  h[j >> 1][2 * (j & 1) + 1] = v[1];
 }
 template <class G>
 constexpr int saved_pieces() { return 2 * G::NT; }
+// pieces of a layer the 64-row kernels move: with a thin last tile (TH: at most two blocks, registers 2 and 3 of the tile are zeros
+// by construction, layer_fwd) the last piece is neither stored nor loaded -- a sixth of the copy at H = 36; its slot stays unused
+template <class G, bool TH>
+constexpr int line_pieces() {
+  static_assert(!TH || (G::THIN && G::NB <= 2), "a thin tile's registers 2 and 3 are padding");
+  return 2 * G::NT - (TH ? 1 : 0);
+}
 // piece j of layer l: tile j >> 1, registers 2 (j & 1) and 2 (j & 1) + 1
 template <class G, int NTI>
 __device__ __forceinline__ void save_piece(double* hs, int l, const v4d (&h)[NTI], int j) {
@@ -420,14 +443,14 @@ __global__ __launch_bounds__(TWO ? 512 : 256) void mlp_chain_fwd_kernel(MlpArgs<
   lds_barrier();
   STAMP(1);
   v4d h0[G::NT], h1[G::NT];
-  double* hs = SAVE ? saved_ptr<G>(a, wave, lane) : nullptr;
+  double* hs = SAVE ? line_ptr<G>(a, wave, lane) : nullptr;
   // step q: commit the image of layer q + 1 (loaded during step q - 1), request layer q + 2, compute layer q
   // (SAVE: the activations of layer q - 1 are stored under layer q's matrix instructions)
 #define LGN_CHAIN_STEP(Q, HIN, HOUT, KS, NTI)                                                                        \
   layer_fwd<G, KS, NTI, GEN, TH, (Q == 3)>(Wl + (Q & 1) * G::WSIZE, HIN, HOUT, c, g, a.act, [&](int i) {           \
     constexpr int NI = Items<G, KS, TH>::N;                                                                          \
     if (!TWO && !LGN_DBG_NOSTAGE) deal<NI, stage_pieces<G>()>(i, [&](int j) { stage_piece<G, false, Q>(a, Wl, wrA, wrB, tid, j); });      \
-    if (SAVE && Q > 0) deal<NI, 2 * NTI>(i, [&](int j) { save_piece<G>(hs, Q - 1, HIN, j); });                      \
+    if (SAVE && Q > 0) deal<NI, (Q > 0 ? line_pieces<G, TH>() : 1)>(i, [&](int j) { save_line<G>(hs, Q - 1, HIN, j); });            \
   });                                                                                                                \
   lds_barrier();                                                                                                     \
   STAMP(2 + Q);
@@ -440,7 +463,7 @@ __global__ __launch_bounds__(TWO ? 512 : 256) void mlp_chain_fwd_kernel(MlpArgs<
 #undef LGN_CHAIN_STEP
   if (SAVE) {
 #pragma unroll
-    for (int j = 0; j < saved_pieces<G>(); ++j) save_piece<G>(hs, G::NH - 1, h1, j);
+    for (int j = 0; j < line_pieces<G, TH>(); ++j) save_line<G>(hs, G::NH - 1, h1, j);
   }
   const v4d y = layer_out<G>(Wl + (G::NH & 1) * G::WSIZE, h1, c, g);
 #pragma unroll
@@ -547,16 +570,20 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
     gout[0][r] = ok ? x : 0.0;
   }
   v4d h[NH][NT];
-  const double* hs = SAVE ? saved_ptr<G>(a, wave, lane) : nullptr;
+  if constexpr (SAVE && TH) {      // registers 2 and 3 of the thin tile are not in the copy: zeros, as layer_fwd leaves them
+#pragma unroll
+    for (int l = 0; l < NH; ++l) h[l][NT - 1] = v4d{0, 0, 0, 0};
+  }
+  const double* hs = SAVE ? line_ptr<G>(a, wave, lane) : nullptr;
   if constexpr (SAVE) {
     // the forward's copy: the six recompute steps go away; the images start at the output layer (steps NH, NH + 1, ...: the same
     // buffers and register sets as in the recompute form)
     issue_image<G, NH>(a, wrA, tid);
     issue_image<G, NH - 1>(a, wrB, tid);
 #pragma unroll
-    for (int j = 0; j < saved_pieces<G>(); ++j) load_piece<G>(hs, NH - 1, h[NH - 1], j);      // needed by the first two steps; the
+    for (int j = 0; j < line_pieces<G, TH>(); ++j) load_line<G>(hs, NH - 1, h[NH - 1], j);      // needed by the first two steps; the
 #pragma unroll
-    for (int j = 0; j < saved_pieces<G>(); ++j) load_piece<G>(hs, NH - 2, h[NH - 2], j);      // others follow two steps ahead of their use
+    for (int j = 0; j < line_pieces<G, TH>(); ++j) load_line<G>(hs, NH - 2, h[NH - 2], j);      // others follow two steps ahead of their use
     commit_image<G, NH>(Wl, wrA, tid);
     issue_image<G, NH - 2>(a, wrA, tid);
     lds_barrier();
@@ -584,7 +611,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
   // successive layers alternate between two register arrays: the running stream still reads the old one as its B operands.
   v4d gpA[NT] = {}, gpB[NT] = {}, gin[NT];      // (TH: fin never sees registers r >= NB of the last tile: they stay zero)
   {  // q = 6, l = 6: the output layer
-    constexpr int NI = Items<G, G::KS0, TH>::N, NSV = SAVE && NH >= 3 ? saved_pieces<G>() : 0, NPC = 4 + 4 * NT + stage_pieces<G>() + NSV;
+    constexpr int NI = Items<G, G::KS0, TH>::N, NSV = SAVE && NH >= 3 ? line_pieces<G, TH>() : 0, NPC = 4 + 4 * NT + stage_pieces<G>() + NSV;
     auto fin = [&](int u, int r) {
       double y = gin[u][r] * act_slope_t<GEN>(h[NH - 1][u][r], a.act);
       pin(y);
@@ -595,7 +622,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
         if (j < 4) publish_piece<G, 1>(Gt, gout, wave, c, g, j);
         else if (j < 4 + 4 * NT) publish_piece<G, NT>(Xt, h[NH - 1], wave, c, g, j - 4);
         else if (j < 4 + 4 * NT + stage_pieces<G>()) stage_piece<G, true, NH>(a, Wl, wrA, wrB, tid, j - 4 - 4 * NT);
-        else if constexpr (NSV > 0) load_piece<G>(hs, NH - 3, h[NH >= 3 ? NH - 3 : 0], j - 4 - 4 * NT - stage_pieces<G>());
+        else if constexpr (NSV > 0) load_line<G>(hs, NH - 3, h[NH >= 3 ? NH - 3 : 0], j - 4 - 4 * NT - stage_pieces<G>());
       });
     });
 #pragma unroll
@@ -605,7 +632,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
   }
 #define LGN_CHAIN_BSTEP(L, GP, GN)                                                                                   \
   {                                                                                                                  \
-    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NSV = SAVE && (L) >= 3 ? saved_pieces<G>() : 0,               \
+    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NSV = SAVE && (L) >= 3 ? line_pieces<G, TH>() : 0,          \
                   NPC = 8 * NT + stage_pieces<G>() + NSV;                                                            \
     auto fin = [&](int u, int r) {                                                                                   \
       double y = gin[u][r] * act_slope_t<GEN>(h[(L) - 1][u][r], a.act);                                              \
@@ -617,7 +644,7 @@ __global__ __launch_bounds__(256) void mlp_chain_bwd_kernel(MlpArgs<double> a) {
         if (j < 4 * NT) publish_piece<G, NT>(Gt + ((L) & 1) * G::TSIZE, GP, wave, c, g, j);                          \
         else if (j < 8 * NT) publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], wave, c, g, j - 4 * NT);    \
         else if (j < 8 * NT + stage_pieces<G>()) stage_piece<G, true, q_>(a, Wl, wrA, wrB, tid, j - 8 * NT);         \
-        else if constexpr (NSV > 0) load_piece<G>(hs, (L) - 3, h[(L) >= 3 ? (L) - 3 : 0], j - 8 * NT - stage_pieces<G>()); \
+        else if constexpr (NSV > 0) load_line<G>(hs, (L) - 3, h[(L) >= 3 ? (L) - 3 : 0], j - 8 * NT - stage_pieces<G>()); \
       });                                                                                                            \
     });                                                                                                              \
     auto tail = [&](int i) {                                                                                         \
@@ -797,7 +824,11 @@ __device__ __forceinline__ void dw_thin3(const double* Gt, const double* Xt, dou
 // chain waves did on the side -- the weight gradients dW_l from the published tiles (one step behind the chain, as before) and the
 // staging of the weight images.  Every SIMD then holds two waves with independent instruction streams and the pipe takes whichever is
 // ready.  Same arithmetic, same summation order, same barriers (one per step, over all eight waves); 256 registers per wave.
-template <int H, int D, bool GEN, bool TH = false>
+// SAVE (MlpArgs::h_saved, the two-role forward's copy): no recompute steps -- six steps during which the dW waves had nothing but
+// the images to move.  The images start at the output layer (as in mlp_chain_bwd16s_kernel); the chain waves load layers NH - 1
+// and NH - 2 ahead of the first barrier and layer l - 3 under the matrix stream of step l, as mlp_chain_bwd_kernel<SAVE> does.
+// Every step from q = NH on is statement for statement the one of the recompute form.
+template <int H, int D, bool GEN, bool TH = false, bool SAVE = false>
 __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) {
   using G = Geo<H, D>;
   constexpr int NT = G::NT, NH = G::NH;
@@ -818,12 +849,20 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
     const int tid = (int)threadIdx.x - 256;
     double* part = a.part + (size_t)blockIdx.x * a.psize;
     WRegs<G> wrA, wrB;
-    stage_prologue<G, true>(a, Wl, wrA, wrB, tid);
-    lds_barrier();
 #define LGN_STAGE_ALL(Q)                                                                                             \
   _Pragma("unroll") for (int j = 0; j < stage_pieces<G>(); ++j) stage_piece<G, true, Q>(a, Wl, wrA, wrB, tid, j);
 #define LGN_STAGE_STEP(Q) LGN_STAGE_ALL(Q) lds_barrier();
-    LGN_STAGE_STEP(0) LGN_STAGE_STEP(1) LGN_STAGE_STEP(2) LGN_STAGE_STEP(3) LGN_STAGE_STEP(4) LGN_STAGE_STEP(5)
+    if constexpr (SAVE) {      // the images start at the output layer (steps NH, NH + 1, ...: the same buffers and register sets)
+      issue_image<G, NH>(a, wrA, tid);
+      issue_image<G, NH - 1>(a, wrB, tid);
+      commit_image<G, NH>(Wl, wrA, tid);
+      issue_image<G, NH - 2>(a, wrA, tid);
+      lds_barrier();
+    } else {
+      stage_prologue<G, true>(a, Wl, wrA, wrB, tid);
+      lds_barrier();
+      LGN_STAGE_STEP(0) LGN_STAGE_STEP(1) LGN_STAGE_STEP(2) LGN_STAGE_STEP(3) LGN_STAGE_STEP(4) LGN_STAGE_STEP(5)
+    }
     LGN_STAGE_STEP(6)                                        // the output layer's step: nothing published yet
     // step q = 2 NH - L: weight gradient of Linear L + 1 from the tiles of parity (L + 1) & 1, staging dealt under its matrix stream
     // (NT = 3: the hidden layers' nine tiles dealt evenly, dw_hidden3; the ninth tile's quarter sums of Linear L + 2 are added up by
@@ -873,22 +912,36 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
     gout[0][r] = ok ? x : 0.0;
   }
   v4d h[NH][NT];
-  lds_barrier();
-  STAMP(11);
+  if constexpr (SAVE && TH) {      // registers 2 and 3 of the thin tile are not in the copy: zeros, as layer_fwd leaves them
+#pragma unroll
+    for (int l = 0; l < NH; ++l) h[l][NT - 1] = v4d{0, 0, 0, 0};
+  }
+  const double* hs = SAVE ? line_ptr<G>(a, wave, lane) : nullptr;
+  if constexpr (SAVE) {
+#pragma unroll
+    for (int j = 0; j < line_pieces<G, TH>(); ++j) load_line<G>(hs, NH - 1, h[NH - 1], j);      // needed by the first two steps; the
+#pragma unroll
+    for (int j = 0; j < line_pieces<G, TH>(); ++j) load_line<G>(hs, NH - 2, h[NH - 2], j);      // others follow two steps ahead of their use
+    lds_barrier();
+    STAMP(11);
+  } else {
+    lds_barrier();
+    STAMP(11);
 #define LGN_CHAIN_STEP(Q, HIN, KS, NTI)                                                                              \
   layer_fwd<G, KS, NTI, GEN, TH>(Wl + (Q & 1) * G::WSIZE, HIN, h[Q], c, g, a.act, [&](int) {});                          \
   lds_barrier();                                                                                                     \
   STAMP(12 + Q);
-  LGN_CHAIN_STEP(0, xb, G::KS0, 1)
-  LGN_CHAIN_STEP(1, h[0], G::KSH, NT)
-  LGN_CHAIN_STEP(2, h[1], G::KSH, NT)
-  LGN_CHAIN_STEP(3, h[2], G::KSH, NT)
-  LGN_CHAIN_STEP(4, h[3], G::KSH, NT)
-  LGN_CHAIN_STEP(5, h[4], G::KSH, NT)
+    LGN_CHAIN_STEP(0, xb, G::KS0, 1)
+    LGN_CHAIN_STEP(1, h[0], G::KSH, NT)
+    LGN_CHAIN_STEP(2, h[1], G::KSH, NT)
+    LGN_CHAIN_STEP(3, h[2], G::KSH, NT)
+    LGN_CHAIN_STEP(4, h[3], G::KSH, NT)
+    LGN_CHAIN_STEP(5, h[4], G::KSH, NT)
 #undef LGN_CHAIN_STEP
+  }
   v4d gpA[NT] = {}, gpB[NT] = {}, gin[NT];      // (TH: fin never sees registers r >= NB of the last tile: they stay zero)
   {  // q = 6, l = 6: the output layer
-    constexpr int NI = Items<G, G::KS0, TH>::N, NPC = 4 + 4 * NT;
+    constexpr int NI = Items<G, G::KS0, TH>::N, NSV = SAVE && NH >= 3 ? line_pieces<G, TH>() : 0, NPC = 4 + 4 * NT + NSV;
     auto fin = [&](int u, int r) {
       double y = gin[u][r] * act_slope_t<GEN>(h[NH - 1][u][r], a.act);
       pin(y);
@@ -897,7 +950,8 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
     layer_bwd<G, G::KS0, NT, 1, TH>(Wl + 0 * G::WSIZE, gout, gin, c, g, fin, [&](int i) {
       deal<NI, NPC>(i, [&](int j) {
         if (j < 4) publish_piece<G, 1>(Gt, gout, wave, c, g, j);
-        else publish_piece<G, NT>(Xt, h[NH - 1], wave, c, g, j - 4);
+        else if (j < 4 + 4 * NT) publish_piece<G, NT>(Xt, h[NH - 1], wave, c, g, j - 4);
+        else if constexpr (NSV > 0) load_line<G>(hs, NH - 3, h[NH >= 3 ? NH - 3 : 0], j - 4 - 4 * NT);
       });
     });
 #pragma unroll
@@ -907,7 +961,8 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
   }
 #define LGN_CHAIN_BSTEP(L, GP, GN)                                                                                   \
   {                                                                                                                  \
-    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NPC = 8 * NT;                                                 \
+    constexpr int q_ = 2 * NH - (L), NI = Items<G, G::KSH, TH>::N, NSV = SAVE && (L) >= 3 ? line_pieces<G, TH>() : 0, \
+                  NPC = 8 * NT + NSV;                                                                                \
     auto fin = [&](int u, int r) {                                                                                   \
       double y = gin[u][r] * act_slope_t<GEN>(h[(L) - 1][u][r], a.act);                                              \
       pin(y);                                                                                                        \
@@ -916,10 +971,11 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
     layer_bwd<G, G::KSH, NT, NT, TH>(Wl + (q_ & 1) * G::WSIZE, GP, gin, c, g, fin, [&](int i) {                          \
       deal<NI, NPC>(i, [&](int j) {                                                                                  \
         if (j < 4 * NT) publish_piece<G, NT>(Gt + ((L) & 1) * G::TSIZE, GP, wave, c, g, j);                          \
-        else publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], wave, c, g, j - 4 * NT);                    \
+        else if (j < 8 * NT) publish_piece<G, NT>(Xt + ((L) & 1) * G::TSIZE, h[(L) - 1], wave, c, g, j - 4 * NT);    \
+        else if constexpr (NSV > 0) load_line<G>(hs, (L) - 3, h[(L) >= 3 ? (L) - 3 : 0], j - 8 * NT);                \
       });                                                                                                            \
     });                                                                                                              \
-    STAMP(56 + (L));                                                                                                 \
+    STAMP(56 + (L));                                                                                               \
     _Pragma("unroll") for (int r = 0; r < 4; ++r) fin_last<G, NT, TH>(fin, r);                                                    \
     STAMP(50 + (L));                                                                                                 \
     lds_barrier();                                                                                                   \
@@ -955,8 +1011,8 @@ __global__ __launch_bounds__(512) void mlp_chain_bwd2_kernel(MlpArgs<double> a) 
 // 0.05 GFLOP.  The chain form with roles needs no exchange: a workgroup is ONE chain wave (16 rows through all layers out of
 // registers), one wave for the weight gradients (K = 16 rows: four k-steps per tile, 36 matrix instructions per hidden layer: what
 // the chain wave computes meanwhile) and two waves staging the weight images -- each alone on its SIMD.  The forward keeps the
-// activations for the backward where the step asks for it (MlpArgs::h_saved, <= 8 128 rows since the split kernels below; same register image as the 64-row
-// kernels, one block per workgroup).
+// activations for the backward where the step asks for it (MlpArgs::h_saved, <= 8 128 rows since the split kernels below; the interleaved register
+// image, one block per workgroup).
 template <class G>
 __device__ __forceinline__ double* saved_ptr16(const MlpArgs<double>& a, int lane) {
   return a.h_saved + (size_t)blockIdx.x * (G::NH * G::NT * 256) + lane * 4;
@@ -1531,15 +1587,19 @@ static int launch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   if (backward) LGN_CHECK_ARG(a.psize == G::psize(), "cgmlp: psize %d, expected %d", a.psize, G::psize());
   LGN_CHECK_ARG(!a.h_saved || a.h_rows >= nblk * 64, "cgmlp: the saved-activation buffer has %d rows per layer, %d rows need %d",
                 a.h_rows, a.M, nblk * 64);
-  if (backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {      // (kept activations: the one-role kernel reads them)
-    auto k2 = a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false, TH> : mlp_chain_bwd2_kernel<H, D, true, TH>;
+  // two roles, activations kept (h_saved: the forward stores them, the backward has no recompute steps) or recomputed
+  if (backward && !(a.flags & LVL_MLP_BWD1)) {
+    auto k2 = a.h_saved ? (a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false, TH, true> : mlp_chain_bwd2_kernel<H, D, true, TH, true>)
+                        : (a.act == 0 ? mlp_chain_bwd2_kernel<H, D, false, TH, false> : mlp_chain_bwd2_kernel<H, D, true, TH, false>);
     const size_t smem2 = smem - (TH && G::NT == 3 && G::R == 4 ? sizeof(double) * 2 * 1024 : 0);      // (dw_thin3: no quarter sums)
     return lds_launch(k2, "cgmlp backward (two roles)", dim3(nblk), dim3(512), smem2, stream, a);
   }
-  if (!backward && !a.h_saved && !(a.flags & LVL_MLP_BWD1)) {
-    auto k2 = a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>;
+  if (!backward && !(a.flags & LVL_MLP_BWD1)) {
+    auto k2 = a.h_saved ? (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, true, true, TH> : mlp_chain_fwd_kernel<H, D, true, true, true, TH>)
+                        : (a.act == 0 ? mlp_chain_fwd_kernel<H, D, false, false, true, TH> : mlp_chain_fwd_kernel<H, D, true, false, true, TH>);
     return lds_launch(k2, "cgmlp forward (two roles)", dim3(nblk), dim3(512), smem, stream, a);
   }
+  // LGN_AMD_MLP_BWD1: the one-role kernels, kept or recomputed
   auto kern = a.h_saved ? (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, true, TH> : mlp_chain_fwd_kernel<H, D, false, true, false, TH>)
                                       : (backward ? mlp_chain_bwd_kernel<H, D, true, true, TH> : mlp_chain_fwd_kernel<H, D, true, true, false, TH>))
                         : (a.act == 0 ? (backward ? mlp_chain_bwd_kernel<H, D, false, false, TH> : mlp_chain_fwd_kernel<H, D, false, false, false, TH>)
@@ -1555,7 +1615,8 @@ static int launch_thin(const MlpArgs<double>& a, bool backward, hipStream_t stre
 
 }  // namespace chain
 
-// The reference widths H = 6 * 2C (C = 1 .. 4): 64-row workgroups (large batches, activations recomputed) or 16-row ones (small batches); -2 = not this kernel's shape.
+// The reference widths H = 6 * 2C (C = 1 .. 4): 64-row workgroups (large batches; activations kept where a.h_saved is set -- the step's
+// LGN_NET_MLP_KEEP -- and recomputed otherwise) or 16-row ones (small batches); -2 = not this kernel's shape.
 int mlp_chain_dispatch(const MlpArgs<double>& a, bool backward, hipStream_t stream) {
   if ((a.flags & LVL_MLP_V1) || a.nlin != 7) return -2;
   if (mlp_rows_per_workgroup(a.M, a.H) != 64) {             // small batches: 16-row workgroups (one chain wave + helpers)

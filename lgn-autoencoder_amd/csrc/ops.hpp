@@ -98,13 +98,16 @@ inline int mlp_saved_rows(int M) { return (M + 63) & ~63; }
 inline size_t mlp_saved_doubles(int M, int H, int nlin) {
   return H <= 48 && nlin >= 4 && nlin <= 7 ? (size_t)(nlin - 1) * mlp_saved_rows(M) * ((H + 15) & ~15) : 0;
 }
-// Worth it only for small batches: the copy is 6 x M x 48 doubles per CGMLP (35 MB at 512 x 30 rows: measured, the step got
-// 26 us SLOWER -- writing and re-reading it costs more than the six recomputed layers), while at 64 x 30 rows (4.4 MB) the
-// backward drops from 24 to 17 us.  The step keeps the copy when the batch has at most this many rows.
-// (Round 5, chain kernels at 512 x 30 rows, the copy moved 16 bytes per lane and re-read two steps ahead of its use: backward
-// 33.5 -> 27.7 us, forward 11.5 -> 19.2 us -- a 12 us forward cannot absorb 35 MB of stores.  Recomputation stays.)
+// The copy is 6 x M x 48 doubles per CGMLP (35 MB at 512 x 30 rows; at 64 x 30 rows, 4.4 MB, the backward drops from 24 to 17 us).
+// The step always keeps it when the batch has at most this many rows -- the 16-row regime:
 // (Round 6, 16-row chain kernels with the layers split over three waves: the copy pays up to the last batch size that runs them --
 // 256 jets x 30 rows: 0.439 -> 0.422 ms per step, 200 jets 0.431 -> 0.408 -- so the threshold is the 16-row regime itself.)
+// Beyond it the copy is the descriptor's choice (LGN_NET_MLP_KEEP, set by default; step.hip: carve_net):
+// (Round 5, ONE-role 64-row kernels at 512 x 30 rows, the copy as every other 16 bytes of a 2 KB run, i.e. half of every 128-byte
+// line per store, re-read two steps ahead of its use: backward 33.5 -> 27.7 us, forward 11.5 -> 19.2 us, the step 26 us slower.)
+// (Two-role 64-row kernels, the copy as whole lines -- 1 KB per store of a wave: the six recompute steps were steps in which the
+// four dW waves only staged images.  512 x 30 rows: backward 26.5 -> 22.4 us (H = 48) and 19.5 -> 16.3 us (H = 36), forward
+// 10.5 -> 11.8 us and 7.8 -> 9.4 us, the step 0.451 -> 0.443 ms; DESIGN.md section 5.2 has the traces and the A/B.)
 constexpr int MLP_SAVE_MAX_ROWS = 8128;
 inline size_t mlp_save_max_rows() {          // LGN_AMD_MLP_SAVE_ROWS overrides the threshold (tuning; read once)
   static const long v = [] { const char* e = getenv("LGN_AMD_MLP_SAVE_ROWS"); return e ? atol(e) : (long)MLP_SAVE_MAX_ROWS; }();

@@ -335,6 +335,8 @@ struct NetBuf {                     // per-network activations kept for the back
 // The activations a network keeps on BN = B N nodes.  last_mlp_bwd: does the last level's CGMLP have a backward?  The step never runs
 // it (the last level's scalars never reach the loss), so nothing is kept for it there; a per-network caller's
 // upstream gradient may reach every level.  (A CGMLP that rides on the level kernels recomputes: nothing kept.)
+// The copy is kept in the 16-row regime (BN <= mlp_save_max_rows()) and, beyond it, where the descriptor asks for it
+// (LGN_NET_MLP_KEEP: the 64-row two-role kernels of mlp_chain.hip); levels_fwd / levels_bwd hand on whatever is carved here.
 void carve_net(Bump& b, const lgn_net_desc& d, bool dec, size_t BN, bool last_mlp_bwd, NetBuf& n) {
   const int* ch = dec ? d.dec_channels : d.enc_channels;
   const int L = d.n_levels;
@@ -347,7 +349,7 @@ void carve_net(Bump& b, const lgn_net_desc& d, bool dec, size_t BN, bool last_ml
     n.ag0[l] = b.take(4 * BN * ch[l]);
     n.ag1[l] = b.take(16 * BN * ch[l]);
     n.sep[l] = dec ? b.take((size_t)d.B * sep_sums_doubles(ch[l])) : nullptr;
-    const size_t hs = (last_mlp_bwd || l + 1 < L) && BN <= mlp_save_max_rows()
+    const size_t hs = (last_mlp_bwd || l + 1 < L) && (BN <= mlp_save_max_rows() || (d.flags & LGN_NET_MLP_KEEP))
                           ? mlp_saved_doubles((int)BN, d.mlp_hidden_mul * 2 * ch[l + 1], d.mlp_nlin) : 0;
     n.hsave[l] = hs ? b.take(hs) : nullptr;
   }

@@ -131,6 +131,9 @@ _NET_FLAG_ENV = {"LGN_AMD_NO_STATIC": 1, "LGN_AMD_DEC_PAIRWISE": 2, "LGN_AMD_LEV
                  "LGN_AMD_MLP_BWD1": 1024, "LGN_AMD_MLP_FULLTILE": 2048,
                  # (no LGN_NET_* name in the header: csrc/level.hpp, LVL_DEC_STORE_AG)
                  "LGN_AMD_DEC_STORE_AG": 16384}
+# LGN_NET_MLP_KEEP: a workspace request, not a cross-check -- set unless LGN_AMD_MLP_RECOMPUTE=1 asks for the recomputing CGMLP
+# backward (and the smaller workspace) beyond 8 128 rows
+NET_MLP_KEEP = 8192
 # LGN_ACT_* of include/lgn_amd.h: the names get_activation_fn accepts (lgn/nn/generic_levels.py:119-135)
 ACTIVATIONS = {"leakyrelu": 0, "relu": 1, "elu": 2, "sigmoid": 3, "logsigmoid": 4, "atan": 5}
 
@@ -145,7 +148,8 @@ def activation_id(name: str) -> int:
 def net_flags() -> int:
     """LGN_NET_* bits of a descriptor created now (include/lgn_amd.h): the debug switches are read HERE, once, and frozen into
     the descriptor -- the native whole-network calls never read the environment."""
-    return sum(bit for name, bit in _NET_FLAG_ENV.items() if os.environ.get(name, "") == "1")
+    keep = 0 if os.environ.get("LGN_AMD_MLP_RECOMPUTE", "") == "1" else NET_MLP_KEEP
+    return keep + sum(bit for name, bit in _NET_FLAG_ENV.items() if os.environ.get(name, "") == "1")
 
 
 class LossDesc(C.Structure):
