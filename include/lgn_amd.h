@@ -438,6 +438,86 @@ int lgn_step_train_opt_f64(const lgn_net_desc* d, double* params, double* grads,
                            long long* step_dev, int do_step, double* loss_out, const lgn_loss_desc* loss,
                            int* assignment /* nullable */, int* status /* nullable */, void* stream);
 
+/* ---- guarded finalize: gradient-norm clipping, skip on a non-finite or exploding step, a learning rate that lives on the device.
+ * The reference meets a diverging run on the host (utils/train.py: BLOW_UP_THRESHOLD = 1e32 on every batch_loss.item()); a
+ * device-resident epoch has no host in the loop, so the decision is taken where the gradient is finished.  The call sits where the
+ * descriptor finalize sits -- behind lgn_step_fwd_bwd_f64 and, under data parallelism, behind the all-reduce (every rank sees the
+ * same reduced buffer and takes the same decision) -- and takes its arguments plus a host descriptor, read when the call is made,
+ * and a device control block of LGN_CTL_DOUBLES doubles (caller-owned, zero-filled once).  These only ADD a struct, constants and
+ * functions: LGN_AMD_ABI_VERSION stays 19.  Per call, with w the weights before the update and g the reduced loss gradient:
+ *   G     = g + l1_lambda sign(w) + 2 l2_lambda w, written to `grads` (ALWAYS the unclipped regularised gradient);
+ *   norm  = sqrt(sum G^2) over all n_params, summed in a fixed order (per-workgroup partials, then in index order);
+ *   total = data + l1_lambda sum|w| + l2_lambda sum w^2;  loss_out[0..3] as the descriptor finalize writes them;
+ *   bad_nf = skip_nonfinite && !(isfinite(norm) && isfinite(total));   bad_bu = threshold on && fabs(total) > blow_up_threshold;
+ *   coef  = min(1, max_grad_norm / (norm + 1e-6)) with clipping on (torch.nn.utils.clip_grad_norm_; a NaN norm gives a NaN
+ *           coefficient, as there), else exactly 1.0;
+ *   t     = *step_dev + 1 (the number Adam uses);  lr of this step by lr_kind:
+ *     LGN_LR_HOST           opt->lr
+ *     LGN_LR_DEVICE         ctl[LGN_CTL_LR] (an 8-byte device write between two replays changes it; no re-capture)
+ *     LGN_LR_WARMUP_COSINE  t <= W: base t / W;  else min + (base - min) 1/2 (1 + cos(pi min(t - W, T - W) / (T - W)))
+ *     LGN_LR_WARMUP_STEP    t <= W: base t / W;  else base gamma^floor((t - W - 1) / step_size)
+ *     (W = warmup_steps, T = total_steps; the closed form is also a host function, below)
+ *   apply: only when do_step and neither bad_nf nor bad_bu -- the optimiser's update (LGN_OPT_ADAM / LGN_OPT_RMSPROP as above) on
+ *     G coef with that lr: new weights, both state tensors, *step_dev + 1.  A skipped step writes none of them, so t does not
+ *     advance.  With every control off and LGN_LR_HOST the weights, state, gradients and counter are the descriptor finalize's
+ *     bit for bit (G * 1.0 is exact; Adam's powers are cached in this call's own block under the same protocol).
+ * Control block: per-step fields LGN_CTL_LR_USED, LGN_CTL_GRAD_NORM, LGN_CTL_CLIP_COEF, LGN_CTL_FLAGS (bits LGN_CTL_CLIPPED,
+ * LGN_CTL_SKIP_NONFINITE, LGN_CTL_SKIP_BLOWUP, as a double) are written by every call; the running fields -- LGN_CTL_APPLIED,
+ * LGN_CTL_CLIPPED_STEPS, LGN_CTL_SKIPPED (counts), LGN_CTL_FIRST_SKIPPED (t of the first skipped step since the last reset, 0: none),
+ * LGN_CTL_GRAD_NORM_MAX (largest finite norm), LGN_CTL_APPLIED_LOSS_SUM (sum of total over applied steps, one fp64 add per step in
+ * step order) -- only with do_step (a capture's warm-up leaves no trace).  LGN_CTL_APPLY / LGN_CTL_BC1 / LGN_CTL_BC2_SQRT hand the
+ * decision from the first launch to the second.  The reset call clears the running fields in a kernel (no memset node) and keeps
+ * LGN_CTL_LR.
+ * Two launches behind the reductions: gradient + partial sums + decision (the last workgroup to arrive assembles, as in the
+ * finalize calls above: atomic exchange -> counter, no fence), then the update, which reads the decision across the launch
+ * boundary (one launch with do_step == 0).  No workgroup waits for another.  loss_out must hold 4 + LGN_FINALIZE_CTL_SCRATCH
+ * doubles: the 4 results, then scratch of this call's own -- THREE arrays of (LGN_FINALIZE_CTL_SCRATCH - 12) / 3 partial sums
+ * (|w|, w^2, G^2), slots -7 .. -2 the cached powers of LGN_OPT_ADAM, slot -1 the finished-workgroup counter; zero-filled once by
+ * the caller, partial sums and counter are zero again after every call.  Only enqueues (capturable); refuses before the first
+ * launch with a negative code and the last-error message: null pointers, an unknown lr_kind, warmup_steps < 0, total_steps <=
+ * warmup_steps under the cosine, step_size < 1 or gamma <= 0 under the step schedule, a negative base_lr or min_lr, missing state
+ * with do_step, and whatever the descriptor finalize refuses. */
+#define LGN_LR_HOST 0
+#define LGN_LR_DEVICE 1
+#define LGN_LR_WARMUP_COSINE 2
+#define LGN_LR_WARMUP_STEP 3
+typedef struct {
+  double max_grad_norm;       /* <= 0 or +inf: no clipping */
+  double blow_up_threshold;   /* <= 0 or +inf: off */
+  int skip_nonfinite;
+  int lr_kind;                /* LGN_LR_* */
+  double base_lr, min_lr;
+  long long warmup_steps, total_steps;
+  double gamma;
+  long long step_size;
+} lgn_train_ctl;
+#define LGN_CTL_LR 0
+#define LGN_CTL_LR_USED 1
+#define LGN_CTL_GRAD_NORM 2
+#define LGN_CTL_CLIP_COEF 3
+#define LGN_CTL_FLAGS 4
+#define LGN_CTL_APPLIED 5
+#define LGN_CTL_CLIPPED_STEPS 6
+#define LGN_CTL_SKIPPED 7
+#define LGN_CTL_FIRST_SKIPPED 8
+#define LGN_CTL_GRAD_NORM_MAX 9
+#define LGN_CTL_APPLIED_LOSS_SUM 10
+#define LGN_CTL_APPLY 11
+#define LGN_CTL_BC1 12
+#define LGN_CTL_BC2_SQRT 13
+#define LGN_CTL_DOUBLES 16
+#define LGN_CTL_CLIPPED 1
+#define LGN_CTL_SKIP_NONFINITE 2
+#define LGN_CTL_SKIP_BLOWUP 4
+#define LGN_FINALIZE_CTL_SCRATCH 4096
+int lgn_step_finalize_ctl_f64(double* params, double* grads, long long n_params, const double* loss_part, int n_loss,
+                              const lgn_optim_desc* opt, double* state_m, double* state_v, long long* step_dev, int do_step,
+                              double* loss_out, const lgn_train_ctl* tc, double* ctl, void* stream);
+int lgn_train_ctl_reset(double* ctl, void* stream);
+/* the learning rate of step t >= 1 under *tc (device_lr: what LGN_LR_DEVICE returns; LGN_LR_HOST has no descriptor here and returns
+ * device_lr as well); NaN for a null or refused descriptor.  Pure host arithmetic: the same inline function the kernel runs. */
+double lgn_lr_schedule_value(const lgn_train_ctl* tc, long long t, double device_lr);
+
 /* ---- evaluation step (the reference's validate() / test.py loop under torch.no_grad(), utils/train.py:390): encoder -> decoder ->
  * get_real(., d->get_real) -> Chamfer [+ d->jet_loss_scale * jet-feature term] or the assignment loss of `loss`, forward only and without L1 (regularization =
  * is_train, utils/train.py:308-314).  Takes every descriptor lgn_step_fwd_bwd_f64 takes and the same inputs; nothing is kept for a

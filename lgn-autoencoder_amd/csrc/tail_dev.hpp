@@ -60,4 +60,47 @@ __device__ __forceinline__ AdamOut l1_l2_rmsprop_one(double w, double gsum, doub
   return o;
 }
 
+// ---- the guarded finalize (step_ctl.hip): the same rules in two halves, because the update waits for the norm of the WHOLE
+// regularised gradient.  reg_grad is the gradient both rules above form (their words: l2_grad, then + l1 sign(w));
+// adam_update_one / rmsprop_update_one are l1_adam_one / l1_l2_rmsprop_one from that point on, on a gradient that is already
+// regularised (and clipped: G * coef, coef == 1.0 keeps the bits).  AdamOut::g is the gradient handed in.
+__device__ __forceinline__ double reg_grad(double w, double gsum, double l1, double l2) {
+  return l2_grad(w, gsum, l2) + l1 * (double)((w > 0.0) - (w < 0.0));
+}
+__device__ __forceinline__ AdamOut adam_update_one(double w, double g, double m, double v, double lr, double beta1, double beta2,
+                                                   double eps, double bc1, double bc2_sqrt) {
+  AdamOut o;
+  o.g = g;
+  o.m = __builtin_fma(o.g - m, 1.0 - beta1, m);
+  o.v = __builtin_fma((1.0 - beta2) * o.g, o.g, v * beta2);
+  const double denom = sqrt(o.v) / bc2_sqrt + eps;
+  o.w = w - (lr / bc1) * (o.m / denom);
+  return o;
+}
+__device__ __forceinline__ AdamOut rmsprop_update_one(double w, double g, double buf, double v, double lr, double alpha, double mu,
+                                                      double eps) {
+  AdamOut o;
+  o.g = g;
+  o.v = __builtin_fma((1.0 - alpha) * o.g, o.g, v * alpha);
+  const double q = o.g / (sqrt(o.v) + eps);
+  o.m = mu > 0.0 ? __builtin_fma(mu, buf, q) : buf;
+  o.w = __builtin_fma(-lr, mu > 0.0 ? o.m : q, w);
+  return o;
+}
+
+// The learning rate of step t >= 1 under a schedule (LGN_LR_WARMUP_COSINE / LGN_LR_WARMUP_STEP of include/lgn_amd.h), one closed
+// form for the kernel and for the host (lgn_lr_schedule_value): linear warm-up base t / W over the first W steps, then half a
+// cosine from base down to min_lr at step T (held there), or base gamma^floor((t - W - 1) / step_size).
+constexpr int LR_COSINE = 2, LR_STEP = 3;
+__host__ __device__ inline double lr_schedule(int kind, double base, double min_lr, long long W, long long T, double gamma,
+                                              long long step_size, long long t) {
+  if (t <= W) return base * (double)t / (double)W;
+  if (kind == LR_COSINE) {
+    const long long span = T - W, at = t - W < span ? t - W : span;
+    const double x = 3.14159265358979323846 * (double)at / (double)span;
+    return min_lr + (base - min_lr) * 0.5 * (1.0 + cos(x));
+  }
+  return base * pow(gamma, (double)((t - W - 1) / step_size));
+}
+
 }  // namespace lgn

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("LGN_AMD_LIB") or os.path.join(_HERE, "_lib", "liblgn_
 ABI_VERSION = 19
 FINALIZE_SCRATCH = 2048      # include/lgn_amd.h: LGN_FINALIZE_SCRATCH
 FINALIZE_OPT_SCRATCH = 4096  # LGN_FINALIZE_OPT_SCRATCH: the scratch behind the 4 results of the lgn_optim_desc calls
+FINALIZE_CTL_SCRATCH = 4096  # LGN_FINALIZE_CTL_SCRATCH: the scratch behind the 4 results of lgn_step_finalize_ctl_f64
 
 _lib: Optional[C.CDLL] = None
 
@@ -187,6 +188,23 @@ def loss_ref(desc):
     return C.byref(desc.base) if isinstance(desc, EMDLossDesc) else C.byref(desc)
 
 
+class TrainCtl(C.Structure):
+    """lgn_train_ctl of include/lgn_amd.h: the controls of lgn_step_finalize_ctl_f64 (read when the call is made)."""
+    _fields_ = [("max_grad_norm", C.c_double), ("blow_up_threshold", C.c_double), ("skip_nonfinite", C.c_int), ("lr_kind", C.c_int),
+                ("base_lr", C.c_double), ("min_lr", C.c_double), ("warmup_steps", C.c_longlong), ("total_steps", C.c_longlong),
+                ("gamma", C.c_double), ("step_size", C.c_longlong)]
+
+
+# LGN_LR_*: where the learning rate of a guarded step comes from
+LR_HOST, LR_DEVICE, LR_WARMUP_COSINE, LR_WARMUP_STEP = 0, 1, 2, 3
+# LGN_CTL_*: positions in the device control block (CTL_DOUBLES doubles) ...
+(CTL_LR, CTL_LR_USED, CTL_GRAD_NORM, CTL_CLIP_COEF, CTL_FLAGS, CTL_APPLIED, CTL_CLIPPED_STEPS, CTL_SKIPPED, CTL_FIRST_SKIPPED,
+ CTL_GRAD_NORM_MAX, CTL_APPLIED_LOSS_SUM, CTL_APPLY, CTL_BC1, CTL_BC2_SQRT) = range(14)
+CTL_DOUBLES = 16
+# ... and the bits of its FLAGS field
+CTL_CLIPPED, CTL_SKIP_NONFINITE, CTL_SKIP_BLOWUP = 1, 2, 4
+
+
 OPT_ADAM, OPT_RMSPROP = 0, 1
 LOSS_CHAMFER, LOSS_MSE, LOSS_HUNGARIAN, LOSS_EMD = 0, 1, 2, 3
 ASSIGN_NMAX = 192            # LGN_ANOMALY_NMAX of include/lgn_amd.h: particles per jet of the assignment solver
@@ -217,6 +235,9 @@ _SIGNATURES.update({
     "lgn_step_finalize_opt_f64": [_vp, _vp, _ll, _vp, _i, _op, _vp, _vp, _vp, _i, _vp, _vp],
     "lgn_step_train_opt_f64": [_dp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _op, _vp, _vp, _vp, _i, _vp, _lp,
                                _vp, _vp, _vp],
+    # (the descriptor finalize's arguments, then the control descriptor and the device control block)
+    "lgn_step_finalize_ctl_f64": [_vp, _vp, _ll, _vp, _i, _op, _vp, _vp, _vp, _i, _vp, C.POINTER(TrainCtl), _vp, _vp],
+    "lgn_train_ctl_reset": [_vp, _vp],
     "lgn_step_eval_f64": [_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _lp, _vp, _vp, _vp],
     "lgn_anomaly_scores_f64": [_vp] * 4 + [_i] * 3 + [_vp] * 4,
     "lgn_linear_sum_assignment_f64": [_vp, _i, _i, _vp, _vp, _vp],
@@ -320,7 +341,11 @@ STATS_COUNT = len(STAT_NAMES)
 JET_IMAGE_MAX_NPIX, JET_IMAGE_PARTS = 64, 512
 EQUI_TILE, EQUI_MAX_PARTS = 256, 64         # LGN_EQUI_TILE, LGN_EQUI_MAX_PARTS of include/lgn_amd.h
 LDS_LIMIT = 160 * 1024      # LGN_LDS_LIMIT of include/lgn_amd.h
-EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_SIGNATURES)
+_D_SIGNATURES = {           # entry points that return a double
+    # (tc, t, device_lr)
+    "lgn_lr_schedule_value": [C.POINTER(TrainCtl), _ll, _d],
+}
+EXPORTED_SYMBOLS = ["lgn_abi_version", "lgn_last_error"] + list(_LL_SIGNATURES) + list(_D_SIGNATURES) + list(_SIGNATURES)
 
 
 def lib() -> C.CDLL:
@@ -345,6 +370,10 @@ def lib() -> C.CDLL:
             fn = getattr(l, name)
             fn.argtypes = argtypes
             fn.restype = C.c_longlong
+        for name, argtypes in _D_SIGNATURES.items():
+            fn = getattr(l, name)
+            fn.argtypes = argtypes
+            fn.restype = C.c_double
         _lib = l
     return _lib
 

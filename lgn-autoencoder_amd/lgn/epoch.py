@@ -187,7 +187,13 @@ class EpochRunner:
     ``run_epoch()`` returns {'loss_sum', 'steps', 'avg_loss' (= loss_sum / steps, the reference's epoch_total_loss / len(loader)),
     'status' (0, or LGN_EPOCH_BAD_INDEX), 'collected': {name: (jets covered, ...) tensor; 'latent': {(0, 0): (2, jets covered, ...),
     (1, 1): (2, jets covered, ...)}, the layout of the reference's latent_dict}}.  The collected tensors are the runner's buffers:
-    the next epoch overwrites them."""
+    the next epoch overwrites them.
+
+    A guarded training step (NativeTrainStep built with max_grad_norm / skip_nonfinite / blow_up_threshold / lr_schedule): the
+    running fields of its control block are cleared with the epoch's own reset and come back as 'control': {applied, clipped,
+    skipped, first_skipped, grad_norm_max, applied_loss_sum}, read at the same synchronisation.  'loss_sum' / 'avg_loss' stay the
+    plain sum over all steps, a skipped step's NaN included (what the reference's loop would print); applied_loss_sum / applied is
+    the figure to use."""
 
     def __init__(self, step, dataset: DeviceDataset, shuffle: bool = True, generator: Optional[torch.Generator] = None,
                  collect: Sequence[str] = (), remainder: Optional[str] = None, index: Optional[torch.Tensor] = None):
@@ -341,6 +347,9 @@ class EpochRunner:
         if self.short and self.single_graph and self._short_plan().graph is None:
             self._capture(self._tail)
         self._reset()
+        controlled = self.training and s.opt_state.ctl_form
+        if controlled:                       # a guarded step: the epoch's counters start over with the epoch (the device lr stays)
+            s.opt_state.reset()
         launches = 0
         for it in range(whole):
             n = tail if it == self.steps - 1 else self.B
@@ -363,5 +372,8 @@ class EpochRunner:
         if int(steps) != self.steps or int(self._cursor[0].item()) != self.steps:
             raise RuntimeError(f"the epoch counted {steps} steps on the device, {self.steps} were launched")
         self.launches_per_epoch = launches
-        return {"loss_sum": loss_sum, "steps": int(steps), "avg_loss": loss_sum / steps, "status": status,
-                "collected": dict(self.collected)}
+        out = {"loss_sum": loss_sum, "steps": int(steps), "avg_loss": loss_sum / steps, "status": status,
+               "collected": dict(self.collected)}
+        if controlled:
+            out["control"] = s.opt_state.stats()
+        return out

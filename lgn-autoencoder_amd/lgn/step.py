@@ -133,6 +133,167 @@ def torch_optimizer(params, optimizer_choice: str = "adam", lr: float = 5e-4, ep
     return torch.optim.RMSprop(params, lr=lr, eps=eps, momentum=momentum, alpha=rms_alpha)
 
 
+class LRSchedule:
+    """A closed-form learning-rate schedule of the guarded steps (``lr_schedule=``), evaluated on the device at every step from the
+    optimiser's own step number t = 1, 2, ... (a skipped step does not advance it).  ``kind`` 'cosine': linear warm-up
+    base_lr t / warmup_steps over the first warmup_steps steps, then half a cosine from base_lr down to min_lr at step total_steps
+    (held there); 'step': the same warm-up, then base_lr gamma^floor((t - warmup_steps - 1) / step_size) (torch's StepLR;
+    step_size 1: ExponentialLR).  ``value(t)`` is the same arithmetic in Python (what the torch-side comparators set)."""
+
+    KINDS = {"cosine": 2, "warmup_cosine": 2, "step": 3, "warmup_step": 3}      # LGN_LR_WARMUP_COSINE / LGN_LR_WARMUP_STEP
+
+    def __init__(self, kind: str, base_lr: float, warmup_steps: int = 0, total_steps: int = 0, min_lr: float = 0.0,
+                 gamma: float = 1.0, step_size: int = 1):
+        if str(kind).lower() not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind {kind!r} is none of {sorted(self.KINDS)}")
+        self.kind, self.code = str(kind).lower(), self.KINDS[str(kind).lower()]
+        self.base_lr, self.min_lr, self.gamma = float(base_lr), float(min_lr), float(gamma)
+        self.warmup_steps, self.total_steps, self.step_size = int(warmup_steps), int(total_steps), int(step_size)
+        if self.warmup_steps < 0 or self.base_lr < 0 or self.min_lr < 0:
+            raise ValueError("LRSchedule: warmup_steps, base_lr and min_lr must be >= 0")
+        if self.code == 2 and self.total_steps <= self.warmup_steps:
+            raise ValueError("LRSchedule: the cosine needs total_steps > warmup_steps")
+        if self.code == 3 and (self.step_size < 1 or not self.gamma > 0):
+            raise ValueError("LRSchedule: the step schedule needs step_size >= 1 and gamma > 0")
+
+    def value(self, t: int) -> float:
+        import math
+        W = self.warmup_steps
+        if t <= W:
+            return self.base_lr * t / W
+        if self.code == 2:
+            span = self.total_steps - W
+            return self.min_lr + (self.base_lr - self.min_lr) * 0.5 * (1.0 + math.cos(math.pi * min(t - W, span) / span))
+        return self.base_lr * self.gamma ** ((t - W - 1) // self.step_size)
+
+    def __repr__(self):
+        return (f"LRSchedule({self.kind!r}, base_lr={self.base_lr}, warmup_steps={self.warmup_steps}, total_steps={self.total_steps}, "
+                f"min_lr={self.min_lr}, gamma={self.gamma}, step_size={self.step_size})")
+
+
+def _switch(x) -> float:
+    """max_grad_norm / blow_up_threshold as the native descriptor reads them: None, <= 0 or +inf is off (0.0)."""
+    x = 0.0 if x is None else float(x)
+    return x if 0.0 < x < float("inf") else 0.0
+
+
+def _check_lr_schedule(lr_schedule):
+    if lr_schedule is not None and lr_schedule != "device" and not isinstance(lr_schedule, LRSchedule):
+        raise ValueError(f"lr_schedule is None, 'device' or an lgn.step.LRSchedule; got {lr_schedule!r}")
+    return lr_schedule
+
+
+def _controlled(max_grad_norm, skip_nonfinite, blow_up_threshold, lr_schedule) -> bool:
+    """Was any keyword of the guarded step given?"""
+    return max_grad_norm is not None or bool(skip_nonfinite) or blow_up_threshold is not None or lr_schedule is not None
+
+
+class _TorchGuard:
+    """The controls of the guarded native step restated with torch for the comparator steps (TrainStep, ReferenceLoopStep):
+    clip_grad_norm_ over the given parameters, a host check of loss and norm before the optimiser steps, and the learning rate of
+    step t = applied steps + 1 written into every param_group.  ``admit`` says whether the optimisers may step."""
+
+    def __init__(self, lr, max_grad_norm=None, skip_nonfinite=False, blow_up_threshold=None, lr_schedule=None):
+        self.max_grad_norm, self.threshold = _switch(max_grad_norm), _switch(blow_up_threshold)
+        self.skip_nonfinite, self.schedule = bool(skip_nonfinite), _check_lr_schedule(lr_schedule)
+        self.on = _controlled(max_grad_norm, skip_nonfinite, blow_up_threshold, lr_schedule)
+        self.lr, self.t = float(lr), 0
+        self.stats = dict(applied=0, clipped=0, skipped=0, first_skipped=0, grad_norm_max=0.0, applied_loss_sum=0.0)
+        self.grad_norm = self.clip_coef = self.lr_used = None
+        self.flags = 0
+
+    def set_lr(self, value):
+        if self.schedule != "device":
+            raise ValueError("set_lr needs lr_schedule='device'")
+        self.lr = float(value)
+
+    def admit(self, params, total, optimizers) -> bool:
+        import math
+        if not self.on:
+            return True
+        params = [p for p in params if p.grad is not None]
+        if self.max_grad_norm:
+            norm = float(torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm))
+            c = self.max_grad_norm / (norm + 1e-6)
+            coef = 1.0 if c >= 1.0 else c
+        else:
+            norm, coef = float(torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params]))), 1.0
+        total = float(total)
+        bad_nf = self.skip_nonfinite and not (math.isfinite(norm) and math.isfinite(total))
+        bad_bu = bool(self.threshold) and abs(total) > self.threshold
+        t = self.t + 1
+        lr = self.schedule.value(t) if isinstance(self.schedule, LRSchedule) else self.lr
+        self.grad_norm, self.clip_coef, self.lr_used = norm, coef, lr
+        self.flags = (1 if coef != 1.0 else 0) | (2 if bad_nf else 0) | (4 if bad_bu else 0)
+        s = self.stats
+        if math.isfinite(norm):
+            s["grad_norm_max"] = max(s["grad_norm_max"], norm)
+        if bad_nf or bad_bu:
+            s["skipped"] += 1
+            s["first_skipped"] = s["first_skipped"] or t
+            return False
+        for opt in optimizers:
+            for group in opt.param_groups:
+                group["lr"] = lr
+        self.t = t
+        s["applied"] += 1
+        s["clipped"] += int(coef != 1.0)
+        s["applied_loss_sum"] += total
+        return True
+
+
+class _LRHandle(torch.optim.Optimizer):
+    """What ``lr_handle()`` of a guarded step returns: a one-group dummy optimiser for any torch.optim.lr_scheduler (ReduceLROnPlateau
+    included).  It owns no parameter of the model and ``step()`` does nothing; ``sync_lr()`` copies param_groups[0]['lr'] to the
+    device through the step's ``set_lr``."""
+
+    def __init__(self, step, lr):
+        self._lgn_step = step
+        super().__init__([torch.nn.Parameter(torch.zeros(1))], dict(lr=float(lr)))
+
+    def step(self, closure=None):
+        return None
+
+    def sync_lr(self):
+        self._lgn_step.set_lr(self.param_groups[0]["lr"])
+
+
+class _ControlAPI:
+    """The guarded step as its classes show it (NativeTrainStep, CapturedModuleStep built with any of ``max_grad_norm``,
+    ``skip_nonfinite``, ``blow_up_threshold``, ``lr_schedule``): ``grad_norm`` / ``clip_coef`` / ``lr_used`` / ``ctl_flags`` are device
+    views into the control block (0-d tensors of the LAST step, read without a sync), and the methods below."""
+
+    def _ctl(self):
+        o = self.opt_state
+        if not o.ctl_form:
+            raise ValueError("this step was built without controls (max_grad_norm / skip_nonfinite / blow_up_threshold / lr_schedule)")
+        return o
+
+    def control_stats(self) -> dict:
+        """The running fields since the last reset_control() -- applied, clipped, skipped, first_skipped (the step number t of the
+        first skipped step, 0: none), grad_norm_max, applied_loss_sum -- with ONE synchronisation."""
+        return self._ctl().stats()
+
+    def reset_control(self):
+        """Clears the running fields (a kernel of the library on the current stream); the device learning rate stays."""
+        self._ctl().reset()
+
+    def set_lr(self, value: float):
+        """The learning rate of the next steps under ``lr_schedule='device'`` (ValueError otherwise): an 8-byte device write on the
+        current stream that the next replay of the captured step reads -- nothing is captured again."""
+        o = self._ctl()
+        if o.lr_schedule != "device":
+            raise ValueError("set_lr needs lr_schedule='device' (a step with a host learning rate or a closed-form schedule has it frozen "
+                             "into its calls)")
+        o.ctl[o.N.CTL_LR:o.N.CTL_LR + 1].fill_(float(value))
+        self.lr = float(value)
+
+    def lr_handle(self) -> "_LRHandle":
+        """A dummy torch optimiser for torch.optim.lr_scheduler classes: schedule it, then ``sync_lr()``."""
+        self._ctl()
+        return _LRHandle(self, self.lr)
+
+
 class TrainStep:
     """One data-parallel training step of the autoencoder (see module docstring).  ``optimizer_choice`` / ``l2_lambda`` /
     ``rms_alpha`` / ``momentum``: --optimizer and --l2-lambda of the reference, as NativeTrainStep takes them; ``normalize`` /
@@ -143,8 +304,10 @@ class TrainStep:
     def __init__(self, encoder, decoder, lr: float = 5e-4, l1_lambda: float = 1e-8, get_real_method: str = "sum",
                  process_group: Optional["dist.ProcessGroup"] = None, optimizer: bool = True, optimizer_choice: str = "adam",
                  l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None, normalize: bool = False,
-                 normalize_method: str = "overall_max", loss_choice="chamfer"):
+                 normalize_method: str = "overall_max", loss_choice="chamfer", max_grad_norm=None, skip_nonfinite: bool = False,
+                 blow_up_threshold=None, lr_schedule=None):
         self.encoder, self.decoder = encoder, decoder
+        self.guard = _TorchGuard(lr, max_grad_norm, skip_nonfinite, blow_up_threshold, lr_schedule)
         self.loss_fn = _module_loss(loss_choice, True, False, None, chamfer_loss)     # (no loss here is built for a device)
         self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.l1_lambda, self.get_real_method = l1_lambda, get_real_method
@@ -186,7 +349,7 @@ class TrainStep:
 
     def step(self, batch):
         total, recon = self.forward_backward(batch)
-        if self.opt is not None:
+        if self.opt is not None and self.guard.admit([self.flat_param], total, [self.opt]):
             self.opt.step()
         return total, recon
 
@@ -206,8 +369,10 @@ class ReferenceLoopStep:
                  process_group=None, optimizer: bool = True, native_loss: bool = True, loss_choice: str = "chamfer",
                  hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam",
                  l2_lambda=0.0, rms_alpha: float = 0.99, momentum: float = 0.9, eps=None, normalize: bool = False,
-                 normalize_method: str = "overall_max"):
+                 normalize_method: str = "overall_max", max_grad_norm=None, skip_nonfinite: bool = False, blow_up_threshold=None,
+                 lr_schedule=None):
         self.encoder, self.decoder = encoder, decoder
+        self.guard = _TorchGuard(lr, max_grad_norm, skip_nonfinite, blow_up_threshold, lr_schedule)
         self.normalize, self.norm_code, self.norm_factor = bool(normalize), normalize_code(normalize_method), None
         self.optimizer_choice, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, encoder.device,
@@ -251,7 +416,9 @@ class ReferenceLoopStep:
             for m in (self.encoder, self.decoder):
                 for p in m.parameters():
                     dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=self.group)
-        if self.opt_enc is not None:
+        # (guarded: clip_grad_norm_ over both networks, the host check of loss and norm, param_group['lr'] from the closed form)
+        if self.opt_enc is not None and self.guard.admit(list(self.encoder.parameters()) + list(self.decoder.parameters()),
+                                                         total.detach(), [self.opt_enc, self.opt_dec]):
             self.opt_enc.step()
             self.opt_dec.step()
         return total.detach(), recon
@@ -555,11 +722,17 @@ class _OptimState:
     'rmsprop'``, ``l2_lambda > 0``) through their lgn_optim_desc twins, whose block has a fourth result, ``l2_out`` = sum w^2."""
 
     _force_opt = False      # tests: Adam without L2 through the lgn_optim_desc calls as well (same bits)
+    _force_ctl = False      # tests: a step without controls through lgn_step_finalize_ctl_f64 as well (every control off: same bits)
 
     def __init__(self, flat: FlatParams, l1_lambda, lr, betas, eps, optimizer_choice: str = "adam", l2_lambda=0.0,
-                 rms_alpha: float = 0.99, momentum: float = 0.9, share: Optional["_OptimState"] = None):
+                 rms_alpha: float = 0.99, momentum: float = 0.9, share: Optional["_OptimState"] = None, max_grad_norm=None,
+                 skip_nonfinite: bool = False, blow_up_threshold=None, lr_schedule=None):
         """share: another plan's state on the same parameters -- its two state tensors and its step counter are this one's (a short
-        batch's step updates what the full batch's does); the loss block is this plan's own, zero-filled like any new one."""
+        batch's step updates what the full batch's does); the loss block is this plan's own, zero-filled like any new one.
+        A third form next to the two above, chosen when any of max_grad_norm / skip_nonfinite / blow_up_threshold / lr_schedule is
+        given: the guarded finalize (lgn_step_finalize_ctl_f64) on a descriptor, a control descriptor and a device control block
+        ``ctl`` that this state owns -- part of snapshot() / restore() and of what ``share`` shares, so that a capture's warm-up
+        leaves no trace in it and a short batch's step continues the same counters and schedule."""
         from . import _native as N
         self.N, self.flat = N, flat
         self.kind, self.l2_lambda = optimizer_kind(optimizer_choice), l2_weight(l2_lambda)
@@ -570,10 +743,28 @@ class _OptimState:
             self.adam_m, self.adam_v = torch.zeros_like(flat.flat), torch.zeros_like(flat.flat)
             self.step_dev = torch.zeros(1, device=flat.flat.device, dtype=torch.int64)
         self.momentum_buf, self.square_avg = self.adam_m, self.adam_v
-        self.opt_form = self._force_opt or self.kind != "adam" or self.l2_lambda > 0.0
+        self.lr_schedule = _check_lr_schedule(lr_schedule)
+        self.ctl_form = self._force_ctl or _controlled(max_grad_norm, skip_nonfinite, blow_up_threshold, lr_schedule)
+        self.opt_form = self.ctl_form or self._force_opt or self.kind != "adam" or self.l2_lambda > 0.0
         dev, dt = flat.flat.device, flat.flat.dtype
+        self.ctl = self.tc = None
+        if self.ctl_form:
+            self.tc = tc = N.TrainCtl()
+            tc.max_grad_norm, tc.blow_up_threshold, tc.skip_nonfinite = _switch(max_grad_norm), _switch(blow_up_threshold), int(bool(skip_nonfinite))
+            tc.lr_kind = N.LR_HOST
+            if lr_schedule == "device":
+                tc.lr_kind = N.LR_DEVICE
+            elif lr_schedule is not None:
+                s = lr_schedule
+                tc.lr_kind, tc.base_lr, tc.min_lr, tc.gamma = s.code, s.base_lr, s.min_lr, s.gamma
+                tc.warmup_steps, tc.total_steps, tc.step_size = s.warmup_steps, s.total_steps, s.step_size
+            if share is not None and share.ctl is not None:
+                self.ctl = share.ctl
+            else:
+                self.ctl = torch.zeros(N.CTL_DOUBLES, device=dev, dtype=dt)
+                self.ctl[N.CTL_LR] = float(lr)
         if self.opt_form:
-            self.loss_buf = torch.zeros(4 + N.FINALIZE_OPT_SCRATCH, device=dev, dtype=dt)
+            self.loss_buf = torch.zeros(4 + (N.FINALIZE_CTL_SCRATCH if self.ctl_form else N.FINALIZE_OPT_SCRATCH), device=dev, dtype=dt)
             self.l2_out = self.loss_buf[3:4]
             self.desc = d = N.OptimDesc()
             d.kind = N.OPT_ADAM if self.kind == "adam" else N.OPT_RMSPROP
@@ -585,6 +776,8 @@ class _OptimState:
             self.desc = None
         self.loss_out = self.loss_buf[:3]
         self._state = (flat.flat, self.adam_m, self.adam_v, self.step_dev)          # what a step changes: snapshot() / restore()
+        if self.ctl_form:
+            self._state += (self.ctl,)
         self._head = (N.ptr(flat.flat), N.ptr(flat.grad), flat.flat.numel(), N.ptr(flat.tail))
         self._hyper = (flat.tail.numel(), float(l1_lambda), N.ptr(self.adam_m), N.ptr(self.adam_v), N.ptr(self.step_dev), float(lr),
                        float(betas[0]), float(betas[1]), self.eps)
@@ -599,14 +792,38 @@ class _OptimState:
 
     def finalize(self, do_adam: bool):
         N = self.N
+        if self.ctl_form:
+            import ctypes as C
+            N._check(N.lib().lgn_step_finalize_ctl_f64(*self._head, *self.tail_args(do_adam), C.byref(self.tc), N.ptr(self.ctl),
+                                                       N.stream_ptr()), "lgn_step_finalize_ctl_f64")
+            return
         name = "lgn_step_finalize_opt_f64" if self.opt_form else "lgn_step_finalize_f64"
         N._check(getattr(N.lib(), name)(*self._head, *self.tail_args(do_adam), N.stream_ptr()), name)
 
     def train(self, net_args, loss_args, do_adam: bool):
-        """The whole single-process step in one native call: lgn_step_train_f64, or its twin with the descriptor."""
+        """The whole single-process step in one native call: lgn_step_train_f64, or its twin with the descriptor.  The guarded form
+        is lgn_step_fwd_bwd_f64 (which ends with the reduce-only fused launch) followed by the guarded finalize."""
         N = self.N
+        if self.ctl_form:
+            N._check(N.lib().lgn_step_fwd_bwd_f64(*net_args, *loss_args, N.stream_ptr()), "lgn_step_fwd_bwd_f64")
+            return self.finalize(do_adam)
         name = "lgn_step_train_opt_f64" if self.opt_form else "lgn_step_train_f64"
         N._check(getattr(N.lib(), name)(*net_args, *self.tail_args(do_adam), *loss_args, N.stream_ptr()), name)
+
+    def stats(self) -> dict:
+        """The running fields of the control block (one device-to-host copy: a synchronisation)."""
+        return self.stats_of(self.ctl.cpu())
+
+    def stats_of(self, c) -> dict:
+        """The running fields of a host copy of the control block."""
+        N = self.N
+        return dict(applied=int(c[N.CTL_APPLIED]), clipped=int(c[N.CTL_CLIPPED_STEPS]), skipped=int(c[N.CTL_SKIPPED]),
+                    first_skipped=int(c[N.CTL_FIRST_SKIPPED]), grad_norm_max=float(c[N.CTL_GRAD_NORM_MAX]),
+                    applied_loss_sum=float(c[N.CTL_APPLIED_LOSS_SUM]))
+
+    def reset(self):
+        N = self.N
+        N._check(N.lib().lgn_train_ctl_reset(N.ptr(self.ctl), N.stream_ptr()), "lgn_train_ctl_reset")
 
     def snapshot(self):
         return tuple(t.clone() for t in self._state)
@@ -624,6 +841,11 @@ def _adopt_optim_state(step, o: _OptimState):
     step.square_avg, step.momentum_buf, step.l2_out = o.square_avg, o.momentum_buf, o.l2_out
     step.optimizer_choice, step.l2_lambda, step.eps = o.kind, o.l2_lambda, o.eps
     step._finalize = o.finalize
+    step.ctl = o.ctl
+    if o.ctl_form:      # 0-d device views of the last step's fields (ctl_flags: the LGN_CTL_* bits as a double)
+        N = o.N
+        step.grad_norm, step.clip_coef, step.lr_used, step.ctl_flags = (o.ctl[i] for i in (N.CTL_GRAD_NORM, N.CTL_CLIP_COEF, N.CTL_LR_USED,
+                                                                                             N.CTL_FLAGS))
 
 
 class _StaticInputs:
@@ -683,7 +905,7 @@ class _StaticInputs:
                     t[n:].zero_()
 
 
-class NativeTrainStep:
+class NativeTrainStep(_ControlAPI):
     """Same step as TrainStep, executed by lgn_step_fwd_bwd_f64 / lgn_step_finalize_f64 (csrc/step.hip):
     no autograd graph, no PyTorch kernels, every buffer static.  With ``use_graph=True`` the two native calls
     are captured once into HIP graphs (torch.cuda.CUDAGraph around the ctypes calls -- the kernels are
@@ -730,6 +952,16 @@ class NativeTrainStep:
     is False only because tests pin the refusal of such a pair here and its fall-back to the module route in the choosers; a later
     change flips it.
 
+    ``max_grad_norm`` / ``skip_nonfinite`` / ``blow_up_threshold`` / ``lr_schedule`` (the guarded step; all off by default, and then
+    the native calls are exactly the ones above): the step becomes lgn_step_fwd_bwd_f64 + lgn_step_finalize_ctl_f64
+    (csrc/step_ctl.hip), two small launches behind the reductions.  ``max_grad_norm``: torch.nn.utils.clip_grad_norm_ on the
+    regularised gradient (``flat.grad`` keeps the unclipped one).  ``skip_nonfinite``: a step whose gradient norm or loss is not
+    finite changes neither weights nor optimiser state nor the step counter; ``blow_up_threshold``: the same when |loss| exceeds it
+    (the reference's BLOW_UP_THRESHOLD is 1e32).  ``lr_schedule``: 'device' -- ``set_lr(value)`` / ``lr_handle()`` change the rate
+    between replays of the captured graph without capturing again -- or an ``LRSchedule`` evaluated on the device from the
+    optimiser's step number.  ``grad_norm``, ``clip_coef``, ``lr_used``, ``ctl_flags`` are device views of the last step;
+    ``control_stats()`` / ``reset_control()`` read and clear the running counters (see _ControlAPI).
+
     ``short_step(n)``: the step of a short last batch of n < batch_size jets -- a second plan with the same options and the means
     over n, on this step's parameters and optimiser state (what lgn.epoch.EpochRunner replays under ``remainder='short'``)."""
 
@@ -739,7 +971,8 @@ class NativeTrainStep:
                  chamfer_jet_features: bool = False, loss_choice: str = "chamfer", hungarian_abs_coord: bool = True,
                  hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0, rms_alpha: float = 0.99,
                  momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max", native_emd: bool = False,
-                 table_split: bool = False, _share: Optional["NativeTrainStep"] = None):
+                 table_split: bool = False, max_grad_norm=None, skip_nonfinite: bool = False, blow_up_threshold=None, lr_schedule=None,
+                 _share: Optional["NativeTrainStep"] = None):
         import ctypes as C
         from . import _native as N
         self.N = N
@@ -749,7 +982,9 @@ class NativeTrainStep:
                              get_real_method=get_real_method, chamfer_jet_features=chamfer_jet_features, loss_choice=loss_choice,
                              hungarian_abs_coord=hungarian_abs_coord, hungarian_polar_coord=hungarian_polar_coord,
                              optimizer_choice=optimizer_choice, l2_lambda=l2_lambda, rms_alpha=rms_alpha, momentum=momentum,
-                             normalize=normalize, normalize_method=normalize_method, native_emd=native_emd, table_split=table_split)
+                             normalize=normalize, normalize_method=normalize_method, native_emd=native_emd, table_split=table_split,
+                             max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, blow_up_threshold=blow_up_threshold,
+                             lr_schedule=lr_schedule)
         self._short = {}
         self.split = _check_native_pair(encoder, decoder, table_split)
         self.world = _world_size(process_group)
@@ -791,7 +1026,8 @@ class NativeTrainStep:
         self.recon = torch.empty(2, d.B, decoder.num_output_particles, 4, device=dev, dtype=dt)
         self.loss_part = self.flat.tail
         self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum,
-                                         share=None if _share is None else _share.opt_state)
+                                         share=None if _share is None else _share.opt_state, max_grad_norm=max_grad_norm,
+                                         skip_nonfinite=skip_nonfinite, blow_up_threshold=blow_up_threshold, lr_schedule=lr_schedule)
         _adopt_optim_state(self, o)
         self.inputs = i = _StaticInputs(encoder, decoder, d.B, self.split, self.loss_desc is not None, alias_target=True,
                                         normalize=normalize, normalize_method=normalize_method)
@@ -922,7 +1158,7 @@ class NativeTrainStep:
         return self.loss_out[0], self.recon
 
 
-class CapturedModuleStep:
+class CapturedModuleStep(_ControlAPI):
     """The training step for every configuration the MODULES run but lgn_step_fwd_bwd_f64 refuses -- ``jet_features`` / extra
     input scalars of maxdim-3 networks (unless planned with ``table_split=True``), mixed maxdim-2 / maxdim-3 networks,
     ``map_to_latent='sum'``, levels without CGMLP: ``encoder(batch) -> decoder(latent) -> lgn.losses.ChamferLoss -> backward()``
@@ -936,7 +1172,8 @@ class CapturedModuleStep:
                  eps: Optional[float] = None, process_group=None, optimizer: bool = True, use_graph: bool = True,
                  get_real_method: str = "sum", chamfer_jet_features: bool = False, extra_scalars: int = 0, loss_choice: str = "chamfer",
                  hungarian_abs_coord: bool = True, hungarian_polar_coord: bool = False, optimizer_choice: str = "adam", l2_lambda=0.0,
-                 rms_alpha: float = 0.99, momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max"):
+                 rms_alpha: float = 0.99, momentum: float = 0.9, normalize: bool = False, normalize_method: str = "overall_max",
+                 max_grad_norm=None, skip_nonfinite: bool = False, blow_up_threshold=None, lr_schedule=None):
         from . import _native as N
         self.N = N
         optimizer_kind(optimizer_choice)
@@ -958,7 +1195,9 @@ class CapturedModuleStep:
         self.loss_fn = _module_loss(loss_choice, hungarian_abs_coord, hungarian_polar_coord, dev, jet_features=chamfer_jet_features)
         self._loss_weight = _loss_weight(loss_choice, self.world)
         self.loss_part = self.flat.tail
-        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum)
+        self.opt_state = o = _OptimState(self.flat, l1_lambda, lr, betas, eps, optimizer_choice, l2_lambda, rms_alpha, momentum,
+                                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                                         blow_up_threshold=blow_up_threshold, lr_schedule=lr_schedule)
         _adopt_optim_state(self, o)
         self.recon = None
         self._g1 = self._g2 = None
