@@ -290,9 +290,10 @@ def tiled_jets(B, N, K=7, seed=0):
     copies_k term_k of the K jets, gradient included; K = 7 is coprime to every power of two, so a kernel that reads a neighbour's
     jet at an offset of 1, 2, 4 .. 512 lands on other data."""
     from oracle import lgn_oracle as O
+    import _jets
     p4, labels = O.synthetic_jets(K, N, seed=seed, pad=True)
-    idx = torch.arange(B) % K
-    return p4[idx].contiguous(), labels[idx].contiguous(), p4, labels, torch.bincount(idx, minlength=K)
+    tiled, tiled_labels, copies = _jets.tile(p4, labels, B)
+    return tiled, tiled_labels, p4, labels, copies
 
 
 def assert_rep_close(rep, ref, tol, what="", check_order=True):

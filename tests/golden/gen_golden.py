@@ -38,6 +38,9 @@ Fixtures
   g16_dropin.json     the drop-in boundary: every `lgn` import of the reference's callers of the hot path (main.py, test.py,
                       covariance_test.py, anomaly_detection.py, utils/**), and the keyword arguments utils.initialize.
                       initialize_autoencoder passes to LGNEncoder / LGNDecoder for one fixed argument set (names and values only)
+  g28_masks_maxdim2.npz / g28_masks_maxdim3.npz  end-to-end on jets with holes (tests/_jets.py: the HOLED mask patterns, then the same
+                      batch with labels and momenta disagreeing: 22 jets) at LIVE weights (sigma * randn on every parameter): maxdim 2
+                      N=12 ch 233/332, maxdim 3 N=10 ch 246/642
 
 `python gen_golden.py g6 g7` regenerates only the named fixtures.
 """
@@ -69,6 +72,7 @@ ZF = sys.modules["lgn.cg_lib.zonal_functions"]
 OUT = os.path.dirname(os.path.abspath(__file__))
 CPU = torch.device("cpu")
 F64 = torch.float64
+G28_SIGMA = {2: 0.1, 3: 0.1}      # {maxdim: sigma of go_live for the g28 fixtures}
 
 
 def npy(t):
@@ -107,12 +111,50 @@ def build(N, maxdim, ch_enc, ch_dec, seed, map_to_latent="min&max", activation="
     return enc, dec
 
 
+def mask_jets(N, seed):
+    """tests/_jets.py's HOLED batch followed by its `disagree` copy (22 jets), restated with the reference's normalize_p4: the mask
+    patterns and the disagreements are that module's own (plain torch, it is imported from the tests directory), the momenta are
+    pattern_jets' recipe -- p3 ~ N(0, 1), m^2 ~ U(0.01, 0.25) per particle, overall_max, masked rows multiplied to zero."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import _jets
+    g = torch.Generator().manual_seed(seed)
+    P = _jets.mask_patterns(N, g)
+    labels = torch.stack([P[n] for n in _jets.HOLED]).to(torch.uint8)
+    B = len(_jets.HOLED)
+    p3 = torch.randn(B, N, 3, dtype=F64, generator=g)
+    m2 = 0.01 + 0.24 * torch.rand(B, N, 1, dtype=F64, generator=g)
+    e = torch.sqrt((p3 * p3).sum(-1, keepdim=True) + m2)
+    p4, _ = normalize_p4(torch.cat([e, p3], -1), "overall_max")
+    p4 = p4 * labels.unsqueeze(-1).to(F64)
+    q4, qlabels = _jets.disagree(p4, labels, torch.Generator().manual_seed(seed + 1))
+    return torch.cat([p4, q4]), torch.cat([labels, qlabels])
+
+
+def go_live(enc, dec, sigma, seed):
+    """sigma * randn on every state_dict tensor of the two reference modules (one generator: the encoder's tensors first, in
+    state_dict order): off the initial weights, where the network does almost nothing.  The stored state dicts are the moved ones."""
+    g = torch.Generator().manual_seed(seed)
+    for mod in (enc, dec):
+        sd = {k: v.detach().clone() for k, v in mod.state_dict().items()}
+        for v in sd.values():
+            v.add_(sigma * torch.randn(v.shape, dtype=v.dtype, generator=g))
+        mod.load_state_dict(sd)
+
+
 def e2e(name, B, N, maxdim, ch_enc, ch_dec, seed, pad_rows=(), map_to_latent="min&max", activation="leakyrelu", jet_features=False,
-        extra_scalars=0, mlp_depth=6, num_basis_fn=10, mlp_width=6):
+        extra_scalars=0, mlp_depth=6, num_basis_fn=10, mlp_width=6, inputs=None, live=None, nodes=True):
+    """inputs: (p4, labels) in place of jets(B, N, seed + 100, pad_rows).  live: (sigma, seed) of go_live.  nodes=False: without the
+    per-level node features (a fixture that would exceed 1 MB with them)."""
     enc, dec = build(N, maxdim, ch_enc, ch_dec, seed, map_to_latent, activation, jet_features, 1 + extra_scalars, mlp_depth, num_basis_fn,
                      mlp_width)
-    p4, labels = jets(B, N, seed + 100, pad_rows)
+    p4, labels = jets(B, N, seed + 100, pad_rows) if inputs is None else inputs
+    assert tuple(p4.shape) == (B, N, 4)
     meta = dict(B=B, N=N, maxdim=maxdim, ch_enc=list(ch_enc), ch_dec=list(ch_dec), seed=seed, l1_lambda=1e-8, map_to_latent=map_to_latent)
+    if live is not None:
+        go_live(enc, dec, *live)
+        meta["live"] = list(live)
+    if not nodes:
+        meta["nodes"] = False
     if activation != "leakyrelu":
         meta["activation"] = activation
     if jet_features or extra_scalars:
@@ -138,9 +180,9 @@ def e2e(name, B, N, maxdim, ch_enc, ch_dec, seed, pad_rows=(), map_to_latent="mi
     n_enc = len(nodes_all)
     put_rep(store, "latent", latent)
     gen, nodes_all = dec(latent, covariance_test=True, nodes_all=nodes_all)
-    for i, rep in enumerate(nodes_all[:n_enc]):
+    for i, rep in enumerate(nodes_all[:n_enc] if nodes else ()):
         put_rep(store, f"enc_nodes.{i}", rep)
-    for i, rep in enumerate(nodes_all[n_enc:]):
+    for i, rep in enumerate(nodes_all[n_enc:] if nodes else ()):
         put_rep(store, f"dec_nodes.{i}", rep)
 
     # training-step forward/backward (utils/train.py:283-343), Chamfer only and Chamfer + L1
@@ -424,6 +466,12 @@ if __name__ == "__main__":
         e2e("g14_e2e_mlpwidth5_maxdim3.npz", 2, 10, 3, (2, 4, 6), (6, 4, 2), seed=15, pad_rows=((1, 6),), mlp_width=5)
     if want("g12"):       # 150 particles at maxdim 3 (the product of two BASELINE axes; the jet's packed features exceed a CU's LDS)
         e2e("g12_e2e_n150_maxdim3.npz", 1, 150, 3, (4, 4, 6, 6), (6, 6, 4, 4), seed=9, pad_rows=((0, 137),))
+    if want("g28"):       # holed and sparse jets, labels and momenta that disagree (mask_jets: 22 jets), at LIVE weights: every other
+        # fixture is prefix-padded and sits at the initial weights.  Sigma: the smallest of 0.1, 0.13 .. at which U.assert_live holds on
+        # the stored outputs (tests/test_oracle_golden.py asserts it)
+        e2e("g28_masks_maxdim2.npz", 22, 12, 2, (2, 3, 3), (3, 3, 2), seed=28, inputs=mask_jets(12, 128), live=(G28_SIGMA[2], 77))
+        e2e("g28_masks_maxdim3.npz", 22, 10, 3, (2, 4, 6), (6, 4, 2), seed=29, inputs=mask_jets(10, 129), live=(G28_SIGMA[3], 77),
+            nodes=False)
     if want("g16"):
         dropin()
     if want("g10"):

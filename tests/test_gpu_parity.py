@@ -194,8 +194,26 @@ def test_level_decoder_pair_sweep(dev, O, monkeypatch, C, CO, N, B):
     _level_case(dev, O, True, C, CO, N, B)
 
 
-def _level_case(dev, O, decoder, C, CO, N, B):
+def _tiled(jets, tile_to, B):
+    """(index of the distinct jet behind every jet the kernel gets, per-jet weight of the oracle's cotangent) of a level case: the
+    identity and None unless the batch is tiled (_jets.tile: distinct jet b % B, the oracle's loss weighted by the copy counts)."""
+    if tile_to is None:
+        return torch.arange(B), None
+    assert jets is not None and B % 2 == 1
+    idx = torch.arange(tile_to) % B
+    return idx, torch.bincount(idx, minlength=B).to(torch.float64)
+
+
+def _level_case(dev, O, decoder, C, CO, N, B, jets=None, tile_to=None):
+    """jets: (p4 (B, N, 4), labels (B, N)) in place of the synthetic prefix-padded batch (encoder only).  tile_to: the kernel gets
+    that many jets, jet b a copy of jet b % B with its features and cotangent; the oracle runs on the B jets with its loss weighted
+    by the copy counts, so that the parameter gradients are those of the tiled batch, and every tiled jet's outputs and input
+    gradients are compared with its distinct jet's."""
     from lgn import ops
+    assert jets is None or (not decoder and tuple(jets[0].shape) == (B, N, 4))
+    idx, copies = _tiled(jets, tile_to, B)
+    tl = (lambda t, axis=1: t) if tile_to is None else (lambda t, axis=1: t.index_select(axis, idx))      # noqa: E731
+    per_copy = (lambda t: t) if tile_to is None else (lambda t: t / copies.view(1, B, *[1] * (t.dim() - 2)))   # noqa: E731
     g = torch.Generator().manual_seed(100 * C + 10 * CO + N + int(decoder))
     cfg, plans, P = _rand_level_params(O, C, CO, decoder, g)
     P = {k: v.requires_grad_(True) for k, v in P.items()}
@@ -207,7 +225,7 @@ def _level_case(dev, O, decoder, C, CO, N, B):
         mask = None
         emask = torch.zeros(2, B, N, N, dtype=torch.float64)
     else:
-        p4, labels = O.synthetic_jets(B, N, seed=N + C, pad=N > 4)
+        p4, labels = O.synthetic_jets(B, N, seed=N + C, pad=N > 4) if jets is None else jets
         p, mask = p4, labels
         zonal, norms, _ = O.zonal_rel(p, p, "cartesian")
         em = mask.unsqueeze(1) * mask.unsqueeze(2)
@@ -216,13 +234,19 @@ def _level_case(dev, O, decoder, C, CO, N, B):
     edge = {k: O.scalar_times_irrep(rad[k], zonal[k]) for k in rad}
     out = O.node_level(P, O.get_cg(2), cfg, 0, plans[0], node, edge)
     cot = {k: torch.randn(v.shape, dtype=torch.float64, generator=g) for k, v in out.items()}
-    sum((out[k] * cot[k]).sum() for k in out).backward()
+    weigh = (lambda t: t) if copies is None else (lambda t: t * copies.view(1, B, *[1] * (t.dim() - 2)))     # noqa: E731
+    sum((out[k] * weigh(cot[k])).sum() for k in out).backward()
+    node_grad = {k: tl(per_copy(t.grad)) for k, t in node.items()}
+    if tile_to is not None:         # what every tiled jet is compared with: its distinct jet's outputs and per-copy input gradients
+        out = {k: tl(v.detach()) for k, v in out.items()}
+        cot = {k: tl(v) for k, v in cot.items()}
 
     # native
     d = lambda t: t.detach().to(dev).requires_grad_(t.requires_grad)  # noqa: E731
-    s_in = d(node[(0, 0)].squeeze(-1).detach().requires_grad_(True))
-    v_in = d(node[(1, 1)])
-    pd = d(p)
+    s_in = d(tl(node[(0, 0)].squeeze(-1).detach()).requires_grad_(True))
+    v_in = d(tl(node[(1, 1)].detach()).requires_grad_(True))
+    pd = d(tl(p, 0) if not decoder else p)
+    mask = mask if decoder else tl(mask, 0)
     pre = "rad_funcs.rad_funcs.0."
     names = ["a", "b", "c", "linear.0.weight", "linear.0.bias", "linear.1.weight", "linear.1.bias"]
     radp = [d(P[pre + n]) for n in names]
@@ -232,8 +256,8 @@ def _level_case(dev, O, decoder, C, CO, N, B):
     U.assert_close(s_out.unsqueeze(-1), out[(0, 0)], FWD_TOL, "s_out")
     U.assert_close(v_out, out[(1, 1)], FWD_TOL, "v_out")
     ((s_out.unsqueeze(-1) * cot[(0, 0)].to(dev)).sum() + (v_out * cot[(1, 1)].to(dev)).sum()).backward()
-    U.assert_close(s_in.grad.unsqueeze(-1), node[(0, 0)].grad, GRAD_TOL, "g_s_in")
-    U.assert_close(v_in.grad, node[(1, 1)].grad, GRAD_TOL, "g_v_in")
+    U.assert_close(s_in.grad.unsqueeze(-1), node_grad[(0, 0)], GRAD_TOL, "g_s_in")
+    U.assert_close(v_in.grad, node_grad[(1, 1)], GRAD_TOL, "g_v_in")
     if decoder:
         U.assert_close(pd.grad, p.grad, GRAD_TOL, "g_p")
     for n, t in zip(names, radp):
@@ -668,10 +692,12 @@ def test_generic_level_alternative_moments_kernels(dev, O, monkeypatch, flag, de
     _generic_level_case(dev, O, decoder, maxdim, full, C, CO, N, B)
 
 
-def _generic_level_case(dev, O, decoder, maxdim, full, C, CO, N, B):
+def _generic_level_case(dev, O, decoder, maxdim, full, C, CO, N, B, jets=None):
+    """jets: (p4 (B, N, 4), labels (B, N)) in place of the synthetic prefix-padded batch (encoder only)."""
     from lgn import ops, _native as Nn
     from lgn.cg_lib import CGDict
     from lgn.plan import build_level_plans, build_local_tables, param_key_order
+    assert jets is None or (not decoder and tuple(jets[0].shape) == (B, N, 4))
     g = torch.Generator().manual_seed(1000 * maxdim + 10 * C + CO + N + int(decoder) + int(full))
     node_order = [(1, 1), (2, 0), (0, 2), (2, 2), (0, 0)] if full else [(1, 1), (0, 0)]
     cfg = O.NetConfig(num_channels=(C, CO), maxdim=maxdim)
@@ -691,7 +717,7 @@ def _generic_level_case(dev, O, decoder, maxdim, full, C, CO, N, B):
         zonal, norms, _ = O.zonal_rel(p, p, "canonical")
         mask, emask = None, torch.zeros(2, B, N, N, dtype=torch.float64)
     else:
-        p, mask = O.synthetic_jets(B, N, seed=N + C, pad=N > 4)
+        p, mask = O.synthetic_jets(B, N, seed=N + C, pad=N > 4) if jets is None else jets
         zonal, norms, _ = O.zonal_rel(p, p, "cartesian")
         emask = (mask.unsqueeze(1) * mask.unsqueeze(2)) * (norms != 0).byte()
     rad = O.radial_filters(P, cfg, 0, norms, emask, decoder)

@@ -21,8 +21,60 @@ def _cfgs(m):
                                   "g7_e2e_meanmax.npz", "g9_e2e_elu.npz", "g10_e2e_jetfeat.npz", "g11_e2e_mlpdepth4.npz",
                                   "g11_e2e_mlpdepth3_maxdim3.npz", "g12_e2e_n150_maxdim3.npz", "g13_e2e_basis5.npz",
                                   "g13_e2e_basis5_maxdim3.npz", "g14_e2e_mlpwidth4.npz", "g14_e2e_mlpwidth5.npz", "g14_e2e_mlpwidth7.npz",
-                                  "g14_e2e_mlpwidth5_maxdim3.npz", "g15_e2e_basis12.npz", "g15_e2e_basis20_maxdim3.npz"])
+                                  "g14_e2e_mlpwidth5_maxdim3.npz", "g15_e2e_basis12.npz", "g15_e2e_basis20_maxdim3.npz",
+                                  "g28_masks_maxdim2.npz", "g28_masks_maxdim3.npz"])
 def test_end_to_end_forward_backward(name):
+    _end_to_end(name)
+
+
+@pytest.mark.parametrize("name", ["g28_masks_maxdim2.npz", "g28_masks_maxdim3.npz"])
+def test_mask_patterns_live_weights(name):
+    """The g28 fixtures: the reference on jets with holes, sparse jets and a batch whose labels and momenta disagree (_jets.HOLED, then
+    its `disagree` copy), at live weights.  The stored inputs are _jets' own recipe; the reference's outputs are live (U.assert_live on
+    the STORED outputs); the oracle reproduces latent and reconstruction PER JET -- a sparse jet's reconstruction is orders below a
+    full jet's, so the batch-wide maximum of test_end_to_end_forward_backward holds it to much less -- and every gradient tensor at
+    1e-10 of its own maximum; an all-masked jet's reconstruction is exactly zero in the reference and in the oracle."""
+    import _jets
+    z = U.load(name)
+    m = U.meta(z)
+    ce, cd = _cfgs(m)
+    K, N = len(_jets.HOLED), m["N"]
+    p4, labels = torch.from_numpy(z["p4"]), torch.from_numpy(z["labels"])
+    seed = {2: 128, 3: 129}[m["maxdim"]]
+    h4, hl = _jets.pattern_jets(N, _jets.HOLED, seed)
+    q4, ql = _jets.disagree(h4, hl, torch.Generator().manual_seed(seed + 1))
+    assert torch.equal(labels, torch.cat([hl, ql])), "the fixture's mask patterns are not _jets.HOLED's"
+    U.assert_close(p4, torch.cat([h4, q4]), 1e-15, "the fixture's momenta against _jets.pattern_jets / disagree")
+    assert bool((p4[:K][~labels[:K].bool()] == 0).all()) and bool((p4[K][~labels[K].bool()] != 0).any())
+    rec_ref = torch.from_numpy(z["recon"])
+    grads_ref = {k[len("grad."):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("grad.")}
+    low = U.assert_live(O, rec_ref, grads_ref, p4, torch.from_numpy(z["recon_real"]), mask=labels)
+    print(f"[{name}] reference: max |recon| {float(rec_ref.abs().max()):.3e}, {low} of {len(grads_ref)} gradient tensors under 1e-4 of the largest")
+
+    Pe = {k: v.clone() for k, v in U.params_from(z, "enc").items()}
+    Pd = {k: v.clone() for k, v in U.params_from(z, "dec").items()}
+    loss, rec, grads, lat, _ = U.oracle_step(O, Pe, Pd, ce, cd, p4, labels, with_latent=True)
+    U.assert_close(loss, z["loss_chamfer"], TOL, "chamfer")
+    lat_ref = U.rep_from(z, "latent")
+    empty = [b for b in range(2 * K) if int(labels[b].sum()) == 0]
+    assert empty, "the batch holds no all-masked jet"
+    for b in range(2 * K):
+        what = f"jet {b} ({_jets.HOLED[b % K]}{', disagreeing' if b >= K else ''})"
+        if b in empty:
+            assert float(rec_ref[:, b].abs().max()) == 0 and float(rec[:, b].abs().max()) == 0, f"{what}: reconstruction must be exactly 0"
+        else:
+            U.assert_close(rec[:, b], rec_ref[:, b], TOL, f"recon of {what}")
+        for k in lat_ref:
+            U.assert_close(lat[k][:, b], lat_ref[k][:, b], TOL, f"latent {k} of {what}")
+    for k, ref in grads_ref.items():
+        g = grads[k] if grads[k] is not None else torch.zeros_like(ref)
+        if ref.abs().max() == 0:
+            assert g.abs().max() == 0, f"grad {k} must be exactly zero"
+        else:
+            U.assert_close(g, ref, 1e-10, f"grad {k}")
+
+
+def _end_to_end(name):
     z = U.load(name)
     m = U.meta(z)
     ce, cd = _cfgs(m)
@@ -33,10 +85,12 @@ def test_end_to_end_forward_backward(name):
 
     lat, enc_nodes = O.encoder_forward(Pe, ce, p4, labels, covariance_test=True, extra_scalars=xs)
     U.assert_rep_close(lat, U.rep_from(z, "latent"), TOL, "latent")
-    for i, rep in enumerate(enc_nodes):
+    stored = m.get("nodes", True)          # (False: a fixture that would exceed 1 MB with the per-level node features)
+    assert stored or not any(k.startswith(("enc_nodes.", "dec_nodes.")) for k in z.files)
+    for i, rep in enumerate(enc_nodes if stored else ()):
         U.assert_rep_close(rep, U.rep_from(z, f"enc_nodes.{i}"), TOL, f"enc_nodes[{i}]")
     gen, dec_nodes = O.decoder_forward(Pd, cd, lat, covariance_test=True)
-    for i, rep in enumerate(dec_nodes):
+    for i, rep in enumerate(dec_nodes if stored else ()):
         U.assert_rep_close(rep, U.rep_from(z, f"dec_nodes.{i}"), TOL, f"dec_nodes[{i}]")
 
     rec = O.decoder_forward(Pd, cd, O.encoder_forward(Pe, ce, p4, labels, extra_scalars=xs))
