@@ -74,6 +74,19 @@ def disagree(p4, labels, g):
     return q, lab
 
 
+def recon_like(p4, labels, g, rel=0.05):
+    """A stand-in for a decoder's reconstruction of the target (p4, labels), for the calls that take (reconstruction, target) without
+    the networks.  A row that is real by its label AND carries momenta: every component times 1 + rel N(0, 1).  Every other row
+    (masked, or a real row of zeros as `disagree` makes one): 1e-3 N(0, 1) per component -- a decoder never returns zeros there, and
+    never returns the target's stray momenta of a masked row either.  A jet without a real label: exactly zero, as the decoder returns
+    it (g28).  g: the torch.Generator; the draws do not depend on the labels, so a batch and its `disagree` copy share them."""
+    noise = torch.randn(p4.shape, dtype=torch.float64, generator=g)
+    small = 1e-3 * torch.randn(p4.shape, dtype=torch.float64, generator=g)
+    real = labels.bool() & (p4 != 0).any(-1)
+    x = torch.where(real.unsqueeze(-1), p4 * (1.0 + rel * noise), small)
+    return torch.where((labels.sum(1) > 0).view(-1, 1, 1), x, torch.zeros_like(x))
+
+
 def tile(p4, labels, B):
     """B jets made of the K given ones laid out cyclically (jet b = given jet b % K; K odd, so coprime to every power of two).
     Returns (p4 (B, N, 4), labels (B, N), copies (K,): how often each given jet occurs).  A loss that is a sum over jets is then

@@ -38,6 +38,9 @@ Fixtures
   g16_dropin.json     the drop-in boundary: every `lgn` import of the reference's callers of the hot path (main.py, test.py,
                       covariance_test.py, anomaly_detection.py, utils/**), and the keyword arguments utils.initialize.
                       initialize_autoencoder passes to LGNEncoder / LGNDecoder for one fixed argument set (names and values only)
+  g29_loss_masks.npz     the reference's HungarianMSELoss (four frames: loss, gradient, assignment), anomaly_scores (21 scores) and
+                         reconstruction analysis on the 22 jets of mask_jets at N = 12 against tests/_jets.py's recon_like
+                         reconstruction (needs scipy; loads the analysis files as gen_golden_g18.py / gen_golden_g22.py do)
   g28_masks_maxdim2.npz / g28_masks_maxdim3.npz  end-to-end on jets with holes (tests/_jets.py: the HOLED mask patterns, then the same
                       batch with labels and momenta disagreeing: 22 jets) at LIVE weights (sigma * randn on every parameter): maxdim 2
                       N=12 ch 233/332, maxdim 3 N=10 ch 246/642
@@ -128,6 +131,74 @@ def mask_jets(N, seed):
     p4 = p4 * labels.unsqueeze(-1).to(F64)
     q4, qlabels = _jets.disagree(p4, labels, torch.Generator().manual_seed(seed + 1))
     return torch.cat([p4, q4]), torch.cat([labels, qlabels])
+
+
+def loss_masks(name, N, seed):
+    """g29: the reference's HungarianMSELoss in its four frames, its anomaly_scores (an.*: 21 scores, scipy's assignments on the
+    reference's six cost matrices) and its reconstruction analysis (ra.*: the arrays of gen_golden_g22.py, get_rel_err_find_match
+    route) on mask_jets (HOLED, then its `disagree` copy: 22 jets) against the
+    reconstruction tests/_jets.py's recon_like gives for them: x, t, labels, and per frame f loss.f, grad.f = d loss / d x and col.f
+    (linear_sum_assignment of torch.cdist of every jet, as the reference takes it).  The target rows that are zero tie exactly."""
+    from scipy import optimize
+    from utils.losses.hungarian_mse.hungarian_mse import HungarianMSELoss, preprocess
+    t, labels = mask_jets(N, seed)
+    import _jets
+    x = _jets.recon_like(t, labels, torch.Generator().manual_seed(seed + 2))
+    store = {"x": npy(x), "t": npy(t), "labels": labels.numpy(), "meta": np.array(json.dumps(dict(N=N, seed=seed)))}
+    for f, (a, p) in {"abs_cart": (True, False), "abs_polar": (True, True), "rel_polar": (False, True), "rel_cart": (False, False)}.items():
+        xx = x.clone().requires_grad_(True)
+        loss = HungarianMSELoss()(xx, t.clone(), abs_coord=a, polar_coord=p)
+        loss.backward()
+        with torch.no_grad():
+            rp, tp = preprocess(x.clone(), t.clone(), abs_coord=a, polar_coord=p)
+            cost = torch.cdist(rp, tp).numpy()
+        col = np.stack([optimize.linear_sum_assignment(c)[1] for c in cost])
+        store[f"loss.{f}"], store[f"grad.{f}"], store[f"col.{f}"] = npy(loss), npy(xx.grad), col.astype(np.int16)
+        print(f"{name} {f}: loss {loss.item():.12g}")
+
+    # the reference's anomaly_scores (21 scores) and the assignments scipy finds on ITS cost matrices, every jet kept
+    from scipy.optimize import linear_sum_assignment
+    import gen_golden_g18 as G18
+    import gen_golden_g22 as G22
+    import _anomaly_ref as AR
+    AD = G18.load_reference()
+    xn, tn = G18.normalize(x.numpy()), G18.normalize(t.numpy())
+    ref = AD.anomaly_scores(x.clone(), t.clone(), torch.from_numpy(xn), torch.from_numpy(tn), include_emd=False, batch_size=-1)
+    assert tuple(ref) == AR.SCORE_KEYS
+    B = x.shape[0]
+    col = np.zeros((6, B, N), dtype=np.int16)
+    for f, (p, q, lor) in enumerate(AR.frames(x.numpy(), t.numpy(), xn, tn)):
+        pt, qt = (torch.from_numpy(np.ascontiguousarray(v[..., :3] if f == 4 else v)) for v in (p, q))
+        cost = AD.norm_sq_Lorentz(pt.unsqueeze(-2) - qt.unsqueeze(-3)).numpy() if lor else torch.cdist(pt, qt).numpy()
+        col[f] = np.stack([linear_sum_assignment(c)[1] for c in cost])
+    store.update({"an.scores": np.stack([np.asarray(ref[k]) for k in ref], -1), "an.col": col, "an.recons_n": xn, "an.target_n": tn})
+
+    # the reference's reconstruction analysis (get_rel_err_find_match route, abs_coord=True), every jet kept
+    import inspect
+    UJ, PR, JR = G22.load_reference()
+    t3, r3 = t[..., 1:], x[..., 1:]
+    tp, rp = UJ.get_p_polar_tensor(t), UJ.get_p_polar_tensor(x)
+    tq, rq = UJ.get_p_polarrel_tensor(t), UJ.get_p_polarrel_tensor(x)
+    with np.errstate(all="ignore"):
+        rel = [e.numpy().reshape(B, N, 3) for e in PR.get_rel_err_find_match(t3, r3, tp, rp, tq, rq, gpu=False)]
+    jc = [UJ.get_jet_feature_cartesian(v, gpu=False, return_arr=True).numpy() for v in (t, x)]
+    jp = [UJ.get_jet_feature_polar(v, gpu=False, return_arr=True) for v in (t, x)]
+    lam = inspect.signature(JR.plot_jet_recon_err).parameters["get_rel_err"].default
+    eps = inspect.signature(JR.plot_jet_recon_err).parameters["eps"].default
+    with np.errstate(all="ignore"):
+        jre = [np.stack([lam(f[1][:, i], f[0][:, i], eps) for i in range(4)], -1) for f in (jc, jp)]
+    jet_keep = []
+    for f in (jc, jp):
+        _, kept = JR.filter_out_zeros(tuple(f[0][:, i] for i in range(4)), tuple(np.arange(B) for _ in range(4)))
+        mask = np.zeros(B, bool)
+        mask[kept[0]] = True
+        jet_keep.append(mask)
+    col2 = np.stack([np.stack([linear_sum_assignment(c)[1] for c in torch.cdist(a, b).numpy()]) for a, b in ((t3, r3), (tq, rq))])
+    store.update({"ra.rel_err": np.stack(rel), "ra.part_polar": np.stack((tp.numpy(), rp.numpy())),
+                  "ra.part_polarrel": np.stack((tq.numpy(), rq.numpy())), "ra.jet_cart": np.stack(jc), "ra.jet_polar": np.stack(jp),
+                  "ra.jet_rel_err": np.stack(jre), "ra.jet_keep": np.stack(jet_keep), "ra.col": col2.astype(np.int16),
+                  "ra.is_padded": np.isinf(rel[0]).any(-1)})
+    np.savez_compressed(os.path.join(OUT, name), **store)
 
 
 def go_live(enc, dec, sigma, seed):
@@ -472,6 +543,8 @@ if __name__ == "__main__":
         e2e("g28_masks_maxdim2.npz", 22, 12, 2, (2, 3, 3), (3, 3, 2), seed=28, inputs=mask_jets(12, 128), live=(G28_SIGMA[2], 77))
         e2e("g28_masks_maxdim3.npz", 22, 10, 3, (2, 4, 6), (6, 4, 2), seed=29, inputs=mask_jets(10, 129), live=(G28_SIGMA[3], 77),
             nodes=False)
+    if want("g29"):       # the reference's HungarianMSELoss on the holed and disagreeing jets, reconstruction by _jets.recon_like
+        loss_masks("g29_loss_masks.npz", 12, 130)
     if want("g16"):
         dropin()
     if want("g10"):

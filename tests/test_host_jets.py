@@ -64,6 +64,40 @@ def test_disagree_changes_three_jets_and_no_label():
     assert bool((q4[2, r2[1]] == 0).all()) and int(labels[2, r2[1]]) == 1 and int((q4[2] != p4[2]).any(-1).sum()) == 1
 
 
+@pytest.mark.parametrize("names", [J.HOLED, J.SPARSE], ids=["holed", "sparse"])
+@pytest.mark.parametrize("N", [12, 30, 65])
+def test_recon_like_rows(N, names):
+    p4, labels = J.pattern_jets(N, names, 11)
+    x = J.recon_like(p4, labels, torch.Generator().manual_seed(13))
+    assert x.dtype == torch.float64 and tuple(x.shape) == tuple(p4.shape)
+    assert torch.equal(x, J.recon_like(p4, labels, torch.Generator().manual_seed(13))), "same generator state, same reconstruction"
+    assert not torch.equal(x, J.recon_like(p4, labels, torch.Generator().manual_seed(14)))
+    real = labels.bool()
+    empty = labels.sum(1) == 0
+    assert int(empty.sum()) == names.count("empty") >= 1
+    assert bool((x[empty] == 0).all()) and not bool(torch.signbit(x[empty]).any()), "an all-masked jet is +0 on both sides"
+    assert bool((p4[empty] == 0).all())
+    assert bool((x[~empty] != 0).all()), "no other row holds a zero: a decoder never returns one"
+    rel = ((x - p4) / p4)[real]                                          # real rows: within 5 sigma of rel = 0.05, and moved
+    assert float(rel.abs().max()) < 0.25 + 1e-12 and float(rel.abs().min()) > 0
+    masked = (~real) & (~empty).unsqueeze(1)
+    assert float(x[masked].abs().max()) < 5e-3 and float(x[masked].abs().max()) < 0.1 * float(x[real].abs().max())
+
+
+def test_recon_like_on_disagreeing_labels():
+    """The draws do not depend on the labels or the momenta: the disagreeing copy's reconstruction differs from the batch's only where
+    the target does, never follows a masked row's stray momenta, and fills the real row of zeros."""
+    p4, labels = J.pattern_jets(12, J.HOLED, 11)
+    q4, q_labels = J.disagree(p4, labels, torch.Generator().manual_seed(12))
+    x, y = (J.recon_like(t, labels, torch.Generator().manual_seed(13)) for t in (p4, q4))
+    assert torch.equal(x[3:], y[3:]) and torch.equal(x[0], y[0])
+    masked0 = ~labels[0].bool()
+    assert float(y[0][masked0].abs().max()) < 5e-3 < float(q4[0][masked0].abs().max())
+    zeroed = labels[2].nonzero().flatten()[1]
+    assert bool((q4[2, zeroed] == 0).all()) and bool((y[2, zeroed] != 0).all()) and float(y[2, zeroed].abs().max()) < 5e-3
+    assert int((x[1] != y[1]).any(-1).sum()) == 1 and int((x[2] != y[2]).any(-1).sum()) == 1
+
+
 def test_tile_is_the_cyclic_layout_of_tiled_jets():
     p4, labels = J.pattern_jets(12, J.HOLED, 3)
     t4, t_labels, copies = J.tile(p4, labels, 275)
